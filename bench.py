@@ -9,7 +9,12 @@ NES matrix.  Workload = BASELINE.json configs[1]: Costanzo-2016-shaped network (
 nodes, default metric) x 4373 GO-BP-like binary attributes x 1000 permutations, on a
 seeded surrogate (safe-data is not available offline; safepy_amd/workloads.py).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line (ms_per_step = the mean timed step);
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).  --full adds, after the headline and
+outside its timed region, the other measurements: the unseeded call, the CPU baseline, the HBM- and matrix-core-bound
+kernels, the drop-in calls and, N > 1, the exchange diagnostics and the other multi-GPU configurations.
 
 N > 1: one rank per GPU (launched by torch.distributed.run; when WORLD_SIZE is not set the script
 starts that launcher itself as a child process, before anything touches a GPU, and relays rank
@@ -43,8 +48,9 @@ def parse():
     ap.add_argument('--attrs', type=int, default=4373)
     ap.add_argument('--metric', default='shortpath_weighted_layout')
     ap.add_argument('--radius', type=float, default=0.1)
-    ap.add_argument('--cpu-perms', type=int, default=40, help='permutations timed for the CPU baseline (0 = skip)')
-    ap.add_argument('--extras', type=int, default=1, help='also time the HBM-bound kernels (K1 distance, K4 hypergeometric)')
+    ap.add_argument('--cpu-perms', type=int, default=40, help='--full: permutations timed for the CPU baseline (0 = skip)')
+    ap.add_argument('--extras', type=int, default=1, help='--full: also time the unseeded call, the HBM-bound kernels (K1 distance, '
+                                                          'K4 hypergeometric), the matrix-core kernel and the drop-in calls')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='N > 1: weak = every rank its own block of --attrs columns (the default line); strong = --attrs columns '
                          'split over the ranks (np.array_split, safe.py:1339): `--scaling strong --perms 10000` is BASELINE configs[2]')
@@ -52,9 +58,18 @@ def parse():
                     help='cfg1 = the Costanzo-shaped binary workload of configs[1]/[2]; cfg4 = BASELINE configs[4]: 20 000 nodes, '
                          '6250 quantitative f64 columns per rank x 1000 permutations (matrix-core kernel)')
     ap.add_argument('--multi-extras', type=int, default=1,
-                    help='N > 1: after the timed weak-scaling line also time configs[2] (strong scaling, 10 000 permutations) and one '
+                    help='--full, N > 1: after the timed weak-scaling line also time configs[2] (strong scaling, 10 000 permutations) and one '
                          'step of the configs[4] rank share, reported inside the same JSON line')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run what --cpu-perms, --extras and --multi-extras select, and for N > 1 the '
+                         'exchange diagnostics; without it the run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float64; arrays of more than %d elements '
+                         'as a fixed seeded sample of that many, see dump_outputs)' % DUMP_ELEMENTS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def _by_decile(step_ms, values):
@@ -820,25 +835,50 @@ def thread_cpu_ms():
     return out
 
 
-def run_mode(wl, n_steps, n_warmup, ctx, dist, torch, np, be, sharding, world, diag_exchange=False, seed=0):
+DUMP_ELEMENTS = 1 << 20        # per array: 8 MB of f64; a step leaves at most seven arrays, so a dump stays under 64 MB
+
+
+def dump_outputs(dirname, arrays, np, torch):
+    """--dump-outputs: every device tensor of `arrays` as <dirname>/<name>.npy, float64.  An array of at most DUMP_ELEMENTS
+    elements is written whole, in its own shape; a larger one as a 1-D sample: its elements at DUMP_ELEMENTS flat (row-major)
+    indices drawn without replacement by np.random.default_rng(0) and sorted.  The indices depend on the array's size alone, so
+    two runs with the same arguments, of any build, write the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    picks = {}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        size = int(flat.numel())
+        if size > DUMP_ELEMENTS:
+            if size not in picks:
+                idx = np.sort(np.random.default_rng(0).choice(size, DUMP_ELEMENTS, replace=False))
+                picks[size] = torch.from_numpy(idx).to(flat.device)
+            host = flat.index_select(0, picks[size]).cpu().numpy()
+        else:
+            host = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + '.npy'), host.astype(np.float64, copy=False))
+
+
+def run_mode(wl, n_steps, n_warmup, ctx, dist, torch, np, be, sharding, world, diag_exchange=False, seed=0, after_timed=None):
     """Warm-up + exactly n_steps timed steps of sharding.randomization_step on `wl` (barrier + synchronize on both sides, MAX over
     ranks); returns the numbers of the mode.  A step = one compute_pvalues pass of this rank's block: statistics for the
     dispatch rule, whole-matrix row flags (N > 1: one small all-gather), the seeded legacy stream (one per node) + table
     kernels, the permutation-test kernels with the fused p-value / NES / binarisation epilogue and -- N > 1 -- the all-gather
-    of every rank's result over RCCL / xGMI."""
+    of every rank's result over RCCL / xGMI.  after_timed(outputs): called right after the timed steps with what the last one
+    computed (name -> device tensor: this rank's output blocks, num_neighborhoods_enriched and, N > 1, the gathered full_nes)."""
     n, m, P = wl.n, wl.m, wl.P
     out = {k: torch.empty((n, m), dtype=torch.float64, device='cuda') for k in sharding.RANDOMIZATION_OUTPUTS}
     enriched = torch.empty((m,), dtype=torch.float64, device='cuda')
     table = be.nes_table(P)
     timings = []
+    returned = [None]
 
     def step(exchange=True):
         attr = be.Attributes.from_device(ctx, wl.b_dev.data_ptr(), wl.dtype, n, m, order=wl.order)
         t = {}
         try:
             # seed 0: the NumPy-compatible seeded stream (BASELINE's configuration); None: an unseeded call, tables generated on the device
-            sharding.randomization_step(ctx, wl.nbr, attr, wl.m_total, P, seed, out, enriched, 'sum', 'both', 0.05,
-                                        table=table, exchange=exchange, timing=t)
+            returned[0] = sharding.randomization_step(ctx, wl.nbr, attr, wl.m_total, P, seed, out, enriched, 'sum', 'both', 0.05,
+                                                      table=table, exchange=exchange, timing=t)
             timings.append(t)
         finally:
             attr.close()
@@ -891,6 +931,11 @@ def run_mode(wl, n_steps, n_warmup, ctx, dist, torch, np, be, sharding, world, d
         if gc_was_enabled:
             gc.enable()
         gc.unfreeze()
+    if after_timed is not None:
+        outputs = dict(out, num_neighborhoods_enriched=enriched)
+        if returned[0] is not None and returned[0] is not out['nes']:
+            outputs['full_nes'] = returned[0]
+        after_timed(outputs)
     res = {'elapsed': elapsed, 'step_ms': step_ms, 'host_cpu_ms': 1e3 * (time.process_time() - cpu0) / n_steps,
            'timings': list(timings), 'kernel': ctx.last_kernel(), 'out': out, 'step_probe': probe.report(step_ms, timings)}
     mean = lambda key: float(np.mean([t.get(key, 0.0) for t in timings])) if timings else 0.0      # noqa: E731
@@ -1050,8 +1095,11 @@ def main():
     probe_unseeded = os.environ.get('SAFE_BENCH_SEED') == 'none'       # (probes only: the headline mode as an unseeded call)
     if probe_unseeded:
         wl.name += ' [SAFE_BENCH_SEED=none: random_seed=None, tables generated on the device -- NOT the headline configuration]'
-    res = run_mode(wl, args.steps, args.warmup, ctx, dist, torch, np, be, sharding, world, diag_exchange=True,
-                   seed=None if probe_unseeded else 0)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda outputs: dump_outputs(args.dump_outputs, outputs, np, torch)      # noqa: E731
+    res = run_mode(wl, args.steps, args.warmup, ctx, dist, torch, np, be, sharding, world, diag_exchange=args.full,
+                   seed=None if probe_unseeded else 0, after_timed=dump)
 
     line = None
     if rank == 0:
@@ -1104,9 +1152,10 @@ def main():
         }
         if 'exchange_report' in res:
             line['exchange'] = res['exchange_report']
+    # ---------------- --full only: everything below is measured outside the timed region, after the headline -----------------
     # the same workload as an UNSEEDED call (random_seed=None, the reference's default): tables generated on the device, no host
     # stream -- outside the timed region, reported beside the seeded headline
-    if args.extras and args.workload == 'cfg1' and args.scaling == 'weak':
+    if args.full and args.extras and args.workload == 'cfg1' and args.scaling == 'weak':
         unseeded = {}
         for perms_u, steps_u in ((wl.P, max(5, min(args.steps, 20))), (10000, 5)):
             wl_u = wl if perms_u == wl.P else Workload(args, 'cfg1', 'weak', perms_u, rank, world, local_rank, ctx, torch, np)
@@ -1123,12 +1172,12 @@ def main():
             line['unseeded_device_stream'] = dict(unseeded, note='random_seed=None (the reference default: OS entropy, no stream to reproduce): '
                                                   'i.i.d. uniform permutations generated on the GPU (Philox4x32-10 + Fisher-Yates in LDS); '
                                                   'the seeded headline above reproduces NumPy\'s MT19937 stream on the host')
-    a_dense = wl.sf.neighborhoods if (rank == 0 and args.cpu_perms > 0 and world == 1 and wl.kind == 'cfg1') else None
+    a_dense = wl.sf.neighborhoods if (args.full and rank == 0 and args.cpu_perms > 0 and world == 1 and wl.kind == 'cfg1') else None
     b_host = wl.b_host
     del res
 
     # ---------------- N > 1: the other configurations BASELINE.json names for several GPUs, outside the timed region -----------
-    if world > 1 and args.multi_extras and args.workload == 'cfg1' and args.scaling == 'weak':
+    if args.full and world > 1 and args.multi_extras and args.workload == 'cfg1' and args.scaling == 'weak':
         extras = {}
         wl2 = Workload(args, 'cfg1', 'strong', 10000, rank, world, local_rank, ctx, torch, np)
         r2 = run_mode(wl2, 3, 1, ctx, dist, torch, np, be, sharding, world)
@@ -1161,7 +1210,7 @@ def main():
         if a_dense is not None:                               # the CPU leg runs on rank 0 at N = 1 only
             line['cpu_baseline'] = cpu_baseline(a_dense, b_host, args.cpu_perms)
             line['cpu_baseline']['gpu_over_cpu'] = line['value'] / line['cpu_baseline']['value']      # mostly the algorithm (sparse bit slices vs dense dgemm), not kernel quality
-        if args.extras and world == 1 and args.workload == 'cfg1':
+        if args.full and args.extras and world == 1 and args.workload == 'cfg1':
             del wl
             line['hbm_bound_kernels'] = hbm_kernels(ctx, torch, np, be)
             line['mfma_bound_kernels'] = mfma_kernel(ctx, np, be)

@@ -99,7 +99,7 @@ def test_bench_starts_its_own_ranks():
     if _device_count() < 2:
         pytest.skip('needs 2 devices')
     line = _bench_line(['--gpus', '2', '--steps', '3', '--warmup', '1', '--nodes', '1200', '--attrs', '640', '--perms', '200',
-                        '--cpu-perms', '0', '--extras', '0'])
+                        '--cpu-perms', '0', '--extras', '0', '--full'])
     assert line['n_gpus'] == 2 and line['scaling'] == 'weak' and line['value'] > 0
     assert line['exchange']['d2h_only_ms_per_step'] > 0 and line['exchange']['all_gather_ms_per_step'] > 0
 
@@ -115,7 +115,8 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     import time
     pre = ['taskset', '-c', '0-15'] if shutil.which('taskset') and (os.cpu_count() or 1) >= 16 else []
     t0 = time.time()
-    res = subprocess.run(pre + [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '5', '--warmup', '1', '--cpu-perms', '0'],
+    res = subprocess.run(pre + [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '5', '--warmup', '1', '--cpu-perms', '0',
+                                '--full'],
                          env=dict(os.environ, SAFE_BENCH_SHARE_DEVICE='1'), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          timeout=900, cwd=ROOT)
     wall = time.time() - t0
@@ -143,6 +144,6 @@ def test_bench_single_rank_rccl_group_reports_the_exchange():
     if _device_count() < 1:
         pytest.skip('needs a HIP device')
     line = _bench_line(['--gpus', '1', '--steps', '3', '--warmup', '1', '--nodes', '1200', '--attrs', '640', '--perms', '200',
-                        '--cpu-perms', '0', '--extras', '0'],
+                        '--cpu-perms', '0', '--extras', '0', '--full'],
                        env={'SAFE_BENCH_FORCE_DIST': '1', 'MASTER_PORT': str(_free_port())})
     assert line['n_gpus'] == 1 and 'exchange' in line and line['exchange']['form'].startswith('packed 10 + 10 bit')

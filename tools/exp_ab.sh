@@ -6,7 +6,7 @@ for rep in $(seq 1 $N); do
     env $cfg python - <<PY
 import json, os, subprocess, sys
 ROOT = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
-out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '200', '--extras', '1' if os.environ.get('SEED') == 'none' else '0', '--cpu-perms', '0'],
+out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '200', '--extras', '1' if os.environ.get('SEED') == 'none' else '0', '--cpu-perms', '0', '--full'],
                      capture_output=True, text=True).stdout
 d = json.loads(out.strip().splitlines()[-1]); r = d['per_rank'][0]
 u = d.get('unseeded_device_stream', {})

@@ -8,7 +8,7 @@ for i in $(seq $rounds); do
   for cfg in "${cfgs[@]}"; do
     set -- $cfg
     if [ "$2" = "-" ]; then unset SAFE_HIP_XCHG_TAIL; else export SAFE_HIP_XCHG_TAIL=$2; fi
-    SAFE_HIP_XCHG_OVERLAP=$1 SAFE_BENCH_FORCE_DIST=1 python3 bench.py --steps $steps --warmup 5 --extras 0 --cpu-perms 0 2>/dev/null | python3 -c "
+    SAFE_HIP_XCHG_OVERLAP=$1 SAFE_BENCH_FORCE_DIST=1 python3 bench.py --steps $steps --warmup 5 --extras 0 --cpu-perms 0 --full 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

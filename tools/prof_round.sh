@@ -13,7 +13,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --steps 3 --warmup 1 --cpu-perms 0"
+CMD="python3 $ROOT/bench.py --steps 3 --warmup 1 --cpu-perms 0 --full"
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o r -- $CMD > $OUT/trace.log 2>&1
 python3 $ROOT/tools/rocpd_summary.py $OUT/trace/r_results.db > $OUT/kernel_stats.txt
 grep '^{' $OUT/trace.log | tail -1 > $OUT/bench_line.json
@@ -27,7 +27,7 @@ rm -rf $OUT/trace_h
 timeout 300 rocprofv3 --kernel-trace -d $OUT/tr -o r -- python3 $ROOT/tools/trace_step.py > $OUT/trace_step.log 2>&1
 python3 $ROOT/tools/rocpd_timeline.py $(ls $OUT/tr/*.db $OUT/tr/*/*.db 2>/dev/null | head -1) > $OUT/timeline.txt 2>&1
 rm -rf $OUT/tr
-CMD1="python3 $ROOT/bench.py --steps 1 --warmup 1 --cpu-perms 0"
+CMD1="python3 $ROOT/bench.py --steps 1 --warmup 1 --cpu-perms 0 --full"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o r -- $CMD1 > $OUT/fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/write -o r -- $CMD1 > $OUT/write.log 2>&1
 python3 $ROOT/tools/rocpd_counters.py $OUT/fetch/r_results.db > $OUT/pmc_traffic.txt

@@ -1,8 +1,8 @@
 #!/bin/bash
 # the round's bench lines: the default run (50 + 200 steps, extras) and three driver-style runs (5 + 20 steps, extras)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/${1:-r6lines}; mkdir -p $O
-python bench.py > $O/default.json 2> $O/default.err; echo "default rc=$?"
-for i in 1 2 3; do python bench.py --steps 20 --warmup 5 > $O/driver_$i.json 2> $O/driver_$i.err; echo "driver $i rc=$?"; done
+python bench.py --full > $O/default.json 2> $O/default.err; echo "default rc=$?"
+for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --full > $O/driver_$i.json 2> $O/driver_$i.err; echo "driver $i rc=$?"; done
 python - <<PY
 import json, glob
 for p in sorted(glob.glob("$O/*.json")):

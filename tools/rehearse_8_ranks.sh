@@ -9,7 +9,7 @@ export SAFE_BENCH_SHARE_DEVICE=1
 RANKS=${1:-8}; STEPS=${2:-10}
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/rehearse8; mkdir -p $O
 t0=$(date +%s.%N)
-taskset -c 0-15 python $R/bench.py --gpus $RANKS --steps $STEPS --warmup 2 --cpu-perms 0 2> $O/err.txt | tail -1 > $O/line.json
+taskset -c 0-15 python $R/bench.py --gpus $RANKS --steps $STEPS --warmup 2 --cpu-perms 0 --full 2> $O/err.txt | tail -1 > $O/line.json
 rc=$?
 t1=$(date +%s.%N)
 echo "exit $rc, wall $(echo "$t1 - $t0" | bc) s"

@@ -98,20 +98,20 @@ entry('k_mfma_planes01_rows', 'k_mfma_planes01_rows')
 entry('k_permute_cols', 'k_permute_cols')
 entry('k_counts_finalize', 'k_counts_finalize')
 out['_source'] = ('rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) -- python3 bench.py --steps 1 --warmup 1 '
-                  '--cpu-perms 0 (tools/prof_round.sh), round %s, MI355X; counter unit KiB; FETCH_SIZE x 2 for every kernel (gfx950 counts 128-byte '
+                  '--cpu-perms 0 --full (tools/prof_round.sh), round %s, MI355X; counter unit KiB; FETCH_SIZE x 2 for every kernel (gfx950 counts 128-byte '
                   'requests at 64 B: MI355X_MICROARCH.md, HBM section, re-measured for the access widths of these kernels in '
                   'profiles/pmc_calibration.json); Infinity-Cache hits are counted too: these are FABRIC bytes, an upper bound of the HBM bytes; '
                   'see profiles/%s_pmc_traffic.txt' % (rnd, rnd))
 out['_stamp'] = stamp
 json.dump(out, open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json'), 'w'), indent=1)
-hdr = ('# rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --steps 1 --warmup 1 --cpu-perms 0 '
+hdr = ('# rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --steps 1 --warmup 1 --cpu-perms 0 --full '
        '(tools/prof_round.sh; round %s, commit %s, MI355X); sums over launches, unit KiB\n' % (rnd, commit))
 open(os.path.join(ROOT, 'profiles', '%s_pmc_traffic.txt' % rnd), 'w').write(hdr + open(os.path.join(src_dir, 'pmc_traffic.txt')).read())
 
 # ---- kernel statistics
 ks = open(os.path.join(src_dir, 'kernel_stats.txt')).read()
 line = open(os.path.join(src_dir, 'bench_line.json')).read().strip()
-hdr = ('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --cpu-perms 0 (tools/prof_round.sh; round %s, commit %s, '
+hdr = ('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --cpu-perms 0 --full (tools/prof_round.sh; round %s, commit %s, '
        'MI355X): headline steps + extras (K1 distance, K4 hypergeometric at 20000 x 10000, matrix-core permutation kernel at one rank\'s '
        'configs[4] share)\n# bench line of the same run: %s ...\n' % (rnd, commit, line[:900]))
 open(os.path.join(ROOT, 'profiles', '%s_bench_kernel_stats.txt' % rnd), 'w').write(hdr + ks)
