@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 3
+#define SAFE_HIP_ABI_VERSION 4
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -150,6 +150,21 @@ int safe_euclidean_dense_dev(safe_ctx *ctx, const double *xy_dev, int64_t n, dou
  * sqrt(dx*dx + dy*dy) of the edge's end points, without the N x N detour. */
 int safe_edge_lengths(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t n_edges,
                       const int32_t *edge_u, const int32_t *edge_v, double *out_host);
+
+/* Spring-embedded layout: the nx.spring_layout(G, k=0.2, iterations=100, seed=...) of apply_network_layout
+ * (safepy/safe_io.py:288-308), before networkx's rescale_layout.  Restates networkx 3.4.2's
+ * _fruchterman_reingold (dtype SAFE_DTYPE_F64, what it runs below 500 nodes) or _sparse_fruchterman_reingold
+ * (SAFE_DTYPE_F32, 500 nodes and more) operation by operation, with each node's force summed over the other
+ * nodes in node order, so the coordinates equal networkx's bit for bit.  The adjacency is the CSR row_ptr [n+1],
+ * col [nnz] (strictly increasing columns per row, both directions of every edge; SAFE_E_VALUE otherwise) with
+ * weights weight [nnz] (NULL = 1; rounded to f32 in the F32 form); pos0_f64 [n,2] row-major is the initial
+ * seed.rand(n, 2) draw.  pos_out [n,2] receives the positions in the form's precision (f32 values widened
+ * exactly), *iterations_run how many iterations ran before norm(delta_pos) / n < threshold stopped them (that
+ * norm is summed in another order than numpy's, so the stop can differ only when the ratio lies within rounding
+ * of the threshold).  n <= 65536 (SAFE_E_UNSUPPORTED beyond).  Host pointers; synchronous. */
+int safe_layout_spring(safe_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const double *weight,
+                       int dtype, const double *pos0_f64, double k, int iterations, double threshold,
+                       double *pos_out, int *iterations_run);
 
 /* --------------------------------------------------------------- attributes ---- */
 /* self.node2attribute (safepy/safe_io.py:410): [n,m], f32 or f64, NaN = missing, with

@@ -251,6 +251,25 @@ class Context:
         check(lib.safe_edge_lengths(self.handle, _ptr(xy), xy.shape[0], eu.shape[0], _ptr(eu), _ptr(ev), _ptr(out)))
         return out
 
+    def layout_spring(self, row_ptr, col, weight, pos0, k, iterations, threshold, dtype):
+        """networkx's Fruchterman-Reingold iterations on the device (safe_layout_spring): CSR adjacency with
+        strictly increasing columns per row (weight None = 1), pos0 [n,2] f64, dtype np.float32 (the sparse
+        form networkx runs from 500 nodes) or np.float64.  Returns (positions [n,2] in dtype, iterations run)."""
+        pos0 = np.ascontiguousarray(pos0, dtype=np.float64)
+        n = pos0.shape[0]
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        cl = np.ascontiguousarray(col, dtype=np.int32)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        if rp.shape[0] != n + 1 or cl.shape[0] != rp[-1] or (w is not None and w.shape[0] != cl.shape[0]):
+            raise ValueError('layout_spring: CSR arrays do not match %d nodes' % n)
+        code = {np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.float64): _lib.DTYPE_F64}[np.dtype(dtype)]
+        out = np.empty((n, 2), dtype=np.float64)
+        ran = C.c_int(0)
+        check(lib.safe_layout_spring(self.handle, n, _ptr(rp), _ptr(cl) if cl.size else None,
+                                     _ptr(w) if w is not None and w.size else None, code, _ptr(pos0), float(k),
+                                     int(iterations), float(threshold), _ptr(out), C.byref(ran)))
+        return out.astype(dtype), ran.value
+
     def euclidean_dense(self, xy_dev_ptr, n, nr, mask_dev_ptr=None, dist_dev_ptr=None):
         check(lib.safe_euclidean_dense_dev(self.handle, C.c_void_p(xy_dev_ptr), int(n), float(nr),
                                            C.c_void_p(mask_dev_ptr) if mask_dev_ptr else None,

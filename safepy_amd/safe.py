@@ -333,10 +333,12 @@ class SAFE:
     def load_network(self, **kwargs):
         """safepy/safe.py:244-324 for in-memory graphs (`graph=` / `network_file=` a networkx.Graph
         with node attributes x, y -- and edge attribute 'length' for the default metric -- or a
-        `LayoutGraph`), `.gpickle` files and `.scatter` files (with their Euclidean pseudo-network,
-        safe.py:296-309, built on the device).  The reference's other file loaders and layouts
-        (safe_io.py:30-268, 288-308) are out of scope.  Sets self.graph, self.graph_euclidean (for
-        .scatter) and self.nodes (safe.py:311-324)."""
+        `LayoutGraph`), `.gpickle` files, edge lists (`.txt` / `.tsv`, optionally `.gz`: parsed, laid
+        out with the spring-embedded layout on the device from self.random_seed, edge lengths added;
+        safe.py:289-293, safe_io.py:30-121) and `.scatter` files (with their Euclidean pseudo-network,
+        safe.py:296-309, built on the device).  The MATLAB and Cytoscape loaders (safe_io.py:124-268)
+        are out of scope.  Sets self.graph, self.graph_euclidean (for .scatter) and self.nodes
+        (safe.py:311-324)."""
         import pandas as pd
         from . import safe_io
         if 'network_file' in kwargs and isinstance(kwargs['network_file'], str):
@@ -355,7 +357,7 @@ class SAFE:
             graph = self.path_to_network_file          # the configured network (INI networkfile / safe_data), safe.py:263-264
         if graph is None:
             raise NotImplementedError('safepy_amd.SAFE.load_network needs graph=<networkx.Graph | LayoutGraph> or '
-                                      'network_file=<.gpickle | .scatter>; the default safe-data network is not bundled')
+                                      'network_file=<.gpickle | .txt | .tsv | .scatter>; the default safe-data network is not bundled')
         if isinstance(graph, str):
             path = self.path_to_network_file
             assert os.path.exists(path), path
@@ -365,6 +367,9 @@ class SAFE:
                 logging.info('Loading network from %s' % path)
             if ext == '.gpickle':
                 graph = safe_io.load_network_from_gpickle(path, verbose=self.verbose)
+            elif ext in ('.txt', '.tsv'):
+                graph = safe_io.load_network_from_txt(path, node_key_attribute=self.node_key_attribute,
+                                                      seed=self.random_seed, verbose=self.verbose, device=self.device)
             elif ext == '.scatter':
                 graph = safe_io.load_network_from_scatter(path, node_key_attribute=self.node_key_attribute,
                                                           verbose=self.verbose)
@@ -372,8 +377,8 @@ class SAFE:
                     graph, self.neighborhood_radius, device=self.device,
                     as_networkx=kwargs.get('pseudo_network', 'networkx') == 'networkx')
             else:
-                raise NotImplementedError('network files of type %r need the reference\'s loaders and layouts, which are '
-                                          'out of scope for the hot-path build (supported: .gpickle, .scatter)' % ext)
+                raise NotImplementedError('network files of type %r need the reference\'s MATLAB / Cytoscape loaders, '
+                                          'which are out of scope (supported: .gpickle, .txt, .tsv, .scatter)' % ext)
         self.graph = graph
         self._invalidate_neighborhoods()
         if isinstance(graph, LayoutGraph):

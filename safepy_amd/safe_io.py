@@ -6,6 +6,11 @@ Host-side mirror of the pieces of `safepy/safe_io.py` that feed `define_neighbor
   calculate_edge_lengths      safe_io.py:311-333   per-edge kernel instead of the N x N pdist matrix,
                                                    the dense adjacency and the Python ndenumerate loop
   load_network_from_scatter   safe_io.py:271-285   (host parse, pandas like the reference)
+  load_network_from_txt       safe_io.py:30-121    edge lists (.txt / .tsv, optionally .gz): host parse with pandas
+                                                   like the reference, then the layout and the edge lengths
+  apply_network_layout        safe_io.py:288-308   'spring_embedded': networkx 3.4.2's spring_layout(k=0.2,
+                                                   iterations=100) on the device (layout.hip), coordinates equal
+                                                   to networkx's bit for bit
   euclidean_pseudo_network    safe.py:302-309      the `.scatter` pseudo-network: all-pairs distance +
                                                    threshold kernel, edges read back from the device CSR
   read_attributes             safe_io.py:336-430   parse with pandas like the reference; the alignment to
@@ -13,7 +18,7 @@ Host-side mirror of the pieces of `safepy/safe_io.py` that feed `define_neighbor
                                                    census of the log run on the device, and the aligned
                                                    matrix can stay resident for compute_pvalues
 
-Layouts (spring / Kamada-Kawai), Cytoscape / MATLAB loaders and plotting stay out of scope.
+The Kamada-Kawai layout, the Cytoscape / MATLAB loaders and plotting stay out of scope.
 There is no CPU fallback: every function that computes needs a HIP device.
 """
 import logging
@@ -81,6 +86,138 @@ def load_network_from_gpickle(filename, verbose=True):
     """safepy/safe_io.py:124-130."""
     with open(os.path.expanduser(filename), 'rb') as f:
         return pickle.load(f)
+
+
+def _random_state(seed):
+    """networkx's np_random_state conversion: None -> NumPy's global RandomState (so the caller's stream
+    advances as under the reference), an int -> RandomState(seed), a RandomState -> itself."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return np.random.RandomState(seed)
+    raise ValueError('%r cannot be used to create a numpy.random.RandomState instance' % (seed,))
+
+
+def _rescale_layout(pos):
+    """networkx rescale_layout(pos, scale=1) (drawing/layout.py), in the array's dtype, then `+ center`."""
+    pos -= pos.mean(axis=0)
+    lim = np.abs(pos).max()
+    if lim > 0:
+        pos *= 1 / lim
+    return pos + np.zeros(2)
+
+
+def _spring_layout(n, row_ptr, col, weight, seed, device):
+    """nx.spring_layout(G, k=0.2, iterations=100, seed=seed) for a graph of n nodes given as CSR (node order):
+    [n,2] f64.  networkx draws the initial positions only for n >= 2 and runs its f64 form below 500 nodes,
+    the f32 one from 500 (layout.py: spring_layout)."""
+    if n == 0:
+        return np.zeros((0, 2))
+    if n == 1:
+        return np.zeros((1, 2))
+    pos0 = _random_state(seed).rand(n, 2)
+    dtype = np.float32 if n >= 500 else np.float64
+    pos, _ = be.Context.default(device).layout_spring(row_ptr, col, weight, pos0, k=0.2, iterations=100,
+                                                      threshold=1e-4, dtype=dtype)
+    return _rescale_layout(np.ascontiguousarray(pos))
+
+
+def apply_network_layout(G, layout='kamada_kawai', seed=None, verbose=True, device=0):
+    """safepy/safe_io.py:288-308.  'spring_embedded' runs nx.spring_layout(G, k=0.2, iterations=100,
+    seed=seed) on the device: the adjacency is the graph's, in node order, with edge attribute 'weight'
+    (default 1); the initial positions are drawn with NumPy from `seed` (None = the global stream, an int,
+    or a RandomState).  Sets node attributes 'x' / 'y' (a `LayoutGraph`: its `.xy`) and returns G.
+    'kamada_kawai' is not implemented (no path of SAFE reaches it)."""
+    from .safe import LayoutGraph
+    if layout == 'kamada_kawai':
+        raise NotImplementedError("the Kamada-Kawai layout is not implemented; use layout='spring_embedded'")
+    if layout != 'spring_embedded':
+        raise ValueError("unknown layout %r (supported: 'spring_embedded')" % (layout,))
+    if verbose:
+        logging.info('Applying the spring-embedded network layout...')
+    import scipy.sparse as sps
+    if isinstance(G, LayoutGraph):
+        n = G.number_of_nodes()
+        w = np.ones(G.edge_u.size) if G.weight is None else G.weight
+        loops = G.edge_u == G.edge_v
+        rows = np.concatenate([G.edge_u, G.edge_v[~loops]])
+        cols = np.concatenate([G.edge_v, G.edge_u[~loops]])
+        A = sps.csr_array((np.concatenate([w, w[~loops]]), (rows, cols)), shape=(n, n))
+    else:
+        import networkx as nx
+        n = G.number_of_nodes()
+        A = nx.to_scipy_sparse_array(G, weight='weight', dtype=np.float64, format='csr') if n else None
+    if n >= 2:
+        A.sum_duplicates()
+        A.sort_indices()
+        pos = _spring_layout(n, A.indptr, A.indices, A.data, seed, device)
+    else:
+        pos = _spring_layout(n, None, None, None, seed, device)
+    if isinstance(G, LayoutGraph):
+        G.xy = np.ascontiguousarray(pos)
+        return G
+    nodes = list(G)
+    for name, values in (('x', pos[:, 0]), ('y', pos[:, 1])):
+        for node, v in zip(nodes, values):
+            G.nodes[node][name] = v
+    return G
+
+
+def _read_edge_list(filename):
+    """The parse of safe_io.py:47-107: (edge table with node_index1 / node_index2, node table in index order
+    with node_label1 / node_key1).  '.txt' has no header, '.tsv' one; 3 columns (key1, key2, weight; the
+    labels are the keys) or 5 (label1, key1, label2, key2, weight); '.gz' compressed either way."""
+    import gzip
+    import pandas as pd
+    from pathlib import Path
+    filename = os.path.expanduser(filename)
+    opener = gzip.open if Path(filename).suffix == '.gz' else open
+    with opener(filename, 'rt') as f:
+        num_cols = len(f.readline().split('\t'))
+    ext = Path(filename).suffixes[0]
+    if ext == '.txt':
+        kws = dict(header=None)
+    elif ext == '.tsv':
+        kws = dict(header=0, names=range(num_cols))
+    else:
+        raise ValueError(f'extension {ext} not supported')
+    if num_cols == 3:
+        data = pd.read_table(filename, sep='\t', dtype={0: str, 1: str, 2: float}, **kws)
+        data = data.rename(columns={0: 'node_key1', 1: 'node_key2', 2: 'edge_weight'})
+        data['node_label1'] = data['node_key1']
+        data['node_label2'] = data['node_key2']
+    elif num_cols == 5:
+        data = pd.read_table(filename, sep='\t', **kws)
+        data = data.rename(columns={0: 'node_label1', 1: 'node_key1', 2: 'node_label2', 3: 'node_key2', 4: 'edge_weight'})
+    else:
+        raise ValueError('Unknown network file format. 3 or 5 columns are expected.')
+    t1 = data[['node_label1', 'node_key1']]
+    t2 = data[['node_label2', 'node_key2']].rename(columns={'node_label2': 'node_label1', 'node_key2': 'node_key1'})
+    nodes = pd.concat([t1, t2], ignore_index=True).drop_duplicates().reset_index(drop=True)
+    by_label = nodes.reset_index().set_index('node_label1')
+    data['node_index1'] = by_label.loc[data['node_label1'], 'index'].values
+    data['node_index2'] = by_label.loc[data['node_label2'], 'index'].values
+    return data, nodes
+
+
+def load_network_from_txt(filename, layout='spring_embedded', node_key_attribute='key', seed=None, verbose=True,
+                          device=0):
+    """safepy/safe_io.py:30-121: a tab-separated edge list -> networkx graph with nodes 0..N-1 numbered in order
+    of first appearance, node attributes 'label' and `node_key_attribute`, unweighted edges (the file's weight
+    column is read but not attached, as in the reference), the layout (apply_network_layout: spring-embedded
+    on the device) and edge 'length' (calculate_edge_lengths)."""
+    import networkx as nx
+    data, nodes = _read_edge_list(filename)
+    G = nx.Graph()
+    n = len(nodes)
+    G.add_nodes_from(range(n))
+    nx.set_node_attributes(G, dict(zip(range(n), nodes['node_label1'].to_numpy())), 'label')
+    nx.set_node_attributes(G, dict(zip(range(n), nodes['node_key1'].to_numpy())), node_key_attribute)
+    G.add_edges_from(zip(data['node_index1'].tolist(), data['node_index2'].tolist()))
+    G = apply_network_layout(G, layout=layout, seed=seed, verbose=verbose, device=device)
+    return calculate_edge_lengths(G, verbose=verbose, device=device)
 
 
 def load_network_from_scatter(filename, node_key_attribute='key', verbose=True):
