@@ -473,9 +473,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_permtest_scatter(
 // member per 32 attributes instead of 32 adds.  The comparison with the observed sum and
 // the two permutation counters are bit-sliced too, so every instruction works on 32
 // attributes x 64 neighborhoods.  Exact integer arithmetic; no atomics; cost independent of
-// the attribute density.  A workgroup = 4 adjacent slices x one 64-attribute word group;
-// it keeps the word column T (8 B per node) and the current permutation (2 B per node,
-// double buffered) in LDS; one barrier per permutation.
+// the attribute density.  A workgroup = adjacent slices (one per wave) x one 64-attribute
+// word group; it keeps the word column T (8 B per node) in LDS.  The forms (bits_form):
+// k_permtest_bits_blk (blocked member lists, 8 (N + 1) < 65536), k_permtest_bits_pre (sixteen
+// waves, N up to 20 470) and k_permtest_bits_pre32 (half words, N up to 32 767).
 // --------------------------------------------------------------------------------------
 #define BT_LV 10               // levels of a neighborhood sum: max row count < 1024
 
@@ -519,56 +520,10 @@ __device__ __forceinline__ void vripple(uint32_t (&s)[LV], uint32_t t8) {
     }
 }
 
-// One pass over a lane's neighborhood: s = sum over members of T[cur[member]] (vertical).
-// cols2 holds 2*member id (the LDS byte offset into the u16 permutation row); with SCALED the
-// row itself holds 8*row id (the LDS byte offset into T, which starts at LDS address 0), so a
-// member costs two LDS reads and one address add.  `first` = the first block's ids (the same
-// for every permutation, loaded once per task); the ids of block b+1 are fetched as soon as
-// block b's look-ups have been issued.  The carry into the eights is rippled only when some
-// lane of the wave has one (sums rarely reach 8 on sparse annotations).
+// LDS views: one u16 (a permutation row entry), one word pair of T
 typedef const __attribute__((address_space(3))) unsigned short *lds_u16_ptr;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(3))) u32x2 *lds_u2_ptr;
-
-template <bool IDENT, bool SCALED>
-__device__ __forceinline__ void bits_accumulate(const uint16_t *__restrict__ cols2, int wdt, const uint32_t (&first)[8],
-                                                uint32_t cur_addr, uint32_t t_addr, uint32_t (&s0)[BT_LV],
-                                                uint32_t (&s1)[BT_LV]) {
-    // cur_addr / t_addr: absolute LDS byte addresses of the permutation row and of T; with
-    // SCALED the row entries already are absolute addresses of T rows
-#pragma unroll
-    for (int l = 0; l < BT_LV; ++l) s0[l] = s1[l] = 0;
-    uint32_t c[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) c[u] = first[u];
-    const uint16_t *pc = cols2 + 8 * 64;                                              // next block's ids
-    for (int t0 = 0; t0 < wdt; t0 += 8, pc += 8 * 64) {
-        uint32_t r[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (IDENT) r[u] = (c[u] << 2) + t_addr;                                   // 2*id -> address of T[id]
-            else {
-                const uint32_t v = *(lds_u16_ptr)(uintptr_t)(cur_addr + c[u]);
-                r[u] = SCALED ? v : (v << 3) + t_addr;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) c[u] = pc[u * 64];                                // (the array has a tail)
-        uint32_t x0[8], x1[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const u32x2 w = *(lds_u2_ptr)(uintptr_t)(r[u]);
-            x0[u] = w.x;
-            x1[u] = w.y;
-        }
-        const uint32_t e0 = vadd8(s0, x0);
-        const uint32_t e1 = vadd8(s1, x1);
-        if (__builtin_amdgcn_ballot_w64((e0 | e1) != 0)) {
-            vripple(s0, e0);
-            vripple(s1, e1);
-        }
-    }
-}
 
 // bit-sliced counter c[0..CL) += mask, with the carries out of the low three levels parked
 // in `pend` (a position wraps at most once per 8 increments) and rippled every 8th call
@@ -645,164 +600,8 @@ __device__ __forceinline__ void transpose32(uint32_t (&a)[32]) {
     }
 }
 
-// WV = waves (= adjacent slices of a task) per workgroup.  4 is the form of the small networks; 16 (round 6) is for networks whose
-// word column + permutation rows leave room for ONE workgroup per CU (N > 8190: 12 bytes per node): the sixteen waves share that
-// one copy and the SIMDs keep four waves each, where four-wave workgroups ran one wave per SIMD.
-template <int CL, bool SCALED, int WV = 4>
-__global__ __launch_bounds__(64 * WV) void k_permtest_bits(
-    int64_t n, int64_t n_perm, const uint16_t *__restrict__ cur16, int64_t stride16,
-    const int32_t *__restrict__ sell_row, const int64_t *__restrict__ slice_off,
-    const int32_t *__restrict__ slice_width, const uint16_t *__restrict__ sell_col2, int64_t n_slices,
-    const uint2 *__restrict__ bbits, int64_t n_tasks, const int4 *__restrict__ tasks, int64_t p_base, int64_t p_limit,
-    unsigned int *__restrict__ queue, int64_t mloc, unsigned int *__restrict__ gl_counts, int64_t n_pad,
-    double *__restrict__ ns_out) {
-    extern __shared__ unsigned int lds[];
-    const int64_t t_words = 2 * ((n + 2) & ~int64_t(1));               // T: (n+1) uint2 at LDS address 0, 16-B padded
-    uint2 *T = reinterpret_cast<uint2 *>(lds);
-    unsigned short *CUR = reinterpret_cast<unsigned short *>(lds + t_words);     // [2][stride16]
-    unsigned int *slot_box = lds + t_words + stride16;                  // after the two u16 buffers
-    // absolute LDS byte addresses (the dynamic segment need not start at 0)
-    const uint32_t t_addr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) unsigned int *)lds);
-    const uint32_t cur_bytes0 = t_addr + static_cast<uint32_t>(t_words * 4);
-    const uint32_t cur_bytes1 = cur_bytes0 + static_cast<uint32_t>(stride16 * 2);
-    const uint32_t t_addr2 = t_addr | (t_addr << 16);                    // both u16 halves
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int vec_per_row = static_cast<int>(stride16 / 8);              // uint4 (8 x u16) per table row
-    constexpr int NT = 64 * WV;
-
-    // a table row (8 x u16 per vector) scaled to T byte offsets
-    auto scale_row = [=](uint4 v) {
-        if (SCALED) {                         // 8 * row + address of T, per u16 half (no carries: < 65536)
-            v.x = ((v.x << 3) & 0xFFF8FFF8u) + t_addr2;
-            v.y = ((v.y << 3) & 0xFFF8FFF8u) + t_addr2;
-            v.z = ((v.z << 3) & 0xFFF8FFF8u) + t_addr2;
-            v.w = ((v.w << 3) & 0xFFF8FFF8u) + t_addr2;
-        }
-        return v;
-    };
-
-    for (;;) {
-        if (threadIdx.x == 0) *slot_box = atomicAdd(queue, 1u);
-        __syncthreads();
-        const int64_t slot = *slot_box;
-        __syncthreads();
-        if (slot >= n_tasks) break;
-        const int4 task = tasks[slot];
-        const int wg = task.x, sg = task.y;
-        // this task's permutations (task ranges are relative to the launch's chunk)
-        const int64_t p_begin = p_base + task.z;
-        const int64_t p_end = p_base + task.w < p_limit ? p_base + task.w : p_limit;
-        if (p_end <= p_begin) continue;                                   // a launch shorter than the task grid's span
-
-        load_word_column<NT>(T, bbits + static_cast<int64_t>(wg) * (n + 1), n);
-        if (p_end > p_begin)
-            for (int v = threadIdx.x; v < vec_per_row; v += NT)
-                reinterpret_cast<uint4_alias *>(CUR)[v] =
-                    scale_row(reinterpret_cast<const uint4_alias *>(cur16 + p_begin * stride16)[v]);
-
-        const int64_t s = static_cast<int64_t>(sg) * WV + wave;
-        const bool active = s < n_slices;
-        const int32_t row = active ? sell_row[s * 64 + lane] : -1;
-        const uint16_t *cols2 = sell_col2 + (active ? slice_off[s] : 0) + lane;
-        const int wdt = active ? slice_width[s] : 0;
-        uint32_t first[8];                                               // 2 * member id of the first block
-#pragma unroll
-        for (int u = 0; u < 8; ++u) first[u] = cols2[u * 64];
-        __syncthreads();
-
-        uint32_t o0[BT_LV], o1[BT_LV];                                   // observed sums (safe.py:496-499)
-        bits_accumulate<true, SCALED>(cols2, wdt, first, 0u, t_addr, o0, o1);
-
-        uint32_t g0[CL], g1[CL], l0[CL], l1[CL];                          // #(S_p > S_obs), #(S_p < S_obs)
-        uint32_t gp0 = 0, gp1 = 0, lp0 = 0, lp1 = 0;
-#pragma unroll
-        for (int l = 0; l < CL; ++l) g0[l] = g1[l] = l0[l] = l1[l] = 0;
-
-        for (int64_t p = p_begin; p < p_end; ++p) {
-            const int64_t rel = p - p_begin;
-            const uint32_t cur_base = (rel & 1) ? cur_bytes1 : cur_bytes0;
-            // next permutation's row: global -> registers now, registers -> LDS after the compute
-            uint4 nxt = make_uint4(0, 0, 0, 0);
-            const bool fetch = (p + 1 < p_end) && (static_cast<int>(threadIdx.x) < vec_per_row);
-            if (fetch) nxt = reinterpret_cast<const uint4_alias *>(cur16 + (p + 1) * stride16)[threadIdx.x];
-
-            uint32_t s0[BT_LV], s1[BT_LV];
-            bits_accumulate<false, SCALED>(cols2, wdt, first, cur_base, t_addr, s0, s1);
-
-            // bit-sliced compare as two borrow chains, least significant level first:
-            // lt = borrow out of (S - O), gt = borrow out of (O - S); per level
-            // borrow' = (s != o) ? subtrahend bit : borrow   -- one v_bitop3_b32 each
-            uint32_t gt0 = 0, gt1 = 0, lt0 = 0, lt1 = 0;
-#pragma unroll
-            for (int l = 0; l < BT_LV; ++l) {
-                // f(s, o, b) = (s != o) ? o : b  -> 0x8E ;  (s != o) ? s : b -> 0xB2
-                lt0 = __builtin_amdgcn_bitop3_b32(s0[l], o0[l], lt0, 0x8E);
-                gt0 = __builtin_amdgcn_bitop3_b32(s0[l], o0[l], gt0, 0xB2);
-                lt1 = __builtin_amdgcn_bitop3_b32(s1[l], o1[l], lt1, 0x8E);
-                gt1 = __builtin_amdgcn_bitop3_b32(s1[l], o1[l], gt1, 0xB2);
-            }
-            vcount<CL>(g0, gp0, gt0);
-            vcount<CL>(g1, gp1, gt1);
-            vcount<CL>(l0, lp0, lt0);
-            vcount<CL>(l1, lp1, lt1);
-            if ((rel & 7) == 7) {
-                vflush<CL>(g0, gp0);
-                vflush<CL>(g1, gp1);
-                vflush<CL>(l0, lp0);
-                vflush<CL>(l1, lp1);
-            }
-
-            if (vec_per_row > NT) {                                      // rows longer than one vector per thread: strided copy
-                for (int v = threadIdx.x + NT; v < vec_per_row; v += NT)
-                    if (p + 1 < p_end)
-                        reinterpret_cast<uint4_alias *>(CUR + ((rel + 1) & 1) * stride16)[v] =
-                            scale_row(reinterpret_cast<const uint4_alias *>(cur16 + (p + 1) * stride16)[v]);
-            }
-            if (fetch) reinterpret_cast<uint4_alias *>(CUR + ((rel + 1) & 1) * stride16)[threadIdx.x] = scale_row(nxt);
-            __syncthreads();
-        }
-        vflush<CL>(g0, gp0);
-        vflush<CL>(g1, gp1);
-        vflush<CL>(l0, lp0);
-        vflush<CL>(l1, lp1);
-
-        // ---- epilogue: un-slice the counters of this permutation range (bit-matrix transpose:
-        //      rows 0..15 = #greater levels, rows 16..31 = #less levels -> word b = less<<16 | greater
-        //      of attribute b) and add them to the totals, laid out [attribute][SELL position] so
-        //      that the 64 lanes of a wave update one contiguous 256-byte run
-        const bool live = row >= 0;
-        const int64_t spos = s * 64 + lane;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            uint32_t m[32];
-#pragma unroll
-            for (int l = 0; l < 16; ++l) {
-                m[l] = l < CL ? (half ? g1[l < CL ? l : 0] : g0[l < CL ? l : 0]) : 0u;
-                m[16 + l] = l < CL ? (half ? l1[l < CL ? l : 0] : l0[l < CL ? l : 0]) : 0u;
-            }
-            transpose32(m);
-#pragma unroll
-            for (int bit = 0; bit < 32; ++bit) {
-                const int64_t jc = static_cast<int64_t>(wg) * 64 + half * 32 + bit;
-                if (jc < mloc && active && m[bit]) atomicAdd(&gl_counts[jc * n_pad + spos], m[bit]);
-            }
-        }
-        if (ns_out && p_begin == 0 && live) {
-            const int64_t obase = static_cast<int64_t>(row) * mloc;
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-                for (int bit = 0; bit < 32; ++bit) {
-                    const int64_t jc = static_cast<int64_t>(wg) * 64 + half * 32 + bit;
-                    if (jc >= mloc) break;
-                    ns_out[obase + jc] = static_cast<double>(half ? vextract<BT_LV>(o1, bit) : vextract<BT_LV>(o0, bit));
-                }
-        }
-        __syncthreads();
-    }
-}
-
 // --------------------------------------------------------------------------------------
-// K5 bit-sliced form with PRE-PERMUTED member lists (the default when 8*(N+1) < 65536).
+// K5 bit-sliced forms with PRE-PERMUTED member lists (every form of bits_form).
 // For every permutation p of a span a small kernel writes ids_p[e] = 8 * cur_p[member e]
 // for all SELL entries (u16: the LDS byte offset of the member's word pair).  The main
 // kernel then streams those lists from L2/MALL -- coalesced 128-byte loads, one block ahead
@@ -812,9 +611,10 @@ __global__ __launch_bounds__(64 * WV) void k_permtest_bits(
 __global__ __launch_bounds__(256) void k_permute_cols(const uint16_t *__restrict__ cur16, int64_t stride16,
                                                       const uint16_t *__restrict__ sell_col2, int64_t entries,
                                                       int64_t entries_pad, int64_t p0, int64_t count, uint32_t pad_off,
-                                                      uint16_t *__restrict__ out, int diag_banks = 0, int sh = 3) {
+                                                      uint16_t *__restrict__ out, int sh) {
     // sh: ids are written as id << sh -- 3: the LDS byte offset of the member's word pair (8 (N + 1) < 65536); 1: 2 * id for the
-    // larger networks of k_permtest_bits_pre<.., 16, 2>, whose byte offsets do not fit 16 bits (the kernel shifts once more)
+    // larger networks of k_permtest_bits_pre, whose byte offsets do not fit 16 bits (the kernel shifts once more); 0: the ids
+    // themselves (k_permtest_bits_pre32)
     // one permutation row (<= 16 KB) staged in LDS per block, 4096 member entries per block: the
     // random 2-byte reads hit LDS instead of L2 sectors
     extern __shared__ uint16_t row[];
@@ -833,16 +633,8 @@ __global__ __launch_bounds__(256) void k_permute_cols(const uint16_t *__restrict
         uint4 o;
         if (e + 8 <= entries) {
             const uint4 c = *reinterpret_cast<const uint4 *>(sell_col2 + e);
-            uint32_t a0 = row[(c.x & 0xFFFFu) >> 1], a1 = row[c.x >> 17], a2 = row[(c.y & 0xFFFFu) >> 1], a3 = row[c.y >> 17];
-            uint32_t a4 = row[(c.z & 0xFFFFu) >> 1], a5 = row[c.z >> 17], a6 = row[(c.w & 0xFFFFu) >> 1], a7 = row[c.w >> 17];
-            if (diag_banks) {
-                // diagnostic (WRONG results): the low five bits of every member's row become the lane's -- in each gather instruction
-                // the 32 lanes of a half-wave then hit 32 different bank pairs: what would conflict-free gathers be worth?
-                const uint32_t lb = static_cast<uint32_t>((e >> 3) & 31);
-                auto fix = [&](uint32_t a) { return (a & ~31u) | lb; };
-                a0 = fix(a0), a1 = fix(a1), a2 = fix(a2), a3 = fix(a3);
-                a4 = fix(a4), a5 = fix(a5), a6 = fix(a6), a7 = fix(a7);
-            }
+            const uint32_t a0 = row[(c.x & 0xFFFFu) >> 1], a1 = row[c.x >> 17], a2 = row[(c.y & 0xFFFFu) >> 1], a3 = row[c.y >> 17];
+            const uint32_t a4 = row[(c.z & 0xFFFFu) >> 1], a5 = row[c.z >> 17], a6 = row[(c.w & 0xFFFFu) >> 1], a7 = row[c.w >> 17];
             o.x = (a0 << sh) | (a1 << (16 + sh));
             o.y = (a2 << sh) | (a3 << (16 + sh));
             o.z = (a4 << sh) | (a5 << (16 + sh));
@@ -860,9 +652,8 @@ __global__ __launch_bounds__(256) void k_permute_cols(const uint16_t *__restrict
     }
 }
 
-// ids: u16 LDS byte offsets (relative to T) of the members, SELL layout; SHIFT = 2 turns the
-// resident 2*id list into 8*id (observed pass), 0 takes pre-permuted offsets as they are
-template <int SHIFT, int LV = BT_LV>
+// ids: u16 LDS byte offsets (relative to T) of the members, SELL layout, shifted by SHIFT: 2 turns a 2*id list into 8*id
+template <int SHIFT, int LV>
 __device__ __forceinline__ void bits_accumulate_ids(const uint16_t *__restrict__ ids, int wdt, uint32_t t_addr,
                                                     uint32_t (&s0)[LV], uint32_t (&s1)[LV]) {
 #pragma unroll
@@ -893,13 +684,13 @@ __device__ __forceinline__ void bits_accumulate_ids(const uint16_t *__restrict__
     }
 }
 
-// WV = 16, PSHIFT = 2 (round 6): networks of 8191 .. 20 470 nodes -- T alone (8 bytes per node) fills most of a CU's LDS, so ONE
-// workgroup of sixteen waves shares it (four waves per SIMD as in the small form), and the permuted lists hold 2 * id (the byte
-// offset 8 * id no longer fits 16 bits; the shift that is left costs one operation per member).
-// LVS = levels of the vertical sums: BT_LV (neighborhoods below 1024 members); the sixteen-wave form also exists with eleven (below
-// 2048: a few hub neighborhoods no longer send a whole call to the scatter or matrix-core kernels).
-template <int CL, int WV = 4, int PSHIFT = 0, int LVS = BT_LV>
-__global__ __launch_bounds__(64 * WV, WV == 4 ? (CL <= 8 ? 4 : 3) : 1) void k_permtest_bits_pre(
+// Round 6: networks of 8191 .. 20 470 nodes -- T alone (8 bytes per node) fills most of a CU's LDS, so ONE workgroup of sixteen
+// waves shares it (four waves per SIMD as in the small form), and the permuted lists hold 2 * id (the byte offset 8 * id no longer
+// fits 16 bits; the shift that is left costs one operation per member).  A task counts at most 255 permutations: eight counter
+// levels.  LVS = levels of the vertical sums: BT_LV (neighborhoods below 1024 members) or eleven (below 2048: a few hub
+// neighborhoods no longer send a whole call to the scatter or matrix-core kernels; any network size).
+template <int LVS>
+__global__ __launch_bounds__(1024, 1) void k_permtest_bits_pre(
     int64_t n, const uint16_t *__restrict__ ids_p, int64_t entries_pad, const int32_t *__restrict__ sell_row,
     const int64_t *__restrict__ slice_off, const int32_t *__restrict__ slice_width,
     const uint16_t *__restrict__ sell_col2, int64_t n_slices, const uint2 *__restrict__ bbits, int64_t n_tasks,
@@ -911,6 +702,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? (CL <= 8 ? 4 : 3) : 1) void k_pe
     unsigned int *slot_box = lds + t_words;
     const uint32_t t_addr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) unsigned int *)lds);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    constexpr int CL = 8, WV = 16;                                       // counter levels, waves (= adjacent slices of a task)
 
     for (;;) {
         if (threadIdx.x == 0) *slot_box = atomicAdd(queue, 1u);
@@ -933,7 +725,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? (CL <= 8 ? 4 : 3) : 1) void k_pe
         __syncthreads();                                                  // T is complete; waves are independent from here
 
         uint32_t o0[LVS], o1[LVS];                                   // observed sums (safe.py:496-499)
-        bits_accumulate_ids<2, LVS>(sell_col2 + my_off, wdt, t_addr, o0, o1);
+        bits_accumulate_ids<2, LVS>(sell_col2 + my_off, wdt, t_addr, o0, o1);          // 2 * id -> 8 * id
 
         uint32_t g0[CL], g1[CL], l0[CL], l1[CL];                          // #(S_p > S_obs), #(S_p < S_obs)
         uint32_t gp0 = 0, gp1 = 0, lp0 = 0, lp1 = 0;
@@ -942,7 +734,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? (CL <= 8 ? 4 : 3) : 1) void k_pe
 
         for (int64_t p = p_begin; p < p_end; ++p) {
             uint32_t s0[LVS], s1[LVS];
-            bits_accumulate_ids<PSHIFT, LVS>(ids_p + (p - p_base) * entries_pad + my_off, wdt, t_addr, s0, s1);
+            bits_accumulate_ids<2, LVS>(ids_p + (p - p_base) * entries_pad + my_off, wdt, t_addr, s0, s1);     // 2 * id -> 8 * id
             uint32_t gt0 = 0, gt1 = 0, lt0 = 0, lt1 = 0;
 #pragma unroll
             for (int l = 0; l < LVS; ++l) {
@@ -1410,27 +1202,22 @@ __device__ __forceinline__ void blk_sum(const u32x4 *__restrict__ ids, int lane,
     if (b < nblk) blk_add8<LV, SHIFT, GATHER, RIP2>(ca, pc, s0, s1);
 }
 
-// one wave, one task: observed sums, then every permutation of the task's range; counters come back in g / l
-// (levels above CL stay zero), the observed sums in oo (levels above LV zero)
-// CLT <= CL: levels the task really counts with (a task of at most 2^CLT - 1 permutations); OBSMEM: the observed sums are
-// re-read from memory (L1 / L2 resident: 2 * LV coalesced 256-byte loads per permutation) in the compare step instead of
-// being held in 2 * LV registers for the whole task -- the wide classes trade them for a fifth wave per SIMD.
-template <int LV, int CLT, int DBG, bool OBSMEM>
+// one wave, one task: observed sums, then every permutation of the task's range; counters come back in g / l, zeroed by the
+// caller (a task of at most 255 permutations: CL = 8 levels)
+template <int LV, int CL, int DBG>
 __device__ __forceinline__ void blk_task_core(const uint32_t *__restrict__ obs, const u32x4 *__restrict__ perm_ids, int64_t perm_stride,
-                                              int lane, int nblk, int np, uint32_t (&g0)[CLT], uint32_t (&g1)[CLT], uint32_t (&l0)[CLT],
-                                              uint32_t (&l1)[CLT]) {
+                                              int lane, int nblk, int np, uint32_t (&g0)[CL], uint32_t (&g1)[CL], uint32_t (&l0)[CL],
+                                              uint32_t (&l1)[CL]) {
     constexpr int GATHER = (DBG & 1) ? 0 : (DBG & 8) ? 2 : (DBG & 16) ? 3 : 1;
     // observed sums of this (word group, slice): computed once per call by k_bits_observed, vertical like the permuted sums
-    uint32_t o0[OBSMEM ? 1 : LV], o1[OBSMEM ? 1 : LV];
-    if (!OBSMEM) {
+    uint32_t o0[LV], o1[LV];
 #pragma unroll
-        for (int l = 0; l < LV; ++l) {
-            o0[OBSMEM ? 0 : l] = obs[l * 64 + lane];
-            o1[OBSMEM ? 0 : l] = obs[(BT_LV + l) * 64 + lane];
-        }
+    for (int l = 0; l < LV; ++l) {
+        o0[l] = obs[l * 64 + lane];
+        o1[l] = obs[(BT_LV + l) * 64 + lane];
     }
     uint32_t gp0 = 0, gp1 = 0, lp0 = 0, lp1 = 0;
-    constexpr bool STREAM = (DBG & 256) == 0;                         // (the five-waves build passes bit 8: it has no registers 112-119)
+    constexpr bool STREAM = (DBG & 256) == 0;                         // (the plain build passes bit 8: it has no registers 112-119)
     // STREAM (the default): the task's blocks -- permutation after permutation -- are ONE stream through two id quads that are
     // refilled IN PLACE with the block after next (blk_add8s), so a permutation's first blocks were requested while the previous
     // permutation was still being added.  !STREAM (SAFE_HIP_BITS_DBG=256, the form of rounds 2-4, same results): every permutation
@@ -1474,23 +1261,21 @@ __device__ __forceinline__ void blk_task_core(const uint32_t *__restrict__ obs, 
         uint32_t gt0 = 0, gt1 = 0, lt0 = 0, lt1 = 0;
 #pragma unroll
         for (int l = 0; l < LV; ++l) {
-            const uint32_t a0 = OBSMEM ? obs[l * 64 + lane] : o0[OBSMEM ? 0 : l];
-            const uint32_t a1 = OBSMEM ? obs[(BT_LV + l) * 64 + lane] : o1[OBSMEM ? 0 : l];
             // f(s, o, b) = (s != o) ? o : b  -> 0x8E ;  (s != o) ? s : b -> 0xB2
-            lt0 = __builtin_amdgcn_bitop3_b32(s0[l], a0, lt0, 0x8E);
-            gt0 = __builtin_amdgcn_bitop3_b32(s0[l], a0, gt0, 0xB2);
-            lt1 = __builtin_amdgcn_bitop3_b32(s1[l], a1, lt1, 0x8E);
-            gt1 = __builtin_amdgcn_bitop3_b32(s1[l], a1, gt1, 0xB2);
+            lt0 = __builtin_amdgcn_bitop3_b32(s0[l], o0[l], lt0, 0x8E);
+            gt0 = __builtin_amdgcn_bitop3_b32(s0[l], o0[l], gt0, 0xB2);
+            lt1 = __builtin_amdgcn_bitop3_b32(s1[l], o1[l], lt1, 0x8E);
+            gt1 = __builtin_amdgcn_bitop3_b32(s1[l], o1[l], gt1, 0xB2);
         }
-        vcount<CLT>(g0, gp0, gt0);
-        vcount<CLT>(g1, gp1, gt1);
-        vcount<CLT>(l0, lp0, lt0);
-        vcount<CLT>(l1, lp1, lt1);
+        vcount<CL>(g0, gp0, gt0);
+        vcount<CL>(g1, gp1, gt1);
+        vcount<CL>(l0, lp0, lt0);
+        vcount<CL>(l1, lp1, lt1);
         if ((p & 7) == 7) {
-            vflush<CLT>(g0, gp0);
-            vflush<CLT>(g1, gp1);
-            vflush<CLT>(l0, lp0);
-            vflush<CLT>(l1, lp1);
+            vflush<CL>(g0, gp0);
+            vflush<CL>(g1, gp1);
+            vflush<CL>(l0, lp0);
+            vflush<CL>(l1, lp1);
         }
     };
     if (STREAM) {
@@ -1572,34 +1357,22 @@ __device__ __forceinline__ void blk_task_core(const uint32_t *__restrict__ obs, 
             settle(p, s0, s1);
         }
     }
-    vflush<CLT>(g0, gp0);
-    vflush<CLT>(g1, gp1);
-    vflush<CLT>(l0, lp0);
-    vflush<CLT>(l1, lp1);
+    vflush<CL>(g0, gp0);
+    vflush<CL>(g1, gp1);
+    vflush<CL>(l0, lp0);
+    vflush<CL>(l1, lp1);
     // (the two fetches past the stream's end: landed before anything else is asked of the vector-memory counter)
     if (STREAM) asm volatile("s_waitcnt vmcnt(0)" : : : "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119");
 }
 #pragma clang diagnostic pop
 
-template <int LV, int CL, int DBG, int CLT = CL, bool OBSMEM = false>
+// (a call level of its own: inlined in one piece with its caller, the body gets another register allocation in
+// k_permtest_bits_blk -- more spills)
+template <int LV, int CL, int DBG>
 __device__ __forceinline__ void blk_task(const uint32_t *__restrict__ obs, const u32x4 *__restrict__ perm_ids, int64_t perm_stride,
-                                         int lane, int nblk, int np, uint32_t (&G0)[CL], uint32_t (&G1)[CL], uint32_t (&L0)[CL],
-                                         uint32_t (&L1)[CL]) {
-    if constexpr (CLT == CL) {
-        blk_task_core<LV, CL, DBG, OBSMEM>(obs, perm_ids, perm_stride, lane, nblk, np, G0, G1, L0, L1);      // (zeroed by the caller)
-    } else {
-        uint32_t g0[CLT], g1[CLT], l0[CLT], l1[CLT];
-#pragma unroll
-        for (int l = 0; l < CLT; ++l) g0[l] = g1[l] = l0[l] = l1[l] = 0;
-        blk_task_core<LV, CLT, DBG, OBSMEM>(obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-#pragma unroll
-        for (int l = 0; l < CLT; ++l) {
-            G0[l] = g0[l];
-            G1[l] = g1[l];
-            L0[l] = l0[l];
-            L1[l] = l1[l];
-        }
-    }
+                                         int lane, int nblk, int np, uint32_t (&g0)[CL], uint32_t (&g1)[CL], uint32_t (&l0)[CL],
+                                         uint32_t (&l1)[CL]) {
+    blk_task_core<LV, CL, DBG>(obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
 }
 
 // Observed neighborhood sums of every (word group, slice), once per call (safe.py:496-499): vertical counters
@@ -1704,10 +1477,7 @@ constexpr int BLK_TRACE_MAX = 1 << 17;
 __device__ unsigned long long g_blk_trace[BLK_TRACE_MAX * 8];
 __device__ unsigned int g_blk_trace_n;
 
-// WPS = waves per SIMD the kernel is built for: 4 (128 registers; every class keeps its observed sums in registers and counts
-// with CL levels) or 5 (96 registers: the classes of more than 56 members count with five levels -- their tasks hold at most
-// 31 permutations -- and re-read the observed sums; five workgroups per CU when T fits five times).
-template <int CL, int DBG, int WPS>
+template <int CL, int DBG>
 __device__ __forceinline__ void bits_blk_body(
 
     int64_t n, const uint16_t *__restrict__ ids_p, int64_t entries_pad, const int32_t *__restrict__ sell_row,
@@ -1773,20 +1543,17 @@ __device__ __forceinline__ void bits_blk_body(
         uint32_t g0[CL], g1[CL], l0[CL], l1[CL];                          // #(S_p > S_obs), #(S_p < S_obs)
 #pragma unroll
         for (int l = 0; l < CL; ++l) g0[l] = g1[l] = l0[l] = l1[l] = 0;
-        constexpr int CLW = WPS > 4 ? 5 : CL;                             // counter levels of the wide classes
-        constexpr int CLN = WPS > 4 ? 6 : CL;                             // ... and of the narrow ones (tasks of at most 63 permutations)
-        constexpr bool OM = WPS > 4;                                      // the wide classes' observed sums come from memory
         // a neighborhood of wdt members cannot sum past wdt: levels by slice width (wave-uniform branch)
         if (np <= 0) {
         } else if (DBG & 1024) {       // (diagnostic, WRONG results: every class counts with four levels -- what bounding the levels by the attributes' carrier counts could gain at most)
-            blk_task<4, CL, DBG, CLN>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+            blk_task<4, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
         } else if (DBG & 2048) {       // (the same with six levels)
-            blk_task<6, CL, DBG, CLN>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-        } else if (wdt <= 8) blk_task<4, CL, DBG, CLN>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-        else if (wdt <= 56) blk_task<6, CL, DBG, CLN>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-        else if (wdt <= 248) blk_task<8, CL, DBG, CLW, OM>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-        else if (wdt <= 504) blk_task<9, CL, DBG, CLW, OM>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
-        else blk_task<BT_LV, CL, DBG, CLW, OM>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+            blk_task<6, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+        } else if (wdt <= 8) blk_task<4, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+        else if (wdt <= 56) blk_task<6, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+        else if (wdt <= 248) blk_task<8, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+        else if (wdt <= 504) blk_task<9, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
+        else blk_task<BT_LV, CL, DBG>(my_obs, perm_ids, perm_stride, lane, nblk, np, g0, g1, l0, l1);
 
         if (DBG & 128) {
             asm volatile("" : "+v"(g0[0]), "+v"(l0[0]));                  // (the counters exist: the counting is over)
@@ -1816,7 +1583,7 @@ __device__ __forceinline__ void bits_blk_body(
 // The two builds of the body.  The default one holds the id stream's two quads in registers 112-119 behind the compiler's back
 // (blk_add8s): it is compiled with 112 registers (the attribute counts in pairs on gfx90a and later: 56), and the clobber lists of the
 // stream's asm statements make the allocation 120.
-// The plain one (five waves per SIMD, SAFE_HIP_BITS_DBG bit 8) runs without the stream.
+// The plain one (SAFE_HIP_BITS_DBG bit 8, and a library whose build could not check those registers) runs without the stream.
 template <int CL, int DBG>
 __global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_vgpr(56))) void k_permtest_bits_blk(
 
@@ -1825,17 +1592,17 @@ __global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_vgpr(56))) void k
     const uint32_t *__restrict__ obs, int64_t n_slices, const uint2 *__restrict__ bbits, BitsQueues qs,
     const int4 *__restrict__ tasks, int64_t p_base, int64_t p_limit, unsigned int *__restrict__ queue, int64_t mloc,
     unsigned int *__restrict__ gl_counts, int64_t n_pad) {
-    bits_blk_body<CL, DBG & ~256, 4>(n, ids_p, entries_pad, sell_row, slice_off, slice_width, obs, n_slices, bbits, qs, tasks, p_base, p_limit, queue, mloc, gl_counts, n_pad);
+    bits_blk_body<CL, DBG & ~256>(n, ids_p, entries_pad, sell_row, slice_off, slice_width, obs, n_slices, bbits, qs, tasks, p_base, p_limit, queue, mloc, gl_counts, n_pad);
 }
-template <int CL, int DBG, int WPS>
-__global__ __launch_bounds__(256, WPS) void k_permtest_bits_blk_plain(
+template <int CL, int DBG>
+__global__ __launch_bounds__(256, 4) void k_permtest_bits_blk_plain(
 
     int64_t n, const uint16_t *__restrict__ ids_p, int64_t entries_pad, const int32_t *__restrict__ sell_row,
     const int64_t *__restrict__ slice_off, const int32_t *__restrict__ slice_width,
     const uint32_t *__restrict__ obs, int64_t n_slices, const uint2 *__restrict__ bbits, BitsQueues qs,
     const int4 *__restrict__ tasks, int64_t p_base, int64_t p_limit, unsigned int *__restrict__ queue, int64_t mloc,
     unsigned int *__restrict__ gl_counts, int64_t n_pad) {
-    bits_blk_body<CL, DBG | 256, WPS>(n, ids_p, entries_pad, sell_row, slice_off, slice_width, obs, n_slices, bbits, qs, tasks, p_base, p_limit, queue, mloc, gl_counts, n_pad);
+    bits_blk_body<CL, DBG | 256>(n, ids_p, entries_pad, sell_row, slice_off, slice_width, obs, n_slices, bbits, qs, tasks, p_base, p_limit, queue, mloc, gl_counts, n_pad);
 }
 
 // counts -> everything compute_pvalues derives from them (safe.py:528-554, 468-472).
@@ -2677,27 +2444,152 @@ static int launch_scatter(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     return SAFE_OK;
 }
 
+// LDS of a word column plus the permutation rows, the layout of the row-in-LDS kernel of rounds 1-5 (removed): it still sets the
+// number of workgroup slots per CU that the bit-sliced forms' task sizes are cut for (launch_bits)
 static size_t bits_lds_bytes(int64_t n, int64_t stride16) {
     const size_t t_words = 2 * ((static_cast<size_t>(n) + 2) & ~size_t(1));
     return (t_words + static_cast<size_t>(stride16) + 4) * sizeof(unsigned int);
 }
-
-// the pre-permuted form with sixteen-wave workgroups (k_permtest_bits_pre<8, 16, 2>): networks beyond the 16-bit LDS offsets whose
-// word column still fits a CU's LDS (8 bytes per node: N <= 20 470) and whose doubled ids fit 16 bits
+// the word column T of the full-word forms (8 bytes per node) and of the half-word form (4 bytes per node), with the queue slot
 static size_t bits_pre_lds_bytes(int64_t n) { return (2 * ((static_cast<size_t>(n) + 2) & ~size_t(1)) + 4) * sizeof(unsigned int); }
-// ... or with neighborhoods of 1024 .. 2047 members at any size (eleven levels of the vertical sums, which only this form has)
-static bool bits_pre_wide_applicable(int64_t n, int64_t max_count) {
-    const char *pe = getenv("SAFE_HIP_BITS_PRE");
-    return ((n + 1) * 8 >= 65536 || max_count >= (1 << BT_LV)) && max_count < (2 << BT_LV) && n < 32768 &&
-           bits_pre_lds_bytes(n) <= 160 * 1024 && !(pe && !strcmp(pe, "0"));
+static size_t bits_half_lds_bytes(int64_t n) { return (((static_cast<size_t>(n) + 4) & ~size_t(3)) + 4) * sizeof(unsigned int); }
+
+// The bit-sliced forms, chosen here and nowhere else:
+//   BITS_BLK    k_permtest_bits_blk: four waves per workgroup, blocked member lists of 8 * id (the LDS byte offsets fit 16 bits:
+//               8 (N + 1) < 65536), neighborhoods below 1024 members;
+//   BITS_PRE16  k_permtest_bits_pre: sixteen waves share one word column (N <= 20 470), lists of 2 * id; also the form of
+//               neighborhoods of 1024 .. 2047 members on the small networks;
+//   BITS_PRE32  k_permtest_bits_pre32: the same over 32-attribute half words (4 bytes per node), lists of ids, up to N = 32 767
+//               (the resident 2 * id lists are u16: sell_col2 exists below N = 32 768 only).
+// levels: of the vertical sums, eleven when a neighborhood has 1024 .. 2047 members (the PRE forms only), else ten.
+enum BitsKind { BITS_NONE = 0, BITS_BLK, BITS_PRE16, BITS_PRE32 };
+struct BitsForm {
+    BitsKind kind;
+    int levels;
+};
+static BitsForm bits_form(int64_t n, int64_t max_count, bool has_col2, size_t lds_limit) {
+    if (!has_col2 || n >= 32768 || max_count >= (2 << BT_LV)) return {BITS_NONE, 0};
+    const int levels = max_count >= (1 << BT_LV) ? BT_LV + 1 : BT_LV;
+    if ((n + 1) * 8 < 65536 && levels == BT_LV) return {BITS_BLK, levels};
+    if (bits_pre_lds_bytes(n) <= lds_limit) return {BITS_PRE16, levels};
+    if (bits_half_lds_bytes(n) <= lds_limit) return {BITS_PRE32, levels};
+    return {BITS_NONE, 0};
 }
 
-// ... and the half-word form (k_permtest_bits_pre32): the networks whose full word column no longer fits, up to the 2 * id lists' 32 767
-static size_t bits_half_lds_bytes(int64_t n) { return (((static_cast<size_t>(n) + 4) & ~size_t(3)) + 4) * sizeof(unsigned int); }
-static bool bits_pre_half_applicable(int64_t n, int64_t max_count) {
-    const char *pe = getenv("SAFE_HIP_BITS_PRE");
-    return bits_pre_lds_bytes(n) > 160 * 1024 && bits_half_lds_bytes(n) <= 160 * 1024 && n < 32768 && max_count < (2 << BT_LV) &&
-           !(pe && !strcmp(pe, "0"));
+// The 8-member blocks of the widest slice of each group of `wv` adjacent slices (at least one): what a permutation costs the wave
+// group of a task
+static std::vector<int64_t> slice_group_blocks(const std::vector<int32_t> &slice_width, int64_t n_slices, int wv) {
+    std::vector<int64_t> blocks(ceil_div(n_slices, wv), 0);
+    for (int64_t s = 0; s < n_slices; ++s) blocks[s / wv] = std::max<int64_t>(blocks[s / wv], slice_width[s] / 8);
+    for (int64_t &b : blocks) b = std::max<int64_t>(b, 1);
+    return blocks;
+}
+
+// Tasks (column unit w in [w_lo, w_hi), slice group g, permutations [p0, p1) of a launch of `span`) cut to about equal cost:
+// tasks_per_unit tasks per column unit, each at least 256 block-permutations and 16 permutations and at most ppt_cap
+// permutations; stably sorted heaviest first for the kernels' dynamic queues.  half_words: a unit is one half (32 columns) of a
+// word group, and a last half without columns has no task.
+static std::vector<int4> cost_sorted_tasks(const std::vector<int64_t> &sg_blocks, int64_t span, int64_t w_lo, int64_t w_hi,
+                                           int64_t tasks_per_unit, int64_t ppt_cap, bool half_words, int64_t mloc) {
+    int64_t blocks_per_perm = 0;
+    for (const int64_t bl : sg_blocks) blocks_per_perm += bl;
+    const int64_t target = std::max<int64_t>(256, blocks_per_perm * span / tasks_per_unit);      // block-permutations per task
+    struct TaskCost { int4 t; int64_t cost; };
+    std::vector<TaskCost> tc;
+    for (size_t g = 0; g < sg_blocks.size(); ++g) {
+        const int64_t bl = sg_blocks[g];
+        int64_t ppt = std::min<int64_t>(std::min<int64_t>(span, ppt_cap), std::max<int64_t>(16, target / bl));
+        const int64_t chunks = ceil_div(span, ppt);
+        ppt = ceil_div(span, chunks);
+        for (int64_t c = 0; c < chunks; ++c) {
+            const int64_t p0 = c * ppt, p1 = std::min<int64_t>(span, p0 + ppt);
+            for (int64_t w = w_lo; w < w_hi; ++w)
+                if (!half_words || (w >> 1) * 64 + (w & 1) * 32 < mloc)
+                    tc.push_back({make_int4(static_cast<int>(w), static_cast<int>(g), static_cast<int>(p0), static_cast<int>(p1)),
+                                  bl * (p1 - p0)});
+        }
+    }
+    std::stable_sort(tc.begin(), tc.end(), [](const TaskCost &a, const TaskCost &b) { return a.cost > b.cost; });
+    std::vector<int4> out(tc.size());
+    for (size_t i = 0; i < tc.size(); ++i) out[i] = tc[i].t;
+    return out;
+}
+
+// The blocked kernel's per-XCD queues: the tasks of one (slice group, permutation range) -- one per word group, adjacent after the
+// stable sort -- go to one queue, (group, range) pairs dealt round-robin in heaviest-first order.  Returns the list queue by queue.
+static std::vector<int4> split_xcd_queues(const std::vector<int4> &list, BitsQueues &bq) {
+    std::vector<std::vector<int4>> q(8);
+    int64_t pair = -1;
+    int last_g = -1, last_p0 = -1;
+    for (const int4 &t : list) {
+        if (t.y != last_g || t.z != last_p0) {
+            ++pair;
+            last_g = t.y;
+            last_p0 = t.z;
+        }
+        q[pair & 7].push_back(t);
+    }
+    std::vector<int4> out;
+    out.reserve(list.size());
+    bq.off[0] = 0;
+    for (int k = 0; k < 8; ++k) {
+        out.insert(out.end(), q[k].begin(), q[k].end());
+        bq.off[k + 1] = static_cast<int>(out.size());
+    }
+    return out;
+}
+
+// The task lists of one launch plan of the bit-sliced forms (all but plan.key): one list per DISTINCT stage-launch size over all
+// n_units column units (word groups, or their halves), then -- the exchange tail -- one per column chunk of xc_wpc word groups
+// over the tail's permutations (starts[n_major] .. the end).  slots: workgroup slots of the chip; one task per slot and unit set.
+// One list per launch size: the stream's stages are 32, 96, 128 ... and short last ones, and a list cut for 128 permutations
+// leaves a 32-permutation launch with half-empty and empty tasks (each still reloads T): a 32-permutation launch took 207 us,
+// 6.5 us per permutation against 3.2 in the long launches.
+static void plan_bits_tasks(BitsTaskPlan &plan, const std::vector<int32_t> &slice_width, int64_t n_slices, int wv, int64_t slots,
+                            const std::vector<int64_t> &starts, int64_t n_units, int64_t mloc, bool half_words, int64_t n_major,
+                            int64_t n_tail, int64_t xc_wpc) {
+    // queue depth per workgroup slot: every task reloads T and flushes its counters (64 wave-atomics + two 32 x 32 bit transposes
+    // per wave: 11 % of the kernel at depth 2, tools/bits_ablate.py dbg=2), so as few tasks as fill the chip once -- depth 1 vs 2:
+    // seeded step 3.52 -> 3.41 ms, 10 000 unseeded permutations 25.8 -> 24.4 ms (tools/exp_ab.sh; round 3 had chosen 2 while the
+    // host stream bound the step)
+    constexpr int64_t tasks_per_slot = 1;
+    // SHORT launches (the ramp at the head of the stream, the stage behind the last draw: nothing else runs beside them) cost
+    // ~150 us + 2 us per permutation alone on the chip (10 / 16 / 32 / 64 / 128 permutations: 160 / 200 / 186 / 266 / 413 us,
+    // tools/r6/short_launch.sh): their heaviest slice group's tasks are the critical path (16 permutations x 40-49 blocks x
+    // 420-700 clocks) and every wave-task carries 13 + 30 + 30-60 kclk of table load, start-up and counter flush.  Cutting
+    // their tasks finer (4 or 8 permutations per task at least) shortened a lone 16-permutation launch to 170 / 145 us but the
+    // seeded step got LONGER (3.16-3.34 -> 3.30-3.38 ms: twice the wave-tasks, each with its fixed part) -- not kept.
+    const std::vector<int64_t> sg_blocks = slice_group_blocks(slice_width, n_slices, wv);
+    // (a column chunk of the tail has fewer word groups: its tasks are cut so that ITS launch fills the slots once too -- with the
+    // stage launches' task size a chunk of the last stage had 288 tasks for 960 slots and lasted as long as a whole stage)
+    auto one_list = [&](int64_t span, int64_t w_lo, int64_t w_hi, int64_t list_span) {
+        BitsQueues bq{};
+        const int64_t tpu = std::max<int64_t>(1, ceil_div(tasks_per_slot * slots, std::max<int64_t>(1, w_hi - w_lo)));
+        // (a task counts at most 255 permutations: eight counter levels)
+        const std::vector<int4> one =
+            w_hi > w_lo ? split_xcd_queues(cost_sorted_tasks(sg_blocks, span, w_lo, w_hi, tpu, 255, half_words, mloc), bq)
+                        : std::vector<int4>();
+        plan.list_queues.push_back(bq);
+        plan.list_span.push_back(list_span);
+        plan.list_first.push_back(static_cast<int64_t>(plan.tasks.size()));
+        plan.list_count.push_back(static_cast<int64_t>(one.size()));
+        plan.tasks.insert(plan.tasks.end(), one.begin(), one.end());
+    };
+    plan = BitsTaskPlan{};
+    plan.launch_list.assign(std::max<int64_t>(n_major + n_tail, 1), 0);
+    for (int64_t k = 0; k < n_tail; ++k) {             // one list per column chunk (possibly empty on a rank with fewer columns)
+        const int64_t w_lo = std::min<int64_t>(k * xc_wpc, n_units);
+        const int64_t w_hi = k + 1 == n_tail ? n_units : std::min<int64_t>((k + 1) * xc_wpc, n_units);
+        plan.launch_list[n_major + k] = static_cast<int64_t>(plan.list_span.size());
+        one_list(starts.back() - starts[n_major], w_lo, w_hi, -1 - k);          // (a list span that never matches a stage's)
+    }
+    for (int64_t c = 0; c < n_major; ++c) {
+        const int64_t span_c = starts[c + 1] - starts[c];
+        size_t k = 0;
+        while (k < plan.list_span.size() && plan.list_span[k] != span_c) ++k;
+        if (k == plan.list_span.size()) one_list(span_c, 0, n_units, span_c);
+        plan.launch_list[c] = static_cast<int64_t>(k);
+    }
 }
 
 enum PermPath { PATH_GATHER = 0, PATH_SCATTER = 1, PATH_BITS = 2 };
@@ -2711,9 +2603,7 @@ static PermPath choose_path(const safe_ctx *ctx, const safe_nbr *nbr, safe_attr 
     if (z || n_perm < 1 || n_perm > 65535) return PATH_GATHER;
     if (safe_attr_prepare(attr) != SAFE_OK || attr->n_other != 0) return PATH_GATHER;
     if (nbr->n >= 65535) return PATH_GATHER;
-    const bool bits_ok = nbr->sell_col2 != nullptr &&
-                         ((nbr->max_count < (1 << BT_LV) && bits_lds_bytes(nbr->n, (nbr->n + 8) / 8 * 8) <= 160 * 1024) ||
-                          bits_pre_wide_applicable(nbr->n, nbr->max_count) || bits_pre_half_applicable(nbr->n, nbr->max_count));
+    const bool bits_ok = bits_form(nbr->n, nbr->max_count, nbr->sell_col2 != nullptr, 160 * 1024).kind != BITS_NONE;
     const bool scatter_ok = nbr->max_count < SC_EPOCH && scatter_lds_bytes(nbr->n) <= 160 * 1024;
     if (force && !strcmp(force, "bits") && bits_ok) return PATH_BITS;
     if (force && !strcmp(force, "scatter") && scatter_ok) return attr_build_support(attr) == SAFE_OK ? PATH_SCATTER : PATH_GATHER;
@@ -2788,6 +2678,13 @@ static void blk_trace_dump(int n_launch) {
 static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1,
                        const PermOut &out) {
     const int64_t n = nbr->n, mloc = col1 - col0, n_wg = ceil_div(mloc, 64), P = perms->count;
+    const BitsForm form = bits_form(n, nbr->max_count, nbr->sell_col2 != nullptr, 160 * 1024);
+    SAFE_REQUIRE(form.kind != BITS_NONE, "launch_bits: no bit-sliced form for %lld nodes with neighborhoods of up to %lld members",
+                 static_cast<long long>(n), static_cast<long long>(nbr->max_count));
+    const bool blk = form.kind == BITS_BLK, half = form.kind == BITS_PRE32;
+    const int wv = blk ? 4 : 16;                         // waves (= adjacent slices of a task) per workgroup
+    const int id_shift = blk ? 3 : half ? 0 : 1;         // the permuted member lists hold id << id_shift
+    const int64_t n_wgt = half ? 2 * n_wg : n_wg;        // column units of the tasks: word groups, or their halves
     safe_trace("launch_bits: enter");
     uint2 *d_bits = nullptr;
     SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
@@ -2795,14 +2692,13 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     safe_trace("launch_bits: prep launched");
     // The permutations are consumed in launches of `span` permutations so that the host's draw
     // stream for the next span overlaps this span's kernel.  Inside a launch, tasks = (word
-    // group, group of 4 adjacent slices, permutation sub-range), sized to about equal cost
+    // group, group of adjacent slices, permutation sub-range), sized to about equal cost
     // with several per workgroup slot, heaviest first for the dynamic queue.
-    int64_t span = 1;
-    // launches follow the stream's stages, one launch per stage (a launch over m stages after the start-up has fewer tails and
+    // Launches follow the stream's stages, one launch per stage (a launch over m stages after the start-up has fewer tails and
     // less per-task fixed cost -- kernel time per 1000 permutations 4.06 -> 3.94 / 3.89 ms at m = 2 / 3 in round 3 -- but the
     // step gets LONGER, 5.2 -> 5.5 / 5.8 ms: a merged launch waits for its last stage's draws)
-    const int merge = 1;                               // (round 6, kernel-bound step: 2 / 3 stages per launch 3.13 -> 3.33-3.42 / 3.65 ms, kernels busy 2.54 -> 2.8)
-    const std::vector<int64_t> starts = perm_launch_starts(perms, &span, merge);
+    int64_t span = 1;
+    const std::vector<int64_t> starts = perm_launch_starts(perms, &span);
     // Exchange overlap of the sharded step (safe_set_exchange_chunks): the LAST permutations -- the tail -- run as one launch per
     // COLUMN chunk over all of the tail instead of one launch per stage over all columns.  A chunk's counters are then final when
     // its launch ends, and its all-gather overlaps the launches of the later chunks (xc_events; sharding.ChunkedExchange).
@@ -2821,18 +2717,11 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     // It hides at most the exchange of K - 1 chunks (~0.9 ms of 1.2 ms at 8 ranks) and never paid for itself at this size, so the
     // tail is OFF by default (SAFE_HIP_XCHG_TAIL=<fraction of the permutations> switches it on; 1e-9 = the last stage); the
     // chunked exchange itself (sharding.ChunkedExchange) then runs its collectives right after the kernels, chunk by chunk
-    // beside the derivation of the previous chunk's matrices.
-    const bool pre_w = bits_pre_wide_applicable(n, nbr->max_count);     // the sixteen-wave pre-permuted form (k_permtest_bits_pre<8, 16, 2, ..>)
-    const bool pre_h = bits_pre_half_applicable(n, nbr->max_count);     // ... with 32-attribute half words (k_permtest_bits_pre32): tasks per HALF word group
-    const int64_t n_wgt = pre_h ? 2 * n_wg : n_wg;
-    const bool blk_expected = [&] {
-        const char *pe = getenv("SAFE_HIP_BITS_PRE"), *ke = getenv("SAFE_HIP_BITS_KERNEL");
-        return !pre_w && !pre_h && (n + 1) * 8 < 65536 && !(pe && !strcmp(pe, "0")) && nbr->sell_col2b != nullptr && !(ke && !strcmp(ke, "pre"));
-    }();
+    // beside the derivation of the previous chunk's matrices.  Only the blocked form has a tail.
     int64_t n_major = static_cast<int64_t>(starts.size()) - 1, p_split = P, xc_wpc = 0;
     int xc_k = 0;
     ctx->xc_made = 0;
-    if (ctx->xc_want >= 2 && ctx->xc_cols >= 64 && ctx->xc_cols % 64 == 0 && blk_expected && n_major >= 3 &&
+    if (ctx->xc_want >= 2 && ctx->xc_cols >= 64 && ctx->xc_cols % 64 == 0 && blk && n_major >= 3 &&
         static_cast<int64_t>(std::min<int>(ctx->xc_want, safe_ctx::XC_MAX)) * ctx->xc_cols >= mloc) {
         double frac = 0.0;                              // (off unless asked for: see the measurements above)
         if (const char *e = getenv("SAFE_HIP_XCHG_TAIL")) frac = std::min(1.0, std::max(0.0, atof(e)));
@@ -2846,126 +2735,15 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
         }
     }
     const int64_t n_tail = xc_k, tail_span = P - p_split;
-    const size_t lds_bytes = bits_lds_bytes(n, perms->stride16);
-    const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_bytes)));
-    const int64_t slots = static_cast<int64_t>(ctx->num_cu) * per_cu;
-    // waves (= adjacent slices of a task) per workgroup: 4; 16 when the word column and the permutation rows leave room for one
-    // workgroup per CU only (k_permtest_bits<.., 16>: N > 8190, where neither the pre-permuted nor the blocked lists apply)
-    const int wv = (n + 1) * 8 < 65536 && !pre_w && !pre_h ? 4 : 16;
-    const int64_t n_sg = ceil_div(nbr->n_slices, wv);
-    std::vector<int64_t> sg_blocks(n_sg, 0);
-    int64_t blocks_per_perm = 0;
-    for (int64_t s = 0; s < nbr->n_slices; ++s) sg_blocks[s / wv] = std::max<int64_t>(sg_blocks[s / wv], nbr->h_slice_width[s] / 8);
-    for (int64_t g = 0; g < n_sg; ++g) blocks_per_perm += std::max<int64_t>(sg_blocks[g], 1);
-    // five waves per SIMD (k_permtest_bits_blk<.., 5>) when T fits five times into a CU's LDS; its wide classes count with five
-    // levels, so their tasks hold at most 31 permutations
-    const size_t lds_T = (2 * ((static_cast<size_t>(n) + 2) & ~size_t(1)) + 4) * sizeof(unsigned int);
-    (void)lds_T;
-    const bool occ5 = false;                             // (five waves per SIMD: built and measured in round 3, slower; the kernel form stays for reference)
-    int tasks_per_slot = 1;                              // queue depth per workgroup slot: every task reloads T and flushes its counters (64 wave-atomics
-                                                         // + two 32 x 32 bit transposes per wave: 11 % of the kernel at depth 2, tools/bits_ablate.py dbg=2), so
-                                                         // as few tasks as fill the chip once -- depth 1 vs 2: seeded step 3.52 -> 3.41 ms, 10 000 unseeded
-                                                         // permutations 25.8 -> 24.4 ms (tools/exp_ab.sh; round 3 had chosen 2 while the host stream bound the step)
-    const int64_t tasks_per_wg = std::max<int64_t>(1, ceil_div(tasks_per_slot * slots, n_wgt));
-    // One task list per DISTINCT launch size: the stream's stages are 32, 96, 128 ... and short last ones, and a list cut for 128
-    // permutations leaves a 32-permutation launch with half-empty and empty tasks (each still reloads T): a 32-permutation launch
-    // took 207 us, 6.5 us per permutation against 3.2 in the long launches.
-    const int64_t min_ppt = 16, target_min = 256;        // floors of a task's size: permutations, block-permutations
-    const int64_t max_ppt = 0;                           // (a cap on a task's permutations -- long launches with short tasks -- measured no gain)
-    // SHORT launches (the ramp at the head of the stream, the stage behind the last draw: nothing else runs beside them) cost
-    // ~150 us + 2 us per permutation alone on the chip (10 / 16 / 32 / 64 / 128 permutations: 160 / 200 / 186 / 266 / 413 us,
-    // tools/r6/short_launch.sh): their heaviest slice group's tasks are the critical path (16 permutations x 40-49 blocks x
-    // 420-700 clocks) and every wave-task carries 13 + 30 + 30-60 kclk of table load, start-up and counter flush.  Cutting
-    // their tasks finer (4 or 8 permutations per task at least) shortened a lone 16-permutation launch to 170 / 145 us but the
-    // seeded step got LONGER (3.16-3.34 -> 3.30-3.38 ms: twice the wave-tasks, each with its fixed part) -- not kept.
-    struct TaskCost { int4 t; int64_t cost; };
-    auto build_tasks = [&](int64_t span_c, int64_t w_lo = 0, int64_t w_hi = -1) {
-        if (w_hi < 0) w_hi = n_wgt;
-        // (a column chunk of the tail has fewer word groups: its tasks are cut so that ITS launch fills the slots once too -- with
-        // the stage launches' task size a chunk of the last stage had 288 tasks for 960 slots and lasted as long as a whole stage)
-        const int64_t tpw = w_hi - w_lo == n_wgt ? tasks_per_wg : std::max<int64_t>(1, ceil_div(tasks_per_slot * slots, std::max<int64_t>(1, w_hi - w_lo)));
-        const int64_t target = std::max<int64_t>(target_min, blocks_per_perm * span_c / tpw);    // block-permutations per task
-        std::vector<TaskCost> tc;
-        for (int64_t g = 0; g < n_sg; ++g) {
-            const int64_t bl = std::max<int64_t>(sg_blocks[g], 1);
-            int64_t ppt_cap = !occ5 ? 255 : (bl * 8 > 56 ? 31 : 63);            // counter levels of the task's class: 8, or 5 / 6
-            if (max_ppt > 0) ppt_cap = std::min<int64_t>(ppt_cap, max_ppt);
-            int64_t ppt = std::min<int64_t>(std::min<int64_t>(span_c, ppt_cap), std::max<int64_t>(min_ppt, target / bl));
-            const int64_t chunks = ceil_div(span_c, ppt);
-            ppt = ceil_div(span_c, chunks);
-            for (int64_t c = 0; c < chunks; ++c) {
-                const int64_t p0 = c * ppt, p1 = std::min<int64_t>(span_c, p0 + ppt);
-                for (int64_t w = w_lo; w < w_hi; ++w)
-                    if (!pre_h || (w >> 1) * 64 + (w & 1) * 32 < mloc)      // (a last half word without columns has no task)
-                    tc.push_back({make_int4(static_cast<int>(w), static_cast<int>(g), static_cast<int>(p0), static_cast<int>(p1)),
-                                  bl * (p1 - p0)});
-            }
-        }
-        std::stable_sort(tc.begin(), tc.end(), [](const TaskCost &a, const TaskCost &b) { return a.cost > b.cost; });
-        std::vector<int4> out(tc.size());
-        for (size_t i = 0; i < tc.size(); ++i) out[i] = tc[i].t;
-        return out;
-    };
-    // the blocked kernel's per-XCD queues: the tasks of one (slice group, permutation range) -- one per word group, adjacent
-    // after the stable sort -- go to one queue, (group, range) pairs dealt round-robin in heaviest-first order
-    const bool xcd_queues = true;
-    auto split_queues = [&](const std::vector<int4> &list, int (&off)[9]) {
-        std::vector<std::vector<int4>> q(8);
-        int64_t pair = -1;
-        int last_g = -1, last_p0 = -1;
-        for (size_t i = 0; i < list.size(); ++i) {
-            if (!xcd_queues) pair = static_cast<int64_t>(i);
-            else if (list[i].y != last_g || list[i].z != last_p0) {
-                ++pair;
-                last_g = list[i].y;
-                last_p0 = list[i].z;
-            }
-            q[pair & 7].push_back(list[i]);
-        }
-        std::vector<int4> out;
-        out.reserve(list.size());
-        off[0] = 0;
-        for (int k = 0; k < 8; ++k) {
-            out.insert(out.end(), q[k].begin(), q[k].end());
-            off[k + 1] = static_cast<int>(out.size());
-        }
-        return out;
-    };
     const int64_t n_launch = n_major + n_tail;           // stage launches over all columns, then the tail's column chunks
+    const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / bits_lds_bytes(n, perms->stride16))));
+    const int64_t slots = static_cast<int64_t>(ctx->num_cu) * per_cu;
     // the lists only depend on the handle and on these numbers: the handle keeps the last plan
-    std::vector<int64_t> plan_key = {n_wg, slots, tasks_per_slot, occ5 ? 1 : 0, xcd_queues ? 1 : 0, min_ppt, target_min, n_launch, max_ppt,
-                                     n_major, n_tail, xc_wpc, wv, pre_h ? 1 : 0, mloc};
+    std::vector<int64_t> plan_key = {n_wg, slots, n_launch, n_major, n_tail, xc_wpc, wv, half ? 1 : 0, mloc};
     plan_key.insert(plan_key.end(), starts.begin(), starts.end());
     BitsTaskPlan &plan = nbr->bits_plan;
     if (plan.key != plan_key) {
-        plan = BitsTaskPlan{};
-        plan.launch_list.assign(std::max<int64_t>(n_launch, 1), 0);
-        for (int64_t k = 0; k < n_tail; ++k) {             // one list per column chunk (possibly empty on a rank with fewer columns)
-            const int64_t w_lo = std::min<int64_t>(k * xc_wpc, n_wg), w_hi = k + 1 == n_tail ? n_wg : std::min<int64_t>((k + 1) * xc_wpc, n_wg);
-            BitsQueues bq{};
-            const std::vector<int4> one = w_hi > w_lo ? split_queues(build_tasks(tail_span, w_lo, w_hi), bq.off) : std::vector<int4>();
-            plan.launch_list[n_major + k] = static_cast<int64_t>(plan.list_span.size());
-            plan.list_queues.push_back(bq);
-            plan.list_span.push_back(-1 - k);                // (never matches a stage's span)
-            plan.list_first.push_back(static_cast<int64_t>(plan.tasks.size()));
-            plan.list_count.push_back(static_cast<int64_t>(one.size()));
-            plan.tasks.insert(plan.tasks.end(), one.begin(), one.end());
-        }
-        for (int64_t c = 0; c < n_major; ++c) {
-            const int64_t span_c = starts[c + 1] - starts[c];
-            size_t k = 0;
-            while (k < plan.list_span.size() && plan.list_span[k] != span_c) ++k;
-            if (k == plan.list_span.size()) {
-                BitsQueues bq{};
-                const std::vector<int4> one = split_queues(build_tasks(span_c), bq.off);
-                plan.list_queues.push_back(bq);
-                plan.list_span.push_back(span_c);
-                plan.list_first.push_back(static_cast<int64_t>(plan.tasks.size()));
-                plan.list_count.push_back(static_cast<int64_t>(one.size()));
-                plan.tasks.insert(plan.tasks.end(), one.begin(), one.end());
-            }
-            plan.launch_list[c] = static_cast<int64_t>(k);
-        }
+        plan_bits_tasks(plan, nbr->h_slice_width, nbr->n_slices, wv, slots, starts, n_wgt, mloc, half, n_major, n_tail, xc_wpc);
         // (plan.key is set LAST, below: an allocation or a wait that fails on the way leaves no key, and the next call rebuilds
         // the plan instead of uploading from a missing or stale pinned copy)
         const size_t bytes = plan.tasks.size() * sizeof(int4);
@@ -3003,37 +2781,25 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     SAFE_HIP_CHECK(hipMemsetAsync(d_gl, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), ctx->stream));
     safe_trace("launch_bits: buffers ready");
     int4 *const d_task_lists = d_tasks;
-    const bool wide = P >= 1024;
-    const bool narrow = true;                         // a task counts at most 255 permutations (ppt above): 8 counter levels do
-    const bool scaled = (n + 1) * 8 < 65536;
-    const char *pre_env = getenv("SAFE_HIP_BITS_PRE");
-    const bool pre = (scaled && !(pre_env && !strcmp(pre_env, "0"))) || pre_w || pre_h;      // pre-permuted member lists
-    const int id_shift = pre_h ? 0 : pre_w ? 1 : 3;                       // the lists hold id << id_shift
     const int64_t entries_pad = (nbr->sell_entries + 1024 + 255) / 256 * 256;    // tail: the kernels fetch ids two blocks (2 x 512) ahead
     // consecutive launches run on NS = 2 streams: a launch is as long as its longest task, the next one fills the slots its short
     // tasks leave.  Three or four launches in flight measured WORSE (unseeded 1000-permutation step 3.01 -> 3.19 -> 3.43 ms,
     // round 4): the later launches' workgroups take slots from the long tasks of the first
     constexpr int NS = 2;
-    const int diag_banks = 0;                          // (k_permute_cols' diagnostic address form: conflict-free gathers measured no gain, round 5)
-    uint16_t *d_ids[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (pre)
-        for (int b = 0; b < NS; ++b)
-            SAFE_TRY(ctx_scratch(ctx, b < 2 ? 4 + b : 10 + b, static_cast<size_t>(span) * entries_pad * sizeof(uint16_t),
-                                 reinterpret_cast<void **>(&d_ids[b])));
+    uint16_t *d_ids[NS] = {nullptr, nullptr};
+    for (int b = 0; b < NS; ++b)
+        SAFE_TRY(ctx_scratch(ctx, 4 + b, static_cast<size_t>(span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids[b])));
     uint16_t *d_ids_tail = nullptr;                   // the tail's permuted member lists: built once, read by every column chunk's launch
     if (n_tail)
         SAFE_TRY(ctx_scratch(ctx, 18, static_cast<size_t>(tail_span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids_tail)));
-    hipStream_t kstreams[4] = {ctx->stream, ctx->side_stream, ctx->more_streams[0], ctx->more_streams[1]};
-    const size_t lds_pre = (2 * ((static_cast<size_t>(n) + 2) & ~size_t(1)) + 4) * sizeof(unsigned int);
-    // blocked member lists (k_permtest_bits_blk) unless SAFE_HIP_BITS_KERNEL=pre; SAFE_HIP_BITS_DBG=<mask>: diagnostic builds
-    const char *kern_env = getenv("SAFE_HIP_BITS_KERNEL");
-    const bool blk = pre && !pre_w && !pre_h && nbr->sell_col2b != nullptr && !(kern_env && !strcmp(kern_env, "pre"));
+    hipStream_t kstreams[NS] = {ctx->stream, ctx->side_stream};
+    const size_t lds_T = half ? bits_half_lds_bytes(n) : bits_pre_lds_bytes(n);     // the kernel's word column and queue slot
     // SAFE_HIP_BITS_DBG: variants of the blocked kernel.  32 / 128 / 256 / 384 / 512 / 640 give correct results (A/B: one-stage carry
     // ripple, ..., 256 = no id stream = no hidden registers, 512 = no half-block gather pipeline); 1 / 2 / 4 / 8 / 16 / 64 skip work
     // (WRONG results) and exist only in a library built with `make DIAG=1`.  Anything else is refused.
     int dbg = 0;
     if (const char *e = getenv("SAFE_HIP_BITS_DBG")) dbg = atoi(e);
-    if (dbg == 0 && !occ5 && !safe_hidden_regs_checked()) {
+    if (dbg == 0 && !safe_hidden_regs_checked()) {
         // the build could not disassemble the stream kernels (no llvm-objdump): nothing vouches for the registers they hide from
         // the compiler, so the form without them runs (the same counts, ~5 % slower)
         static bool told = false;
@@ -3043,11 +2809,11 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     }
     const void *blk_fn = nullptr;
     switch (dbg) {
-        case 0: blk_fn = occ5 ? reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 0, 5>) : reinterpret_cast<const void *>(k_permtest_bits_blk<8, 0>); break;
+        case 0: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 0>); break;
         case 32: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 32>); break;
         case 128: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 128>); break;
-        case 256: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 256, 4>); break;
-        case 384: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 384, 4>); break;
+        case 256: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 256>); break;
+        case 384: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 384>); break;
         case 512: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 512>); break;
         case 640: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 640>); break;
 #ifdef SAFE_HIP_DIAG
@@ -3066,50 +2832,40 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
                                 "work-skipping ones 1 2 4 7 8 16 64 need a library built with make DIAG=1)", dbg);
     }
     if (dbg & (95 | 1024 | 2048)) safe_warn_diagnostic("SAFE_HIP_BITS_DBG");
+    const bool lv11 = form.levels > BT_LV;
+    const void *kfn = blk    ? blk_fn
+                      : half ? (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV + 1>)
+                                     : reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV>))
+                             : (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV + 1>)
+                                     : reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV>));
+    SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_T)));
     uint32_t *d_obs = nullptr;
     if (blk) {
-        SAFE_HIP_CHECK(hipFuncSetAttribute(blk_fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_pre)));
         // observed sums of every (word group, slice), once: the compare operand of every task, and `ns`
         SAFE_TRY(ctx_scratch(ctx, 7, static_cast<size_t>(n_wg) * nbr->n_slices * 2 * BT_LV * 64 * sizeof(uint32_t),
                              reinterpret_cast<void **>(&d_obs)));
-        const size_t lds_obs = lds_pre + (out.ns ? 4 * 64 * 66 * sizeof(uint16_t) : 0);            // + the waves' transposition tiles
+        const size_t lds_obs = lds_T + (out.ns ? 4 * 64 * 66 * sizeof(uint16_t) : 0);            // + the waves' transposition tiles
         SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bits_observed), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            static_cast<int>(lds_obs)));
         hipLaunchKernelGGL(k_bits_observed, dim3(n_wg, ceil_div(nbr->n_slices, 4)), dim3(256), lds_obs, ctx->stream, n, nbr->sell_row,
                            nbr->slice_off, nbr->slice_width, nbr->sell_col2b, nbr->n_slices, d_bits, mloc, d_obs, out.ns);
         SAFE_HIP_CHECK(hipGetLastError());
     }
-    const bool lv11 = nbr->max_count >= (1 << BT_LV);
-    const void *pre_w_fn = pre_h ? (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV + 1>)
-                                         : reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV>))
-                                 : (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre<8, 16, 2, BT_LV + 1>)
-                                         : reinterpret_cast<const void *>(k_permtest_bits_pre<8, 16, 2>));
-    const size_t lds_pre_w = pre_h ? bits_half_lds_bytes(n) : lds_pre;
-    if (pre_w || pre_h)
-        SAFE_HIP_CHECK(hipFuncSetAttribute(pre_w_fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_pre_w)));
-    else if (pre)
-        SAFE_HIP_CHECK(hipFuncSetAttribute(narrow ? reinterpret_cast<const void *>(k_permtest_bits_pre<8>)
-                                           : wide ? reinterpret_cast<const void *>(k_permtest_bits_pre<16>)
-                                                  : reinterpret_cast<const void *>(k_permtest_bits_pre<10>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_pre)));
-    const void *kfn = wide ? (scaled ? reinterpret_cast<const void *>(k_permtest_bits<16, true>)
-                                     : reinterpret_cast<const void *>(k_permtest_bits<16, false>))
-                           : (scaled ? reinterpret_cast<const void *>(k_permtest_bits<10, true>)
-                                     : reinterpret_cast<const void *>(k_permtest_bits<10, false>));
-    SAFE_REQUIRE(pre || lds_bytes <= 160 * 1024, "launch_bits: the word column and the permutation rows of %lld nodes do not fit a CU's LDS",
-                 static_cast<long long>(n));
-    if (!pre) SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-    if (wv == 16 && !pre)         // (a task holds at most 255 permutations -- ppt_cap above --: eight counter levels, whatever P is)
-        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_permtest_bits<8, false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds_bytes)));
-    ctx->last_kernel.name = blk ? "k_permtest_bits_blk" : pre ? "k_permtest_bits_pre" : "k_permtest_bits";
+    // the kernels' workgroups are persistent and fill the register file (4 waves x 128 VGPRs per SIMD): on a CU they hold, the
+    // table kernels of the next pipeline stage (aux stream: scan rounds, row emission) wait for a whole workgroup to finish.  A few
+    // CUs are therefore left out of the grid (16 of 256): the median step shrinks by ~3 % at 1000 permutations, ~6 % at 10 000
+    // (round-3 sweep, CHANGELOG.md; 8 until the kernels got faster than k_permute_cols on 8 CUs: 10 000-permutation step
+    // 27.1 -> 26.3 ms with 16).  Blocked form: four workgroups per CU (the register file holds 16 waves); sixteen-wave forms: one.
+    const int spare = std::min(16, ctx->num_cu / 8);
+    const int64_t grid_max = static_cast<int64_t>(std::max(1, ctx->num_cu - spare)) *
+                             (blk ? std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds_T)) : 1);
+    ctx->last_kernel.name = blk ? "k_permtest_bits_blk" : "k_permtest_bits_pre";
     ctx->last_kernel.total_ms = 0.0;
     ctx->last_kernel.busy_ms = 0.0;
     ctx->last_kernel.launches = 0;
     hipEvent_t *ev = nullptr, *plain = nullptr;                   // pooled on the context
     SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &ev));
     SAFE_TRY(ctx_events(ctx, false, 12, &plain));                 // 0: inputs ready, 1..3: end join, 4..7: join before the tail, 8: tail lists
-    SAFE_REQUIRE(!n_tail || blk, "launch_bits: column-chunked tail without the blocked kernel");
     for (int64_t k = 0; k < n_tail; ++k)
         if (!ctx->xc_events[k]) SAFE_HIP_CHECK(hipEventCreateWithFlags(&ctx->xc_events[k], hipEventDisableTiming));
     // consecutive spans alternate between two streams so the tail of one launch (a few long
@@ -3129,7 +2885,6 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
         const int64_t p_base = tail ? p_split : starts[c], p_limit = tail ? P : starts[c + 1];
         const int64_t n_tasks = list_count[launch_list[c]];                 // this launch size's task list
         const int4 *d_tasks = d_task_lists + list_first[launch_list[c]];
-        const int64_t blocks = std::min<int64_t>(n_tasks, slots);
         hipStream_t ks = kstreams[c % NS];
         if (tail && c == n_major) {
             // the tail's permuted member lists: one k_permute_cols per pipeline stage as its tables arrive, on a stream of their
@@ -3141,7 +2896,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
                 hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), starts[t + 1] - starts[t]), dim3(256),
                                    static_cast<size_t>(perms->stride16) * sizeof(uint16_t), tail_ps, perms->table16, perms->stride16,
                                    nbr->sell_col2b, nbr->sell_entries, entries_pad, starts[t], starts[t + 1] - starts[t],
-                                   static_cast<uint32_t>(8 * n), d_ids_tail + (starts[t] - p_split) * entries_pad, diag_banks, 3);
+                                   static_cast<uint32_t>(8 * n), d_ids_tail + (starts[t] - p_split) * entries_pad, 3);
                 SAFE_HIP_CHECK(hipGetLastError());
             }
             SAFE_HIP_CHECK(hipEventRecord(plain[8], tail_ps));
@@ -3154,77 +2909,36 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
         }
         if (!tail) SAFE_TRY(perms_wait(perms, p_limit, ks));            // host draws + table kernels for this span
         safe_trace("launch_bits: span tables enqueued");
-        if (pre) {
-            if (!tail)
-                hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), p_limit - p_base), dim3(256),
-                                   static_cast<size_t>(perms->stride16) * sizeof(uint16_t), ks, perms->table16,
-                                   perms->stride16, blk ? nbr->sell_col2b : nbr->sell_col2, nbr->sell_entries, entries_pad, p_base,
-                                   p_limit - p_base, static_cast<uint32_t>(static_cast<uint64_t>(n) << id_shift), d_ids[c % NS], diag_banks, id_shift);
-            SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
-            // the kernel's workgroups are persistent and fill the register file (4 waves x 128 VGPRs per SIMD): on a CU they
-            // hold, the table kernels of the next pipeline stage (aux stream: scan rounds, row emission) wait for a whole
-            // workgroup to finish.  A few CUs are therefore left out of the grid (16 of 256):
-            // the median step shrinks by ~3 % at 1000 permutations, ~6 % at 10 000 (round-3 sweep, CHANGELOG.md)
-            const int spare = std::min(16, ctx->num_cu / 8);  // (8 until the kernels got faster than k_permute_cols on 8 CUs: 10 000-permutation step 27.1 -> 26.3 ms with 16)
-            const int64_t blocks_pre = std::min<int64_t>(n_tasks, static_cast<int64_t>(std::max(1, ctx->num_cu - spare)) *
-                                                         std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_pre)));
-            if (blk && tail && n_tasks == 0) {                           // (a rank with fewer columns: nothing in this chunk)
-                SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
-                chunk_final(c, ks);
-                continue;
-            }
-            if (blk) {
-                const uint16_t *ids_c = tail ? d_ids_tail : d_ids[c % NS];
-                unsigned int *queue_c = d_queue + 8 * c;
-                BitsQueues bq = list_queues[launch_list[c]];
-                void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
-                                (void *)&nbr->slice_width, (void *)&d_obs, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&bq,
-                                (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
-                                (void *)&n_pad};
-                const int64_t blocks_blk = std::min<int64_t>(n_tasks, static_cast<int64_t>(std::max(1, ctx->num_cu - spare)) *
-                                                                          std::max<size_t>(1, std::min<size_t>(occ5 ? 5 : 4, (160 * 1024) / lds_pre)));   // 4 (5): the register file holds 16 (20) waves per CU
-                SAFE_HIP_CHECK(hipLaunchKernel(blk_fn, dim3(blocks_blk), dim3(256), args, lds_pre, ks));
-                if (tail) chunk_final(c, ks);
-            } else if (pre_w || pre_h) {
-                const uint16_t *ids_c = d_ids[c % NS];
-                unsigned int *queue_c = d_queue + 8 * c;
-                void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
-                                (void *)&nbr->slice_width, (void *)&nbr->sell_col2, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&n_tasks,
-                                (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
-                                (void *)&n_pad, (void *)&out.ns};
-                SAFE_HIP_CHECK(hipLaunchKernel(pre_w_fn, dim3(std::min<int64_t>(n_tasks, std::max(1, ctx->num_cu - spare))), dim3(1024), args,
-                                               lds_pre_w, ks));
-            } else if (narrow)
-                hipLaunchKernelGGL(k_permtest_bits_pre<8>, dim3(blocks_pre), dim3(256), lds_pre, ks, n, d_ids[c % NS], entries_pad,
-                                   nbr->sell_row, nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_bits,
-                                   n_tasks, d_tasks, p_base, p_limit, d_queue + 8 * c, mloc, d_gl, n_pad, out.ns);
-            else if (wide)
-                hipLaunchKernelGGL(k_permtest_bits_pre<16>, dim3(blocks_pre), dim3(256), lds_pre, ks, n, d_ids[c % NS], entries_pad,
-                                   nbr->sell_row, nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_bits,
-                                   n_tasks, d_tasks, p_base, p_limit, d_queue + 8 * c, mloc, d_gl, n_pad, out.ns);
-            else
-                hipLaunchKernelGGL(k_permtest_bits_pre<10>, dim3(blocks_pre), dim3(256), lds_pre, ks, n, d_ids[c % NS], entries_pad,
-                                   nbr->sell_row, nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_bits,
-                                   n_tasks, d_tasks, p_base, p_limit, d_queue + 8 * c, mloc, d_gl, n_pad, out.ns);
-            SAFE_HIP_CHECK(hipGetLastError());
+        if (!tail)
+            hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), p_limit - p_base), dim3(256),
+                               static_cast<size_t>(perms->stride16) * sizeof(uint16_t), ks, perms->table16,
+                               perms->stride16, blk ? nbr->sell_col2b : nbr->sell_col2, nbr->sell_entries, entries_pad, p_base,
+                               p_limit - p_base, static_cast<uint32_t>(static_cast<uint64_t>(n) << id_shift), d_ids[c % NS], id_shift);
+        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
+        const int64_t grid = std::min<int64_t>(n_tasks, grid_max);
+        unsigned int *queue_c = d_queue + 8 * c;
+        if (tail && n_tasks == 0) {                                  // (a rank with fewer columns: nothing in this chunk)
             SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
+            chunk_final(c, ks);
             continue;
         }
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
-#define LAUNCH_BITS(CLV, SC)                                                                                          \
-        hipLaunchKernelGGL((k_permtest_bits<CLV, SC>), dim3(blocks), dim3(256), lds_bytes, ks, n, P,                  \
-                           perms->table16, perms->stride16, nbr->sell_row, nbr->slice_off, nbr->slice_width,          \
-                           nbr->sell_col2, nbr->n_slices, d_bits, n_tasks, d_tasks, p_base, p_limit, d_queue + 8 * c, mloc, \
-                           d_gl, n_pad, out.ns)
-        if (wv == 16)
-            hipLaunchKernelGGL((k_permtest_bits<8, false, 16>), dim3(blocks), dim3(1024), lds_bytes, ks, n, P, perms->table16, perms->stride16,
-                               nbr->sell_row, nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_bits, n_tasks, d_tasks,
-                               p_base, p_limit, d_queue + 8 * c, mloc, d_gl, n_pad, out.ns);
-        else if (wide && scaled) LAUNCH_BITS(16, true);
-        else if (wide) LAUNCH_BITS(16, false);
-        else if (scaled) LAUNCH_BITS(10, true);
-        else LAUNCH_BITS(10, false);
-#undef LAUNCH_BITS
+        if (blk) {
+            const uint16_t *ids_c = tail ? d_ids_tail : d_ids[c % NS];
+            BitsQueues bq = list_queues[launch_list[c]];
+            void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
+                            (void *)&nbr->slice_width, (void *)&d_obs, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&bq,
+                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
+                            (void *)&n_pad};
+            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(grid), dim3(256), args, lds_T, ks));
+            if (tail) chunk_final(c, ks);
+        } else {
+            const uint16_t *ids_c = d_ids[c % NS];
+            void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
+                            (void *)&nbr->slice_width, (void *)&nbr->sell_col2, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&n_tasks,
+                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
+                            (void *)&n_pad, (void *)&out.ns};
+            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(grid), dim3(1024), args, lds_T, ks));
+        }
         SAFE_HIP_CHECK(hipGetLastError());
         SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
     }
@@ -3333,30 +3047,9 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_bytes)));
     const int64_t slots = static_cast<int64_t>(ctx->num_cu) * per_cu;
     const int NW = 16;                             // waves (= adjacent slices) per workgroup: LDS allows one workgroup per CU
-    const int64_t n_sg = ceil_div(nbr->n_slices, NW);
-    std::vector<int64_t> sg_blocks(n_sg, 0);
-    int64_t blocks_per_perm = 0;
-    for (int64_t s = 0; s < nbr->n_slices; ++s) sg_blocks[s / NW] = std::max<int64_t>(sg_blocks[s / NW], nbr->h_slice_width[s] / 8);
-    for (int64_t g = 0; g < n_sg; ++g) blocks_per_perm += std::max<int64_t>(sg_blocks[g], 1);
     const int64_t tasks_per_tile = std::max<int64_t>(1, ceil_div(6 * slots, n_tiles));
-    const int64_t target = std::max<int64_t>(256, blocks_per_perm * span / tasks_per_tile);
-    struct TaskCost { int4 t; int64_t cost; };
-    std::vector<TaskCost> tc;
-    for (int64_t g = 0; g < n_sg; ++g) {
-        const int64_t bl = std::max<int64_t>(sg_blocks[g], 1);
-        int64_t ppt = std::min<int64_t>(span, std::max<int64_t>(16, target / bl));
-        const int64_t chunks = ceil_div(span, ppt);
-        ppt = ceil_div(span, chunks);
-        for (int64_t c = 0; c < chunks; ++c) {
-            const int64_t p0 = c * ppt, p1 = std::min<int64_t>(span, p0 + ppt);
-            for (int64_t w = 0; w < n_tiles; ++w)
-                tc.push_back({make_int4(static_cast<int>(w), static_cast<int>(g), static_cast<int>(p0), static_cast<int>(p1)),
-                              bl * (p1 - p0)});
-        }
-    }
-    std::stable_sort(tc.begin(), tc.end(), [](const TaskCost &a, const TaskCost &b) { return a.cost > b.cost; });
-    std::vector<int4> tasks(tc.size());
-    for (size_t i = 0; i < tc.size(); ++i) tasks[i] = tc[i].t;
+    const std::vector<int4> tasks = cost_sorted_tasks(slice_group_blocks(nbr->h_slice_width, nbr->n_slices, NW), span, 0, n_tiles,
+                                                      tasks_per_tile, INT64_MAX, false, mloc);
     const int64_t n_launch = static_cast<int64_t>(starts.size()) - 1, n_pad = nbr->n_slices * 64;
     int4 *d_tasks = nullptr;
     unsigned int *d_queue = nullptr, *d_counts = nullptr;

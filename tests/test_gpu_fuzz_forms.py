@@ -1,7 +1,7 @@
 """Short runs of tools/r6/fuzz_forms.py and tools/r6/fuzz_binary.py.  fuzz_forms: random layouts, radii, data kinds, sizes, permutation counts and seeds; the counters
 of the default matrix-core kernels (filtered: high slices + exact resolve) must equal the general kernel's with ALL slices, and
-the f64 kernels' wherever the data is exact on both grids.  fuzz_binary: 0/1 attributes, every kernel family (blocked / pre-permuted /
-LDS-row / stream-less bit-sliced, scatter, f64 gather) against the default.  (The long runs -- 4000 and 490 cases, 6-7 minutes each,
+the f64 kernels' wherever the data is exact on both grids.  fuzz_binary: 0/1 attributes, every kernel family (the default bit-sliced
+form -- blocked, or sixteen-wave on the larger networks --, stream-less bit-sliced, scatter, f64 gather) against the default.  (The long runs -- 4000 and 490 cases, 6-7 minutes each,
 0 failures at the end of round 6 -- are the tools themselves.)"""
 import importlib.util
 import os
@@ -34,13 +34,16 @@ def test_random_cases_every_form_leaves_the_same_counters(monkeypatch):
     assert 'k_permtest_mfma' in names and {3, 4} <= cores, used     # both filtered kernels were among the forms exercised
 
 
-def test_random_binary_cases_every_kernel_family_leaves_the_same_counters(monkeypatch):
+def test_random_binary_cases_every_remaining_kernel_family_leaves_the_same_counters(monkeypatch):
+    """The default bit-sliced form reaches both of its kernels on these cases: the blocked one, and the sixteen-wave one on the
+    networks beyond N = 8190 and the neighborhoods of 1024+ members."""
     fuzz = _tool('fuzz_binary')
     monkeypatch.setenv('SAFE_HIP_NARROW_LDS', '0')
     cases, fails, used = fuzz.run(budget=60.0, first=70000, max_cases=40)
     assert cases >= 20 and fails == 0
     ran = {k[1] for k in used}
-    assert {'k_permtest_bits_blk', 'k_permtest_bits_pre', 'k_permtest_bits', 'k_permtest_scatter'} <= ran, used
+    assert {'k_permtest_bits_blk', 'k_permtest_bits_pre', 'k_permtest_scatter'} <= ran, used
+    assert ('default', 'k_permtest_bits_pre') in used, used
 
 
 @pytest.mark.parametrize('n,nperm', [(9000, 1100), (21000, 1030), (2600, 2000)])

@@ -84,7 +84,7 @@ def test_fdr_rows_equal_statsmodels(amd, golden_fdr, monkeypatch, sort):
 
 # ------------------------------------------------------------------------------- the second size --------
 
-BIG = [('bin', None, None), ('bin', 'bits', None), ('bin', 'bits', 'pre'), ('bin', 'bits', 'barrier'), ('bin', 'scatter', None),
+BIG = [('bin', None, None), ('bin', 'bits', None), ('bin', 'scatter', None),
        ('bin', 'gather', None),
        ('q_sum', None, None), ('q_sum', 'mfma', None), ('q_sum', 'lds', None), ('q_sum', 'gather', None),
        ('q_z', None, None), ('q_z', 'mfma', None), ('q_z', 'lds', None), ('q_z', 'gather', None)]
@@ -97,10 +97,6 @@ def test_second_size_vs_reference(amd, golden_big, monkeypatch, tag, path, kerne
     p-values, NES, nes_binary and per-attribute counts EXACTLY equal for every kernel family; scores to 1e-9."""
     if path:
         monkeypatch.setenv('SAFE_HIP_FORCE_PATH', path)
-    if kernel == 'pre':
-        monkeypatch.setenv('SAFE_HIP_BITS_KERNEL', 'pre')
-    elif kernel == 'barrier':
-        monkeypatch.setenv('SAFE_HIP_BITS_PRE', '0')
     g = golden_big
     mat = (g['b_bin'] if tag == 'bin' else g['b_q']).copy(order='K')
     sf = _safe(amd, g, random_seed=g[tag + '_seed'])

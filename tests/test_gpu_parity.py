@@ -647,25 +647,21 @@ def test_integer_forms_large_support_and_many_permutations(amd, monkeypatch, pat
 
 
 @pytest.mark.parametrize('kernel,nperm', [('blk', 40), ('blk', 300), ('blk', 1), ('blk', 2), ('blk', 3), ('blk', 41), ('blk', 257), ('blk-plain', 41),
-                                          ('blk-unpipelined', 41), ('pre', 40), ('barrier', 40)])
+                                          ('blk-unpipelined', 41)])
 def test_bit_sliced_kernels_every_level_class(amd, monkeypatch, kernel, nperm):
-    """The three bit-sliced kernels (blocked member lists = default, pre-permuted lists, permutation row in LDS) on a
-    membership whose SELL slices fall into every width class of the blocked kernel (<= 8, <= 56, <= 248, <= 504, > 504 members:
+    """The blocked bit-sliced kernel (the form of every network with 8 (N + 1) < 65536 and neighborhoods below 1024 members;
+    the sixteen-wave forms have their own tests below and in test_gpu_fullsize.py) on a membership whose SELL slices fall into
+    every width class of the blocked kernel (<= 8, <= 56, <= 248, <= 504, > 504 members:
     4 / 6 / 8 / 9 / 10 levels of the vertical sums), with columns dense enough that the sums really reach the top
     levels, an empty neighborhood, a ragged last word group; 300 permutations carry the counters past their low levels.  Odd and
     tiny permutation counts walk the blocked kernel's id stream through its tails (a slice of an odd number of blocks takes two
-    permutations per period); 'blk-plain' is the form without the stream (SAFE_HIP_BITS_DBG=256, also the five-waves build's),
+    permutations per period); 'blk-plain' is the form without the stream (SAFE_HIP_BITS_DBG=256),
     'blk-unpipelined' the stream with a block's gathers all at its start (bit 9)."""
     monkeypatch.setenv('SAFE_HIP_FORCE_PATH', 'bits')
     if kernel == 'blk-plain':
         monkeypatch.setenv('SAFE_HIP_BITS_DBG', '256')
     elif kernel == 'blk-unpipelined':
         monkeypatch.setenv('SAFE_HIP_BITS_DBG', '512')
-    kernel = kernel.split('-')[0]
-    if kernel == 'pre':
-        monkeypatch.setenv('SAFE_HIP_BITS_KERNEL', 'pre')
-    elif kernel == 'barrier':
-        monkeypatch.setenv('SAFE_HIP_BITS_PRE', '0')
     rng = np.random.default_rng(77)
     n, m = 1400, 131
     sizes = np.r_[rng.integers(600, 1000, 10), rng.integers(260, 500, 70), rng.integers(100, 248, 150), rng.integers(9, 56, 640),
@@ -681,7 +677,7 @@ def test_bit_sliced_kernels_every_level_class(amd, monkeypatch, kernel, nperm):
     cn_want, cp_want = orc.run_permutations(a, b, 'sum', nperm, 13)
     cn, cp = amd.run_permutations((a, b, 'sum', nperm, 13), verbose=False)
     name = amd.Context.default(0).last_kernel()[0]
-    assert name == {'blk': 'k_permtest_bits_blk', 'pre': 'k_permtest_bits_pre', 'barrier': 'k_permtest_bits'}[kernel]
+    assert name == 'k_permtest_bits_blk'
     assert np.array_equal(cn, cn_want) and np.array_equal(cp, cp_want)
     ns = amd.compute_neighborhood_score(a, b, 'sum')
     assert np.array_equal(ns, orc.compute_neighborhood_score(a, b, 'sum'))

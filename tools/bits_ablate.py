@@ -1,5 +1,5 @@
 """Kernel-only time of the bit-sliced permutation test at configs[1] (tables generated before the call), per kernel
-variant and diagnostic build:  SAFE_HIP_BITS_KERNEL = blk | pre;  SAFE_HIP_BITS_DBG bit 0 = no LDS gathers, bit 1 = no
+diagnostic build of k_permtest_bits_blk:  SAFE_HIP_BITS_DBG bit 0 = no LDS gathers, bit 1 = no
 counter flush, bit 2 = no compare / count (make DIAG=1: wrong results; shows what the time goes to), 128 = the per-task
 clock trace (results stay correct).
 usage: bits_ablate.py [P]   -- each configuration runs in its own child process."""
@@ -48,8 +48,7 @@ if __name__ == '__main__':
         one(int(sys.argv[2]))
         sys.exit(0)
     P = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-    K = 'SAFE_HIP_BITS_KERNEL'
     D = 'SAFE_HIP_BITS_DBG'
-    configs = [{K: 'pre'}, {K: 'blk'}, {K: 'blk', D: '1'}, {K: 'blk', D: '2'}, {K: 'blk', D: '4'}, {K: 'blk', D: '7'}]
+    configs = [{}, {D: '1'}, {D: '2'}, {D: '4'}, {D: '7'}]
     for cfg in configs:
         subprocess.run([sys.executable, os.path.abspath(__file__), '--one', str(P)], env=dict(os.environ, **cfg))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes for the headline bench step (bit-sliced permutation kernel); run on the GPU box through gpurun.
-# usage: pmc_bits.sh <out tag> [env assignments for the bench, e.g. SAFE_HIP_BITS_KERNEL=pre]
+# usage: pmc_bits.sh <out tag> [env assignments for the bench, e.g. SAFE_HIP_BITS_DBG=256]
 # the benched configuration (bench.py / run_batch.py set it for themselves; under rocprofv3 the runtime is initialised
 # before Python runs, so it must come from the shell)
 export GPU_MAX_HW_QUEUES=8

@@ -1,9 +1,10 @@
 """Randomised form-against-form check of the BINARY permutation test (GPU only, no oracle: any size).
 
 Binary 'sum' scores are exact in integers, so every kernel family must leave the same counters for the same seed:
-  default (k_permtest_bits_blk where its limits hold, else what choose_path picks), the f64 gather kernel, the sparse scatter
-  kernel, the pre-permuted, the LDS-row and the stream-less bit-sliced kernels (a forced form that does not apply to a shape
-  falls through to what choose_path picks; the summary line says which kernel ran how often).
+  default (the bit-sliced form of bits_form -- k_permtest_bits_blk, or the sixteen-wave k_permtest_bits_pre / _pre32 -- where
+  one applies, else what choose_path picks), the f64 gather kernel, the sparse scatter kernel and the stream-less blocked
+  bit-sliced kernel (a forced form that does not apply to a shape falls through to what choose_path picks; the summary line says
+  which kernel ran how often).
 The kernels themselves are pinned to the oracle by tests/test_gpu_parity.py; this tool walks shapes those tests do not: random
 sizes up to 32 767 nodes (past the blocked kernel's N <= 8190: the sixteen-wave forms, full and half words), clustered layouts, dense random memberships with rows of every
 size class, NaN rows, empty and full columns, odd permutation counts.
@@ -25,8 +26,6 @@ from fuzz_forms import layout, counts                  # noqa: E402
 
 FORMS = [('gather', {'SAFE_HIP_FORCE_PATH': 'gather'}),
          ('scatter', {'SAFE_HIP_FORCE_PATH': 'scatter'}),
-         ('bits-pre', {'SAFE_HIP_FORCE_PATH': 'bits', 'SAFE_HIP_BITS_KERNEL': 'pre'}),
-         ('bits-row', {'SAFE_HIP_FORCE_PATH': 'bits', 'SAFE_HIP_BITS_PRE': '0'}),
          ('bits-plain', {'SAFE_HIP_FORCE_PATH': 'bits', 'SAFE_HIP_BITS_DBG': '256'})]
 
 

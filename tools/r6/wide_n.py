@@ -1,7 +1,6 @@
 """Binary randomization x 1000 permutations (unseeded: the kernels' own time) on the configs[1] surrogate's recipe scaled to N
 nodes, M = 2048 attributes: call time, kernel, ps per member-word and permutation -- the cost scale of DESIGN section 7's
-"off the fast path" figures.  python tools/r6/wide_n.py 3971 8100 8300 12000 20000 uniform20000
-(SAFE_HIP_BITS_PRE=0 in the environment: without the pre-permuted forms -- what the shapes beyond N = 8190 ran before)"""
+"off the fast path" figures.  python tools/r6/wide_n.py 3971 8100 8300 12000 20000 uniform20000"""
 import os
 import sys
 import time
