@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 4
+#define SAFE_HIP_ABI_VERSION 5
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -455,6 +455,18 @@ int safe_alloc_count(int64_t *calls);
  * polling thread.  Applies to draw threads started after the call (one persistent thread per context, created at the
  * first seeded call).  The library never re-pins its caller's threads. */
 int safe_set_draw_cpus(const int *cpus, int count);
+
+/* The node table of print_output_files without domains (safepy/safe.py:1297-1306: DataFrame(nes) with key / label columns,
+ * to_csv(sep='\t')): rows [r0, r1) of the row-major [n, m] f64 matrix values_dev as the bytes pandas writes, appended to
+ * the open file descriptor fd.  Row r is its prefix -- prefix_host[prefix_off_host[r - r0] .. prefix_off_host[r - r0 + 1]),
+ * the index / key / label fields as pandas writes them, without the trailing separator -- then '\t' + text(v) per value,
+ * then '\n'.  text(v) is NumPy's astype(str) (= repr(float)): the shortest round-trip digits, positional for decimal
+ * exponents -4 .. 15, "inf" / "-inf", "-0.0"; NaN gives an empty field (na_rep='').  The text is made on the device in
+ * row chunks of at most budget_bytes (bounded by 25 bytes per value; at least one row per chunk) and written through two
+ * pinned buffers, chunk c to the file while chunk c + 1 is formatted.  stats_out (may be NULL): double[5] = {format
+ * kernels ms, device-to-host copies ms, file writes ms, whole call ms, bytes written}.  Synchronises. */
+int safe_format_tsv(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, int64_t r0, int64_t r1, const char *prefix_host,
+                    const int64_t *prefix_off_host, int fd, int64_t budget_bytes, double *stats_out);
 
 /* Name and average duration (ms) of the dominant kernel of the last enrichment call,
  * measured with HIP events on the context stream (bench.py's roofline object). */

@@ -270,6 +270,23 @@ class Context:
                                      int(iterations), float(threshold), _ptr(out), C.byref(ran)))
         return out.astype(dtype), ran.value
 
+    FORMAT_BUDGET = 64 << 20            # bytes of text per chunk of safe_format_tsv (two device and two pinned buffers of it)
+
+    def format_tsv(self, values_dev_ptr, n, m, prefixes, prefix_offsets, fd, r0=0, r1=None, budget_bytes=None):
+        """Rows [r0, r1) of the row-major [n, m] f64 device matrix at values_dev_ptr as pandas' to_csv(sep='\t') writes them,
+        appended to the open file descriptor fd (safe_format_tsv): row r is prefixes[prefix_offsets[r - r0]:prefix_offsets[r - r0 + 1]]
+        (bytes), '\t' + NumPy's text of each value (NaN: empty), '\n'.  Returns {'kernel_ms', 'copy_ms', 'write_ms', 'call_ms',
+        'bytes'}."""
+        r1 = n if r1 is None else r1
+        pre = np.frombuffer(bytes(prefixes), dtype=np.uint8) if len(prefixes) else np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(prefix_offsets, dtype=np.int64)
+        if off.shape != (r1 - r0 + 1,):
+            raise ValueError('format_tsv: %d prefix offsets for %d rows' % (off.shape[0], r1 - r0))
+        stats = (C.c_double * 5)()
+        check(lib.safe_format_tsv(self.handle, C.c_void_p(values_dev_ptr) if values_dev_ptr else None, int(n), int(m), int(r0),
+                                  int(r1), _ptr(pre), _ptr(off), int(fd), int(budget_bytes or self.FORMAT_BUDGET), stats))
+        return dict(zip(('kernel_ms', 'copy_ms', 'write_ms', 'call_ms', 'bytes'), list(stats)))
+
     def euclidean_dense(self, xy_dev_ptr, n, nr, mask_dev_ptr=None, dist_dev_ptr=None):
         check(lib.safe_euclidean_dense_dev(self.handle, C.c_void_p(xy_dev_ptr), int(n), float(nr),
                                            C.c_void_p(mask_dev_ptr) if mask_dev_ptr else None,

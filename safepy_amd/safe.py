@@ -3,12 +3,14 @@
 Same constructor signature, attribute names, method names, kwargs, array layouts and
 error behaviour as `safepy.safe.SAFE` (safepy/safe.py:37-608) for
 `define_neighborhoods()` / `compute_pvalues()` (+ the additive `compute_node_distances()`);
-the arithmetic runs in libsafe_hip.so on an MI355X.  File loaders, layouts, plotting,
-domains and output writers of the reference are out of scope.
+the arithmetic runs in libsafe_hip.so on an MI355X.  `print_output_files()` writes the reference's
+three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The
+MATLAB / Cytoscape loaders and plotting are out of scope.
 """
 import configparser
 import logging
 import os
+import pickle
 import sys
 
 import numpy as np
@@ -212,6 +214,7 @@ class SAFE:
         self.domains = None
         self.node2domain = None
         self.output_dir = ''
+        self.output_timing = None        # print_output_files: time split of the last node table made on the device
 
         # device state (never pickled)
         self.device = device
@@ -321,6 +324,13 @@ class SAFE:
         state['_attr_dev_host'] = None
         state['default_config'] = dict(self.default_config) if self.default_config is not None else None
         return state
+
+    def save(self, output_file='', **kwargs):
+        """safepy/safe.py:237-242: pickles the object (device results come to the host first: __getstate__)."""
+        if not output_file:
+            output_file = os.path.join(os.getcwd(), 'safe_output.p')
+        with open(output_file, 'wb') as handle:
+            pickle.dump(self, handle)
 
     def __setstate__(self, state):
         self.__dict__.update(state)
@@ -865,6 +875,114 @@ class SAFE:
         if self.verbose:
             logging.info('Removed %d domains because they were the top choice for less than %d neighborhoods.'
                          % (len(small), min_nodes))
+
+    # ------------------------------------------------------------------ outputs ----
+    def _graph_keys_labels(self):
+        """(ids, keys, labels) of the graph's nodes, as print_output_files reads them (safe.py:1286-1291)."""
+        if isinstance(self.graph, LayoutGraph):
+            return list(range(self.graph.number_of_nodes())), list(self.graph.keys), list(self.graph.labels)
+        import networkx as nx
+        t = nx.get_node_attributes(self.graph, 'key')
+        return list(t.keys()), list(t.values()), list(nx.get_node_attributes(self.graph, 'label').values())
+
+    def print_output_files(self, **kwargs):
+        """safepy/safe.py:1267-1306: domain_properties_annotation.txt (when domains are defined: their row 0 is dropped in
+        place first), attribute_properties_annotation.txt and node_properties_annotation.txt in self.output_dir (kwarg
+        `output_dir` sets it), then self.nodes = the node table.  Without domains the node table is [N, M] NES values: its
+        text is made on the device (backend.Context.format_tsv) from the device-resident nes when compute_pvalues left it
+        there -- read in place, not downloaded first -- and written in chunks of at most `budget_bytes` (additive kwarg);
+        the header, the index / key / label fields and the small tables are pandas', as in the reference.  Byte-identical
+        to the reference's files."""
+        if 'output_dir' in kwargs:
+            self.output_dir = kwargs['output_dir']
+
+        path_domains = os.path.join(self.output_dir, 'domain_properties_annotation.txt')
+        if self.domains is not None:
+            self.domains.drop(labels=[0], axis=0, inplace=True, errors='ignore')
+            self.domains.to_csv(path_domains, sep='\t')
+            logging.info(path_domains)
+
+        path_attributes = os.path.join(self.output_dir, 'attribute_properties_annotation.txt')
+        self.attributes.to_csv(path_attributes, sep='\t')
+        logging.info(path_attributes)
+
+        path_nodes = os.path.join(self.output_dir, 'node_properties_annotation.txt')
+        ids, keys, labels = self._graph_keys_labels()
+        if self.node2domain is not None:
+            domains = self.node2domain['primary_domain'].values
+            ness = self.node2domain['primary_nes'].values
+            num_domains = self.node2domain[self.domains['id']].sum(axis=1).values
+            self.nodes = pd.DataFrame(data={'id': ids, 'key': keys, 'label': labels, 'domain': domains,
+                                            'nes': ness, 'num_domains': num_domains})
+            self.nodes.to_csv(path_nodes, sep='\t')
+        else:
+            self._write_nes_table(path_nodes, keys, labels, kwargs.get('budget_bytes'))
+            self.nodes = pd.DataFrame(self.nes)
+            self.nodes.columns = self.attributes['name']
+            self.nodes.insert(loc=0, column='key', value=keys)
+            self.nodes.insert(loc=1, column='label', value=labels)
+        logging.info(path_nodes)
+
+    def _write_nes_table(self, path, keys, labels, budget_bytes=None):
+        """node_properties_annotation.txt without domains: pandas' to_csv(sep='\t') of DataFrame(nes) with the attribute
+        names as columns and 'key' / 'label' inserted in front (safe.py:1297-1306).  pandas writes the header line and each
+        row's index / key / label fields (quoted where QUOTE_MINIMAL asks); the device writes the values."""
+        src = self.__dict__.get('_r_nes')
+        if isinstance(src, _DeviceResult):
+            n, m = src.shape
+            host = None
+        else:
+            if src is None:
+                raise ValueError('print_output_files needs nes: run compute_pvalues first')
+            host = np.asarray(src)
+            if host.ndim != 2 or host.dtype != np.float64:
+                raise TypeError('nes must be a float64 [N, M] array (got %s %s)' % (host.dtype, host.shape))
+            n, m = host.shape
+        # the header from an empty frame built like the reference's (its column checks raise as the reference's do)
+        head = pd.DataFrame(np.empty((0, m)))
+        head.columns = self.attributes['name']
+        if len(keys) != n or len(labels) != n:
+            raise ValueError('Length of values (%d) does not match length of index (%d)'
+                             % (len(keys) if len(keys) != n else len(labels), n))
+        head.insert(loc=0, column='key', value=[])
+        head.insert(loc=1, column='label', value=[])
+        header = head.to_csv(sep='\t').encode('utf-8')
+        prefixes, offsets = _row_prefixes(keys, labels, n)
+
+        ctx = self._ctx()
+        tmp = None
+        try:
+            if host is not None:
+                tmp = ctx.alloc_f64(n, m)
+                tmp.upload(host)
+                ptr = tmp.ptr
+            else:
+                ptr = src.buf.ptr
+            with open(path, 'wb') as f:
+                f.write(header)
+                f.flush()
+                self.output_timing = ctx.format_tsv(ptr, n, m, prefixes, offsets, f.fileno(), budget_bytes=budget_bytes)
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+
+_ROW_END = '\t\x01\n'      # a sentinel field no key or label text is expected to hold
+
+
+def _row_prefixes(keys, labels, n):
+    """(utf-8 bytes, int64 offsets [n + 1]) of each row's index, key and label fields exactly as pandas writes them in
+    to_csv(sep='\t') of the node table: pandas writes them (one call, a sentinel column marks the row ends); rows whose
+    fields hold the sentinel are written one at a time."""
+    frame = pd.DataFrame({'key': keys, 'label': labels, 'end': '\x01'})
+    text = frame.to_csv(sep='\t', header=False)
+    rows = text.split(_ROW_END)
+    if len(rows) != n + 1 or rows[-1]:
+        rows = [frame.iloc[i:i + 1].to_csv(sep='\t', header=False)[:-len(_ROW_END)] for i in range(n)] + ['']
+    rows = [r.encode('utf-8') for r in rows[:n]]
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=offsets[1:])
+    return b''.join(rows), offsets
 
 
 def _domain_label(names):
