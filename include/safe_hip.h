@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 5
+#define SAFE_HIP_ABI_VERSION 6
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -467,6 +467,31 @@ int safe_set_draw_cpus(const int *cpus, int count);
  * kernels ms, device-to-host copies ms, file writes ms, whole call ms, bytes written}.  Synchronises. */
 int safe_format_tsv(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, int64_t r0, int64_t r1, const char *prefix_host,
                     const int64_t *prefix_off_host, int fd, int64_t budget_bytes, double *stats_out);
+
+/* Domain contours of plot_composite_network_contours (safepy/safe.py:822-829): SciPy 1.15's gaussian_kernel_estimate for
+ * n_sets two-dimensional point sets in one launch.  Set d is the whitened points pts_host[offsets_host[d] .. offsets_host[d+1])
+ * (f64 [., 2] row-major; offsets_host int64 [n_sets + 1], offsets_host[0] == 0, non-decreasing) with weights weights_host
+ * [same rows] and norm_host[d]; it is evaluated at its g whitened grid points xi_host[d] (f64 [n_sets, g, 2]) into z_host
+ * [n_sets, g]: z[d, j] = sum over points i in ascending order of w[i] * (exp(-|p_i - x_j|^2 / 2) * norm[d]), every operation
+ * rounded as SciPy's loop rounds it, exp from the device library.  Sets with too few grid points to fill the device are
+ * summed in contiguous point chunks whose sums are added in chunk order; no atomics, so every run gives the same z.
+ * kernel_ms (may be NULL): the kernels' time.  Synchronises. */
+int safe_kde_grid(safe_ctx *ctx, int64_t n_sets, const int64_t *offsets_host, const double *pts_host, const double *weights_host,
+                  const double *norm_host, int64_t g, const double *xi_host, double *z_host, double *kernel_ms);
+
+/* Composite colours of plot_composite_network (safepy/safe.py:883-886, groupby(level='domain', axis=1).sum()): counts_host
+ * f64 [n, n_domains] = the row-major [n, m] f64 matrix values_dev (read in place, e.g. the device-resident nes_binary) summed
+ * over the columns of each domain; domain_host int32 [m] in [0, n_domains) (SAFE_E_VALUE otherwise).  NaN values are skipped.
+ * 1 <= n_domains <= 4096 (one f64 LDS bin per domain; SAFE_E_UNSUPPORTED beyond).  Sums of whole numbers are exact; other
+ * values are added in an unspecified order.  kernel_ms (may be NULL): the kernel's time.  Synchronises. */
+int safe_domain_counts(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int32_t *domain_host, int64_t n_domains,
+                       double *counts_host, double *kernel_ms);
+
+/* The nes / nes_binary columns plot_sample_attributes reads (safepy/safe.py:1081-1187): out_host f64 [n, k] row-major =
+ * columns cols_host int64 [k] (each in [0, m)) of the row-major [n, m] f64 device matrix values_dev, without copying the
+ * rest of it.  kernel_ms (may be NULL): the kernel's time.  Synchronises. */
+int safe_gather_columns(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t k,
+                        double *out_host, double *kernel_ms);
 
 /* Name and average duration (ms) of the dominant kernel of the last enrichment call,
  * measured with HIP events on the context stream (bench.py's roofline object). */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsafe_hip.so')
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
@@ -162,6 +162,9 @@ PROTOTYPES = {
     'safe_ring_fetch': (C.c_int, [_vp, _i64, _vp, C.c_size_t]),
     'safe_ring_end': (C.c_int, [_vp]),
     'safe_format_tsv': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, C.c_int, _i64, C.POINTER(C.c_double)]),
+    'safe_kde_grid': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(C.c_double)]),
+    'safe_domain_counts': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
+    'safe_gather_columns': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

@@ -287,6 +287,72 @@ class Context:
                                   int(r1), _ptr(pre), _ptr(off), int(fd), int(budget_bytes or self.FORMAT_BUDGET), stats))
         return dict(zip(('kernel_ms', 'copy_ms', 'write_ms', 'call_ms', 'bytes'), list(stats)))
 
+    def _device_matrix(self, values, n, m):
+        """(device pointer, temporary buffer or None) of a row-major [n, m] f64 matrix given as a device pointer (int, e.g. a
+        _DeviceResult's buf.ptr; n and m required) or as a host array (uploaded into a temporary buffer)."""
+        if isinstance(values, (int, np.integer)):
+            if n is None or m is None:
+                raise ValueError('a device pointer needs n and m')
+            return int(values), None, int(n), int(m)
+        host = np.ascontiguousarray(values, dtype=np.float64)
+        if host.ndim != 2:
+            raise ValueError('expected a [n, m] matrix, got shape %s' % (host.shape,))
+        tmp = self.alloc_f64(*host.shape)
+        tmp.upload(host)
+        return tmp.ptr, tmp, host.shape[0], host.shape[1]
+
+    def kde_grid(self, offsets, pts, weights, norm, xi):
+        """SciPy's gaussian_kernel_estimate for D whitened 2-D point sets at once (safe_kde_grid): set d is pts[offsets[d]:
+        offsets[d + 1]] (f64 [., 2]) with weights and norm[d], evaluated at xi[d] (f64 [D, G, 2]).  Returns (z [D, G], kernel
+        ms)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        norm = np.ascontiguousarray(norm, dtype=np.float64).reshape(-1)
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        d = off.shape[0] - 1
+        if d < 0 or xi.ndim != 3 or xi.shape[0] != d or xi.shape[2] != 2 or norm.shape[0] != d:
+            raise ValueError('kde_grid: %d offsets, xi %s, %d norms' % (off.shape[0], xi.shape, norm.shape[0]))
+        if d and (off[-1] != pts.shape[0] or w.shape[0] != pts.shape[0]):
+            raise ValueError('kde_grid: offsets end at %d for %d points and %d weights' % (off[-1], pts.shape[0], w.shape[0]))
+        g = xi.shape[1]
+        z = np.empty((d, g), dtype=np.float64)
+        ms = C.c_double()
+        check(lib.safe_kde_grid(self.handle, d, _ptr(off), _ptr(pts), _ptr(w), _ptr(norm), g, _ptr(xi), _ptr(z), C.byref(ms)))
+        return z, ms.value
+
+    def domain_counts(self, values, domain, n_domains, n=None, m=None):
+        """f64 [n, n_domains]: the [n, m] matrix `values` (device pointer with n, m; or a host array) summed over the columns
+        of each domain, domain int [m] in [0, n_domains) (safe_domain_counts).  Returns (counts, kernel ms)."""
+        ptr, tmp, n, m = self._device_matrix(values, n, m)
+        try:
+            dom = np.ascontiguousarray(domain, dtype=np.int32)
+            if dom.shape != (m,):
+                raise ValueError('domain_counts: %d domain ids for %d columns' % (dom.size, m))
+            out = np.empty((n, int(n_domains)), dtype=np.float64)
+            ms = C.c_double()
+            check(lib.safe_domain_counts(self.handle, C.c_void_p(ptr) if ptr else None, n, m, _ptr(dom), int(n_domains), _ptr(out),
+                                         C.byref(ms)))
+            return out, ms.value
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def gather_columns(self, values, cols, n=None, m=None):
+        """f64 [n, k]: columns `cols` of the [n, m] matrix `values` (device pointer with n, m; or a host array), copied without
+        the rest of it (safe_gather_columns).  Returns (columns, kernel ms)."""
+        ptr, tmp, n, m = self._device_matrix(values, n, m)
+        try:
+            cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+            out = np.empty((n, cols.shape[0]), dtype=np.float64)
+            ms = C.c_double()
+            check(lib.safe_gather_columns(self.handle, C.c_void_p(ptr) if ptr else None, n, m, _ptr(cols), cols.shape[0], _ptr(out),
+                                          C.byref(ms)))
+            return out, ms.value
+        finally:
+            if tmp is not None:
+                tmp.free()
+
     def euclidean_dense(self, xy_dev_ptr, n, nr, mask_dev_ptr=None, dist_dev_ptr=None):
         check(lib.safe_euclidean_dense_dev(self.handle, C.c_void_p(xy_dev_ptr), int(n), float(nr),
                                            C.c_void_p(mask_dev_ptr) if mask_dev_ptr else None,
@@ -906,3 +972,18 @@ def jaccard_condensed(ctx, x):
     out = np.empty(m_top * (m_top - 1) // 2, dtype=np.float64)
     check(lib.safe_jaccard_condensed(ctx.handle, m_top, n, _ptr(x), _ptr(out)))
     return out
+
+
+def kde_grid(ctx, offsets, pts, weights, norm, xi):
+    """Context.kde_grid: (z [D, G], kernel ms)."""
+    return ctx.kde_grid(offsets, pts, weights, norm, xi)
+
+
+def domain_counts(ctx, values, domain, n_domains, n=None, m=None):
+    """Context.domain_counts: (counts [n, n_domains], kernel ms)."""
+    return ctx.domain_counts(values, domain, n_domains, n, m)
+
+
+def gather_columns(ctx, values, cols, n=None, m=None):
+    """Context.gather_columns: (columns [n, k], kernel ms)."""
+    return ctx.gather_columns(values, cols, n, m)

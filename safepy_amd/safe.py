@@ -4,8 +4,10 @@ Same constructor signature, attribute names, method names, kwargs, array layouts
 error behaviour as `safepy.safe.SAFE` (safepy/safe.py:37-608) for
 `define_neighborhoods()` / `compute_pvalues()` (+ the additive `compute_node_distances()`);
 the arithmetic runs in libsafe_hip.so on an MI355X.  `print_output_files()` writes the reference's
-three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The
-MATLAB / Cytoscape loaders and plotting are out of scope.
+three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The plot methods
+(`plot_network`, `plot_sample_attributes`, `plot_composite_network`, `plot_composite_network_contours`) draw with
+matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  The MATLAB / Cytoscape
+loaders are out of scope.
 """
 import configparser
 import logging
@@ -875,6 +877,323 @@ class SAFE:
         if self.verbose:
             logging.info('Removed %d domains because they were the top choice for less than %d neighborhoods.'
                          % (len(small), min_nodes))
+
+    # ------------------------------------------------------------------ plots ----
+    def _columns(self, name, cols):
+        """{column: [N] f64} of the result matrix `name` ('nes' / 'nes_binary') for the column indices cols: gathered on the
+        device (backend.Context.gather_columns) while the matrix is still there, so a plot never downloads it whole;
+        sliced from the host array otherwise."""
+        cols = list(dict.fromkeys(int(c) for c in cols))
+        src = self.__dict__.get('_r_' + name)
+        if isinstance(src, _DeviceResult):
+            n, m = src.shape
+            got, _ = self._ctx().gather_columns(src.buf.ptr, cols, n, m)
+        else:
+            if src is None:
+                raise ValueError('%s is not set: run compute_pvalues first' % name)
+            got = np.asarray(src)[:, cols]
+        return {c: got[:, i] for i, c in enumerate(cols)}
+
+    def plot_network(self, foreground_color='#ffffff', background_color='#000000', labels=[], node_size=10, alpha=0.2,
+                     **kwargs_mark_nodes):
+        """safepy/safe.py:747-784: the network (safe_io.plot_network) and, when `labels` are given, those nodes marked
+        (safe_io.mark_nodes with kwargs_mark_nodes, which must name `kind` as in the reference).  Returns the axes."""
+        from . import safe_io
+        ax = safe_io.plot_network(self.graph, background_color=background_color, node_size=node_size, alpha=alpha)
+        if len(labels) > 0:
+            xy, found = safe_io.get_node_coordinates(graph=self.graph, labels=labels)
+            ax = safe_io.mark_nodes(x=xy[:, 0], y=xy[:, 1], labels=found, ax=ax, foreground_color=foreground_color,
+                                    background_color=background_color, **kwargs_mark_nodes)
+        return ax
+
+    def _domain_colors(self):
+        """(sorted domain ids of the attributes, their colours): safe_colormaps.get_colors('hsv', D) -- NumPy's global
+        stream -- stored in self.domains['rgba'] (safe.py:804-810, 869-875)."""
+        from .safe_colormaps import get_colors
+        domains = np.sort(self.attributes['domain'].unique())
+        domain2rgb = get_colors('hsv', len(domains))
+        self.domains['rgba'] = domain2rgb.tolist()
+        return domains, domain2rgb
+
+    @staticmethod
+    def _figure(num_plots, background_color):
+        """The reference's grid of 10 x 10 panels, two per row, sharing both axes: (figure, flat array of axes)."""
+        import matplotlib.pyplot as plt
+        nrows = int(np.ceil(num_plots / 2))
+        ncols = np.min([num_plots, 2])
+        fig, axes = plt.subplots(nrows=nrows, ncols=ncols, figsize=(10 * ncols, 10 * nrows), sharex=True, sharey=True,
+                                 facecolor=background_color)
+        return fig, (axes.ravel() if isinstance(axes, np.ndarray) else np.array([axes]))
+
+    def plot_composite_network_contours(self, save_fig=None, clabels=False, background_color='#000000'):
+        """safepy/safe.py:786-849: the network, and beside it one contour per domain at density 1e-6 of SciPy's
+        gaussian_kde of the domain's nodes on a 100 x 100 grid over their extent.  The node set of domain number k
+        (k = 0 .. len(self.domains) - 1, domain 0 included) is the nodes with node2domain column k > 0.  Sets
+        self.domains['rgba'].
+
+        The kernel density estimates are SciPy's own objects (bandwidth, covariance factor, weights and errors, e.g.
+        LinAlgError for a domain of collinear nodes); their evaluation on the grids -- O(members x 10^4) exponentials per
+        domain -- runs on the device for every domain in one launch (backend.Context.kde_grid, plot.hip's k_kde_grid).
+
+        Deliberate difference: the reference draws each contour with ax[1].contour where ax is one Axes, which raises
+        TypeError after the first domain's estimate; here the contours are drawn on the second panel (axes[1]), which is
+        what that code means."""
+        import math
+        import matplotlib.pyplot as plt
+        from scipy.linalg import solve_triangular
+        from scipy.stats import gaussian_kde
+        from . import safe_io
+        self._domain_colors()
+        node_xy = safe_io.get_node_coordinates(self.graph)
+        fig, axes = self._figure(2, background_color)
+        ax = safe_io.plot_network(self.graph, ax=axes[0], background_color=background_color)
+
+        labels = self.domains['label'].values
+        grids, pts, weights, norms, offsets = [], [], [], [], [0]
+        for n_domain in range(len(labels)):
+            members = self.node2domain.loc[self.node2domain.loc[:, n_domain] > 0].index.values
+            pos3 = node_xy[members, :]
+            kernel = gaussian_kde(pos3.T)
+            X, Y = np.mgrid[np.min(pos3[:, 0]):np.max(pos3[:, 0]):100j, np.min(pos3[:, 1]):np.max(pos3[:, 1]):100j]
+            positions = np.vstack([X.ravel(), Y.ravel()])
+            # what gaussian_kernel_estimate does before its loop: whitened points and grid, the normalisation
+            cho = kernel.cho_cov
+            pts.append(solve_triangular(cho, kernel.dataset, lower=True).T)
+            grids.append((X, Y, solve_triangular(cho, positions, lower=True).T))
+            weights.append(kernel.weights)
+            norms.append(math.pow(2 * math.pi, -kernel.d / 2.0) / cho[0, 0] / cho[1, 1])
+            offsets.append(offsets[-1] + pos3.shape[0])
+        if labels.shape[0]:
+            z, _ = self._ctx().kde_grid(offsets, np.concatenate(pts), np.concatenate(weights), norms,
+                                        np.stack([g[2] for g in grids]))
+        for n_domain, domain in enumerate(labels):
+            X, Y, _ = grids[n_domain]
+            Z = z[n_domain].reshape(X.shape)
+            C = axes[1].contour(X, Y, Z, [1e-6], colors=self.domains.loc[n_domain, 'rgba'], alpha=1)
+            if clabels:
+                C.levels = [n_domain + 1]
+                plt.clabel(C, C.levels, inline=True, fmt='%d', fontsize=16)
+                print('%d -- %s' % (n_domain + 1, domain))
+        fig.set_facecolor(background_color)
+        if save_fig:
+            print('Output path: %s' % save_fig)
+            plt.savefig(save_fig, facecolor=background_color)
+
+    def plot_composite_network(self, show_each_domain=False, show_domain_ids=True, show_network_contour=True, save_fig=None,
+                               labels=[], foreground_color='#ffffff', background_color='#000000'):
+        """safepy/safe.py:851-1003: the network, and beside it every node coloured by the domains of the attributes it is
+        enriched for (mean of the domain colours weighted by those counts, brightened, brightest on top); with
+        show_each_domain one more panel per domain > 0 with the nodes it is the primary domain of.  Sets
+        self.domains['rgba'].
+
+        The per-node domain counts -- nes_binary [N, M] summed over each domain's columns, the reference's
+        groupby(level='domain', axis=1).sum() -- are made on the device from the device-resident nes_binary, read in place
+        (backend.Context.domain_counts, plot.hip's k_domain_counts; a host nes_binary is uploaded).  The NES frame the
+        reference builds for a per-domain alpha it then discards is not built."""
+        import matplotlib.pyplot as plt
+        from . import safe_io
+        if background_color == '#ffffff':
+            foreground_color = '#000000'
+        domains, domain2rgb = self._domain_colors()
+        column_domain = np.searchsorted(domains, self.attributes['domain'].to_numpy())
+        src = self.__dict__.get('_r_nes_binary')
+        if isinstance(src, _DeviceResult):
+            counts, _ = self._ctx().domain_counts(src.buf.ptr, column_domain, len(domains), *src.shape)
+        else:
+            if src is None:
+                raise ValueError('nes_binary is not set: run compute_pvalues first')
+            counts, _ = self._ctx().domain_counts(np.asarray(src, dtype=np.float64), column_domain, len(domains))
+        total = np.reshape(counts.sum(axis=1), (-1, 1))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            c = np.matmul(counts, domain2rgb) / total
+        t = np.sum(c, axis=1)
+        c[np.isnan(t) | np.isinf(t), :] = [0, 0, 0, 0]
+        coeff_brightness = 0.1 / np.nanmean(np.ravel(c[:, :-1]))
+        if coeff_brightness > 1:
+            c = c * coeff_brightness
+        c = np.clip(c, None, 1)
+        ix = np.argsort(np.sum(c, axis=1))
+
+        node_xy = safe_io.get_node_coordinates(self.graph)
+        num_plots = 2 + (len(domains) - 1 if show_each_domain else 0)
+        fig, axes = self._figure(num_plots, background_color)
+        safe_io.plot_network(self.graph, ax=axes[0], background_color=background_color)
+
+        def decorate(ax):
+            if show_network_contour:
+                safe_io.plot_network_contour(self.graph, ax, background_color=background_color)
+            if len(labels) != 0:
+                xy, found = safe_io.get_node_coordinates(graph=self.graph, labels=labels)
+                safe_io.mark_nodes(x=xy[:, 0], y=xy[:, 1], kind=['label'], labels=found, ax=ax, foreground_color=foreground_color,
+                                   background_color=background_color)
+
+        axes[1].scatter(node_xy[ix, 0], node_xy[ix, 1], c=c[ix], s=60, edgecolor=None)
+        axes[1].set_aspect('equal')
+        axes[1].set_facecolor(background_color)
+        decorate(axes[1])
+        primary = self.node2domain['primary_domain']
+        if show_domain_ids:
+            for domain in domains[domains > 0]:
+                idx = primary == domain
+                axes[1].text(np.nanmean(node_xy[idx, 0]), np.nanmean(node_xy[idx, 1]), str(domain),
+                             fontdict={'size': 16, 'color': foreground_color, 'weight': 'bold'})
+        if show_each_domain:
+            for domain in domains[domains > 0]:
+                ax = axes[1 + domain]
+                idx = primary == domain
+                colour = np.repeat(np.reshape(domain2rgb[domain, :], (1, 4)), node_xy.shape[0], axis=0)
+                ax.scatter(node_xy[idx, 0], node_xy[idx, 1], c=colour[idx], s=60, edgecolor=None)
+                ax.set_aspect('equal')
+                ax.set_facecolor(background_color)
+                ax.set_title('Domain %d\n%s' % (domain, self.domains.loc[domain, 'label']), color=foreground_color)
+                decorate(ax)
+        fig.set_facecolor(background_color)
+        if save_fig:
+            logging.info('Output path: %s' % save_fig)
+            plt.savefig(save_fig, facecolor=background_color)
+
+    def plot_sample_attributes(self, attributes=1, top_attributes_only=False, show_network=True, show_network_contour=True,
+                               show_costanzo2016=False, show_costanzo2016_colors=True, show_costanzo2016_clabels=False,
+                               show_nes=True, show_raw_data=False, show_significant_nodes=False, show_colorbar=True,
+                               colors=['82add6', 'facb66'], foreground_color='#ffffff', background_color='#000000',
+                               labels: list = [], save_fig=None, **kwargs):
+        """safepy/safe.py:1005-1265: one panel per attribute -- its NES on the network, optionally the raw values and the
+        significant nodes -- after the network.  attributes: an int k draws k attribute ids with np.random.choice from
+        NumPy's global stream (all of them when k is not smaller than their count); a name or a list of names selects by
+        name.  kwargs vmin / vmax / midrange set the colour scale.  save_fig is relative to self.output_dir.
+
+        The nes (and, with show_significant_nodes, nes_binary) columns of the chosen attributes are gathered on the device
+        while compute_pvalues' results are still there (backend.Context.gather_columns): the matrices are not downloaded.
+        show_costanzo2016=True needs the reference's safe-data repository and raises NotImplementedError."""
+        import re
+        import textwrap
+        import matplotlib.pyplot as plt
+        from matplotlib.colors import LinearSegmentedColormap
+        from . import safe_io
+        from .safe_colormaps import MidpointRangeNormalize
+        if show_costanzo2016:
+            raise NotImplementedError('show_costanzo2016 draws the Costanzo 2016 network annotations from the safe-data '
+                                      'repository, which safepy_amd does not ship')
+        if background_color == '#ffffff':
+            foreground_color = '#000000'
+
+        all_attributes = self.attributes.index.values
+        if top_attributes_only:
+            all_attributes = all_attributes[self.attributes['top']]
+        if isinstance(attributes, int):
+            if attributes < len(all_attributes):
+                attributes = np.random.choice(all_attributes, attributes, replace=False)
+            else:
+                attributes = np.arange(len(all_attributes))
+        elif isinstance(attributes, str):
+            attributes = [list(self.attributes['name'].values).index(attributes)]
+        elif isinstance(attributes, list):
+            names = list(self.attributes['name'].values)
+            attributes = [names.index(a) for a in attributes]
+
+        node_xy = safe_io.get_node_coordinates(self.graph)
+        nax = 1 if show_network else 0
+        fig, axes = self._figure(len(attributes) + nax, background_color)
+        if show_network:
+            safe_io.plot_network(self.graph, ax=axes[0], background_color=background_color)
+
+        nes = self._columns('nes', attributes) if len(attributes) else {}
+        nes_binary = self._columns('nes_binary', attributes) if show_significant_nodes and len(attributes) else {}
+        for idx_attribute, attribute in enumerate(attributes):
+            ax = axes[idx_attribute + nax]
+            score = nes[int(attribute)]
+            if show_nes:
+                vmin = kwargs['vmin'] if 'vmin' in kwargs else \
+                    np.nanmin([np.log10(1 / self.num_permutations), np.nanmin(-np.abs(score))])
+                vmax = kwargs['vmax'] if 'vmax' in kwargs else \
+                    np.nanmax([-np.log10(1 / self.num_permutations), np.nanmax(np.abs(score))])
+                midrange = kwargs['midrange'] if 'midrange' in kwargs else [np.log10(0.05), 0, -np.log10(0.05)]
+                idx = np.argsort(np.abs(score))                   # the brightest points on top
+                hexes = [re.sub(r'^#', '', h) for h in [colors[0]] + [background_color] * 3 + [colors[1]]]
+                cmap = LinearSegmentedColormap.from_list('my_cmap', [tuple(int(h[i:i + 2], 16) / 255 for i in (0, 2, 4))
+                                                                     for h in hexes])
+                sc = ax.scatter(node_xy[idx, 0], node_xy[idx, 1], c=score[idx], s=60, cmap=cmap,
+                                norm=MidpointRangeNormalize(midrange=midrange, vmin=vmin, vmax=vmax), edgecolors=None)
+            if show_colorbar:
+                self._colorbar(fig, ax, sc, vmin, vmax, midrange, foreground_color)
+            if show_raw_data:
+                self._raw_data(ax, node_xy, attribute, foreground_color, background_color)
+            if show_significant_nodes:
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    idx = np.abs(nes_binary[int(attribute)]) > 0
+                safe_io.mark_nodes(node_xy[idx, 0], node_xy[idx, 1], kind=['mark'], ax=ax,
+                                   legend_label=('p < %.2e' % self.enrichment_threshold), foreground_color=foreground_color,
+                                   background_color=background_color, marker='+')
+            if show_network_contour:
+                safe_io.plot_network_contour(self.graph, ax, background_color=background_color)
+            if len(labels) != 0:
+                xy, found = safe_io.get_node_coordinates(graph=self.graph, labels=labels)
+                ax = safe_io.mark_nodes(x=xy[:, 0], y=xy[:, 1], kind=['label'], labels=found, ax=ax,
+                                        foreground_color=foreground_color, background_color=background_color)
+            ax.set_aspect('equal')
+            ax.set_facecolor(background_color)
+            ax.grid(False)
+            ax.margins(0.1, 0.1)
+            if idx_attribute + nax == 0:
+                ax.invert_yaxis()
+            ax.set_title('\n'.join(textwrap.wrap(self.attributes.loc[attribute, 'name'], width=30)), color=foreground_color)
+            ax.set_frame_on(False)
+        fig.set_facecolor(background_color)
+        if save_fig:
+            path = save_fig if os.path.isabs(save_fig) else os.path.join(self.output_dir, save_fig)
+            logging.info('Output path: %s' % path)
+            plt.savefig(path, facecolor=background_color)
+
+    @staticmethod
+    def _colorbar(fig, ax, sc, vmin, vmax, midrange, foreground_color):
+        """The horizontal NES colour bar along the bottom of a panel (safe.py:1100-1136)."""
+        import matplotlib.pyplot as plt
+        box = ax.get_position()
+        w = box.width * 0.75
+        cax = fig.add_axes([box.x0 + (box.width - w) / 2, box.y0, w, box.height * 0.05])
+        cb = plt.colorbar(sc, cax=cax, orientation='horizontal', ticks=[vmin, midrange[0], midrange[1], midrange[2], vmax],
+                          drawedges=False)
+        cb.set_label('Neighborhood enrichment p-value', color=foreground_color)
+        cax.xaxis.set_tick_params(color=foreground_color)
+        cb.outline.set_edgecolor(foreground_color)
+        cb.outline.set_linewidth(1)
+        plt.setp(plt.getp(cb.ax.axes, 'xticklabels'), color=foreground_color)
+        cb.ax.set_xticklabels([r'$10^{%d}$' % vmin, r'$10^{%d}$' % midrange[0], r'$1$', r'$10^{%d}$' % -midrange[2],
+                               r'$10^{-%d}$' % vmax])
+        cax.text(cax.get_xlim()[0], 1, 'Lower than random', verticalalignment='bottom', fontdict={'color': foreground_color})
+        cax.text(cax.get_xlim()[1], 1, 'Higher than random', verticalalignment='bottom', horizontalalignment='right',
+                 fontdict={'color': foreground_color})
+
+    def _raw_data(self, ax, node_xy, attribute, foreground_color, background_color):
+        """The attribute's own values as dots, sized by magnitude, green above 0, red below (safe.py:1138-1172)."""
+        import matplotlib.pyplot as plt
+        from .safe_io import _legend
+        with np.errstate(divide='ignore', invalid='ignore'):
+            s_zero, s_min, s_max = 5, 5, 55
+            values = self.node2attribute[:, attribute]
+            mag = np.abs(values)
+            if set(np.unique(mag[~np.isnan(mag)])).issubset([0, 1]):          # binary attribute
+                s = np.zeros(len(mag))
+                s[mag > 0] = s_max
+                n_min, n_max = 0, 1
+            else:                                                             # quantitative: 5th-95th percentile to sizes
+                n_min, n_max = np.nanpercentile(np.unique(mag), [5, 95])
+                a = (s_max - s_min) / (n_max - n_min)
+                s = a * mag + (s_min - a * n_min)
+                s[s < s_min] = s_min
+                s[s > s_max] = s_max
+            neg_color, pos_color, zero_color = '#ff1d23', '#00ff44', foreground_color
+            idx = values < 0
+            ax.scatter(node_xy[idx, 0], node_xy[idx, 1], s=s[idx], c=neg_color, marker='.')
+            idx = values > 0
+            ax.scatter(node_xy[idx, 0], node_xy[idx, 1], s=s[idx], c=pos_color, marker='.')
+            idx = values == 0
+            ax.scatter(node_xy[idx, 0], node_xy[idx, 1], s=s_zero, c=zero_color, marker='.')
+            handles = [plt.scatter([], [], s=size, c=col, edgecolors='none')
+                       for size, col in ((s_max, pos_color), (s_min, pos_color), (s_zero, zero_color), (s_min, neg_color),
+                                         (s_max, neg_color))]
+            texts = ['{0:.2f}'.format(v) for v in [n_max, n_min, 0, -n_min, -n_max]]
+            _legend(ax, handles, texts, 'Raw data', foreground_color, background_color)
 
     # ------------------------------------------------------------------ outputs ----
     def _graph_keys_labels(self):

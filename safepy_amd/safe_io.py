@@ -18,7 +18,18 @@ Host-side mirror of the pieces of `safepy/safe_io.py` that feed `define_neighbor
                                                    census of the log run on the device, and the aligned
                                                    matrix can stay resident for compute_pvalues
 
-The Kamada-Kawai layout, the Cytoscape / MATLAB loaders and plotting stay out of scope.
+and the plot helpers of the reference (matplotlib is imported inside them only, so `import safepy_amd` does
+not load it):
+
+  plot_network                safe_io.py:433-486   nx.draw of the network (a LayoutGraph is drawn as the networkx
+                                                   graph of its edge list)
+  plot_network_contour        safe_io.py:489-529   convex hull + fmin circle fit, on the host
+  mark_nodes                  safe_io.py:589-646
+  get_node_coordinates        safe_io.py:649-691   both branches (labels=[] and the label lookup)
+
+The plot methods of SAFE put their data-parallel parts on the device (plot.hip: domain density grids, domain counts,
+column reads of the device-resident results).  The Kamada-Kawai layout and the Cytoscape / MATLAB loaders stay out of
+scope.
 There is no CPU fallback: every function that computes needs a HIP device.
 """
 import logging
@@ -36,12 +47,139 @@ def _xy_in_node_order(G):
     return np.stack([x, y], axis=1) if len(x) else np.zeros((0, 2))
 
 
-def get_node_coordinates(graph):
-    """[N,2] (x, y) in node order: the `labels=[]` branch of safe_io.py:649-662."""
+def get_node_coordinates(graph, labels=[]):
+    """safe_io.py:649-691.  labels empty: [N,2] (x, y) in node order.  Otherwise ([k,2] coordinates, labels found): the
+    nodes whose 'label' is one of `labels`, in the order of `labels` (a label several nodes share names the last of them,
+    as the reference's label -> node dictionary does); the labels not found are logged."""
     from .safe import LayoutGraph
+    xy = graph.xy if isinstance(graph, LayoutGraph) else _xy_in_node_order(graph)
+    if len(labels) == 0:
+        return xy
     if isinstance(graph, LayoutGraph):
-        return graph.xy
-    return _xy_in_node_order(graph)
+        node_of = {lab: i for i, lab in enumerate(graph.labels)}
+    else:
+        import networkx as nx
+        node_of = {lab: node for node, lab in nx.get_node_attributes(graph, 'label').items()}
+    found = [lab for lab in labels if lab in node_of]
+    missing = [lab for lab in labels if lab not in node_of]
+    if missing:
+        logging.warning('These labels are missing from the network (case sensitive): %s' % ', '.join(missing))
+    # the reference indexes the node-order x / y lists with the node id (ids 0..N-1)
+    idx = [node_of[lab] for lab in found]
+    return np.vstack([xy[idx, 0].tolist(), xy[idx, 1].tolist()]).T, found
+
+
+def _as_networkx(graph):
+    """A networkx graph to draw: the graph itself, or one built from a LayoutGraph (nodes 0..N-1, its edges in order)."""
+    from .safe import LayoutGraph
+    if not isinstance(graph, LayoutGraph):
+        return graph
+    import networkx as nx
+    g = nx.Graph()
+    g.add_nodes_from(range(graph.number_of_nodes()))
+    g.add_edges_from(zip(graph.edge_u.tolist(), graph.edge_v.tolist()))
+    return g
+
+
+def plot_network(G, ax=None, foreground_color='#ffffff', background_color='#000000', random_sampling_edges_min=30000,
+                 title='Network', node_size=10, alpha=0.2):
+    """safe_io.py:433-486: the network drawn with nx.draw at the node coordinates; with random_sampling_edges_min edges or
+    more, a tenth of them drawn with Python's global `random`.  A new 20 x 10 figure when ax is None.  Returns the axes.
+    (Like the reference, it turns off the axis of pyplot's current axes too: plt.axis('off').)"""
+    import random
+    import matplotlib.pyplot as plt
+    import networkx as nx
+    if background_color == '#ffffff':
+        foreground_color = '#000000'
+    node_xy = get_node_coordinates(G)
+    fig = None
+    if ax is None:
+        fig, ax = plt.subplots(figsize=(20, 10), facecolor=background_color, edgecolor=foreground_color)
+        fig.set_facecolor(background_color)
+    g = _as_networkx(G)
+    edges = tuple(g.edges())
+    if len(edges) >= random_sampling_edges_min:
+        logging.warning('Edges are randomly sampled because the network (edges=%d) is too big (random_sampling_edges_min=%d).'
+                        % (len(edges), random_sampling_edges_min))
+        edges = random.sample(edges, int(len(edges) * 0.1))
+    nx.draw(g, ax=ax, pos=node_xy, edgelist=edges, node_color=foreground_color, edge_color=foreground_color,
+            node_size=node_size, width=1, alpha=alpha)
+    ax.set_aspect('equal')
+    ax.set_facecolor(background_color)
+    ax.grid(False)
+    ax.invert_yaxis()
+    ax.margins(0.1, 0.1)
+    ax.set_title(title, color=foreground_color)
+    plt.axis('off')
+    if fig is not None:
+        fig.set_facecolor(background_color)
+    return ax
+
+
+def plot_network_contour(graph, ax, background_color='#000000'):
+    """safe_io.py:489-529: a circle around the network -- the circle least-squares fitted (scipy.optimize.fmin, started
+    at the hull vertices' centroid and mean radius) to the vertices of the nodes' convex hull -- drawn with 1 % more
+    radius.  Returns (xf, yf, rf)."""
+    import matplotlib.pyplot as plt
+    from scipy.optimize import fmin
+    from scipy.spatial import ConvexHull
+    from .safe import LayoutGraph
+    foreground_color = '#000000' if background_color == '#ffffff' else '#ffffff'
+    xy = get_node_coordinates(graph)
+    nodes = range(xy.shape[0]) if isinstance(graph, LayoutGraph) else list(graph.nodes)
+    pos = dict(zip(nodes, xy))
+    hull = ConvexHull(xy)
+    # the reference looks the hull's vertex positions up as node ids
+    vx = np.array([pos.get(v)[0] for v in hull.vertices])
+    vy = np.array([pos.get(v)[1] for v in hull.vertices])
+    xm, ym = np.nanmean(vx), np.nanmean(vy)
+    rm = np.nanmean(np.sqrt((vx - xm) ** 2 + (vy - ym) ** 2))
+
+    def err(p):
+        w, v, r = p
+        return (np.array([np.linalg.norm([x - w, y - v]) - r for x, y in zip(vx, vy)]) ** 2).sum()
+
+    xf, yf, rf = fmin(err, [xm, ym, rm], disp=False)
+    ax.add_patch(plt.Circle((xf, yf), radius=rf * 1.01, color=foreground_color, linewidth=1, fill=False))
+    return xf, yf, rf
+
+
+def mark_nodes(x, y, kind, ax=None, foreground_color='#ffffff', background_color='#000000', labels=None, label_va='center',
+               legend_label=None, test=False, **kws):
+    """safe_io.py:589-646: kind 'mark' scatters the points (kws go to scatter), 'label' writes labels[i] at each point
+    (bold, size 14, white on '#000000', else black); legend_label adds a 'Significance' legend for the marks.
+    ax None: pyplot's current axes.  Returns the axes."""
+    import matplotlib.pyplot as plt
+    if ax is None:
+        ax = plt.gca()
+    if isinstance(kind, str):
+        kind = [kind]
+    marks = None
+    if 'mark' in kind:
+        marks = ax.scatter(x, y, **kws)
+    if 'label' in kind:
+        if test:
+            print(x, y, labels)
+        assert len(x) == len(labels), f"len(x)!=len(labels): {len(x)}!={len(labels)}"
+        if test:
+            ax.plot(x, y, 'r*')
+        font = {'color': 'white' if background_color == '#000000' else 'k', 'size': 14, 'weight': 'bold'}
+        for i, label in enumerate(labels):
+            ax.text(x[i], y[i], label, fontdict=font, ha='center', va=label_va)
+    if legend_label is not None:
+        _legend(ax, [marks], [legend_label], 'Significance', foreground_color, background_color)
+    return ax
+
+
+def _legend(ax, handles, texts, title, foreground_color, background_color):
+    """The legends of the plot methods (safe_io.py:633-642, safe.py:1163-1172): upper left, texts and title in the
+    foreground colour on the background colour."""
+    leg = ax.legend(handles, texts, loc='upper left', bbox_to_anchor=(0, 1), title=title, scatterpoints=1, fancybox=False,
+                    facecolor=background_color, edgecolor=background_color)
+    for t in leg.get_texts():
+        t.set_color(foreground_color)
+    leg.get_title().set_color(foreground_color)
+    return leg
 
 
 def calculate_edge_lengths(G, verbose=True, device=0):
