@@ -35,7 +35,6 @@ constexpr int MF_R = 256;             // rows per group = 8 waves x 32
 constexpr int MF_NS = 6;              // i8 slices per value
 constexpr int MF_CN = 6;              // counts form: 32-column tiles per task (one i8 plane each)
 constexpr int MF_SS = 1024 + 16;      // LDS bytes per (k-step, slice): [2 halves][32 lanes][16 B] + 16 B skew
-constexpr int MF_KS = MF_NS * MF_SS;  // LDS bytes per k-step (32 attribute rows)
 // The general kernel's LDS form of a gathered k-step.  mf_trg(slices): rows as they come ([32 rows][RS bytes]; RS = 32 bytes per
 // slice, padded to an ODD multiple of 32 so that the eight rows a transposing read touches fall into eight different groups of
 // eight banks) and the B operand read with ds_read_b64_tr_b8; else transposed in registers by the gather threads (v_perm) into
@@ -49,7 +48,6 @@ constexpr int MF_KS = MF_NS * MF_SS;  // LDS bytes per k-step (32 attribute rows
 constexpr bool mf_trg(int ns) { return SAFE_MFMA_TRG == 2 || (SAFE_MFMA_TRG == 1 && ns >= 6); }
 constexpr int mf_rs(int ns) { return 32 * (ns | 1); }                                  // row bytes in LDS (transposing-read form)
 constexpr int mf_ks(int ns) { return mf_trg(ns) ? 32 * mf_rs(ns) : ns * MF_SS; }       // LDS bytes per k-step
-constexpr int MF_BUF = 4 * MF_KS;     // one buffer = one super-step = 4 k-steps
 constexpr int MF_MAXBLK = 4096;       // column blocks per row group the kernel can index from LDS
 constexpr int MF_SHIFT_BITS = 45;     // |q| < 2^46 after scaling: six balanced base-256 digits hold +-(2^47 - ...)
 
@@ -472,7 +470,7 @@ struct MfmaFilt {
     const double *zobs = nullptr;             // z-scores: the observed scores ns[node][column] (NaN = no test)
 };
 
-template <bool COUNTS, int NS, bool Z = false, bool SKIP = true, int EPI = 0, bool PREF = true, int FM = 0>
+template <bool COUNTS, int NS, bool Z = false, int EPI = 0, int FM = 0>
 __global__ __launch_bounds__(512) void k_permtest_mfma(
     const unsigned char *__restrict__ bs, int64_t row_bytes, int64_t tile_bytes, const int32_t *__restrict__ srcp, int64_t n_src, int n_q,
     const int32_t *__restrict__ blk_ptr, const int32_t *__restrict__ blk_kb, const uint32_t *__restrict__ blk_bits,
@@ -496,7 +494,7 @@ __global__ __launch_bounds__(512) void k_permtest_mfma(
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int lam = lane & 31, h = lane >> 5;
     // this wave's 32 rows of the group: waves w and w + 4 share a SIMD (a workgroup's waves go round the four SIMDs) and own the
-    // ADJACENT pieces 2 (w & 3) and 2 (w & 3) + 1 -- the pairing build_blocks balances, and the one k_permtest_mfma_f's
+    // ADJACENT pieces 2 (w & 3) and 2 (w & 3) + 1 -- the pairing build_blocks balances, and the one k_permtest_mfma_g's
     // 64-row waves have
     const int wrow = (2 * (wave & 3) + (wave >> 2)) * 32;
     // gather role: thread -> (k-step of the super-step, row quad, 16-byte chunk of the row segment)
@@ -686,11 +684,11 @@ __global__ __launch_bounds__(512) void k_permtest_mfma(
                 // schedule and cost four spilled registers.)
                 bool nz[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) nz[k] = !SKIP || __builtin_amdgcn_ballot_w64(aw[k] != 0u) != 0ull;
+                for (int k = 0; k < 4; ++k) nz[k] = __builtin_amdgcn_ballot_w64(aw[k] != 0u) != 0ull;
                 // PF: the B operands of k-step k+1 are read from LDS before the MFMAs of k-step k are issued (two operand sets).
                 // !PF: one operand set, read right before its MFMAs and only for the pieces that hold members -- the SIMD's other
                 // wave covers the LDS latency; the z-score form (seven slices: no room for a second set) always runs this way
-                constexpr bool PF = PREF && (!Z || NS <= 4);
+                constexpr bool PF = !Z || NS <= 4;
                 v4i b_cur[NS], b_nxt[PF ? NS : 1];
                 auto read_operand = [&](int k, int s) -> v4i {
                     if constexpr (MF_TRG) {
@@ -1036,416 +1034,29 @@ __global__ __launch_bounds__(512) void k_permtest_mfma(
 }
 
 // ---------------------------------------------------------------------------------------
-// the filtered form's own kernel (FM = 2 above is the same arithmetic in the general kernel's shape)
-// ---------------------------------------------------------------------------------------
+// k_permtest_mfma_g: the filtered 'sum' test (FM = 2 of the general kernel: same arithmetic) in a shape of its own.
 // What the general kernel's shape costs once only three slices are multiplied: every wave reads the whole operand tile from
 // LDS for its 32 rows (1 KB per MFMA), 320 of its 512 threads repeat gather loads they do not need, the membership words of a
 // k-step arrive as four scalar-width loads, and all eight waves meet at one barrier per 128 gathered rows.  Here
-//   * a workgroup is FOUR waves of 64 rows (two 32 x 32 pieces per wave: every LDS operand read feeds two MFMAs, 96
-//     accumulator registers), and TWO workgroups share a CU -- the other workgroup's matrix work covers this one's barrier,
-//     gather and score completion;
-//   * the membership words of a super-step are one 16-byte load per piece (blk_bits4: [super-step][row][4 k-steps]);
-//   * threads without a gather role take the source maps' padding block (every index = the zero row: one cache line per load
-//     instruction, no select) instead of repeating a neighbour's rows;
-//   * the thresholds are 32-bit: y = floor(V_hi / 16) against Y0 = floor((O - B') / 2^28), B' = B + 15 * 2^24, with one window
-//     width per task (from the group's largest neighborhood: neighborhoods below 2048 members); what the test leaves open is
-//     appended for k_mfma_resolve, which forms that score from all six digits (the record carries no partial sum);
-//   * <= / >= counters are 8-bit fields (two outputs per register), flushed to memory every 255 permutations.
-// (diagnostic builds) keeps a value -- and the loads / MFMAs that produce it -- alive without using it
-__device__ __forceinline__ void mf_keep(uint32_t x) { asm volatile("" ::"v"(x)); }
-__device__ __forceinline__ void mf_keep(const uint4 &x) { asm volatile("" ::"v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w)); }
-__device__ __forceinline__ void mf_keep(const v4i &x) { asm volatile("" ::"v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3])); }
-constexpr int MF_F_MAXBLK = 2048;         // column blocks per row group this kernel can index from LDS (else the general kernel)
-// DBG: diagnostic builds that skip work (WRONG results; only instantiated with -DSAFE_HIP_DIAG, selected by SAFE_HIP_MFMA_DBG):
-// 1 no transposes / LDS stores, 2 no MFMAs, 4 no barrier per super-step, 8 no score completion, 16 no membership-word loads,
-// 32 no source-index loads, 64 no row gathers, 128 always the same LDS buffer, 256 no LDS operand reads.  A template parameter:
-// as a kernel argument the tests cost the main loop 16 spilled registers and made it three times slower.
-// TR: the gathered rows go to LDS AS THEY ARE ([k][three slices x 32 bytes], one ds_write_b128 per row and thread) and the MFMA
-// operand is read with the transposing LDS read (two ds_read_b64_tr_b8 per slice and k-step: within a 16-lane group lane l
-// receives byte l & 7 of the 8-byte pieces 2 j + (l >> 3), j = 0..7 -- pieces laid over eight consecutive rows, that is column l
-// of an 8 x 16 byte tile, eight consecutive k: tools/ubench/tr8_probe.hip) -- no v_perm transposes, no 4-byte scatter stores.
-// !TR: 4 x 4 byte transposes in registers, k-contiguous LDS image, ds_read_b128 (the general kernel's operand path).
-template <int DBG, bool TR = true>
-__global__ __launch_bounds__(256, 2) void k_permtest_mfma_f(
-    const unsigned char *__restrict__ bs, int64_t tile_bytes, const int32_t *__restrict__ srcp, int64_t n_src, int n_q,
-    const int32_t *__restrict__ blk_ptr, const int32_t *__restrict__ blk_kb, const uint4 *__restrict__ blk_bits4,
-    const int32_t *__restrict__ grp_maxcnt, const int2 *__restrict__ tasks, const int32_t *__restrict__ q_off,
-    unsigned int *__restrict__ q_ctr, int64_t mloc, unsigned int *__restrict__ gl_counts, int64_t n_padr, MfmaFilt fa) {
-    constexpr int dbg = DBG;
-    constexpr int NS = MF_NS / 2, KS = TR ? 32 * NS * 32 : NS * MF_SS, BUF = 4 * KS;
-    constexpr int64_t row_bytes = NS * 32;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];       // [2][BUF] | kb list | Y0 [32][256] | counters [8][256]
-    __shared__ int slot_box;
-    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int lam = lane & 31, h = lane >> 5;
-    int32_t *kb_list = reinterpret_cast<int32_t *>(lds + 2 * BUF);
-    int32_t *y0s = reinterpret_cast<int32_t *>(lds + 2 * BUF + MF_F_MAXBLK * sizeof(int32_t)) + tid;
-    // counters: ONE 8-bit field per output in LDS ([8][256] words; output o = 16 p + r in word r & 7, byte 2 p + (r >> 3)) that counts
-    // the permutations NOT certainly greater than the observed score; flushed every 255 permutations as
-    // (#smaller << 16 | #greater) = (field << 16 | permutations - field).  An undecided compare is counted "smaller" and taken back
-    // at once (a rare global atomic of -(1 << 16)); k_mfma_resolve then adds what it really was
-    uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + 2 * BUF + MF_F_MAXBLK * sizeof(int32_t) + 32 * 256 * sizeof(int32_t)) + tid;
-    constexpr int CH = 2 * NS, GT = 4 * 8 * CH;                               // 192 gather threads = waves 0-2
-    const bool gth = tid < GT;
-    const int gt = gth ? tid : 0;
-    const int chunk = gt % CH, rq = (gt / CH) % 8, ks_g = gt / (8 * CH);
-    const int s_g = chunk >> 1, half_g = chunk & 1;
-    // TR: a thread's row i goes to [k-step][row 4 rq + i][chunk]; a lane reads the 8-byte piece (row (l & 15) >> 1 of its eight,
-    // half l & 1) of column half (lane >> 4) & 1 and k half lane >> 5 -- lane l then owns column l & 31 of the tile
-    const uint32_t w_base = TR ? static_cast<uint32_t>(ks_g * KS + (4 * rq) * 96 + chunk * 16)
-                               : static_cast<uint32_t>(ks_g * KS + s_g * MF_SS + (rq >> 2) * 512 + (4 * half_g) * 16 + (rq & 3) * 4);
-    const uint32_t r_base = TR ? static_cast<uint32_t>((16 * h + ((lane & 15) >> 1)) * 96 + 16 * ((lane >> 4) & 1) + 8 * (lane & 1))
-                               : static_cast<uint32_t>(h * 512 + lam * 16);
-    const int col_in_tile = TR ? lam : 16 * ((lam >> 2) & 1) + 4 * (lam >> 3) + (lam & 3);
-    // threads without a gather role (wave 3) take their source indices from the PADDING block of the source maps (index n_kb:
-    // every entry is the zero row n), so their four row loads hit one cache line and need no select
-    const int kb_pad = static_cast<int>(n_src / 32) - 1;
-
-    const int home = blockIdx.x & 7;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        const int qx = (home + attempt) & 7;
-        const int q_begin = q_off[qx], q_len = q_off[qx + 1] - q_begin;
-        for (;;) {
-            if (tid == 0) slot_box = static_cast<int>(atomicAdd(&q_ctr[qx], 1u));
-            __syncthreads();
-            const int slot = slot_box;
-            __syncthreads();
-            if (slot >= q_len) break;
-            const int2 task = tasks[q_begin + slot];
-            const int g = task.x, ct = task.y;
-            const int b0 = blk_ptr[g], nb = blk_ptr[g + 1] - b0, S = nb >> 2;
-            if (S == 0) continue;
-            for (int i = tid; i < nb; i += 256) kb_list[i] = blk_kb[b0 + i];
-
-            const unsigned char *bs_ct = bs + static_cast<int64_t>(ct) * tile_bytes + (gth ? chunk * 16 : 0);
-            const uint4 *bits_w = blk_bits4 + static_cast<int64_t>(b0 >> 2) * MF_R + wave * 64 + lane;   // lane l: row l of the wave's 64
-            const int total = n_q * S;
-            const int64_t colf = static_cast<int64_t>(ct) * 32 + col_in_tile;
-            const int64_t u_lane = static_cast<int64_t>(g) * MF_R + wave * 64 + 4 * h;     // + 32 p + (r & 3) + 8 (r >> 2)
-
-            // thresholds of this lane's 32 outputs (32-bit, in LDS); the window width is one number per task
-            const long long b_max = static_cast<long long>(grp_maxcnt[g]) * MF_LO_MAX;
-            const uint32_t wc = static_cast<uint32_t>((2 * b_max + (15ll << 24)) >> 28) + 2u;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                long long o64[16];
-                int32_t members[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int64_t u = u_lane + 32 * p + (r & 3) + 8 * (r >> 2);
-                    members[r] = fa.rowcnt[u];
-                    o64[r] = colf < mloc ? fa.obs64[colf * n_padr + u] : 0ll;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const long long bp = static_cast<long long>(members[r]) * MF_LO_MAX + (15ll << 24);
-                    // padding rows (-1 members) and padding columns only ever form y = 0: Y0 = 1 counts them "smaller" without any
-                    // further test (their counters are never read); an EMPTY neighborhood of a real row takes the general rule
-                    // (every compare a tie: undecided, settled as "equal" by the resolve kernel)
-                    y0s[(16 * p + r) * 256] = (colf < mloc && members[r] >= 0) ? static_cast<int32_t>((o64[r] - bp) >> 28) : 1;
-                }
-            }
-            __syncthreads();                                         // kb_list
-
-            v16i acc[2][NS];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[p][s][r] = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) cnts[j * 256] = 0;
-            int since_flush = 0;
-            unsigned long long prof_acc[5] = {0, 0, 0, 0, 0};
-
-            auto flush = [&]() __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const uint32_t w = cnts[j * 256];
-                    cnts[j * 256] = 0;
-                    if (colf < mloc) {
-#pragma unroll
-                        for (int f = 0; f < 4; ++f) {                    // byte f: piece f >> 1, accumulator element j + 8 (f & 1)
-                            const uint32_t smaller = (w >> (8 * f)) & 0xFFu;
-                            const int r = j + 8 * (f & 1);
-                            atomicAdd(&gl_counts[colf * n_padr + u_lane + 32 * (f >> 1) + (r & 3) + 8 * (r >> 2)],
-                                      (smaller << 16) | (static_cast<uint32_t>(since_flush) - smaller));
-                        }
-                    }
-                }
-            };
-            auto load_src_kb = [&](int q, int kb) -> int4 {
-                q = q < n_q ? q : n_q - 1;
-                return *reinterpret_cast<const int4 *>(srcp + static_cast<int64_t>(q) * n_src + static_cast<int64_t>(kb) * 32 + 4 * rq);
-            };
-            auto load_src = [&](int q, int t) -> int4 { return load_src_kb(q, gth ? kb_list[4 * t + ks_g] : kb_pad); };
-            auto load_rows = [&](const int4 &src, uint4 (&L)[4]) {
-                L[0] = *reinterpret_cast<const uint4 *>(bs_ct + static_cast<int64_t>(src.x) * row_bytes);
-                L[1] = *reinterpret_cast<const uint4 *>(bs_ct + static_cast<int64_t>(src.y) * row_bytes);
-                L[2] = *reinterpret_cast<const uint4 *>(bs_ct + static_cast<int64_t>(src.z) * row_bytes);
-                L[3] = *reinterpret_cast<const uint4 *>(bs_ct + static_cast<int64_t>(src.w) * row_bytes);
-            };
-            auto store_quarter = [&](const uint4 (&L)[4], int cw, int buf) {
-                unsigned char *dst = lds + buf * BUF + w_base;
-                if constexpr (TR) {
-                    uint4 v;                                                     // row cw of the thread's four, as it came
-                    v.x = cw == 0 ? L[0].x : cw == 1 ? L[1].x : cw == 2 ? L[2].x : L[3].x;
-                    v.y = cw == 0 ? L[0].y : cw == 1 ? L[1].y : cw == 2 ? L[2].y : L[3].y;
-                    v.z = cw == 0 ? L[0].z : cw == 1 ? L[1].z : cw == 2 ? L[2].z : L[3].z;
-                    v.w = cw == 0 ? L[0].w : cw == 1 ? L[1].w : cw == 2 ? L[2].w : L[3].w;
-                    *reinterpret_cast<uint4 *>(dst + cw * 96) = v;
-                    return;
-                }
-                const uint32_t w[4] = {cw == 0 ? L[0].x : cw == 1 ? L[0].y : cw == 2 ? L[0].z : L[0].w,
-                                       cw == 0 ? L[1].x : cw == 1 ? L[1].y : cw == 2 ? L[1].z : L[1].w,
-                                       cw == 0 ? L[2].x : cw == 1 ? L[2].y : cw == 2 ? L[2].z : L[2].w,
-                                       cw == 0 ? L[3].x : cw == 1 ? L[3].y : cw == 2 ? L[3].z : L[3].w};
-                uint32_t o[4];
-                transpose4(w, o);
-#pragma unroll
-                for (int b = 0; b < 4; ++b) *reinterpret_cast<uint32_t *>(dst + (b + 8 * cw) * 16) = o[b];
-            };
-            auto advance = [&](int &qq, int &tt) {
-                if (++tt == S) {
-                    tt = 0;
-                    ++qq;
-                }
-            };
-
-            // the pipeline of k_permtest_mfma: rows of super-step it + 2 requested at the top of iteration it, transposed into
-            // the other buffer during it + 1; their source indices one iteration earlier still
-            uint4 L_a[4], L_b[4];
-            int4 src_a = make_int4(0, 0, 0, 0), src_b = make_int4(0, 0, 0, 0);
-            int q1 = 0, t1 = 0, q2, t2, q3, t3;
-            advance(q1, t1);
-            q2 = q1, t2 = t1;
-            advance(q2, t2);
-            {
-                const int4 s0 = load_src(0, 0);
-                load_rows(s0, L_b);
-                const int4 s1 = load_src(q1, t1);
-                load_rows(s1, L_a);
-                src_a = load_src(q2, t2);
-                if (gth) {
-#pragma unroll
-                    for (int cw = 0; cw < 4; ++cw) store_quarter(L_b, cw, 0);
-                }
-            }
-            // membership words of a super-step: lane l loads the four words of row l; v_permlane32_swap then gives every lane the
-            // words of row (l & 31) of piece 0 and of piece 1 (one 16-byte load per lane instead of two)
-            auto split_rows = [&](const uint4 &raw, uint4 (&w)[2]) __attribute__((always_inline)) {
-                typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-                const v2u x = __builtin_amdgcn_permlane32_swap(raw.x, raw.x, false, false);
-                const v2u y = __builtin_amdgcn_permlane32_swap(raw.y, raw.y, false, false);
-                const v2u z = __builtin_amdgcn_permlane32_swap(raw.z, raw.z, false, false);
-                const v2u ww = __builtin_amdgcn_permlane32_swap(raw.w, raw.w, false, false);
-                w[0] = make_uint4(x[0], y[0], z[0], ww[0]);
-                w[1] = make_uint4(x[1], y[1], z[1], ww[1]);
-            };
-            uint4 aw[2];
-            split_rows(bits_w[0], aw);
-            int kb_next;                                             // column block of the source indices requested next (read one iteration early)
-            {
-                int q3p = q2, t3p = t2;
-                advance(q3p, t3p);
-                kb_next = gth ? kb_list[4 * t3p + ks_g] : kb_pad;
-            }
-            __syncthreads();
-
-            int q = 0, t = 0;
-            auto body = [&](int it, uint4 (&L_store)[4], uint4 (&L_load)[4], const int4 &src_use, int4 &src_load)
-                            __attribute__((always_inline)) {
-                const int buf = it & 1;
-                q3 = q2, t3 = t2;
-                advance(q3, t3);
-                const bool more1 = it + 1 < total;
-                unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-                if (dbg & 512) c0 = __builtin_amdgcn_s_memtime();
-                uint4 aw_raw = aw[0];
-                if (!(dbg & 16)) aw_raw = bits_w[static_cast<int64_t>(t1) * MF_R];
-                if (!(dbg & 32)) src_load = load_src_kb(q3, kb_next);
-                {
-                    int q4 = q3, t4 = t3;
-                    advance(q4, t4);
-                    kb_next = gth ? kb_list[4 * t4 + ks_g] : kb_pad;      // (consumed at the top of the next iteration: no wait here)
-                }
-                // the four row loads of the gather are issued one per k-step below: right after the barrier all four waves of the
-                // workgroup (and often the CU's other workgroup) would queue 24 of them at once -- a wave spent ~450 cycles per
-                // super-step getting its six loads accepted
-                const int32_t row_of[4] = {src_use.x, src_use.y, src_use.z, src_use.w};
-
-                const unsigned char *bbuf = lds + ((dbg & 128) ? 0 : buf * BUF) + r_base;
-                if (dbg & 512) c1 = __builtin_amdgcn_s_memtime();
-                // two operand sets: the slices of k-step k + 1 are read before the MFMAs of k-step k are issued
-                v4i b_cur[NS], b_nxt[NS];
-                auto read_operand = [&](int k, int s) -> v4i {
-                    if constexpr (TR) {
-                        typedef int v2i __attribute__((ext_vector_type(2)));
-                        typedef __attribute__((address_space(3))) v2i lds_v2i;
-                        const unsigned char *at = bbuf + k * KS + s * 32;
-                        const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i *)(at));             // k = 16 h + 0..7
-                        const v2i hi = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_v2i *)(at + 8 * 96));    // k = 16 h + 8..15
-                        v4i r;
-                        r[0] = lo[0], r[1] = lo[1], r[2] = hi[0], r[3] = hi[1];
-                        return r;
-                    } else {
-                        return *reinterpret_cast<const v4i *>(bbuf + k * KS + s * MF_SS);
-                    }
-                };
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    if (!(dbg & 256)) b_cur[s] = read_operand(0, s);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (k < 3) {
-#pragma unroll
-                        for (int s = 0; s < NS; ++s)
-                            if (!(dbg & 256)) b_nxt[s] = read_operand(k + 1, s);
-                    }
-                    if (!(dbg & 64)) L_load[k] = *reinterpret_cast<const uint4 *>(bs_ct + static_cast<int64_t>(row_of[k]) * row_bytes);
-                    __builtin_amdgcn_sched_barrier(0);               // the reads and the row load stay ahead of this k-step's MFMAs
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const uint32_t word = k == 0 ? aw[p].x : k == 1 ? aw[p].y : k == 2 ? aw[p].z : aw[p].w;
-                        if (dbg & 2) {
-                            mf_keep(word);
-#pragma unroll
-                            for (int s = 0; s < NS; ++s) mf_keep(b_cur[s]);
-                        }
-                        if (__builtin_amdgcn_ballot_w64(word != 0u) != 0ull && !(dbg & 2)) {   // (a piece without members is skipped)
-                            v4i a;
-                            if (dbg & 1024) {                        // (diagnostic: what a FREE bit -> i8 expansion would give)
-                                a[0] = a[1] = a[2] = a[3] = static_cast<int>(word);
-                            } else {
-                                a[0] = static_cast<int>(expand4(word, 16 * h));
-                                a[1] = static_cast<int>(expand4(word, 16 * h + 4));
-                                a[2] = static_cast<int>(expand4(word, 16 * h + 8));
-                                a[3] = static_cast<int>(expand4(word, 16 * h + 12));
-                            }
-#pragma unroll
-                            for (int s = 0; s < NS; ++s) acc[p][s] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b_cur[s], acc[p][s], 0, 0, 0);
-                        }
-                    }
-                    if (gth && more1 && !(dbg & 1)) store_quarter(L_store, k, buf ^ 1);
-                    if ((dbg & 1) && k == 3) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) mf_keep(L_store[i]);
-                    }
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) b_cur[s] = b_nxt[s];
-                }
-                uint4 aw_next[2];
-                split_rows(aw_raw, aw_next);
-
-                if (dbg & 512) c2 = __builtin_amdgcn_s_memtime();
-                if (t == S - 1 && !(dbg & 8)) {                      // the scores of permutation q are complete
-                    uint32_t open = 0;                                // outputs the test leaves undecided
-                    const int32_t wcs = static_cast<int32_t>(wc);
-#pragma unroll
-                    for (int jb = 0; jb < 2; ++jb) {                  // sixteen outputs (four counter words) at a time: their thresholds are read together
-                        int32_t y0v[4][4];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                            for (int f = 0; f < 4; ++f) y0v[jj][f] = y0s[(16 * (f >> 1) + 4 * jb + jj + 8 * (f & 1)) * 256];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const int j = 4 * jb + jj;
-                            uint32_t inc = 0;
-#pragma unroll
-                            for (int f = 0; f < 4; ++f) {
-                                const int p = f >> 1, r = j + 8 * (f & 1);
-                                const int32_t y = acc[p][2][r] * 4096 + acc[p][1][r] * 16 + (acc[p][0][r] >> 4);   // floor(V_hi / 16)
-                                const int32_t d = y - y0v[jj][f];
-                                inc |= (d < wcs) ? (1u << (8 * f)) : 0u;               // not certainly greater (d < 0: certainly smaller)
-                                open |= (static_cast<uint32_t>(d) < wc) ? (1u << (16 * p + r)) : 0u;
-                            }
-                            if (inc) __hip_atomic_fetch_add(&cnts[j * 256], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                    }
-                    if (__builtin_expect(open != 0u, 0)) {
-                        // rare (~1e-5 of the compares): the resolve kernel forms the exact score from all six digits.  (Nothing here
-                        // touches the accumulators: a per-lane loop that indexed them dynamically moved all 96 of them to scratch
-                        // memory, unrolled copies cost the main loop its registers.)
-                        for (uint32_t left = open; left;) {
-                            const int o = __builtin_ctz(left);
-                            left &= left - 1u;
-                            const int64_t u = u_lane + 32 * (o >> 4) + (o & 3) + 8 * ((o & 15) >> 2);
-                            atomicAdd(&gl_counts[colf * n_padr + u], 0xFFFF0000u);       // it was counted "smaller" above: taken back
-                            const unsigned int at = atomicAdd(fa.amb_count, 1u);
-                            if (at < fa.amb_cap)
-                                fa.amb[at] = make_ulonglong2(static_cast<unsigned long long>(u) | (static_cast<unsigned long long>(colf) << 32),
-                                                             (1ull << 63) | static_cast<unsigned long long>(fa.p_base + q));
-                        }
-                    }
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                        for (int s = 0; s < NS; ++s)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[p][s][r] = 0;
-                    if (++since_flush == 255) {
-                        flush();
-                        since_flush = 0;
-                    }
-                }
-#pragma unroll
-                for (int p = 0; p < 2; ++p) aw[p] = aw_next[p];
-                if (dbg & 512) {
-                    mf_keep(aw[0]);                                  // (the wait for the membership words belongs to this phase)
-                    mf_keep(aw[1]);
-                    c3 = __builtin_amdgcn_s_memtime();
-                }
-                if (!(dbg & 4)) __syncthreads();
-                if (dbg & 512) {
-                    const unsigned long long c4 = __builtin_amdgcn_s_memtime();
-                    prof_acc[0] += c1 - c0;                          // issue of the look-ahead loads
-                    prof_acc[1] += c2 - c1;                          // operand reads, MFMAs, transposed stores
-                    prof_acc[2] += c3 - c2;                          // score completion (+ the wait for the next membership words)
-                    prof_acc[3] += c4 - c3;                          // barrier
-                    prof_acc[4] += 1;
-                }
-                q = q1, t = t1;
-                q1 = q2, t1 = t2;
-                q2 = q3, t2 = t3;
-            };
-            for (int it = 0; it < total; it += 2) {
-                body(it, L_a, L_b, src_a, src_b);
-                if (it + 1 < total) body(it + 1, L_b, L_a, src_b, src_a);
-            }
-            if ((dbg & 512) && lane == 0 && fa.prof) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    atomicAdd(&fa.prof[wave * 8 + i], prof_acc[i]);
-                    prof_acc[i] = 0;
-                }
-            }
-            if (since_flush) flush();
-            if (dbg & 8) {
-#pragma unroll
-                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                    for (int s = 0; s < NS; ++s)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) mf_keep(static_cast<uint32_t>(acc[p][s][r]));
-            }
-            __syncthreads();                                         // kb_list / buffers / thresholds are reused by the next task
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------
-// k_permtest_mfma_g (round 6): k_permtest_mfma_f's shape -- four waves of 64 rows, two workgroups per CU, thresholds and 8-bit
-// counters in LDS -- with three changes that take instructions and waits out of the super-step:
+//  * a workgroup is FOUR waves of 64 rows (two 32 x 32 pieces per wave: every LDS operand read feeds two MFMAs, 96
+//    accumulator registers), and TWO workgroups share a CU -- the other workgroup's matrix work covers this one's barrier,
+//    gather and score completion;
+//  * the membership words of a super-step are one 16-byte load per piece ([super-step][row][4 k-steps]);
+//  * the gathered rows lie in LDS AS THEY ARE and the MFMA operand is read with the transposing LDS read (two ds_read_b64_tr_b8
+//    per slice and k-step: within a 16-lane group lane l receives byte l & 7 of the 8-byte pieces 2 j + (l >> 3), j = 0..7 --
+//    pieces laid over eight consecutive rows, that is column l of an 8 x 16 byte tile, eight consecutive k:
+//    tools/ubench/tr8_probe.hip) -- no v_perm transposes, no 4-byte scatter stores;
+//  * the thresholds are 32-bit: y = floor(V_hi / 16) against Y0 = floor((O - B') / 2^28), B' = B + 15 * 2^24, with one window
+//    width per task (from the group's largest neighborhood: neighborhoods below 2048 members); what the test leaves open is
+//    appended for k_mfma_resolve, which forms that score from all six digits (the record carries no partial sum);
+//  * <= / >= counters are 8-bit fields in LDS (two outputs per register), flushed to memory every 255 permutations;
 //  * the gather is LDS-DMA (global_load_lds_dwordx4).  A super-step's gathered rows lie in LDS as they are in memory,
 //    [k-step][32 rows][96 bytes]; the DMA's destination is wave-uniform base + lane x 16, so the 192 16-byte chunks of a
 //    k-step are three wave-instructions: wave w stages k-step w, lane l of instruction j the chunk 64 j + l = row (64 j + l) / 6,
 //    bytes 16 ((64 j + l) % 6) .. -- six adjacent lanes read one 96-byte row (1-2 cache lines; a first form with one row per
 //    lane and [plane][row][16 B] in LDS touched 64 lines per instruction and spent 530 cycles per super-step issuing them).
-//    No staging registers (k_permtest_mfma_f: 32), no ds_write, no wait for gathered rows inside the k-loop, all four waves
-//    take part.  The DMAs of super-step it + 1 are issued at the top of super-step it (their buffer was last read in it - 1:
+//    No staging registers (a register-staged gather held 32), no ds_write, no wait for gathered rows inside the k-loop, all four
+//    waves take part.  The DMAs of super-step it + 1 are issued at the top of super-step it (their buffer was last read in it - 1:
 //    the barrier in between orders that) and have the whole super-step to land; the one vmcnt(0) is in front of the barrier.
 //  * the membership words come bit-permuted (bs_bits4p): operand register j of lane half h = (word >> (4 h + j)) & 0x01010101 --
 //    8 VALU per 32 x 32 piece instead of 12 (bit-field extract, multiply, mask per four bits).
@@ -1453,8 +1064,15 @@ __global__ __launch_bounds__(256, 2) void k_permtest_mfma_f(
 //    signs of a counter word are collected with one v_alignbit each (top bytes side by side, one AND + shift per word), and
 //    "undecided" (-W <= d' < 0) is detected for the lane's 32 outputs at once from the unsigned maximum of d' (v_max3_u32);
 //    the per-output mask is only formed in the rare wave that has one (2.5 % of the wave-permutations at configs[4]).
-// DBG (diagnostic builds only): 2 no MFMAs (nor expansions), 4 no barrier, 8 no score completion, 64 no DMA, 512 per-phase cycle
-// counters, 1024 the operand registers without their expansion (the word itself: what a FREE bit -> i8 expansion would give).
+// DBG: diagnostic builds that skip work (WRONG results; only instantiated with -DSAFE_HIP_DIAG, selected by SAFE_HIP_MFMA_DBG):
+// 2 no MFMAs (nor expansions), 4 no barrier, 8 no score completion, 64 no DMA, 512 per-phase cycle counters, 1024 the operand
+// registers without their expansion (the word itself: what a FREE bit -> i8 expansion would give).  A template parameter: as a
+// kernel argument the tests cost the main loop 16 spilled registers and made it three times slower.
+// (diagnostic builds) mf_keep keeps a value -- and the loads / MFMAs that produce it -- alive without using it
+__device__ __forceinline__ void mf_keep(uint32_t x) { asm volatile("" ::"v"(x)); }
+__device__ __forceinline__ void mf_keep(const uint4 &x) { asm volatile("" ::"v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w)); }
+__device__ __forceinline__ void mf_keep(const v4i &x) { asm volatile("" ::"v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3])); }
+constexpr int MF_F_MAXBLK = 2048;         // column blocks per row group this kernel can index from LDS (else the general kernel)
 template <int DBG>
 __global__ __launch_bounds__(256, 2) void k_permtest_mfma_g(
     const unsigned char *__restrict__ bs, int64_t tile_bytes, const int32_t *__restrict__ srcp, int64_t n_src, int n_q,
@@ -1815,7 +1433,7 @@ __global__ __launch_bounds__(256, 2) void k_permtest_mfma_g(
 // observed scores.
 // DBG (diagnostic builds only): 2 no MFMAs, 4 no barrier, 8 no score completion, 64 no DMA, 512 per-phase cycle counters.
 constexpr int MF_GZ_MAXBLK = 1024;        // column blocks per row group this kernel can index from LDS (else the general kernel)
-// F32 (default): the same decision in single precision.  In units of 2^24 x the value grid, u = the high value sum, w = the high
+// The decision is made in single precision.  In units of 2^24 x the value grid, u = the high value sum, w = the high
 // sum of squares, c = count, d = c x MF_LO_MAX / 2^24 >= |low parts|:
 //     T' = u^2 - rho gamma w c,   gamma = sc2 / (sc1^2 2^24) (a power of two),   rho = o^2 / (1 + o^2)   (T = T' x a positive factor)
 //     |T' - its true value| <= d (2 |u| + d) + rho gamma c d     (the low parts)   +   2^-21 (u^2 + rho gamma |w| c)   (f32 roundings)
@@ -1823,7 +1441,7 @@ constexpr int MF_GZ_MAXBLK = 1024;        // column blocks per row group this ke
 // already include the reference's own roundings), so every compare this form decides the f64 form decides the same way, and the
 // counters stay equal to the seven-slice kernel's; per output the workgroup keeps copysign(rho, o) as f32 in LDS (NaN = no test).
 // 16 outputs cost ~800 VALU instructions instead of ~2850 (f64 products, 64-bit sums and two exchanges per output).
-template <int DBG, bool F32 = true>
+template <int DBG>
 __global__ __launch_bounds__(256, 2) void k_permtest_mfma_gz(
     const unsigned char *__restrict__ bs, int64_t tile_bytes, const int32_t *__restrict__ srcp, int64_t n_src, int n_q,
     const int32_t *__restrict__ blk_ptr, const int32_t *__restrict__ blk_kb, const uint4 *__restrict__ blk_bits4p,
@@ -1833,13 +1451,12 @@ __global__ __launch_bounds__(256, 2) void k_permtest_mfma_gz(
     constexpr int dbg = DBG;
     constexpr int NS = MF_NS / 2 + 1, KS = 32 * NS * 32, BUF = 4 * KS;        // k-step = 32 rows x 128 B, buffer = one super-step = 16 KB
     constexpr int64_t row_bytes = NS * 32;
-    // ONE shared array: [2][BUF] | kb list | observed scores f64 [16][256] | counters [8][256] | task slot
+    // ONE shared array: [2][BUF] | kb list | copysign(rho, o) f32 [16][256] (in a space of 16 x 256 x 8 bytes) | counters [8][256] | task slot
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int lam = lane & 31, h = lane >> 5;
     int32_t *kb_list = reinterpret_cast<int32_t *>(lds + 2 * BUF);
-    long long *obs = reinterpret_cast<long long *>(lds + 2 * BUF + MF_GZ_MAXBLK * sizeof(int32_t)) + tid;
-    float *rhos = reinterpret_cast<float *>(lds + 2 * BUF + MF_GZ_MAXBLK * sizeof(int32_t)) + tid;      // (F32: the same space, [16][256] floats)
+    float *rhos = reinterpret_cast<float *>(lds + 2 * BUF + MF_GZ_MAXBLK * sizeof(int32_t)) + tid;
     uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + 2 * BUF + MF_GZ_MAXBLK * sizeof(int32_t) + 16 * 256 * sizeof(long long)) + tid;
     int *slot_box = reinterpret_cast<int *>(lds + 2 * BUF + MF_GZ_MAXBLK * sizeof(int32_t) + 16 * 256 * sizeof(long long) + 8 * 256 * sizeof(uint32_t));
     typedef __attribute__((address_space(3))) unsigned char lds_byte;
@@ -1890,13 +1507,9 @@ __global__ __launch_bounds__(256, 2) void k_permtest_mfma_gz(
                     const int32_t node = rowmap[u_lane + 32 * p + (r & 3) + 8 * (r >> 2)];
                     const bool live = node >= 0 && colz < mloc;
                     const double o = live ? fa.zobs[static_cast<int64_t>(node) * mloc + colz] : __longlong_as_double(0x7FF8000000000000ll);
-                    if constexpr (F32) {
-                        const double o2 = o * o;
-                        const double rho = o2 > 0x1p1000 ? 1.0 : o2 / (1.0 + o2);            // (o = +-inf: the limit)
-                        rhos[(8 * p + rr) * 256] = o == o ? copysignf(static_cast<float>(rho), o < 0.0 ? -1.0f : 1.0f) : __int_as_float(0x7FC00000);
-                    } else {
-                        obs[(8 * p + rr) * 256] = __double_as_longlong(o);
-                    }
+                    const double o2 = o * o;
+                    const double rho = o2 > 0x1p1000 ? 1.0 : o2 / (1.0 + o2);                // (o = +-inf: the limit)
+                    rhos[(8 * p + rr) * 256] = o == o ? copysignf(static_cast<float>(rho), o < 0.0 ? -1.0f : 1.0f) : __int_as_float(0x7FC00000);
                 }
             const float gamma = static_cast<float>(sc2 / (sc1sq * 16777216.0));            // (powers of two: exact)
             __syncthreads();                                         // kb_list
@@ -2061,66 +1674,35 @@ __global__ __launch_bounds__(256, 2) void k_permtest_mfma_gz(
 #pragma unroll
                             for (int e = 0; e < 2; ++e) {
                                 const int rr = 2 * rp + e;
-                                if constexpr (F32) {
-                                    auto hi_sum = [&](int r) -> float {           // acc2 x 65536 + acc1 x 256 + acc0 (each below 2^24: exact conversions)
-                                        return fmaf(static_cast<float>(acc[p][2][r]), 65536.0f,
-                                                    fmaf(static_cast<float>(acc[p][1][r]), 256.0f, static_cast<float>(acc[p][0][r])));
-                                    };
-                                    // (selects between the value lane's and the squares' lane's roles are bit selects with a per-lane mask,
-                                    // the decision is mask logic without short-circuit branches: as written with ?: and && the compiler
-                                    // re-derived the lane predicate for every select and branched around every clause -- 2700 instructions)
-                                    const uint32_t m_lo = __float_as_uint(hi_sum(rr)), m_hi = __float_as_uint(hi_sum(rr + 8));
-                                    const uint32_t got = static_cast<uint32_t>(__shfl_xor(static_cast<int>((m_lo & sq_mask) | (m_hi & ~sq_mask)), 16));
-                                    const float u = __uint_as_float((got & sq_mask) | (m_lo & ~sq_mask));      // high sum of values of MY row
-                                    const float w = __uint_as_float((m_hi & sq_mask) | (got & ~sq_mask));      // high sum of squares
-                                    const float cf = static_cast<float>(static_cast<int>((static_cast<uint32_t>(acc[p][3][rr + 8]) & sq_mask) |
-                                                                                         (static_cast<uint32_t>(acc[p][3][rr]) & ~sq_mask)));
-                                    const float rs = rhos[(8 * p + rr) * 256], rho = fabsf(rs);
-                                    const float d = cf * (static_cast<float>(MF_LO_MAX) / 16777216.0f * 1.000244140625f);   // >= the low parts, in units of 2^24
-                                    const float au = fabsf(u), uu = u * u, gwc = (gamma * w) * cf, kwc = rho * gwc;
-                                    const float slack_u = d * fmaf(2.0f, au, d), gcd = gamma * (cf * d);
-                                    const float T = uu - kwc, V = gwc - uu;
-                                    const float e_t = fmaf(0x1p-19f, uu + fabsf(kwc), fmaf(rho, gcd, slack_u) * 1.0009765625f);
-                                    const float e_v = fmaf(0x1p-18f, uu + fabsf(gwc), (slack_u + gcd) * 1.0009765625f);
-                                    const float m_s = fmaf(au, 0x1p-20f, d);
-                                    // (observed NaN: no test; fewer than 3 values: the permuted score is NaN -- safe_extras.py:30)
-                                    const bool live = (rs == rs) & (cf >= 3.0f), ok = live & (V > e_v);
-                                    const bool t_pos = T > e_t, t_neg = -T > e_t, s_pos = u > m_s, s_neg = -u > m_s;
-                                    const bool nn = __float_as_int(rs) >= 0;                                   // o >= 0
-                                    const bool greater = ok & ((nn & s_pos & t_pos) | (!nn & (s_pos | t_neg)));
-                                    const bool smaller = ok & ((nn & (s_neg | t_neg)) | (!nn & s_neg & t_pos));
-                                    inc |= (greater ? (1u << (16 * e)) : 0u) | (smaller ? (1u << (16 * e + 8)) : 0u);
-                                    undecided |= (live & !greater & !smaller) ? (1u << (8 * p + rr)) : 0u;
-                                } else {
-                                long long x = static_cast<long long>(acc[p][2][rr]), y = static_cast<long long>(acc[p][2][rr + 8]);
-#pragma unroll
-                                for (int s = 1; s >= 0; --s) {
-                                    x = (x << 8) + static_cast<long long>(acc[p][s][rr]);
-                                    y = (y << 8) + static_cast<long long>(acc[p][s][rr + 8]);
-                                }
-                                const long long give = sq ? x : y;
-                                const int g_lo = __shfl_xor(static_cast<int>(give), 16), g_hi = __shfl_xor(static_cast<int>(give >> 32), 16);
-                                const long long got = (static_cast<long long>(g_hi) << 32) | static_cast<long long>(static_cast<uint32_t>(g_lo));
-                                const long long v = sq ? got : x, w = sq ? y : got;        // sums / sums of squares (high digits) of MY row
-                                const double o = __longlong_as_double(obs[(8 * p + rr) * 256]);
-                                const double members = static_cast<double>(sq ? acc[p][3][rr + 8] : acc[p][3][rr]);   // (the not-NaN slice is in both halves)
-                                if (o == o && members >= 3.0) {                  // (observed NaN: no test; fewer than 3 values: the score is NaN -- safe_extras.py:30)
-                                    const double a = static_cast<double>(v) * 16777216.0, b = static_cast<double>(w) * 16777216.0;
-                                    const double eb = members * static_cast<double>(MF_LO_MAX);
-                                    const double o2 = o * o, k1 = sc1sq * (1.0 + o2), k2 = o2 * sc2;
-                                    const double slack1 = 2.0 * fabs(a) * eb + eb * eb;                      // |S1^2 - a^2| <=
-                                    const double p1 = a * a * k1, p2 = b * members * k2;
-                                    const double T = p1 - p2;
-                                    const double E = k1 * slack1 + k2 * members * eb + (p1 + fabs(p2)) * 0x1p-40;
-                                    const double V = b * members * sc2 - a * a * sc1sq;                      // count^2 * variance, high parts
-                                    const bool var_ok = V - (sc2 * members * eb + sc1sq * slack1) > fabs(b) * members * sc2 * 0x1p-20;
-                                    const bool t_pos = T > E, t_neg = T < -E, s_pos = a > eb, s_neg = a < -eb;
-                                    const bool greater = var_ok && (o >= 0.0 ? (s_pos && t_pos) : (s_pos || t_neg));
-                                    const bool smaller = var_ok && (o >= 0.0 ? (s_neg || t_neg) : (s_neg && t_pos));
-                                    inc |= greater ? (1u << (16 * e)) : (smaller ? (1u << (16 * e + 8)) : 0u);
-                                    undecided |= (!greater && !smaller) ? (1u << (8 * p + rr)) : 0u;
-                                }
-                            }
+                                auto hi_sum = [&](int r) -> float {           // acc2 x 65536 + acc1 x 256 + acc0 (each below 2^24: exact conversions)
+                                    return fmaf(static_cast<float>(acc[p][2][r]), 65536.0f,
+                                                fmaf(static_cast<float>(acc[p][1][r]), 256.0f, static_cast<float>(acc[p][0][r])));
+                                };
+                                // (selects between the value lane's and the squares' lane's roles are bit selects with a per-lane mask,
+                                // the decision is mask logic without short-circuit branches: as written with ?: and && the compiler
+                                // re-derived the lane predicate for every select and branched around every clause -- 2700 instructions)
+                                const uint32_t m_lo = __float_as_uint(hi_sum(rr)), m_hi = __float_as_uint(hi_sum(rr + 8));
+                                const uint32_t got = static_cast<uint32_t>(__shfl_xor(static_cast<int>((m_lo & sq_mask) | (m_hi & ~sq_mask)), 16));
+                                const float u = __uint_as_float((got & sq_mask) | (m_lo & ~sq_mask));      // high sum of values of MY row
+                                const float w = __uint_as_float((m_hi & sq_mask) | (got & ~sq_mask));      // high sum of squares
+                                const float cf = static_cast<float>(static_cast<int>((static_cast<uint32_t>(acc[p][3][rr + 8]) & sq_mask) |
+                                                                                     (static_cast<uint32_t>(acc[p][3][rr]) & ~sq_mask)));
+                                const float rs = rhos[(8 * p + rr) * 256], rho = fabsf(rs);
+                                const float d = cf * (static_cast<float>(MF_LO_MAX) / 16777216.0f * 1.000244140625f);   // >= the low parts, in units of 2^24
+                                const float au = fabsf(u), uu = u * u, gwc = (gamma * w) * cf, kwc = rho * gwc;
+                                const float slack_u = d * fmaf(2.0f, au, d), gcd = gamma * (cf * d);
+                                const float T = uu - kwc, V = gwc - uu;
+                                const float e_t = fmaf(0x1p-19f, uu + fabsf(kwc), fmaf(rho, gcd, slack_u) * 1.0009765625f);
+                                const float e_v = fmaf(0x1p-18f, uu + fabsf(gwc), (slack_u + gcd) * 1.0009765625f);
+                                const float m_s = fmaf(au, 0x1p-20f, d);
+                                // (observed NaN: no test; fewer than 3 values: the permuted score is NaN -- safe_extras.py:30)
+                                const bool live = (rs == rs) & (cf >= 3.0f), ok = live & (V > e_v);
+                                const bool t_pos = T > e_t, t_neg = -T > e_t, s_pos = u > m_s, s_neg = -u > m_s;
+                                const bool nn = __float_as_int(rs) >= 0;                                   // o >= 0
+                                const bool greater = ok & ((nn & s_pos & t_pos) | (!nn & (s_pos | t_neg)));
+                                const bool smaller = ok & ((nn & (s_neg | t_neg)) | (!nn & s_neg & t_pos));
+                                inc |= (greater ? (1u << (16 * e)) : 0u) | (smaller ? (1u << (16 * e + 8)) : 0u);
+                                undecided |= (live & !greater & !smaller) ? (1u << (8 * p + rr)) : 0u;
                             }
                             if (inc) __hip_atomic_fetch_add(&cnts[(4 * p + rp) * 256], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         }
@@ -2401,7 +1983,7 @@ int build_blocks(safe_nbr *nbr) {
         std::copy(g_kbs[g].begin(), g_kbs[g].end(), kbs.begin() + ptr[g]);
         std::copy(g_bits[g].begin(), g_bits[g].end(), bits.begin() + static_cast<size_t>(ptr[g]) * MF_R);
     }
-    // the same bits with the four blocks of a super-step side by side, and the largest neighborhood of every group
+    // the same bits with the four blocks of a super-step side by side (a host temporary), and the largest neighborhood of every group
     std::vector<uint32_t> bits4(bits.size());
     for (size_t b = 0; b < kbs.size(); ++b)
         for (int r = 0; r < MF_R; ++r) bits4[((b >> 2) * MF_R + r) * 4 + (b & 3)] = bits[b * MF_R + r];
@@ -2438,9 +2020,7 @@ int build_blocks(safe_nbr *nbr) {
     SAFE_TRY(dev_alloc(&nbr->bs_rowcnt, n_groups * MF_R));
     SAFE_TRY(dev_alloc(&nbr->bs_ptr, n_groups + 1));
     SAFE_TRY(dev_alloc(&nbr->bs_grpmax, n_groups));
-    SAFE_TRY(dev_alloc(&nbr->bs_bits4, bits4.size() / 4));
     SAFE_HIP_CHECK(hipMemcpy(nbr->bs_grpmax, h_grpmax.data(), h_grpmax.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!bits4.empty()) SAFE_HIP_CHECK(hipMemcpy(nbr->bs_bits4, bits4.data(), bits4.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     SAFE_TRY(dev_alloc(&nbr->bs_bits4p, bits4p.size() / 4));
     if (!bits4p.empty()) SAFE_HIP_CHECK(hipMemcpy(nbr->bs_bits4p, bits4p.data(), bits4p.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     SAFE_TRY(dev_alloc(&nbr->bs_kb, kbs.size()));
@@ -2456,7 +2036,6 @@ int build_blocks(safe_nbr *nbr) {
     if (getenv("SAFE_HIP_MFMA_DBG_NOMEMBERS") && !bits.empty())          // diagnostic: every piece empty -> no MFMA is issued (wrong results)
     {
         SAFE_HIP_CHECK(hipMemset(nbr->bs_bits, 0, bits.size() * sizeof(uint32_t)));
-        SAFE_HIP_CHECK(hipMemset(nbr->bs_bits4, 0, bits.size() * sizeof(uint32_t)));
         SAFE_HIP_CHECK(hipMemset(nbr->bs_bits4p, 0, bits.size() * sizeof(uint32_t)));
     }
 #endif
@@ -2755,9 +2334,9 @@ int counts_setup(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, in
                                attr->col_stride, col0, mloc, n_grp, cs->d_bs);
     }
     const size_t lds_bytes = 2 * (4 * mf_ks(MF_CN)) + MF_MAXBLK * sizeof(int32_t);
-    for (const void *fn : {reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, true, 0>),
-                           reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, true, 1>),
-                           reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, true, 2>)})
+    for (const void *fn : {reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, 0>),
+                           reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, 1>),
+                           reinterpret_cast<const void *>(k_permtest_mfma<true, MF_CN, false, 2>)})
         SAFE_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
     return SAFE_OK;
 }
@@ -2766,7 +2345,7 @@ void counts_launch(safe_ctx *ctx, safe_nbr *nbr, const CountsSetup &cs, const Hy
     const size_t lds_bytes = 2 * (4 * mf_ks(MF_CN)) + MF_MAXBLK * sizeof(int32_t);
     const int64_t blocks = std::min<int64_t>(static_cast<int64_t>(cs.tasks->size()), std::max(1, ctx->num_cu - spare_cus));
 #define COUNTS_LAUNCH(EPI)                                                                                                              \
-    hipLaunchKernelGGL((k_permtest_mfma<true, MF_CN, false, true, EPI>), dim3(blocks), dim3(512), lds_bytes, ctx->stream, cs.d_bs,      \
+    hipLaunchKernelGGL((k_permtest_mfma<true, MF_CN, false, EPI>), dim3(blocks), dim3(512), lds_bytes, ctx->stream, cs.d_bs,      \
                        cs.row_bytes, static_cast<int64_t>(MF_CN * 32), cs.d_src, cs.n_src, 1, nbr->bs_ptr, nbr->bs_kb, nbr->bs_bits,    \
                        cs.d_tasks, cs.d_qoff, cs.d_qctr, cs.mloc, static_cast<unsigned int *>(nullptr), nbr->bs_groups * MF_R,           \
                        nbr->bs_rowmap, static_cast<const double *>(nullptr), static_cast<double *>(nullptr), hl, MfmaFilt{})
@@ -3040,10 +2619,9 @@ void nbr_free_blocks(safe_nbr *nbr) {
     (void)hipFree(nbr->bs_rowmap);
     (void)hipFree(nbr->bs_rowcnt);
     (void)hipFree(nbr->bs_grpmax);
-    (void)hipFree(nbr->bs_bits4);
     (void)hipFree(nbr->bs_bits4p);
     nbr->bs_rowcnt = nbr->bs_grpmax = nullptr;
-    nbr->bs_bits4 = nbr->bs_bits4p = nullptr;
+    nbr->bs_bits4p = nullptr;
     (void)hipFree(nbr->bs_ptr);
     (void)hipFree(nbr->bs_kb);
     (void)hipFree(nbr->bs_bits);
@@ -3053,20 +2631,460 @@ void nbr_free_blocks(safe_nbr *nbr) {
     nbr->counts_tasks_grp = -1;
 }
 
+// ---- the switches that steer the permutation test's matrix-core path: read from the environment here and nowhere else (on
+//      every call: a process may change them between calls)
+struct MfmaSwitches {
+    bool force_mfma = false;       // SAFE_HIP_FORCE_PATH=mfma: whatever the network's size, and even where the column check declines
+    bool force_other = false;      // SAFE_HIP_FORCE_PATH=gather / lds: never
+    bool z = true;                 // SAFE_HIP_MFMA_Z=0: z-scores stay on the f64 kernels
+    bool filter = true;            // SAFE_HIP_MFMA_FILTER=0: all six slices on the matrix cores
+    bool general = false;          // SAFE_HIP_MFMA_FORM=general: the general kernel's FM = 2 where _g / _gz would run (any other value: the default)
+    unsigned int filter_cap = 0;   // SAFE_HIP_MFMA_FILTER_CAP: entries of a launch's list of undecided compares (tests: force the fall-back); 0: by size
+};
+static MfmaSwitches mfma_switches() {
+    const auto is = [](const char *e, const char *value) { return e && !strcmp(e, value); };
+    const char *force = getenv("SAFE_HIP_FORCE_PATH");
+    MfmaSwitches sw;
+    sw.force_mfma = is(force, "mfma");
+    sw.force_other = is(force, "gather") || is(force, "lds");
+    sw.z = !is(getenv("SAFE_HIP_MFMA_Z"), "0");
+    sw.filter = !is(getenv("SAFE_HIP_MFMA_FILTER"), "0");
+    sw.general = is(getenv("SAFE_HIP_MFMA_FORM"), "general");
+    if (const char *e = getenv("SAFE_HIP_MFMA_FILTER_CAP")) sw.filter_cap = static_cast<unsigned int>(std::max(1, atoi(e)));
+    return sw;
+}
+
 bool mfma_applicable(const safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const safe_perms *perms, bool z) {
     (void)ctx;
     (void)attr;
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
-    if (force && (!strcmp(force, "gather") || !strcmp(force, "lds"))) return false;
-    const char *z_env = getenv("SAFE_HIP_MFMA_Z");                       // =0: z-scores stay on the f64 kernels
-    if (z && z_env && !strcmp(z_env, "0")) return false;
+    const MfmaSwitches sw = mfma_switches();
+    if (sw.force_other) return false;
+    if (z && !sw.z) return false;
     if (perms->count < 1 || perms->count > 65535) return false;
     // a score is a sum of `members` fixed-point values below 2^46, combined and compared as 64-bit integers: neighborhoods of
     // 2^16 members and more could pass 2^62 (the f64 kernels take those)
     if (nbr->n > (1ll << 30) / 32 || nbr->max_count >= (1 << 16)) return false;
-    if (force && !strcmp(force, "mfma")) return true;
+    if (sw.force_mfma) return true;
     return nbr->n >= 256;                       // below one row group the LDS-resident f64 kernel is the better fit
 }
+
+namespace {
+
+// ---- the slice scratch of a call, laid out BEFORE the column statistics say how many slices the values need (the slice kernels
+//      write every image the call may use): tile-major, bs[column tile][row 0..n][slice][32 bytes]
+//   'sum' scores            one matrix of 2 / 4 / 6 slices; where the filter is wanted and the columns need six, two matrices of three
+//                           (digits 0-2 | digits 3-5, the high one split_off bytes behind the low one: the same space)
+//   z-scores                seven slices (value | square digits, not-NaN flags: tiles of 16 columns)
+//   z-scores, filter wanted ... | high digits + not-NaN slice, 128-byte rows (zf_hi_off) | low digits, 96-byte rows (zf_lo_off)
+struct MfmaLayout {
+    int64_t split_off = 0, zf_hi_off = 0, zf_lo_off = 0;
+    size_t bytes = 0;
+};
+MfmaLayout mfma_layout(bool z, bool want_filter, int64_t n, int64_t n_ct) {
+    MfmaLayout lay;
+    const int64_t tile_rows = n_ct * (n + 1);
+    lay.bytes = static_cast<size_t>(tile_rows) * (z ? MF_NS + 1 : MF_NS) * 32;
+    if (want_filter && !z) lay.split_off = tile_rows * (MF_NS / 2) * 32;
+    if (want_filter && z) {
+        lay.zf_hi_off = static_cast<int64_t>(lay.bytes);
+        lay.zf_lo_off = lay.zf_hi_off + tile_rows * 128;
+        lay.bytes += static_cast<size_t>(tile_rows) * (128 + 96);
+    }
+    return lay;
+}
+
+// The forms of the matrix-core permutation test, chosen here and nowhere else:
+//   MFMA_CLASSIC   k_permtest_mfma, FM = 0: every slice on the matrix cores (2 / 4 / 6 by the bits the columns need; z-scores: seven),
+//                  the observed score is row 0 of every span's source maps;
+//   MFMA_FILTERED  k_permtest_mfma, FM = 2: the high digits only (three slices; z-scores: three + the not-NaN slice), observed scores
+//                  from a pass of their own, undecided compares to the resolve kernels.  Six-slice 'sum' columns and z-scores, where
+//                  the filter is allowed -- but only where the two kernels below cannot run, or SAFE_HIP_MFMA_FORM=general asks for it;
+//   MFMA_G         k_permtest_mfma_g: the filtered 'sum' test, 64 rows per wave and two workgroups per CU -- unless a group is too
+//                  long for its LDS list (MF_F_MAXBLK) or a neighborhood too large for its 32-bit thresholds (2048 members);
+//   MFMA_GZ        k_permtest_mfma_gz: the filtered z-score test in the same shape (groups up to MF_GZ_MAXBLK blocks).
+enum MfmaFamily { MFMA_CLASSIC, MFMA_FILTERED, MFMA_G, MFMA_GZ };
+struct MfmaForm {
+    MfmaFamily family;
+    bool z;
+    int n_slices;                 // i8 slices of the call's values (z-scores: + the not-NaN slice)
+    int core_slices;              // slices the matrix cores multiply in the permutation launches
+    int64_t row_bytes;            // a row of a tile of the permutation launches' operand: core_slices x 32 bytes, tiles (n + 1) rows apart
+    int64_t lo_off, hi_off;       // (filtered) the low / high digit matrices in the slice scratch; hi = the permutation launches' operand
+    size_t lds_bytes;             // dynamic LDS of the permutation launches
+    int block, wgs_per_cu;        // threads per workgroup; the grid is min(tasks, wgs_per_cu x CUs) persistent workgroups
+    bool filtered() const { return family != MFMA_CLASSIC; }
+};
+// dynamic LDS of the general kernel: [2][4 k-steps] | kb list | observed scores [16][512]
+size_t mfma_general_lds(int slices) { return 2 * static_cast<size_t>(4 * mf_ks(slices)) + MF_MAXBLK * sizeof(int32_t) + 16 * 512 * sizeof(long long); }
+
+MfmaForm mfma_form(bool z, bool allow_filter, int n_slices, int64_t max_group_blocks, int64_t max_count, const MfmaLayout &lay,
+                   const MfmaSwitches &sw) {
+    MfmaForm f{};
+    f.z = z;
+    f.n_slices = n_slices;
+    const bool want_filter = allow_filter && sw.filter;      // (neighborhoods below 2^16 members: mfma_applicable)
+    if (!want_filter || (!z && n_slices != MF_NS)) {
+        f.family = MFMA_CLASSIC;
+        f.core_slices = n_slices;
+    } else if (z) {
+        f.family = (max_group_blocks <= MF_GZ_MAXBLK && !sw.general) ? MFMA_GZ : MFMA_FILTERED;
+        f.core_slices = MF_NS / 2 + 1;
+        f.lo_off = lay.zf_lo_off;
+        f.hi_off = lay.zf_hi_off;
+    } else {
+        f.family = (max_group_blocks <= MF_F_MAXBLK && max_count < 2048 && !sw.general) ? MFMA_G : MFMA_FILTERED;
+        f.core_slices = MF_NS / 2;
+        f.hi_off = lay.split_off;
+    }
+    f.row_bytes = static_cast<int64_t>(f.core_slices) * 32;
+    const bool own = f.family == MFMA_G || f.family == MFMA_GZ;
+    f.block = own ? 256 : 512;
+    f.wgs_per_cu = own ? 2 : 1;
+    // _g: [2][4 k-steps of 32 rows x 96 B] | kb list | Y0 + W [32][256] | counters [8][256] | task slot;  _gz: 128-byte rows, observed scores [16][256]
+    f.lds_bytes = f.family == MFMA_G    ? 2 * static_cast<size_t>(4 * 32 * (MF_NS / 2) * 32) + MF_F_MAXBLK * sizeof(int32_t) + 32 * 256 * sizeof(int32_t) + 8 * 256 * sizeof(uint32_t) + 16
+                  : f.family == MFMA_GZ ? 2 * static_cast<size_t>(4 * 32 * (MF_NS / 2 + 1) * 32) + MF_GZ_MAXBLK * sizeof(int32_t) + 16 * 256 * sizeof(long long) + 8 * 256 * sizeof(uint32_t) + 16
+                                        : mfma_general_lds(f.core_slices);
+    return f;
+}
+
+// the kernel of a form's permutation launches (dbg: a diagnostic variant, in a library built with make DIAG=1)
+const void *mfma_form_kernel(const MfmaForm &f, int dbg) {
+    const void *kfn = nullptr;
+    switch (f.family) {
+    case MFMA_G:
+        kfn = reinterpret_cast<const void *>(k_permtest_mfma_g<0>);
+#ifdef SAFE_HIP_DIAG
+#define MF_G_DIAG(D) if (dbg == D) kfn = reinterpret_cast<const void *>(k_permtest_mfma_g<D>);
+        MF_G_DIAG(2) MF_G_DIAG(4) MF_G_DIAG(8) MF_G_DIAG(64) MF_G_DIAG(66) MF_G_DIAG(512) MF_G_DIAG(1024)
+#undef MF_G_DIAG
+#endif
+        break;
+    case MFMA_GZ:
+        kfn = reinterpret_cast<const void *>(k_permtest_mfma_gz<0>);
+#ifdef SAFE_HIP_DIAG
+#define MF_GZ_DIAG(D) if (dbg == D) kfn = reinterpret_cast<const void *>(k_permtest_mfma_gz<D>);
+        MF_GZ_DIAG(2) MF_GZ_DIAG(4) MF_GZ_DIAG(8) MF_GZ_DIAG(64) MF_GZ_DIAG(512)
+#undef MF_GZ_DIAG
+#endif
+        break;
+    case MFMA_FILTERED:
+        kfn = f.z ? reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2 + 1, true, 0, 2>)
+                  : reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2, false, 0, 2>);
+        break;
+    case MFMA_CLASSIC:
+        kfn = f.z                ? reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS + 1, true>)
+              : f.n_slices == 2 ? reinterpret_cast<const void *>(k_permtest_mfma<false, 2>)
+              : f.n_slices == 4 ? reinterpret_cast<const void *>(k_permtest_mfma<false, 4>)
+                                : reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS>);
+        break;
+    }
+    (void)dbg;
+    return kfn;
+}
+
+// ---- column preparation: statistics -> scales -> slices -> verdict
+struct MfmaColumns {
+    MfmaLayout lay;
+    unsigned char *d_bs = nullptr;      // the slice scratch (lay)
+    double *d_scale = nullptr;          // [mloc] power-of-two scales (z-scores: + [mloc] of the squares)
+    long long *d_q64 = nullptr;         // (filtered 'sum' form) the fixed-point values as 64-bit words, [n + 1][mloc]: the resolve kernel's operand
+    longlong2 *d_z64 = nullptr;         // (filtered z form) value | square + not-NaN flag, [n + 1][mloc]
+    int n_slices = MF_NS;               // i8 slices of this call: 2 / 4 / 6 by the bits its columns need (k_mfma_colfinish); z-scores: seven
+    bool bad = false;                   // the values cannot be held on the fixed-point grid without a rounding that could matter
+};
+int mfma_prepare_columns(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, int64_t col0, int64_t mloc, bool z, bool want_filter,
+                         MfmaColumns *cols) {
+    const int64_t n = nbr->n, n_ct = ceil_div(mloc, z ? 16 : 32);
+    const bool f32 = attr->dtype == SAFE_DTYPE_F32;
+    const MfmaLayout lay = cols->lay = mfma_layout(z, want_filter, n, n_ct);
+    if (lay.split_off) SAFE_TRY(ctx_scratch(ctx, 16, static_cast<size_t>(n + 1) * mloc * sizeof(long long), reinterpret_cast<void **>(&cols->d_q64)));
+    if (lay.zf_hi_off) SAFE_TRY(ctx_scratch(ctx, 17, static_cast<size_t>(n + 1) * mloc * sizeof(longlong2), reinterpret_cast<void **>(&cols->d_z64)));
+    SAFE_TRY(ctx_scratch(ctx, 1, lay.bytes, reinterpret_cast<void **>(&cols->d_bs)));
+    void *d_colbuf = nullptr;                    // maxbits u64 | sumsq f64 | scale, scale2 f64 | cnt, small, rounded, neg_lowbit u32 | shift, shift2 i32 | bad, need i32
+    const size_t colbuf_bytes = static_cast<size_t>(mloc) * (8 + 8 + 16 + 4 + 4 + 4 + 4 + 4 + 4 + 8) + 64;   // (+ zeros, inexact u32)
+    SAFE_TRY(ctx_scratch(ctx, 6, colbuf_bytes, &d_colbuf));
+    unsigned long long *d_max = static_cast<unsigned long long *>(d_colbuf);
+    double *d_sumsq = reinterpret_cast<double *>(d_max + mloc);
+    double *d_scale = cols->d_scale = d_sumsq + mloc;
+    unsigned int *d_cnt = reinterpret_cast<unsigned int *>(d_scale + 2 * mloc);
+    unsigned int *d_small = d_cnt + mloc, *d_rounded = d_small + mloc, *d_lowbit = d_rounded + mloc;
+    unsigned int *d_zero = d_lowbit + mloc, *d_inexact = d_zero + mloc;
+    int *d_shift = reinterpret_cast<int *>(d_inexact + mloc);
+    int *d_bad = d_shift + 2 * mloc, *d_need = d_bad + 1;
+    SAFE_HIP_CHECK(hipMemsetAsync(d_colbuf, 0, colbuf_bytes, ctx->stream));
+    const int rows_per_block = 2048;
+    const dim3 grid(ceil_div(mloc, 32), ceil_div(n, rows_per_block));
+    if (f32)
+        hipLaunchKernelGGL(k_mfma_colstats<float>, grid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
+                           attr->col_stride, col0, mloc, rows_per_block, d_max, d_sumsq, d_cnt, d_lowbit);
+    else
+        hipLaunchKernelGGL(k_mfma_colstats<double>, grid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
+                           attr->col_stride, col0, mloc, rows_per_block, d_max, d_sumsq, d_cnt, d_lowbit);
+    hipLaunchKernelGGL(k_mfma_colfinish, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_max, d_lowbit, mloc, d_shift,
+                       d_scale, d_bad, d_need);
+    const dim3 sgrid(n_ct, ceil_div(n + 1, 32));
+    if (z) {
+        hipLaunchKernelGGL(k_mfma_colfinish_sq, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_max, d_lowbit, mloc, d_shift + mloc,
+                           d_scale + mloc, d_inexact, d_bad);
+        if (f32)
+            hipLaunchKernelGGL(k_mfma_slice_z<float>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride, attr->col_stride,
+                               col0, mloc, n_ct, d_shift, d_shift + mloc, d_max, cols->d_bs, d_small, d_rounded, d_zero, lay.zf_hi_off, lay.zf_lo_off,
+                               cols->d_z64);
+        else
+            hipLaunchKernelGGL(k_mfma_slice_z<double>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride, attr->col_stride,
+                               col0, mloc, n_ct, d_shift, d_shift + mloc, d_max, cols->d_bs, d_small, d_rounded, d_zero, lay.zf_hi_off, lay.zf_lo_off,
+                               cols->d_z64);
+    } else if (f32)
+        hipLaunchKernelGGL(k_mfma_slice<float>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride, attr->col_stride,
+                           col0, mloc, n_ct, d_shift, d_max, d_need, cols->d_bs, d_small, d_rounded, lay.split_off, cols->d_q64);
+    else
+        hipLaunchKernelGGL(k_mfma_slice<double>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride, attr->col_stride,
+                           col0, mloc, n_ct, d_shift, d_max, d_need, cols->d_bs, d_small, d_rounded, lay.split_off, cols->d_q64);
+    hipLaunchKernelGGL(k_mfma_colcheck, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_cnt, d_small, d_rounded,
+                       z ? d_zero : static_cast<unsigned int *>(nullptr), d_inexact, mloc, d_bad);
+    SAFE_HIP_CHECK(hipGetLastError());
+    int verdict[2] = {0, 0};                   // {bad, bits needed}
+    SAFE_HIP_CHECK(hipMemcpyAsync(verdict, d_bad, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    cols->bad = verdict[0] != 0;
+    cols->n_slices = z ? MF_NS + 1 : mfma_slices_for(verdict[1]);
+    return SAFE_OK;
+}
+
+// ---- the task and queue plan: (row group, column tile) tasks, one queue per XCD keyed by column tile so the slice rows of a tile
+//      are pulled into one L2; inside a queue tile-major, heavy groups first.  With it the scratch of the launches.
+struct MfmaPlan {
+    std::vector<int2> tasks;                    // (host copies: alive until the call's last synchronisation)
+    int32_t q_off[9] = {0};
+    int64_t n_tasks = 0;
+    int2 *d_tasks = nullptr;
+    int32_t *d_qoff = nullptr;
+    unsigned int *d_qctr = nullptr;             // queue counters: eight per launch, eight spare, eight per observed-score pass
+    std::vector<int64_t> starts;                // permutation launches: [starts[c], starts[c + 1])
+    int64_t span = 1, n_launch = 0;
+    unsigned int *d_counts = nullptr;           // [column][padded row] (#< << 16 | #>) counters
+    int32_t *d_src[2] = {nullptr, nullptr};     // source-row maps of a span, one buffer per stream parity
+    // filtered forms: exact observed scores ('sum'), the undecided compares of a launch (one list per stream parity), their counters
+    long long *d_obs64 = nullptr;
+    ulonglong2 *d_amb[2] = {nullptr, nullptr};
+    int32_t *d_src_id = nullptr;                // the identity source map (observed-score passes)
+    unsigned int *d_amb_cnt = nullptr;
+    unsigned int amb_cap = 0;
+};
+int mfma_make_plan(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const MfmaForm &form, int64_t mloc, const MfmaSwitches &sw,
+                   MfmaPlan *plan) {
+    const int64_t n = nbr->n, n_ct = ceil_div(mloc, form.z ? 16 : 32), n_src = nbr->bs_src, n_padr = nbr->bs_groups * MF_R;
+    std::vector<int32_t> g_order(nbr->bs_groups);
+    std::iota(g_order.begin(), g_order.end(), 0);
+    const std::vector<int32_t> &bp = nbr->h_bs_ptr;
+    std::stable_sort(g_order.begin(), g_order.end(), [&](int32_t a, int32_t b) { return bp[a + 1] - bp[a] > bp[b + 1] - bp[b]; });
+    std::vector<int2> &tasks = plan->tasks;
+    int32_t(&q_off)[9] = plan->q_off;
+    tasks.reserve(nbr->bs_groups * n_ct);
+    for (int qx = 0; qx < 8; ++qx) {
+        for (int64_t ct = qx; ct < n_ct; ct += 8)
+            for (int32_t g : g_order) tasks.push_back(make_int2(g, static_cast<int>(ct)));
+        q_off[qx + 1] = static_cast<int32_t>(tasks.size());
+    }
+    plan->n_tasks = static_cast<int64_t>(tasks.size());
+    plan->starts = perm_launch_starts(perms, &plan->span);
+    const int64_t span = plan->span, n_launch = plan->n_launch = static_cast<int64_t>(plan->starts.size()) - 1;
+    void *ws = nullptr;
+    SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + (8 * n_launch + 8 + 16) * sizeof(unsigned int), &ws));
+    plan->d_tasks = static_cast<int2 *>(ws);
+    plan->d_qoff = reinterpret_cast<int32_t *>(plan->d_tasks + tasks.size());
+    plan->d_qctr = reinterpret_cast<unsigned int *>(plan->d_qoff + 16);
+    SAFE_TRY(ctx_scratch(ctx, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&plan->d_counts)));
+    for (int b = 0; b < 2; ++b)
+        SAFE_TRY(ctx_scratch(ctx, 4 + b, static_cast<size_t>(span + 1) * n_src * sizeof(int32_t), reinterpret_cast<void **>(&plan->d_src[b])));
+    SAFE_HIP_CHECK(hipMemcpyAsync(plan->d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK(hipMemcpyAsync(plan->d_qoff, q_off, sizeof(q_off), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK(hipMemsetAsync(plan->d_qctr, 0, (8 * n_launch + 8 + 16) * sizeof(unsigned int), ctx->stream));
+    SAFE_HIP_CHECK(hipMemsetAsync(plan->d_counts, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), ctx->stream));
+    if (form.filtered()) {
+        if (!form.z) SAFE_TRY(ctx_scratch(ctx, 12, static_cast<size_t>(n_padr) * mloc * sizeof(long long), reinterpret_cast<void **>(&plan->d_obs64)));
+        const double per_launch = static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(span);
+        plan->amb_cap = sw.filter_cap ? sw.filter_cap : static_cast<unsigned int>(std::min(67108864.0, std::max(1048576.0, per_launch / 512.0)));
+        for (int b = 0; b < 2; ++b)
+            SAFE_TRY(ctx_scratch(ctx, 13 + b, static_cast<size_t>(plan->amb_cap) * sizeof(ulonglong2), reinterpret_cast<void **>(&plan->d_amb[b])));
+        void *small = nullptr;
+        SAFE_TRY(ctx_scratch(ctx, 15, static_cast<size_t>(n_src) * sizeof(int32_t) + static_cast<size_t>(n_launch) * sizeof(unsigned int), &small));
+        plan->d_src_id = static_cast<int32_t *>(small);
+        plan->d_amb_cnt = reinterpret_cast<unsigned int *>(plan->d_src_id + n_src);
+        SAFE_HIP_CHECK(hipMemsetAsync(plan->d_amb_cnt, 0, static_cast<size_t>(n_launch) * sizeof(unsigned int), ctx->stream));
+    }
+    return SAFE_OK;
+}
+
+// ---- one launch of the general kernel (the permutation test's instantiations): what varies between launches, and the one
+//      argument list
+struct MfmaGeneralLaunch {
+    const void *kfn = nullptr;
+    size_t lds_bytes = 0;
+    const unsigned char *bs = nullptr;          // operand matrix: rows of row_bytes, tiles (n + 1) rows apart
+    int64_t row_bytes = 0;
+    const int32_t *src = nullptr;               // n_q source-row maps
+    int n_q = 1;
+    unsigned int *q_ctr = nullptr;
+    double *ns_out = nullptr;
+    int dbg = 0;                                // (diagnostic builds) 1: no transposes / LDS stores of the gathered rows, 4: no barrier per super-step, 8: no score completion
+    MfmaFilt fa;
+};
+int mfma_launch_general(safe_ctx *ctx, const safe_nbr *nbr, const MfmaPlan &plan, const double *d_scale, int64_t mloc,
+                        const MfmaGeneralLaunch &l, hipStream_t stream) {
+    const int64_t n_src = nbr->bs_src, n_padr = nbr->bs_groups * MF_R, tile_bytes = (nbr->n + 1) * l.row_bytes;
+    const int64_t blocks = std::min<int64_t>(plan.n_tasks, ctx->num_cu);
+    HypLookup no_lookup{};
+    no_lookup.dbg = l.dbg;
+    void *args[] = {(void *)&l.bs, (void *)&l.row_bytes, (void *)&tile_bytes, (void *)&l.src, (void *)&n_src, (void *)&l.n_q, (void *)&nbr->bs_ptr,
+                    (void *)&nbr->bs_kb, (void *)&nbr->bs_bits, (void *)&plan.d_tasks, (void *)&plan.d_qoff, (void *)&l.q_ctr, (void *)&mloc,
+                    (void *)&plan.d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&d_scale, (void *)&l.ns_out, (void *)&no_lookup, (void *)&l.fa};
+    SAFE_HIP_CHECK(hipLaunchKernel(l.kfn, dim3(blocks), dim3(512), args, l.lds_bytes, stream));
+    return SAFE_OK;
+}
+
+// ---- the observed scores of the filtered forms, by the general kernel over the identity source map.
+//   'sum'     exact fixed-point scores to d_obs64: low digits stored, high digits added << 24 (FM = 1, two short launches);
+//   z-scores  one pass of the seven-slice kernel writes them to ns_out (exact sums, the reference's formula); the filtered
+//             launches compare against them
+int mfma_observe(safe_ctx *ctx, const safe_nbr *nbr, const MfmaForm &form, const MfmaColumns &cols, const MfmaPlan &plan, int64_t mloc,
+                 double *ns_out) {
+    const int64_t n_src = nbr->bs_src, n_padr = nbr->bs_groups * MF_R;
+    hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), 1), dim3(256), 0, ctx->stream, nbr->bs_order, n_src, nbr->n,
+                       static_cast<const int32_t *>(nullptr), 0, plan.d_src_id, 0);
+    const int obs_slices = form.z ? MF_NS + 1 : MF_NS / 2;
+    MfmaGeneralLaunch l;
+    l.kfn = form.z ? reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS + 1, true>)
+                   : reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2, false, 0, 1>);
+    l.lds_bytes = mfma_general_lds(obs_slices);
+    SAFE_HIP_CHECK(hipFuncSetAttribute(l.kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(l.lds_bytes)));
+    l.row_bytes = static_cast<int64_t>(obs_slices) * 32;
+    l.src = plan.d_src_id;
+    l.ns_out = form.z ? ns_out : nullptr;
+    l.fa.obs64 = plan.d_obs64;
+    for (int pass = 0; pass < (form.z ? 1 : 2); ++pass) {
+        l.bs = form.z ? cols.d_bs : cols.d_bs + (pass ? form.hi_off : form.lo_off);
+        l.q_ctr = plan.d_qctr + 8 * plan.n_launch + 8 + 8 * pass;
+        l.fa.obs_shift = pass ? 24 : 0;
+        SAFE_TRY(mfma_launch_general(ctx, nbr, plan, cols.d_scale, mloc, l, ctx->stream));
+    }
+    if (!form.z && ns_out)
+        hipLaunchKernelGGL(k_mfma_obs_ns, dim3(n_padr / 32, ceil_div(mloc, 32)), dim3(256), 0, ctx->stream, plan.d_obs64, n_padr, nbr->bs_rowmap,
+                           cols.d_scale, mloc, ns_out);
+    SAFE_HIP_CHECK(hipGetLastError());
+    return SAFE_OK;
+}
+
+// ---- the permutation launches: span c on the main (even c) or the side stream, its source maps in front of it, the resolve
+//      kernel of a filtered form behind it.  ev[2 c], ev[2 c + 1] bracket the launch.  *overflowed: the pilot launch left too much
+//      undecided (the caller runs the call again without the filter).
+int mfma_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const MfmaForm &form, const MfmaColumns &cols, const MfmaPlan &plan,
+                      int64_t mloc, double *ns_out, int dbg, hipEvent_t *ev, bool *overflowed) {
+    const int64_t n = nbr->n, n_src = nbr->bs_src, n_padr = nbr->bs_groups * MF_R, n_launch = plan.n_launch;
+    const bool filtered = form.filtered();
+    const void *kfn = mfma_form_kernel(form, dbg);
+    SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(form.lds_bytes)));
+    // The kernel is persistent and takes a CU whole (256 VGPRs x 2 waves per SIMD): table kernels of the next span that are
+    // queued while it runs (aux stream: scan rounds, row emission) get a CU only as its workgroups retire and trickle through
+    // the whole tail of the launch -- harmless for the result, but they then show launch-long durations in a kernel trace
+    // (half of the "GPU time" of a profile).  Leaving CUs free does not help unless every XCD has one (workgroups are dealt to
+    // XCDs round-robin), which costs 3 % of the matrix-core throughput.  Long launches therefore make the table stream wait for
+    // their predecessor instead (below): the tables of a span are needed only when that launch has ended.
+    const int64_t blocks = std::min<int64_t>(plan.n_tasks, form.wgs_per_cu * static_cast<int64_t>(ctx->num_cu));
+    const int64_t tile_bytes = (n + 1) * form.row_bytes;
+    const bool long_launches = static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(plan.span) >= 2e9;   // >~ 20 ms each
+    const unsigned char *d_bs_lo = cols.d_bs + form.lo_off, *d_bs_hi = cols.d_bs + form.hi_off;
+#ifdef SAFE_HIP_DIAG
+    static const int dbg_window = getenv("SAFE_HIP_MFMA_DBG_WINDOW") ? atoi(getenv("SAFE_HIP_MFMA_DBG_WINDOW")) : 0;
+    if (dbg_window > 0) safe_warn_diagnostic("SAFE_HIP_MFMA_DBG_WINDOW");
+#else
+    constexpr int dbg_window = 0;
+#endif
+    for (int64_t c = 0; c < n_launch; ++c) {
+        const int64_t p_base = plan.starts[c], p_limit = plan.starts[c + 1], cnt = p_limit - p_base;
+        hipStream_t ks = (c & 1) ? ctx->side_stream : ctx->stream;
+        if (long_launches && c >= 1) SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ev[2 * (c - 1) + 1], 0));
+        SAFE_TRY(perms_wait(perms, p_limit, ks));
+        // (the source-map buffer of span c - 1 is reused by span c + 1: same stream, ordered)
+        hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), cnt + 1), dim3(256), 0, ks, nbr->bs_order, n_src, n, perms->table,
+                           p_base, plan.d_src[c & 1], dbg_window);
+        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
+        // classic: row 0 of the source maps is the identity (the observed score is formed once per task); filtered forms:
+        // the observed scores are there already and every q is a permutation
+        const int32_t *src_c = filtered ? plan.d_src[c & 1] + n_src : plan.d_src[c & 1];
+        int n_q = static_cast<int>(filtered ? cnt : cnt + 1);
+        unsigned int *qctr_c = plan.d_qctr + 8 * c;
+        MfmaFilt fa;
+        if (filtered) {
+            fa.obs64 = plan.d_obs64;
+            fa.zobs = ns_out;
+            fa.rowcnt = nbr->bs_rowcnt;
+            fa.amb = plan.d_amb[c & 1];
+            fa.amb_count = plan.d_amb_cnt + c;
+            fa.amb_cap = plan.amb_cap;
+            fa.p_base = static_cast<int>(p_base);
+#ifdef SAFE_HIP_DIAG
+            if (dbg == 512) {
+                if (!ctx->diag_prof) SAFE_HIP_CHECK(hipMalloc(&ctx->diag_prof, 64 * sizeof(unsigned long long)));
+                if (c == 0) SAFE_HIP_CHECK(hipMemsetAsync(ctx->diag_prof, 0, 64 * sizeof(unsigned long long), ks));
+                fa.prof = static_cast<unsigned long long *>(ctx->diag_prof);
+            }
+#endif
+        }
+        if (form.family == MFMA_GZ) {
+            void *args[] = {(void *)&d_bs_hi, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
+                            (void *)&nbr->bs_kb, (void *)&nbr->bs_bits4p, (void *)&plan.d_tasks, (void *)&plan.d_qoff, (void *)&qctr_c,
+                            (void *)&mloc, (void *)&plan.d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&cols.d_scale, (void *)&fa};
+            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(form.block), args, form.lds_bytes, ks));
+        } else if (form.family == MFMA_G) {
+            void *args[] = {(void *)&d_bs_hi, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
+                            (void *)&nbr->bs_kb, (void *)&nbr->bs_bits4p, (void *)&nbr->bs_grpmax, (void *)&plan.d_tasks, (void *)&plan.d_qoff,
+                            (void *)&qctr_c, (void *)&mloc, (void *)&plan.d_counts, (void *)&n_padr, (void *)&fa};
+            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(form.block), args, form.lds_bytes, ks));
+        } else {
+            MfmaGeneralLaunch l;
+            l.kfn = kfn;
+            l.lds_bytes = form.lds_bytes;
+            l.bs = d_bs_hi;                       // (classic: the one matrix, offset 0)
+            l.row_bytes = form.row_bytes;
+            l.src = src_c;
+            l.n_q = n_q;
+            l.q_ctr = qctr_c;
+            l.ns_out = (c == 0 && !filtered) ? ns_out : nullptr;
+            l.dbg = dbg;
+            l.fa = fa;
+            SAFE_TRY(mfma_launch_general(ctx, nbr, plan, cols.d_scale, mloc, l, ks));
+        }
+        SAFE_HIP_CHECK(hipGetLastError());
+        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
+        if (!filtered) continue;
+        if (form.z)
+            hipLaunchKernelGGL(k_mfma_resolve_z, dim3(4 * ctx->num_cu), dim3(256), 0, ks, plan.d_amb[c & 1], plan.d_amb_cnt + c, plan.amb_cap, ns_out,
+                               mloc, n_padr, nbr->bs_rowmap, nbr->row_ptr, nbr->col, perms->table, n, d_bs_lo, d_bs_hi, cols.d_z64, cols.d_scale,
+                               plan.d_counts);
+        else
+            hipLaunchKernelGGL(k_mfma_resolve, dim3(4 * ctx->num_cu), dim3(256), 0, ks, plan.d_amb[c & 1], plan.d_amb_cnt + c, plan.amb_cap,
+                               plan.d_obs64, n_padr, nbr->bs_rowmap, nbr->row_ptr, nbr->col, perms->table, n, d_bs_lo, tile_bytes, form.hi_off,
+                               cols.d_q64, mloc, plan.d_counts);
+        SAFE_HIP_CHECK(hipGetLastError());
+        if (c == 0 && long_launches && n_launch > 1) {
+            // pilot: data with many equal scores (sparse columns, few distinct values) leaves the high digits little to
+            // decide -- if the first launch sent more than 2 in 1000 compares to the resolve kernel, stop here and let the
+            // caller run all six slices (a launch of this size is long: the wait is nothing beside it)
+            unsigned int seen0 = 0;
+            SAFE_HIP_CHECK(hipMemcpyAsync(&seen0, plan.d_amb_cnt, sizeof(seen0), hipMemcpyDeviceToHost, ks));
+            SAFE_HIP_CHECK(safe_stream_sync(ks));
+            if (static_cast<double>(seen0) > 2e-3 * static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(cnt)) {
+                ctx->last_undecided = seen0;
+                *overflowed = true;
+                return SAFE_OK;
+            }
+        }
+    }
+    return SAFE_OK;
+}
+
+}  // namespace
 
 // Runs the permutation test of columns [col0, col1) on the MFMA path.  *declined = true (and
 // SAFE_OK) when the attribute values cannot be represented on the fixed-point grid without a
@@ -3077,205 +3095,28 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
     *overflowed = false;
     SAFE_TRY(build_blocks(nbr));
     PermOut out = out_in;
-    const int64_t n = nbr->n, mloc = col1 - col0, P = perms->count;
-    // z-scores: tiles of 16 columns (value digits | square digits) and a seventh slice of not-NaN flags
-    const int64_t n_ct = ceil_div(mloc, z ? 16 : 32), n_src = nbr->bs_src;
-    int64_t row_bytes = n_ct * (z ? MF_NS + 1 : MF_NS) * 32;   // (the largest form; the call's slice count is known after the column statistics)
-    const int64_t n_padr = nbr->bs_groups * MF_R;
-    const bool f32 = attr->dtype == SAFE_DTYPE_F32;
-
-    // ---- the filtered form (six-slice 'sum' columns: three slices on the matrix cores, see k_permtest_mfma)
-    const char *filt_env = getenv("SAFE_HIP_MFMA_FILTER");                // =0: all six slices on the matrix cores
-    const bool want_filter = allow_filter && !(filt_env && !strcmp(filt_env, "0"));      // (neighborhoods below 2^16 members: mfma_applicable)
-    const int64_t split_off = (want_filter && !z) ? n_ct * (n + 1) * (MF_NS / 2) * 32 : 0;   // high digits behind the low digits
-    // z-scores, filtered: the seven-slice layout (observed pass) | high digits + not-NaN slice, 128-byte rows | low digits, 96-byte rows
-    const int64_t zf_hi_off = (want_filter && z) ? n_ct * (n + 1) * (MF_NS + 1) * 32 : 0;
-    const int64_t zf_lo_off = zf_hi_off + n_ct * (n + 1) * 128;
-    if (want_filter && z) row_bytes += n_ct * (128 + 96);        // (the scratch below is sized (n + 1) * row_bytes)
-
-    // ---- column scales and slices
-    int n_slices = MF_NS;                        // i8 slices of this call: 2 / 4 / 6 by the bits its columns need (k_mfma_colfinish)
-    long long *d_q64 = nullptr;                  // (filtered 'sum' form) the fixed-point values as 64-bit words, [n + 1][mloc]: the resolve kernel's operand
-    if (split_off) SAFE_TRY(ctx_scratch(ctx, 16, static_cast<size_t>(n + 1) * mloc * sizeof(long long), reinterpret_cast<void **>(&d_q64)));
-    longlong2 *d_z64 = nullptr;                  // (filtered z form) value | square + not-NaN flag, [n + 1][mloc]
-    if (zf_hi_off) SAFE_TRY(ctx_scratch(ctx, 17, static_cast<size_t>(n + 1) * mloc * sizeof(longlong2), reinterpret_cast<void **>(&d_z64)));
-    unsigned char *d_bs = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n + 1) * row_bytes, reinterpret_cast<void **>(&d_bs)));
-    void *d_colbuf = nullptr;                    // maxbits u64 | sumsq f64 | scale, scale2 f64 | cnt, small, rounded, neg_lowbit u32 | shift, shift2 i32 | bad, need i32
-    const size_t colbuf_bytes = static_cast<size_t>(mloc) * (8 + 8 + 16 + 4 + 4 + 4 + 4 + 4 + 4 + 8) + 64;   // (+ zeros, inexact u32)
-    SAFE_TRY(ctx_scratch(ctx, 6, colbuf_bytes, &d_colbuf));
-    unsigned long long *d_max = static_cast<unsigned long long *>(d_colbuf);
-    double *d_sumsq = reinterpret_cast<double *>(d_max + mloc);
-    double *d_scale = d_sumsq + mloc;
-    unsigned int *d_cnt = reinterpret_cast<unsigned int *>(d_scale + 2 * mloc);
-    unsigned int *d_small = d_cnt + mloc, *d_rounded = d_small + mloc, *d_lowbit = d_rounded + mloc;
-    unsigned int *d_zero = d_lowbit + mloc, *d_inexact = d_zero + mloc;
-    int *d_shift = reinterpret_cast<int *>(d_inexact + mloc);
-    int *d_bad = d_shift + 2 * mloc, *d_need = d_bad + 1;
-    SAFE_HIP_CHECK(hipMemsetAsync(d_colbuf, 0, colbuf_bytes, ctx->stream));
-    {
-        const int rows_per_block = 2048;
-        const dim3 grid(ceil_div(mloc, 32), ceil_div(n, rows_per_block));
-        if (f32)
-            hipLaunchKernelGGL(k_mfma_colstats<float>, grid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                               attr->col_stride, col0, mloc, rows_per_block, d_max, d_sumsq, d_cnt, d_lowbit);
-        else
-            hipLaunchKernelGGL(k_mfma_colstats<double>, grid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                               attr->col_stride, col0, mloc, rows_per_block, d_max, d_sumsq, d_cnt, d_lowbit);
-        hipLaunchKernelGGL(k_mfma_colfinish, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_max, d_lowbit, mloc, d_shift,
-                           d_scale, d_bad, d_need);
-        const dim3 sgrid(n_ct, ceil_div(n + 1, 32));
-        if (z) {
-            hipLaunchKernelGGL(k_mfma_colfinish_sq, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_max, d_lowbit, mloc, d_shift + mloc,
-                               d_scale + mloc, d_inexact, d_bad);
-            if (f32)
-                hipLaunchKernelGGL(k_mfma_slice_z<float>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                                   attr->col_stride, col0, mloc, n_ct, d_shift, d_shift + mloc, d_max, d_bs, d_small, d_rounded, d_zero, zf_hi_off, zf_lo_off, d_z64);
-            else
-                hipLaunchKernelGGL(k_mfma_slice_z<double>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                                   attr->col_stride, col0, mloc, n_ct, d_shift, d_shift + mloc, d_max, d_bs, d_small, d_rounded, d_zero, zf_hi_off, zf_lo_off, d_z64);
-        } else if (f32)
-            hipLaunchKernelGGL(k_mfma_slice<float>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                               attr->col_stride, col0, mloc, n_ct, d_shift, d_max, d_need, d_bs, d_small, d_rounded, split_off, d_q64);
-        else
-            hipLaunchKernelGGL(k_mfma_slice<double>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride,
-                               attr->col_stride, col0, mloc, n_ct, d_shift, d_max, d_need, d_bs, d_small, d_rounded, split_off, d_q64);
-        hipLaunchKernelGGL(k_mfma_colcheck, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_cnt, d_small, d_rounded,
-                           z ? d_zero : static_cast<unsigned int *>(nullptr), d_inexact, mloc, d_bad);
-        SAFE_HIP_CHECK(hipGetLastError());
-        int verdict[2] = {0, 0};                   // {bad, bits needed}
-        SAFE_HIP_CHECK(hipMemcpyAsync(verdict, d_bad, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-        const char *force = getenv("SAFE_HIP_FORCE_PATH");
-        if (verdict[0] && !(force && !strcmp(force, "mfma"))) {
-            *declined = true;
-            return SAFE_OK;
-        }
-        n_slices = z ? MF_NS + 1 : mfma_slices_for(verdict[1]);
-        row_bytes = static_cast<int64_t>(n_slices) * 32;          // tile-major: a row of a tile is n_slices x 32 bytes, tiles (n + 1) rows apart
-    }
-    const bool zfilt = want_filter && z;
-    const bool filt = want_filter && !z && n_slices == MF_NS;
-    // its own kernel (64 rows per wave, two workgroups per CU) unless a group is too long for its LDS list / a neighborhood too
-    // large for its 32-bit thresholds; SAFE_HIP_MFMA_FORM=general: the general kernel's FM = 2 (A/B)
-    const char *form_env = getenv("SAFE_HIP_MFMA_FORM");
-    const bool filt_own = filt && nbr->bs_max_group_blocks <= MF_F_MAXBLK && nbr->max_count < 2048 && !(form_env && !strcmp(form_env, "general"));
-    const int core_slices = filt ? MF_NS / 2 : zfilt ? MF_NS / 2 + 1 : n_slices;         // slices the matrix cores multiply
-    if (filt) row_bytes = static_cast<int64_t>(core_slices) * 32;
-    const unsigned char *d_bs_lo = zfilt ? d_bs + zf_lo_off : d_bs, *d_bs_hi = zfilt ? d_bs + zf_hi_off : d_bs + split_off;
-
-    // ---- tasks: (row group, column tile), one queue per XCD keyed by column tile so the slice
-    //      rows of a tile are pulled into one L2; inside a queue tile-major, heavy groups first
-    std::vector<int32_t> g_order(nbr->bs_groups);
-    std::iota(g_order.begin(), g_order.end(), 0);
-    const std::vector<int32_t> &bp = nbr->h_bs_ptr;
-    std::stable_sort(g_order.begin(), g_order.end(), [&](int32_t a, int32_t b) { return bp[a + 1] - bp[a] > bp[b + 1] - bp[b]; });
-    std::vector<int2> tasks;
-    tasks.reserve(nbr->bs_groups * n_ct);
-    int32_t q_off[9] = {0};
-    for (int qx = 0; qx < 8; ++qx) {
-        for (int64_t ct = qx; ct < n_ct; ct += 8)
-            for (int32_t g : g_order) tasks.push_back(make_int2(g, static_cast<int>(ct)));
-        q_off[qx + 1] = static_cast<int32_t>(tasks.size());
-    }
-    int64_t span = 1;
-    const std::vector<int64_t> starts = perm_launch_starts(perms, &span);
-    const int64_t n_launch = static_cast<int64_t>(starts.size()) - 1;
-    void *ws = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + (8 * n_launch + 8 + 16) * sizeof(unsigned int), &ws));
-    int2 *d_tasks = static_cast<int2 *>(ws);
-    int32_t *d_qoff = reinterpret_cast<int32_t *>(d_tasks + tasks.size());
-    unsigned int *d_qctr = reinterpret_cast<unsigned int *>(d_qoff + 16);
-    unsigned int *d_counts = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_counts)));
-    int32_t *d_src[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; ++b)
-        SAFE_TRY(ctx_scratch(ctx, 4 + b, static_cast<size_t>(span + 1) * n_src * sizeof(int32_t), reinterpret_cast<void **>(&d_src[b])));
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_qoff, q_off, sizeof(q_off), hipMemcpyHostToDevice, ctx->stream));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_qctr, 0, (8 * n_launch + 8 + 16) * sizeof(unsigned int), ctx->stream));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_counts, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), ctx->stream));
-    // filtered form: exact observed scores, the undecided compares of a launch (one list per stream parity), their counters
-    long long *d_obs64 = nullptr;
-    ulonglong2 *d_amb[2] = {nullptr, nullptr};
-    int32_t *d_src_id = nullptr;
-    unsigned int *d_amb_cnt = nullptr;
-    unsigned int amb_cap = 0;
-    const bool any_filt = filt || zfilt;
-    if (any_filt) {
-        if (filt) SAFE_TRY(ctx_scratch(ctx, 12, static_cast<size_t>(n_padr) * mloc * sizeof(long long), reinterpret_cast<void **>(&d_obs64)));
-        const double per_launch = static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(span);
-        amb_cap = static_cast<unsigned int>(std::min(67108864.0, std::max(1048576.0, per_launch / 512.0)));
-        if (const char *e = getenv("SAFE_HIP_MFMA_FILTER_CAP")) amb_cap = static_cast<unsigned int>(std::max(1, atoi(e)));   // (tests: force the fall-back)
-        for (int b = 0; b < 2; ++b)
-            SAFE_TRY(ctx_scratch(ctx, 13 + b, static_cast<size_t>(amb_cap) * sizeof(ulonglong2), reinterpret_cast<void **>(&d_amb[b])));
-        void *small = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, 15, static_cast<size_t>(n_src) * sizeof(int32_t) + static_cast<size_t>(n_launch) * sizeof(unsigned int), &small));
-        d_src_id = static_cast<int32_t *>(small);
-        d_amb_cnt = reinterpret_cast<unsigned int *>(d_src_id + n_src);
-        SAFE_HIP_CHECK(hipMemsetAsync(d_amb_cnt, 0, static_cast<size_t>(n_launch) * sizeof(unsigned int), ctx->stream));
-    }
-
-    const size_t lds_bytes = 2 * static_cast<size_t>(4 * mf_ks(core_slices)) + MF_MAXBLK * sizeof(int32_t) + 16 * 512 * sizeof(long long);
-    const void *kfn_obs = reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2, false, true, 0, true, 1>);
-    const void *kfn_zobs = reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS + 1, true>);     // z-scores, all seven slices
-    const size_t lds_zobs = 2 * static_cast<size_t>(4 * mf_ks(MF_NS + 1)) + MF_MAXBLK * sizeof(int32_t) + 16 * 512 * sizeof(long long);
-    const void *kfn = zfilt           ? reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2 + 1, true, true, 0, true, 2>)
-                      : z             ? kfn_zobs
-                      : filt          ? reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS / 2, false, true, 0, true, 2>)
-                      : n_slices == 2 ? reinterpret_cast<const void *>(k_permtest_mfma<false, 2>)
-                      : n_slices == 4 ? reinterpret_cast<const void *>(k_permtest_mfma<false, 4>)
-                                      : reinterpret_cast<const void *>(k_permtest_mfma<false, MF_NS>);
-    SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-    if (filt) SAFE_HIP_CHECK(hipFuncSetAttribute(kfn_obs, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-    if (zfilt) SAFE_HIP_CHECK(hipFuncSetAttribute(kfn_zobs, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_zobs)));
+    const int64_t n = nbr->n, mloc = col1 - col0, P = perms->count, n_padr = nbr->bs_groups * MF_R;
+    const MfmaSwitches sw = mfma_switches();
 #ifdef SAFE_HIP_DIAG
     static const int mfma_dbg = getenv("SAFE_HIP_MFMA_DBG") ? atoi(getenv("SAFE_HIP_MFMA_DBG")) : 0;
     if (mfma_dbg) safe_warn_diagnostic("SAFE_HIP_MFMA_DBG");
 #else
     constexpr int mfma_dbg = 0;
 #endif
-    // SAFE_HIP_MFMA_FORM=f: round 5's kernel (register-staged gather); default: k_permtest_mfma_g (LDS-DMA gather)
-    const bool form_f = form_env && !strcmp(form_env, "f");
-    const void *kfn_own = !form_f                            ? reinterpret_cast<const void *>(k_permtest_mfma_g<0>)
-                                                             : reinterpret_cast<const void *>(k_permtest_mfma_f<0>);
-#ifdef SAFE_HIP_DIAG
-#define MF_F_DIAG(D) if (form_f && mfma_dbg == D) kfn_own = reinterpret_cast<const void *>(k_permtest_mfma_f<D>);
-    MF_F_DIAG(1) MF_F_DIAG(2) MF_F_DIAG(4) MF_F_DIAG(8) MF_F_DIAG(15) MF_F_DIAG(31) MF_F_DIAG(47) MF_F_DIAG(79) MF_F_DIAG(271) MF_F_DIAG(127) MF_F_DIAG(383) MF_F_DIAG(511) MF_F_DIAG(512) MF_F_DIAG(1024)
-#undef MF_F_DIAG
-#define MF_G_DIAG(D) if (!form_f && mfma_dbg == D) kfn_own = reinterpret_cast<const void *>(k_permtest_mfma_g<D>);
-    MF_G_DIAG(2) MF_G_DIAG(4) MF_G_DIAG(8) MF_G_DIAG(64) MF_G_DIAG(66) MF_G_DIAG(512) MF_G_DIAG(1024)
-#undef MF_G_DIAG
-#endif
-    // filtered z-scores: their own kernel in the same shape (SAFE_HIP_MFMA_FORM=general keeps the general kernel's FM = 2)
-    const bool zfilt_own = zfilt && nbr->bs_max_group_blocks <= MF_GZ_MAXBLK && !(form_env && (!strcmp(form_env, "general") || !strcmp(form_env, "f")));
-    const void *kfn_gz = (form_env && !strcmp(form_env, "gz64")) ? reinterpret_cast<const void *>(k_permtest_mfma_gz<0, false>)   // (A/B: the f64 test)
-                                                                 : reinterpret_cast<const void *>(k_permtest_mfma_gz<0>);
-#ifdef SAFE_HIP_DIAG
-#define MF_GZ_DIAG(D) if (mfma_dbg == D) kfn_gz = reinterpret_cast<const void *>(k_permtest_mfma_gz<D>);
-    MF_GZ_DIAG(2) MF_GZ_DIAG(4) MF_GZ_DIAG(8) MF_GZ_DIAG(64) MF_GZ_DIAG(512)
-#undef MF_GZ_DIAG
-#endif
-    const size_t lds_gz = 2 * static_cast<size_t>(4 * 32 * (MF_NS / 2 + 1) * 32) + MF_GZ_MAXBLK * sizeof(int32_t) + 16 * 256 * sizeof(long long) + 8 * 256 * sizeof(uint32_t) + 16;
-    if (zfilt_own) SAFE_HIP_CHECK(hipFuncSetAttribute(kfn_gz, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_gz)));
-    const size_t lds_own = form_f ? 2 * static_cast<size_t>(4 * (MF_NS / 2) * MF_SS) + MF_F_MAXBLK * sizeof(int32_t) + 32 * 256 * sizeof(int32_t) + 8 * 256 * sizeof(uint32_t)
-                                  : 2 * static_cast<size_t>(4 * 32 * (MF_NS / 2) * 32) + MF_F_MAXBLK * sizeof(int32_t) + 32 * 256 * sizeof(int32_t) + 8 * 256 * sizeof(uint32_t) + 16;
-    const uint4 *bits_own = form_f ? nbr->bs_bits4 : nbr->bs_bits4p;
-    if (filt_own)
-        SAFE_HIP_CHECK(hipFuncSetAttribute(kfn_own, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_own)));
-    ctx->last_slices = n_slices;
-    ctx->last_core_slices = core_slices;
+
+    MfmaColumns cols;
+    SAFE_TRY(mfma_prepare_columns(ctx, nbr, attr, col0, mloc, z, allow_filter && sw.filter, &cols));
+    if (cols.bad && !sw.force_mfma) {
+        *declined = true;
+        return SAFE_OK;
+    }
+    const MfmaForm form = mfma_form(z, allow_filter, cols.n_slices, nbr->bs_max_group_blocks, nbr->max_count, cols.lay, sw);
+    MfmaPlan plan;
+    SAFE_TRY(mfma_make_plan(ctx, nbr, perms, form, mloc, sw, &plan));
+    const int64_t n_launch = plan.n_launch;
+    ctx->last_slices = form.n_slices;
+    ctx->last_core_slices = form.core_slices;
     ctx->last_undecided = 0;
-    // The kernel is persistent and takes a CU whole (256 VGPRs x 2 waves per SIMD): table kernels of the next span that are
-    // queued while it runs (aux stream: scan rounds, row emission) get a CU only as its workgroups retire and trickle through
-    // the whole tail of the launch -- harmless for the result, but they then show launch-long durations in a kernel trace
-    // (half of the "GPU time" of a profile).  Leaving CUs free does not help unless every XCD has one (workgroups are dealt to
-    // XCDs round-robin), which costs 3 % of the matrix-core throughput.  Long launches therefore make the table stream wait for
-    // their predecessor instead (below): the tables of a span are needed only when that launch has ended.
-    const int64_t blocks = std::min<int64_t>(static_cast<int64_t>(tasks.size()), ctx->num_cu);
-    if (zfilt) row_bytes = 128;                                // the filtered z form's rows: three value | square slices + the not-NaN slice
-    const int64_t tile_bytes = (n + 1) * row_bytes;
-    const bool long_launches = static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(span) >= 2e9;   // >~ 20 ms each
     // z-scores: the counters compare against the observed score itself, which may be NaN (k_counts_finalize<true> reads it)
     if (z && !out.ns) SAFE_TRY(ctx_scratch(ctx, 2, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&out.ns)));
     ctx->last_kernel.name = "k_permtest_mfma";
@@ -3286,146 +3127,19 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
     SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &ev));
     SAFE_TRY(ctx_events(ctx, false, 2, &plain));
     hipEvent_t ready = plain[0], side_done = plain[1];
-    if (filt) {
-        // the exact observed scores: low digits stored, high digits added << 24 (two short launches over the identity map)
-        hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), 1), dim3(256), 0, ctx->stream, nbr->bs_order, n_src, n,
-                           static_cast<const int32_t *>(nullptr), 0, d_src_id, 0);
-        for (int pass = 0; pass < 2; ++pass) {
-            const unsigned char *bs_p = pass ? d_bs_hi : d_bs_lo;
-            const int32_t *src_c = d_src_id;
-            int n_q = 1;
-            unsigned int *qctr_c = d_qctr + 8 * n_launch + 8 + 8 * pass;
-            double *ns_c = nullptr;
-            HypLookup no_lookup{};
-            MfmaFilt fa;
-            fa.obs64 = d_obs64;
-            fa.obs_shift = pass ? 24 : 0;
-            void *args[] = {(void *)&bs_p, (void *)&row_bytes, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
-                            (void *)&nbr->bs_kb, (void *)&nbr->bs_bits, (void *)&d_tasks, (void *)&d_qoff, (void *)&qctr_c, (void *)&mloc,
-                            (void *)&d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&d_scale, (void *)&ns_c, (void *)&no_lookup, (void *)&fa};
-            SAFE_HIP_CHECK(hipLaunchKernel(kfn_obs, dim3(blocks), dim3(512), args, lds_bytes, ctx->stream));
-        }
-        if (out.ns)
-            hipLaunchKernelGGL(k_mfma_obs_ns, dim3(n_padr / 32, ceil_div(mloc, 32)), dim3(256), 0, ctx->stream, d_obs64, n_padr, nbr->bs_rowmap,
-                               d_scale, mloc, out.ns);
-        SAFE_HIP_CHECK(hipGetLastError());
-    }
-    if (zfilt) {
-        // the observed z-scores: one pass of the seven-slice kernel over the identity map writes them to out.ns (exact sums, the
-        // reference's formula); the filtered launches compare against them
-        hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), 1), dim3(256), 0, ctx->stream, nbr->bs_order, n_src, n,
-                           static_cast<const int32_t *>(nullptr), 0, d_src_id, 0);
-        const unsigned char *bs_p = d_bs;
-        int64_t rb7 = (MF_NS + 1) * 32, tb7 = (n + 1) * rb7;
-        const int32_t *src_c = d_src_id;
-        int n_q = 1;
-        unsigned int *qctr_c = d_qctr + 8 * n_launch + 8;
-        double *ns_c = out.ns;
-        HypLookup no_lookup{};
-        MfmaFilt fa;
-        void *args[] = {(void *)&bs_p, (void *)&rb7, (void *)&tb7, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
-                        (void *)&nbr->bs_kb, (void *)&nbr->bs_bits, (void *)&d_tasks, (void *)&d_qoff, (void *)&qctr_c, (void *)&mloc,
-                        (void *)&d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&d_scale, (void *)&ns_c, (void *)&no_lookup, (void *)&fa};
-        SAFE_HIP_CHECK(hipLaunchKernel(kfn_zobs, dim3(blocks), dim3(512), args, lds_zobs, ctx->stream));
-        SAFE_HIP_CHECK(hipGetLastError());
-    }
+    if (form.filtered()) SAFE_TRY(mfma_observe(ctx, nbr, form, cols, plan, mloc, out.ns));
     SAFE_HIP_CHECK(hipEventRecord(ready, ctx->stream));
     SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ready, 0));
-    for (int64_t c = 0; c < n_launch; ++c) {
-        const int64_t p_base = starts[c], p_limit = starts[c + 1], cnt = p_limit - p_base;
-        hipStream_t ks = (c & 1) ? ctx->side_stream : ctx->stream;
-        if (long_launches && c >= 1) SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->aux_stream, ev[2 * (c - 1) + 1], 0));
-        SAFE_TRY(perms_wait(perms, p_limit, ks));
-#ifdef SAFE_HIP_DIAG
-        static const int dbg_window = getenv("SAFE_HIP_MFMA_DBG_WINDOW") ? atoi(getenv("SAFE_HIP_MFMA_DBG_WINDOW")) : 0;
-        if (dbg_window > 0) safe_warn_diagnostic("SAFE_HIP_MFMA_DBG_WINDOW");
-#else
-        constexpr int dbg_window = 0;
-#endif
-        hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), cnt + 1), dim3(256), 0, ks, nbr->bs_order, n_src, n, perms->table,
-                           p_base, d_src[c & 1], dbg_window);
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
-        {
-            // classic: row 0 of the source maps is the identity (the observed score is formed once per task); filtered form:
-            // the observed scores are in d_obs64 and every q is a permutation
-            const int32_t *src_c = any_filt ? d_src[c & 1] + n_src : d_src[c & 1];
-            int n_q = static_cast<int>(any_filt ? cnt : cnt + 1);
-            unsigned int *qctr_c = d_qctr + 8 * c;
-            double *ns_c = (c == 0 && !any_filt) ? out.ns : static_cast<double *>(nullptr);
-            HypLookup no_lookup{};
-            no_lookup.dbg = mfma_dbg;        // 1: no transposes / LDS stores of the gathered rows, 4: no barrier per super-step, 8: no score completion
-            MfmaFilt fa;
-            if (any_filt) {
-                fa.obs64 = d_obs64;
-                fa.zobs = out.ns;
-                fa.rowcnt = nbr->bs_rowcnt;
-                fa.amb = d_amb[c & 1];
-                fa.amb_count = d_amb_cnt + c;
-                fa.amb_cap = amb_cap;
-                fa.p_base = static_cast<int>(p_base);
-#ifdef SAFE_HIP_DIAG
-                if (mfma_dbg == 512) {
-                    if (!ctx->diag_prof) SAFE_HIP_CHECK(hipMalloc(&ctx->diag_prof, 64 * sizeof(unsigned long long)));
-                    if (c == 0) SAFE_HIP_CHECK(hipMemsetAsync(ctx->diag_prof, 0, 64 * sizeof(unsigned long long), ks));
-                    fa.prof = static_cast<unsigned long long *>(ctx->diag_prof);
-                }
-#endif
-            }
-            const unsigned char *bs_main = any_filt ? d_bs_hi : d_bs;
-            if (zfilt_own) {
-                const int64_t blocks_own = std::min<int64_t>(static_cast<int64_t>(tasks.size()), 2 * static_cast<int64_t>(ctx->num_cu));
-                void *args[] = {(void *)&bs_main, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
-                                (void *)&nbr->bs_kb, (void *)&nbr->bs_bits4p, (void *)&d_tasks, (void *)&d_qoff, (void *)&qctr_c,
-                                (void *)&mloc, (void *)&d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&d_scale, (void *)&fa};
-                SAFE_HIP_CHECK(hipLaunchKernel(kfn_gz, dim3(blocks_own), dim3(256), args, lds_gz, ks));
-            } else if (filt_own) {
-                const int64_t blocks_own = std::min<int64_t>(static_cast<int64_t>(tasks.size()), 2 * static_cast<int64_t>(ctx->num_cu));
-                void *args[] = {(void *)&bs_main, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
-                                (void *)&nbr->bs_kb, (void *)&bits_own, (void *)&nbr->bs_grpmax, (void *)&d_tasks, (void *)&d_qoff, (void *)&qctr_c,
-                                (void *)&mloc, (void *)&d_counts, (void *)&n_padr, (void *)&fa};
-                SAFE_HIP_CHECK(hipLaunchKernel(kfn_own, dim3(blocks_own), dim3(256), args, lds_own, ks));
-            } else {
-            void *args[] = {(void *)&bs_main, (void *)&row_bytes, (void *)&tile_bytes, (void *)&src_c, (void *)&n_src, (void *)&n_q, (void *)&nbr->bs_ptr,
-                            (void *)&nbr->bs_kb, (void *)&nbr->bs_bits, (void *)&d_tasks, (void *)&d_qoff, (void *)&qctr_c, (void *)&mloc,
-                            (void *)&d_counts, (void *)&n_padr, (void *)&nbr->bs_rowmap, (void *)&d_scale, (void *)&ns_c, (void *)&no_lookup, (void *)&fa};
-            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(blocks), dim3(512), args, lds_bytes, ks));
-            }
-        }
-        SAFE_HIP_CHECK(hipGetLastError());
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
-        if (any_filt) {
-            if (zfilt)
-                hipLaunchKernelGGL(k_mfma_resolve_z, dim3(4 * ctx->num_cu), dim3(256), 0, ks, d_amb[c & 1], d_amb_cnt + c, amb_cap, out.ns, mloc, n_padr,
-                                   nbr->bs_rowmap, nbr->row_ptr, nbr->col, perms->table, n, d_bs_lo, d_bs_hi, d_z64, d_scale, d_counts);
-            else
-                hipLaunchKernelGGL(k_mfma_resolve, dim3(4 * ctx->num_cu), dim3(256), 0, ks, d_amb[c & 1], d_amb_cnt + c, amb_cap, d_obs64, n_padr,
-                                   nbr->bs_rowmap, nbr->row_ptr, nbr->col, perms->table, n, d_bs_lo, tile_bytes, split_off, d_q64, mloc, d_counts);
-            SAFE_HIP_CHECK(hipGetLastError());
-            if (c == 0 && long_launches && n_launch > 1) {
-                // pilot: data with many equal scores (sparse columns, few distinct values) leaves the high digits little to
-                // decide -- if the first launch sent more than 2 in 1000 compares to the resolve kernel, stop here and let the
-                // caller run all six slices (a launch of this size is long: the wait is nothing beside it)
-                unsigned int seen0 = 0;
-                SAFE_HIP_CHECK(hipMemcpyAsync(&seen0, d_amb_cnt, sizeof(seen0), hipMemcpyDeviceToHost, ks));
-                SAFE_HIP_CHECK(safe_stream_sync(ks));
-                if (static_cast<double>(seen0) > 2e-3 * static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(cnt)) {
-                    ctx->last_undecided = seen0;
-                    *overflowed = true;
-                    return SAFE_OK;
-                }
-            }
-        }
-        if (c >= 1) {
-            // the source-map buffer of span c-1 is reused by span c+1: same stream, ordered
-        }
-    }
+    SAFE_TRY(mfma_launch_spans(ctx, nbr, perms, form, cols, plan, mloc, out.ns, mfma_dbg, ev, overflowed));
+    if (*overflowed) return SAFE_OK;
     SAFE_HIP_CHECK(hipEventRecord(side_done, ctx->side_stream));
     SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->stream, side_done, 0));
-    std::vector<unsigned int> amb_seen(any_filt ? n_launch : 0, 0u);
-    if (any_filt) SAFE_HIP_CHECK(hipMemcpyAsync(amb_seen.data(), d_amb_cnt, amb_seen.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    SAFE_TRY(enrich_finalize_counts(ctx, d_counts, n_padr, nbr->bs_rowmap, mloc, P, out, z ? out.ns : nullptr));
+    std::vector<unsigned int> amb_seen(form.filtered() ? n_launch : 0, 0u);
+    if (form.filtered())
+        SAFE_HIP_CHECK(hipMemcpyAsync(amb_seen.data(), plan.d_amb_cnt, amb_seen.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_TRY(enrich_finalize_counts(ctx, plan.d_counts, n_padr, nbr->bs_rowmap, mloc, P, out, z ? out.ns : nullptr));
     if (!z) {                                                 // (z-score counters depend on NaN observed scores: not exported)
-        ctx->packed_counts = d_counts;
+        ctx->packed_counts = plan.d_counts;
         ctx->packed_n_pad = n_padr;
         ctx->packed_m = mloc;
         ctx->packed_perms = P;
@@ -3441,14 +3155,14 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
         SAFE_HIP_CHECK(hipMemcpy(prof, ctx->diag_prof, sizeof(prof), hipMemcpyDeviceToHost));
         for (int w = 0; w < 4; ++w) {
             const double it = static_cast<double>(std::max<unsigned long long>(prof[w * 8 + 4], 1));
-            fprintf(stderr, "mfma_f wave %d: %.0f iterations; cycles per iteration: loads %.0f, k-loop %.0f, completion %.0f, barrier %.0f\n", w, it,
+            fprintf(stderr, "mfma_g wave %d: %.0f iterations; cycles per iteration: loads %.0f, k-loop %.0f, completion %.0f, barrier %.0f\n", w, it,
                     prof[w * 8] / it, prof[w * 8 + 1] / it, prof[w * 8 + 2] / it, prof[w * 8 + 3] / it);
         }
     }
 #endif
     for (unsigned int seen : amb_seen) {
         ctx->last_undecided += seen;
-        if (seen > amb_cap) *overflowed = true;          // a launch left more undecided compares than its list holds
+        if (seen > plan.amb_cap) *overflowed = true;     // a launch left more undecided compares than its list holds
     }
     return SAFE_OK;
 }
