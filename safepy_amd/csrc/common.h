@@ -66,6 +66,7 @@ struct KernelStat {
     double total_ms = 0.0;
     int64_t launches = 0;
     double busy_ms = 0.0;           // union of the launches' intervals (consecutive launches overlap on two streams); 0 = not measured
+    bool summed = false;            // the launches' own events were summed (kernel_stat_from_events): k0 / k1 do not apply
 };
 
 struct safe_perms;
@@ -276,6 +277,14 @@ static inline double nes_p_cut(double enrichment_threshold) {
     return p;
 }
 
+// what a permutation-test kernel writes (PermOut::mode)
+enum PermMode {
+    PERM_SCORE = 0,    // the observed score only
+    PERM_COUNTS = 1,   // raw counts
+    PERM_FULL = 2,     // full post-processing: p-values, NES, nes_binary, enriched counters
+    PERM_SUBSET = 4,   // any subset of p-values / NES / nes_binary (NULL = not wanted) from 'sum' counters (k_counts_finalize)
+};
+
 // outputs of the permutation-test kernels (enrich.hip, mfma.hip)
 struct PermOut {
     double *ns;            // [n][mloc] or NULL
@@ -289,7 +298,7 @@ struct PermOut {
     const double *nes_table;  // [P+1]
     double nes_threshold;     // -log10(enrichment_threshold)
     int sign_mode;
-    int mode;                 // 0 = score only, 1 = raw counts, 2 = full post-processing
+    int mode;                 // PermMode
     int64_t ld;               // row pitch of the output matrices in elements (0 = the column count of the call)
 };
 
@@ -427,10 +436,11 @@ int perms_wait(safe_perms *perms, int64_t upto, hipStream_t s);   // make stream
 // counters [column][position] (#less << 16 | #greater) -> outputs; rowmap[position] = row or -1 (enrich.hip)
 int enrich_finalize_counts(safe_ctx *ctx, const unsigned int *counts, int64_t n_pad, const int32_t *rowmap, int64_t mloc,
                            int64_t n_perm, const PermOut &out, const double *ns_direct, hipStream_t on = nullptr, bool pk20 = false);
-// MFMA (i8, exact fixed point) form of the permutation test for quantitative attributes (mfma.hip)
-bool mfma_applicable(const safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const safe_perms *perms, bool z);
+// MFMA (i8, exact fixed point) form of the permutation test for quantitative attributes (mfma.hip); force_mfma =
+// SAFE_HIP_FORCE_PATH=mfma (parsed by the caller, enrich.hip route_switches)
+bool mfma_applicable(const safe_nbr *nbr, const safe_perms *perms, bool z, bool force_mfma);
 int launch_mfma(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1, bool z,
-                const PermOut &out, bool *declined);
+                const PermOut &out, bool force_mfma, bool *declined);
 // X = A . B0 for 0/1 attributes on the matrix cores (block-sparse, one i8 plane per 32-column tile),
 // written through `hl` (mfma.hip); sets ctx->last_kernel and the k0/k1 timing events
 int launch_mfma_counts(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, int64_t col1, const HypLookup &hl);

@@ -157,13 +157,13 @@ __global__ __launch_bounds__(256) void k_permtest_gather(
             const bool ok = live && (jbase + c < mloc);
             const bool obs_nan = obs[c] != obs[c];
             if (ok && out.ns) out.ns[o + c] = obs[c];
-            if (out.mode == 1) {
+            if (out.mode == PERM_COUNTS) {
                 // run_permutations returns plain counts (no NaN masking, safe_extras.py:70)
                 if (ok) {
                     out.counts_neg[o + c] = static_cast<double>(cneg[c]);
                     out.counts_pos[o + c] = static_cast<double>(cpos[c]);
                 }
-            } else if (out.mode == 2) {
+            } else if (out.mode == PERM_FULL) {
                 const double qnan = __longlong_as_double(0x7FF8000000000000ll);
                 // safe.py:528-533: counts[isnan(ns)] = nan; p = counts / P
                 const double pn = obs_nan ? qnan : static_cast<double>(cneg[c]) / static_cast<double>(n_perm);
@@ -441,10 +441,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_permtest_scatter(
             const unsigned int cpos = so == 0 ? static_cast<unsigned int>(n_perm) : (ct & 0xFFFFu);
             const int64_t o = i * mloc + j;
             if (out.ns) out.ns[o] = static_cast<double>(so);
-            if (out.mode == 1) {
+            if (out.mode == PERM_COUNTS) {
                 out.counts_neg[o] = static_cast<double>(cneg);
                 out.counts_pos[o] = static_cast<double>(cpos);
-            } else if (out.mode == 2) {
+            } else if (out.mode == PERM_FULL) {
                 const double en = out.nes_table[cneg], ep = out.nes_table[cpos];
                 double nes = ep - en;
                 if (out.sign_mode == SAFE_SIGN_HIGHEST) nes = ep;
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_permtest_scatter(
                 hits += hit;
             }
         }
-        if (out.mode == 2) {
+        if (out.mode == PERM_FULL) {
             for (int off = 32; off > 0; off >>= 1) hits += __shfl_down(hits, off);
             if (lane == 0 && hits) atomicAdd(&out.enriched[j], hits);
         }
@@ -1611,7 +1611,7 @@ __global__ __launch_bounds__(256, 4) void k_permtest_bits_blk_plain(
 // 512-byte writes along the columns of each row.
 // DIRECT = false: counters hold (#less << 16 | #greater)  (bit-sliced kernel)
 // DIRECT = true : counters hold (#>=   << 16 | #<=) and NaN observed scores matter (f64 kernel)
-// MODE = out.mode (1 raw counts, 2 everything, 3 NES only, 4 any subset), a template parameter so that the row loop has no
+// MODE = out.mode (PERM_COUNTS, PERM_FULL, or PERM_SUBSET without DIRECT), a template parameter so that the row loop has no
 // branches; TAB_LDS: the NES table (P + 1 doubles) is staged in LDS.  The row loop then holds no global load at all (row ids
 // and the table come from LDS), so its stores stream: the first form loaded the row id, the two table entries and (DIRECT) the
 // observed score per row with `s_waitcnt vmcnt(0)` between them -- vmcnt retires in order, so every row also waited for the
@@ -1660,7 +1660,7 @@ __global__ __launch_bounds__(256) void k_counts_finalize(const unsigned int *__r
         }
     }
     if (threadIdx.x < FIN_TP) rows[threadIdx.x] = sell_row[spos0 + threadIdx.x];
-    if (TAB_LDS && MODE != 1)
+    if (TAB_LDS && MODE != PERM_COUNTS)
         for (int64_t i = threadIdx.x; i <= n_perm; i += 256) {
             tab_lds[i] = out.nes_table[i];
             if (pv_lds) tab_lds[n_perm + 1 + i] = static_cast<double>(i) / static_cast<double>(n_perm);
@@ -1693,20 +1693,17 @@ __global__ __launch_bounds__(256) void k_counts_finalize(const unsigned int *__r
                 cneg = P - (v & 0xFFFFu);           // #(S_p <= S_obs) = P - #greater
                 cpos = P - (v >> 16);               // #(S_p >= S_obs) = P - #less
             }
-            if (MODE == 1) {
+            if (MODE == PERM_COUNTS) {
                 out.counts_neg[o] = static_cast<double>(cneg);
                 out.counts_pos[o] = static_cast<double>(cpos);
-            } else if (MODE == 3) {                                  // NES only (all-gathered counters of other ranks)
-                const double en = tab[cneg], ep = tab[cpos];
-                out.nes[o] = out.sign_mode == SAFE_SIGN_HIGHEST ? ep : out.sign_mode == SAFE_SIGN_LOWEST ? en : ep - en;
-            } else if (MODE == 4) {                                  // any subset of the matrices from all-gathered 'sum' counters
+            } else if (MODE == PERM_SUBSET) {                        // any subset of the matrices from all-gathered 'sum' counters
                 const double en = tab[cneg], ep = tab[cpos];
                 const double nes = out.sign_mode == SAFE_SIGN_HIGHEST ? ep : out.sign_mode == SAFE_SIGN_LOWEST ? en : ep - en;
                 if (out.pvalues_neg) out.pvalues_neg[o] = pv ? pv[cneg] : static_cast<double>(cneg) / p_f;
                 if (out.pvalues_pos) out.pvalues_pos[o] = pv ? pv[cpos] : static_cast<double>(cpos) / p_f;
                 if (out.nes) out.nes[o] = nes;
                 if (out.nes_binary) out.nes_binary[o] = fabs(nes) > out.nes_threshold ? 1.0 : 0.0;
-            } else if (MODE == 2) {
+            } else if (MODE == PERM_FULL) {
                 const double qnan = __longlong_as_double(0x7FF8000000000000ll);
                 const double en = obs_nan ? qnan : tab[cneg], ep = obs_nan ? qnan : tab[cpos];
                 double nes = ep - en;
@@ -1721,7 +1718,7 @@ __global__ __launch_bounds__(256) void k_counts_finalize(const unsigned int *__r
             }
         }
     }
-    if (MODE == 2) {
+    if (MODE == PERM_FULL) {
 #pragma unroll
         for (int ct = 0; ct < FIN_TC / 64; ++ct) part[wave][ct * 64 + lane] = hits[ct];
         __syncthreads();
@@ -1738,32 +1735,30 @@ int enrich_finalize_counts(safe_ctx *ctx, const unsigned int *counts, int64_t n_
     const hipStream_t fin_stream = on ? on : ctx->stream;
     const dim3 grid(n_pad / FIN_TP, ceil_div(mloc, FIN_TC));
     const size_t tab_bytes = static_cast<size_t>(n_perm + 1) * sizeof(double);
-    const bool tab_lds = out.mode != 1 && tab_bytes <= 20 * 1024;          // (next to 43 KB of static LDS)
+    const bool tab_lds = out.mode != PERM_COUNTS && tab_bytes <= 20 * 1024;  // (next to 43 KB of static LDS)
     const int pv_lds = tab_lds && 2 * tab_bytes <= 20 * 1024 ? 1 : 0;                                  // k / P table behind the NES table
     const size_t dyn = tab_lds ? (pv_lds ? 2 : 1) * tab_bytes : 0;
-#define FIN(D, M, L) hipLaunchKernelGGL((k_counts_finalize<D, M, L>), grid, dim3(256), dyn, fin_stream, counts, n_pad, rowmap, ns_direct, mloc, n_perm, out, pv_lds)
-#define FIN_MODE(D, L)                      \
-    do {                                    \
-        if (out.mode == 1) FIN(D, 1, false); \
-        else if (out.mode == 2) FIN(D, 2, L); \
-        else if (out.mode == 3) FIN(D, 3, L); \
-        else if (out.mode == 4) FIN(D, 4, L); \
+    // PERM_SUBSET serves the exchanged 'sum' counters of other ranks (no observed scores), and the 20-bit pairs serve only it
+    SAFE_REQUIRE(!pk20 || (!ns_direct && out.mode == PERM_SUBSET && n_perm <= 1023),
+                 "enrich_finalize_counts: 20-bit counter pairs serve the exchanged 'sum' counters of at most 1023 permutations");
+    SAFE_REQUIRE(!ns_direct || out.mode != PERM_SUBSET, "enrich_finalize_counts: a subset of the outputs has no observed scores");
+#define FIN(D, M, L, PK) hipLaunchKernelGGL((k_counts_finalize<D, M, L, PK>), grid, dim3(256), dyn, fin_stream, counts, n_pad, rowmap, ns_direct, mloc, n_perm, out, pv_lds)
+#define FIN_TAB(D, M, PK)                       \
+    do {                                        \
+        if (tab_lds) FIN(D, M, true, PK);       \
+        else FIN(D, M, false, PK);              \
     } while (0)
-    if (pk20) {                                        // (exchanged slabs only: mode 4, no observed scores)
-        if (ns_direct || out.mode != 4 || n_perm > 1023) {
-            safe_set_error("enrich_finalize_counts: 20-bit counter pairs serve the exchanged 'sum' counters of at most 1023 permutations");
-            return SAFE_E_INVALID;
-        }
-        if (tab_lds) hipLaunchKernelGGL((k_counts_finalize<false, 4, true, true>), grid, dim3(256), dyn, fin_stream, counts, n_pad, rowmap, ns_direct, mloc, n_perm, out, pv_lds);
-        else hipLaunchKernelGGL((k_counts_finalize<false, 4, false, true>), grid, dim3(256), dyn, fin_stream, counts, n_pad, rowmap, ns_direct, mloc, n_perm, out, pv_lds);
-    } else if (ns_direct) {
-        if (tab_lds) FIN_MODE(true, true);
-        else FIN_MODE(true, false);
-    } else {
-        if (tab_lds) FIN_MODE(false, true);
-        else FIN_MODE(false, false);
+    if (out.mode == PERM_COUNTS) {
+        if (ns_direct) FIN(true, PERM_COUNTS, false, false);
+        else FIN(false, PERM_COUNTS, false, false);
+    } else if (out.mode == PERM_FULL) {
+        if (ns_direct) FIN_TAB(true, PERM_FULL, false);
+        else FIN_TAB(false, PERM_FULL, false);
+    } else if (out.mode == PERM_SUBSET) {
+        if (pk20) FIN_TAB(false, PERM_SUBSET, true);
+        else FIN_TAB(false, PERM_SUBSET, false);
     }
-#undef FIN_MODE
+#undef FIN_TAB
 #undef FIN
     SAFE_HIP_CHECK(hipGetLastError());
     return SAFE_OK;
@@ -2592,26 +2587,6 @@ static void plan_bits_tasks(BitsTaskPlan &plan, const std::vector<int32_t> &slic
     }
 }
 
-enum PermPath { PATH_GATHER = 0, PATH_SCATTER = 1, PATH_BITS = 2 };
-
-// Picks the kernel form.  The two integer forms need 'sum' scores of 0/1 data (exact in
-// integers); scatter additionally wants sparse attributes (its work is nnz(A)*nnz(B)/N per
-// permutation, the bit-sliced form's is nnz(A)*M/64 word-adds).
-static PermPath choose_path(const safe_ctx *ctx, const safe_nbr *nbr, safe_attr *attr, int64_t n_perm, bool z) {
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
-    if (force && !strcmp(force, "gather")) return PATH_GATHER;
-    if (z || n_perm < 1 || n_perm > 65535) return PATH_GATHER;
-    if (safe_attr_prepare(attr) != SAFE_OK || attr->n_other != 0) return PATH_GATHER;
-    if (nbr->n >= 65535) return PATH_GATHER;
-    const bool bits_ok = bits_form(nbr->n, nbr->max_count, nbr->sell_col2 != nullptr, 160 * 1024).kind != BITS_NONE;
-    const bool scatter_ok = nbr->max_count < SC_EPOCH && scatter_lds_bytes(nbr->n) <= 160 * 1024;
-    if (force && !strcmp(force, "bits") && bits_ok) return PATH_BITS;
-    if (force && !strcmp(force, "scatter") && scatter_ok) return attr_build_support(attr) == SAFE_OK ? PATH_SCATTER : PATH_GATHER;
-    if (bits_ok) return PATH_BITS;
-    if (scatter_ok && attr_build_support(attr) == SAFE_OK) return PATH_SCATTER;
-    return PATH_GATHER;
-}
-
 // ev[2c], ev[2c+1] bracket launch c (recorded on alternating streams, all complete): sum of the durations, their count, and the
 // union of the intervals -- consecutive launches overlap, so the sum exceeds the time the GPU spent on them
 int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch) {
@@ -2627,6 +2602,7 @@ int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch) {
         covered_to = std::max(covered_to, b);
     }
     ctx->last_kernel.busy_ms = busy;
+    ctx->last_kernel.summed = true;
     return SAFE_OK;
 }
 
@@ -2972,14 +2948,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     return SAFE_OK;
 }
 
-// X = A . B0 for a binary attribute block through the bit-sliced count kernel; false if the
-// block does not qualify (not binary, or neighborhoods of 1024+ members)
-static bool counts_bits_applicable(const safe_nbr *nbr, safe_attr *attr) {
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
-    if (force && !strcmp(force, "gather")) return false;
-    return safe_attr_prepare(attr) == SAFE_OK && attr->n_other == 0 && nbr->max_count < (1 << BT_LV);
-}
-
+// X = A . B0 for a binary attribute block through the bit-sliced count kernel (counts_route)
 static int launch_counts_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, int64_t col1, double *out_dev) {
     const int64_t n = nbr->n, mloc = col1 - col0, n_wg = ceil_div(mloc, 64);
     uint2 *d_bits = nullptr;
@@ -2996,26 +2965,6 @@ static int launch_counts_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int
 
 static size_t ldsf64_bytes(int64_t n, int64_t stride16) {
     return (8 * static_cast<size_t>(n + 1) + static_cast<size_t>(stride16) + 4) * sizeof(unsigned int);
-}
-
-static bool lds_f64_applicable(const safe_nbr *nbr, const safe_perms *perms) {
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
-    if (force && !strcmp(force, "gather")) return false;
-    return nbr->sell_col2 != nullptr && perms->table16 != nullptr && perms->count >= 1 && perms->count <= 65535 &&
-           ldsf64_bytes(nbr->n, perms->stride16) <= 160 * 1024;
-}
-
-// A NARROW block of quantitative columns (the reference's own Example 3 tests ONE attribute with 10 000 permutations,
-// examples/Example_3_Scatterplot_annotation.ipynb:104,147): the matrix-core kernel pads the block to 32 columns and its launches
-// are latency-bound (0.67 ms per 128 permutations whatever the width up to ~256 columns), the LDS-resident f64 kernel is bound
-// by its 4-column tiles -- 2-2.6 x faster until n x columns ~ 2e5 (tools/probe/narrow_paths.py: 1586 x 1: 2.85 vs 5.59 ms per
-// 2000 permutations; 3971 x 32: 2.55 vs 3.78; 3971 x 64: 4.16 vs 3.78).
-static bool narrow_block_prefers_lds(const safe_nbr *nbr, const safe_perms *perms, int64_t mloc) {
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
-    if (force && !strcmp(force, "mfma")) return false;
-    const char *knob = getenv("SAFE_HIP_NARROW_LDS");                  // =0: A/B, and the matrix-core tests at small sizes
-    const bool off = knob && !strcmp(knob, "0");
-    return !off && lds_f64_applicable(nbr, perms) && nbr->n * mloc <= 204800;
 }
 
 // general f64 permutation test with LDS-resident tiles (k_permtest_lds), pipelined over spans like launch_bits
@@ -3046,7 +2995,7 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     const size_t lds_bytes = ldsf64_bytes(n, perms->stride16);
     const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_bytes)));
     const int64_t slots = static_cast<int64_t>(ctx->num_cu) * per_cu;
-    const int NW = 16;                             // waves (= adjacent slices) per workgroup: LDS allows one workgroup per CU
+    constexpr int NW = 16;                         // waves (= adjacent slices) per workgroup: LDS allows one workgroup per CU
     const int64_t tasks_per_tile = std::max<int64_t>(1, ceil_div(6 * slots, n_tiles));
     const std::vector<int4> tasks = cost_sorted_tasks(slice_group_blocks(nbr->h_slice_width, nbr->n_slices, NW), span, 0, n_tiles,
                                                       tasks_per_tile, INT64_MAX, false, mloc);
@@ -3061,22 +3010,9 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     SAFE_HIP_CHECK(hipMemsetAsync(d_counts, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), ctx->stream));
     const int64_t blocks = std::min<int64_t>(static_cast<int64_t>(tasks.size()), slots);
     const int64_t n_tasks = static_cast<int64_t>(tasks.size());
-#define LDS_DISPATCH(ACTION)                                      \
-    do {                                                          \
-        if (z) {                                                  \
-            if (NW == 16) ACTION(true, 16);                       \
-            else if (NW == 8) ACTION(true, 8);                    \
-            else ACTION(true, 4);                                 \
-        } else {                                                  \
-            if (NW == 16) ACTION(false, 16);                      \
-            else if (NW == 8) ACTION(false, 8);                   \
-            else ACTION(false, 4);                                \
-        }                                                         \
-    } while (0)
-#define LDS_SETATTR(ZZ, W)                                                                                            \
-    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_permtest_lds<ZZ, W>),                         \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)))
-    LDS_DISPATCH(LDS_SETATTR);
+    const auto kfn = z ? k_permtest_lds<true, NW> : k_permtest_lds<false, NW>;
+    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds_bytes)));
     ctx->last_kernel.name = "k_permtest_lds";
     ctx->last_kernel.total_ms = 0.0;
     ctx->last_kernel.busy_ms = 0.0;
@@ -3092,11 +3028,9 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
         hipStream_t ks = (c & 1) ? ctx->side_stream : ctx->stream;
         SAFE_TRY(perms_wait(perms, p_limit, ks));
         SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
-#define LDS_LAUNCH(ZZ, W)                                                                                              \
-    hipLaunchKernelGGL((k_permtest_lds<ZZ, W>), dim3(blocks), dim3(64 * W), lds_bytes, ks, n, perms->table16,          \
-                       perms->stride16, nbr->sell_row, nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, \
-                       d_tiles, n_tasks, d_tasks, p_base, p_limit, d_queue + c, mloc, d_counts, n_pad, d_ns)
-        LDS_DISPATCH(LDS_LAUNCH);
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * NW), lds_bytes, ks, n, perms->table16, perms->stride16, nbr->sell_row,
+                           nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_tiles, n_tasks, d_tasks, p_base,
+                           p_limit, d_queue + c, mloc, d_counts, n_pad, d_ns);
         SAFE_HIP_CHECK(hipGetLastError());
         SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
     }
@@ -3269,16 +3203,178 @@ __global__ __launch_bounds__(256) void k_counts_to_outputs(const double *__restr
     if (hit) atomicAdd(&out.enriched[idx % m], 1u);
 }
 
+// the dominant kernel's time from k0 / k1 -- unless its launcher summed the events of its own launches (kernel_stat_from_events)
 static int finish_kernel_timing(safe_ctx *ctx) {
     SAFE_HIP_CHECK(hipEventSynchronize(ctx->k1));
-    if (ctx->last_kernel.name == "k_permtest_bits" || ctx->last_kernel.name == "k_permtest_bits_pre" || ctx->last_kernel.name == "k_permtest_bits_blk" ||
-        ctx->last_kernel.name == "k_permtest_lds" || ctx->last_kernel.name == "k_permtest_mfma")
-        return SAFE_OK;   // per-launch events already summed
+    const bool summed = ctx->last_kernel.summed;
+    ctx->last_kernel.summed = false;
+    if (summed) return SAFE_OK;
     float ms = 0.f;
     SAFE_HIP_CHECK(hipEventElapsedTime(&ms, ctx->k0, ctx->k1));
     ctx->last_kernel.total_ms = ms;
     ctx->last_kernel.busy_ms = ms;
     ctx->last_kernel.launches = 1;
+    return SAFE_OK;
+}
+
+// ---- the routes of the enrichment entry points -------------------------------------------------------------------------
+
+// The switches that steer the routes: read from the environment here and nowhere else, once per call (a process may change
+// them between calls).  The matrix-core path's own switches: mfma_switches (mfma.hip).
+enum ForcePath { FORCE_NONE, FORCE_GATHER, FORCE_SCATTER, FORCE_BITS, FORCE_MFMA, FORCE_LDS };
+struct RouteSwitches {
+    ForcePath force = FORCE_NONE;  // SAFE_HIP_FORCE_PATH=gather / scatter / bits / mfma / lds (any other value: none)
+    bool narrow_lds = true;        // SAFE_HIP_NARROW_LDS=0: narrow blocks stay on the matrix cores (A/B, the matrix-core tests)
+    int counts_mfma = -1;          // SAFE_HIP_COUNTS: 1 = "mfma", 0 = any other value, -1 = unset (the dense-network rule)
+    bool hyper_table = true;       // SAFE_HIP_HYPER_TABLE=0: the per-element hypergeometric kernel
+};
+static RouteSwitches route_switches() {
+    const auto is = [](const char *e, const char *value) { return e && !strcmp(e, value); };
+    RouteSwitches sw;
+    const char *f = getenv("SAFE_HIP_FORCE_PATH");
+    sw.force = is(f, "gather")    ? FORCE_GATHER
+               : is(f, "scatter") ? FORCE_SCATTER
+               : is(f, "bits")    ? FORCE_BITS
+               : is(f, "mfma")    ? FORCE_MFMA
+               : is(f, "lds")     ? FORCE_LDS
+                                  : FORCE_NONE;
+    sw.narrow_lds = !is(getenv("SAFE_HIP_NARROW_LDS"), "0");
+    if (const char *c = getenv("SAFE_HIP_COUNTS")) sw.counts_mfma = !strcmp(c, "mfma");
+    sw.hyper_table = !is(getenv("SAFE_HIP_HYPER_TABLE"), "0");
+    return sw;
+}
+
+static bool lds_f64_applicable(const RouteSwitches &sw, const safe_nbr *nbr, const safe_perms *perms) {
+    return sw.force != FORCE_GATHER && nbr->sell_col2 != nullptr && perms->table16 != nullptr && perms->count >= 1 &&
+           perms->count <= 65535 && ldsf64_bytes(nbr->n, perms->stride16) <= 160 * 1024;
+}
+
+enum PermRoute { ROUTE_BITS, ROUTE_SCATTER, ROUTE_MFMA, ROUTE_LDS_F64, ROUTE_GATHER };
+
+// The kernel family of a permutation test, decided here and nowhere else (F = SAFE_HIP_FORCE_PATH, P permutations, N nodes):
+//   * F = gather: GATHER (no other family, no safe_attr_prepare).
+//   * The integer forms, for 'sum' scores with 1 <= P <= 65535 of a prepared attribute with n_other == 0 (0/1 data: exact in
+//     integers), N < 65535.  Scatter wants sparse attributes: its work is nnz(A) nnz(B) / N per permutation, the bit-sliced
+//     form's nnz(A) M / 64 word-adds.
+//       - F = scatter where scatter fits (max_count < SC_EPOCH, its LDS within 160 KiB): SCATTER if the support lists can be
+//         built, else the f64 chain (BITS is not tried);
+//       - otherwise (F = bits or scatter whose form does not fit included): BITS if bits_form gives a form, else SCATTER if it
+//         fits and the support lists can be built, else the f64 chain.  (attr_build_support is expensive: only there.)
+//   * The f64 chain:
+//       - MFMA if F is neither gather nor lds, mfma_applicable (z-scores: SAFE_HIP_MFMA_Z is not 0; 1 <= P <= 65535,
+//         N <= 2^30 / 32, max_count < 2^16; F = mfma or N >= 256) and the block is not narrow.  Narrow: F is not mfma,
+//         SAFE_HIP_NARROW_LDS is not 0, the LDS f64 kernel fits and N x columns <= 204 800.  Data the matrix cores decline
+//         (launch_mfma; never with F = mfma) goes on to LDS_F64 (run_perm_route);
+//       - LDS_F64 if lds_f64_applicable: sell_col2 and table16 exist, 1 <= P <= 65535, the kernel fits 160 KiB, F is not gather;
+//       - otherwise GATHER.
+//   (With F = lds a binary 'sum' block still goes to BITS.)
+// A NARROW block of quantitative columns (the reference's own Example 3 tests ONE attribute with 10 000 permutations,
+// examples/Example_3_Scatterplot_annotation.ipynb:104,147): the matrix-core kernel pads the block to 32 columns and its launches
+// are latency-bound (0.67 ms per 128 permutations whatever the width up to ~256 columns), the LDS-resident f64 kernel is bound
+// by its 4-column tiles -- 2-2.6 x faster until n x columns ~ 2e5 (tools/probe/narrow_paths.py: 1586 x 1: 2.85 vs 5.59 ms per
+// 2000 permutations; 3971 x 32: 2.55 vs 3.78; 3971 x 64: 4.16 vs 3.78).
+// perms == NULL (safe_randomization_plan, which asks only whether the route is BITS): the f64 chain is not looked at, GATHER
+// stands for all of it.
+static PermRoute perm_route(const RouteSwitches &sw, const safe_nbr *nbr, safe_attr *attr, int64_t n_perm, const safe_perms *perms,
+                            int64_t mloc, bool z) {
+    if (sw.force == FORCE_GATHER) return ROUTE_GATHER;
+    if (!z && n_perm >= 1 && n_perm <= 65535 && safe_attr_prepare(attr) == SAFE_OK && attr->n_other == 0 && nbr->n < 65535) {
+        const bool bits_ok = bits_form(nbr->n, nbr->max_count, nbr->sell_col2 != nullptr, 160 * 1024).kind != BITS_NONE;
+        const bool scatter_ok = nbr->max_count < SC_EPOCH && scatter_lds_bytes(nbr->n) <= 160 * 1024;
+        if (sw.force == FORCE_SCATTER && scatter_ok) {
+            if (attr_build_support(attr) == SAFE_OK) return ROUTE_SCATTER;
+        } else if (bits_ok) {
+            return ROUTE_BITS;
+        } else if (scatter_ok && attr_build_support(attr) == SAFE_OK) {
+            return ROUTE_SCATTER;
+        }
+    }
+    if (!perms) return ROUTE_GATHER;
+    const bool lds_ok = lds_f64_applicable(sw, nbr, perms);
+    const bool narrow = sw.force != FORCE_MFMA && sw.narrow_lds && lds_ok && nbr->n * mloc <= 204800;
+    if (sw.force != FORCE_LDS && !narrow && mfma_applicable(nbr, perms, z, sw.force == FORCE_MFMA)) return ROUTE_MFMA;
+    return lds_ok ? ROUTE_LDS_F64 : ROUTE_GATHER;
+}
+
+// Runs a permutation test on its route into `out`; a block the matrix cores decline goes on down the f64 chain
+static int run_perm_route(safe_ctx *ctx, const RouteSwitches &sw, PermRoute route, safe_nbr *nbr, safe_attr *attr, safe_perms *perms,
+                          int64_t col0, int64_t col1, bool z, const PermOut &out) {
+    if (route == ROUTE_MFMA) {
+        bool declined = false;
+        SAFE_TRY(launch_mfma(ctx, nbr, attr, perms, col0, col1, z, out, sw.force == FORCE_MFMA, &declined));
+        if (!declined) return SAFE_OK;
+        route = lds_f64_applicable(sw, nbr, perms) ? ROUTE_LDS_F64 : ROUTE_GATHER;
+    }
+    if (route == ROUTE_BITS) return launch_bits(ctx, nbr, attr, perms, col0, col1, out);
+    if (route == ROUTE_SCATTER) return launch_scatter(ctx, nbr, attr, perms, col0, col1, out);
+    if (route == ROUTE_LDS_F64) return launch_lds_f64(ctx, nbr, attr, perms, col0, col1, z, out);
+    Tiles tiles;
+    SAFE_TRY(build_tiles(ctx, attr, col0, col1, z, &tiles));
+    int rc = perms_wait(perms, perms->count, ctx->stream);          // (rc from here on: the tile buffer is freed on every path)
+    if (rc == SAFE_OK) rc = launch_gather(ctx, nbr, tiles, perms->table, perms->count, col1 - col0, z, out);
+    (void)hipFree(tiles.bt);
+    return rc;
+}
+
+// The counts X = A . B0 of a binary 'sum' block: through the bit-sliced count kernel (F is not gather, the attribute is binary,
+// neighborhoods below 1024 members) and there on the matrix cores (SAFE_HIP_COUNTS=mfma if it is set, else large
+// neighborhoods: N >= 256, nnz >= 128 N).  Not bit-sliced: the f64 kernels.
+struct CountsRoute {
+    bool bits, mfma;
+};
+static CountsRoute counts_route(const RouteSwitches &sw, const safe_nbr *nbr, safe_attr *attr) {
+    CountsRoute r{};
+    r.bits = sw.force != FORCE_GATHER && safe_attr_prepare(attr) == SAFE_OK && attr->n_other == 0 && nbr->max_count < (1 << BT_LV);
+    r.mfma = r.bits && (sw.counts_mfma >= 0 ? sw.counts_mfma == 1 : nbr->n >= 256 && nbr->nnz >= 128 * nbr->n);
+    return r;
+}
+
+// the NES look-up table tab[k] = -log10(k / P), k = 0 .. P (k = 0 as k = 1): the caller's, or computed here
+static std::vector<double> nes_table(const double *host, int64_t P) {
+    if (host) return std::vector<double>(host, host + P + 1);
+    std::vector<double> tab(P + 1);
+    for (int64_t k = 0; k <= P; ++k) tab[k] = -std::log10(static_cast<double>(std::max<int64_t>(k, 1)) / static_cast<double>(P));
+    return tab;
+}
+
+// the p-value / NES outputs of PERM_FULL or PERM_SUBSET (NULL: not wanted) against the NES table d_tab on the device
+static PermOut perm_outputs(int mode, double *pvalues_neg, double *pvalues_pos, double *nes, double *nes_binary, const double *d_tab,
+                            double enrichment_threshold, int sign_mode) {
+    PermOut out{};
+    out.mode = mode;
+    out.pvalues_neg = pvalues_neg;
+    out.pvalues_pos = pvalues_pos;
+    out.nes = nes;
+    out.nes_binary = nes_binary;
+    out.nes_table = d_tab;
+    out.nes_threshold = enrichment_threshold > 0.0 ? -std::log10(enrichment_threshold) : 0.0;
+    out.sign_mode = sign_mode;
+    return out;
+}
+
+// Chunk `chunk` of the last call's counters for the chunk exports: its columns [*c0, *c1) of the armed grid, whether or not the
+// call ran its tail chunk by chunk (it did not: a kernel form without the tail, too few stages -- then the call has ended, the
+// counters are final and no event is waited for), and the stream *s to copy on, which waits for the chunk's event.
+// narrow: 20-bit pairs, n_pad / 8 * 5 words per column (safe_export_packed_chunk_narrow), else n_pad counters.
+static int packed_chunk_prepare(safe_ctx *ctx, int chunk, const uint32_t *dst_dev, int64_t capacity, bool narrow, void *stream,
+                                int64_t *c0, int64_t *c1, hipStream_t *s) {
+    const char *fn = narrow ? "safe_export_packed_chunk_narrow" : "safe_export_packed_chunk";
+    SAFE_REQUIRE(ctx && dst_dev, "%s: NULL argument", fn);
+    SAFE_REQUIRE(ctx->packed_layout >= 0 && ctx->xc_want >= 1 && chunk >= 0 && chunk < ctx->xc_want, "%s: chunk %d of %d armed, counters %s",
+                 fn, chunk, ctx->xc_want, ctx->packed_layout >= 0 ? "present" : "absent");
+    SAFE_REQUIRE(!narrow || (ctx->packed_perms >= 1 && ctx->packed_perms <= 1023), "%s: %lld permutations do not fit 10-bit counters", fn,
+                 (long long)ctx->packed_perms);
+    *c0 = std::min<int64_t>(chunk * ctx->xc_cols, ctx->packed_m);
+    *c1 = chunk + 1 == ctx->xc_want ? ctx->packed_m : std::min<int64_t>((chunk + 1) * ctx->xc_cols, ctx->packed_m);
+    const int64_t need = (*c1 - *c0) * (narrow ? ctx->packed_n_pad / 8 * 5 : ctx->packed_n_pad);
+    SAFE_REQUIRE(capacity >= need, "%s: buffer holds %lld %s, %lld needed", fn, (long long)capacity, narrow ? "words" : "counters", (long long)need);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    *s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    if (ctx->xc_made > 0) {
+        SAFE_REQUIRE(ctx->xc_made == ctx->xc_want && ctx->xc_bounds[chunk] == *c0 && ctx->xc_bounds[chunk + 1] == *c1,
+                     "%s: the call's chunks are not the armed ones", fn);
+        SAFE_HIP_CHECK(hipStreamWaitEvent(*s, ctx->xc_events[chunk], 0));
+    }
     return SAFE_OK;
 }
 
@@ -3291,10 +3387,9 @@ int safe_score(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int score_type, in
     SAFE_REQUIRE(score_type == SAFE_SCORE_SUM || score_type == SAFE_SCORE_ZSCORE, "safe_score: bad score_type %d", score_type);
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     const bool z = score_type == SAFE_SCORE_ZSCORE;
-    if (!z && counts_bits_applicable(nbr, attr)) {
-        const char *counts_env = getenv("SAFE_HIP_COUNTS");
-        const bool dense_nbr = nbr->n >= 256 && nbr->nnz >= 128 * nbr->n;
-        if (counts_env ? !strcmp(counts_env, "mfma") : dense_nbr) {      // 0/1 data, large neighborhoods: matrix cores
+    const CountsRoute route = z ? CountsRoute{} : counts_route(route_switches(), nbr, attr);
+    if (route.bits) {
+        if (route.mfma) {
             HypLookup hl{};
             hl.pvalues_pos = out_dev;                                     // tab == NULL: plain counts
             SAFE_TRY(launch_mfma_counts(ctx, nbr, attr, col0, col1, hl));
@@ -3307,7 +3402,7 @@ int safe_score(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int score_type, in
     SAFE_TRY(build_tiles(ctx, attr, col0, col1, z, &tiles));
     PermOut out{};
     out.ns = out_dev;
-    out.mode = 0;
+    out.mode = PERM_SCORE;
     int rc = launch_gather(ctx, nbr, tiles, nullptr, 0, col1 - col0, z, out);
     if (rc == SAFE_OK) rc = finish_kernel_timing(ctx);
     (void)hipFree(tiles.bt);
@@ -3328,29 +3423,10 @@ int safe_permtest_counts(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_per
     out.ns = ns_dev;
     out.counts_neg = counts_neg_dev;
     out.counts_pos = counts_pos_dev;
-    out.mode = 1;
-    const PermPath path = choose_path(ctx, nbr, attr, perms->count, z);
-    if (path != PATH_GATHER) {
-        SAFE_TRY(path == PATH_BITS ? launch_bits(ctx, nbr, attr, perms, col0, col1, out)
-                                   : launch_scatter(ctx, nbr, attr, perms, col0, col1, out));
-        return finish_kernel_timing(ctx);
-    }
-    if (mfma_applicable(ctx, nbr, attr, perms, z) && !narrow_block_prefers_lds(nbr, perms, col1 - col0)) {
-        bool declined = false;
-        SAFE_TRY(launch_mfma(ctx, nbr, attr, perms, col0, col1, z, out, &declined));
-        if (!declined) return finish_kernel_timing(ctx);
-    }
-    if (lds_f64_applicable(nbr, perms)) {
-        SAFE_TRY(launch_lds_f64(ctx, nbr, attr, perms, col0, col1, z, out));
-        return finish_kernel_timing(ctx);
-    }
-    Tiles tiles;
-    SAFE_TRY(build_tiles(ctx, attr, col0, col1, z, &tiles));
-    int rc = perms_wait(perms, perms->count, ctx->stream);          // (rc from here on: the tile buffer is freed on every path)
-    if (rc == SAFE_OK) rc = launch_gather(ctx, nbr, tiles, perms->table, perms->count, col1 - col0, z, out);
-    if (rc == SAFE_OK) rc = finish_kernel_timing(ctx);
-    (void)hipFree(tiles.bt);
-    return rc;
+    out.mode = PERM_COUNTS;
+    const RouteSwitches sw = route_switches();
+    SAFE_TRY(run_perm_route(ctx, sw, perm_route(sw, nbr, attr, perms->count, perms, col1 - col0, z), nbr, attr, perms, col0, col1, z, out));
+    return finish_kernel_timing(ctx);
 }
 
 int safe_randomization(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int score_type, int sign_mode,
@@ -3370,69 +3446,24 @@ int safe_randomization(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     ctx->packed_layout = -1;
     const bool z = score_type == SAFE_SCORE_ZSCORE;
     const int64_t mloc = col1 - col0, P = perms->count;
-    std::vector<double> tab(P + 1);
-    if (nes_table_host) {
-        std::copy(nes_table_host, nes_table_host + P + 1, tab.begin());
-    } else {
-        tab[0] = -std::log10(1.0 / static_cast<double>(P));
-        for (int64_t k = 1; k <= P; ++k) tab[k] = -std::log10(static_cast<double>(k) / static_cast<double>(P));
-    }
-    double *d_tab = nullptr;
-    unsigned int *d_enr = nullptr;
-    Tiles tiles;
-    const PermPath path = choose_path(ctx, nbr, attr, P, z);
-    bool mfma = path == PATH_GATHER && mfma_applicable(ctx, nbr, attr, perms, z) && !narrow_block_prefers_lds(nbr, perms, mloc);
-    const bool lds64 = path == PATH_GATHER && lds_f64_applicable(nbr, perms);
+    const RouteSwitches sw = route_switches();
+    const PermRoute route = perm_route(sw, nbr, attr, P, perms, mloc, z);
+    const std::vector<double> tab = nes_table(nes_table_host, P);
     void *small = nullptr;                           // NES table f64 [P + 1] | enriched counters u32 [mloc + 16] (grow-only scratch)
-    int rc = ctx_scratch(ctx, 10, static_cast<size_t>(P + 1) * sizeof(double) + static_cast<size_t>(mloc + 16) * sizeof(unsigned int), &small);
-    if (rc == SAFE_OK) {
-        d_tab = static_cast<double *>(small);
-        d_enr = reinterpret_cast<unsigned int *>(d_tab + P + 1);
-    }
-    if (rc == SAFE_OK) {
-        hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_enr, 0, (mloc + 16) * sizeof(unsigned int), ctx->stream);
-        if (e != hipSuccess) {
-            safe_set_error("safe_randomization: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-        }
-    }
-    if (rc == SAFE_OK) {
-        PermOut out{};
-        out.ns = ns_dev;
-        out.pvalues_neg = pvalues_neg_dev;
-        out.pvalues_pos = pvalues_pos_dev;
-        out.nes = nes_dev;
-        out.nes_binary = nes_binary_dev;
-        out.enriched = d_enr;
-        out.nes_table = d_tab;
-        out.nes_threshold = -std::log10(enrichment_threshold);
-        out.sign_mode = sign_mode;
-        out.mode = 2;
-        if (mfma) {
-            bool declined = false;
-            rc = launch_mfma(ctx, nbr, attr, perms, col0, col1, z, out, &declined);
-            if (declined) mfma = false;
-        }
-        if (rc == SAFE_OK && !mfma) {
-            if (path == PATH_GATHER && !lds64) rc = build_tiles(ctx, attr, col0, col1, z, &tiles);
-            if (rc == SAFE_OK)
-                rc = lds64                  ? launch_lds_f64(ctx, nbr, attr, perms, col0, col1, z, out)
-                     : path == PATH_BITS    ? launch_bits(ctx, nbr, attr, perms, col0, col1, out)
-                     : path == PATH_SCATTER ? launch_scatter(ctx, nbr, attr, perms, col0, col1, out)
-                                            : (perms_wait(perms, P, ctx->stream) == SAFE_OK
-                                                   ? launch_gather(ctx, nbr, tiles, perms->table, P, mloc, z, out)
-                                                   : SAFE_E_HIP);
-        }
-    }
-    if (rc == SAFE_OK) {
-        hipLaunchKernelGGL(k_u32_to_f64, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, mloc);
-        if (hipGetLastError() != hipSuccess) rc = SAFE_E_HIP;
-    }
-    if (rc == SAFE_OK) rc = finish_kernel_timing(ctx);
-    if (rc == SAFE_OK && safe_stream_sync(ctx->stream) != hipSuccess) rc = SAFE_E_HIP;   // tab (host) + temporaries
-    (void)hipFree(tiles.bt);
-    return rc;
+    SAFE_TRY(ctx_scratch(ctx, 10, static_cast<size_t>(P + 1) * sizeof(double) + static_cast<size_t>(mloc + 16) * sizeof(unsigned int), &small));
+    double *d_tab = static_cast<double *>(small);
+    unsigned int *d_enr = reinterpret_cast<unsigned int *>(d_tab + P + 1);
+    SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, (mloc + 16) * sizeof(unsigned int), ctx->stream));
+    PermOut out = perm_outputs(PERM_FULL, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
+    out.ns = ns_dev;
+    out.enriched = d_enr;
+    SAFE_TRY(run_perm_route(ctx, sw, route, nbr, attr, perms, col0, col1, z, out));
+    hipLaunchKernelGGL(k_u32_to_f64, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, mloc);
+    SAFE_HIP_CHECK(hipGetLastError());
+    SAFE_TRY(finish_kernel_timing(ctx));
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));   // tab (host) + temporaries
+    return SAFE_OK;
 }
 
 int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichment_threshold, int64_t col0,
@@ -3448,12 +3479,9 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
     double *d_lf = nullptr, *d_hits = nullptr, *d_size = nullptr;
     unsigned int *d_enr = nullptr;
     Tiles tiles;
-    const bool bits = counts_bits_applicable(nbr, attr);
-    const char *table_env = getenv("SAFE_HIP_HYPER_TABLE");
-    const bool table = bits && !(table_env && !strcmp(table_env, "0"));
-    const char *counts_env = getenv("SAFE_HIP_COUNTS");
-    const bool dense_nbr = nbr->n >= 256 && nbr->nnz >= 128 * nbr->n;       // matrix cores pay off for large neighborhoods
-    const bool use_mfma = counts_env ? !strcmp(counts_env, "mfma") : dense_nbr;
+    const RouteSwitches sw = route_switches();
+    const CountsRoute route = counts_route(sw, nbr, attr);
+    const bool bits = route.bits, table = bits && sw.hyper_table, use_mfma = route.mfma;
     void *small = nullptr;                                                  // d_size f64 [n] | d_enr u32 [mloc + 64]
     int rc = ctx_scratch(ctx, 9, static_cast<size_t>(n) * sizeof(double) + static_cast<size_t>(mloc + 64) * sizeof(unsigned int), &small);
     if (rc == SAFE_OK) {
@@ -3501,7 +3529,7 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
         }
         PermOut out{};
         out.ns = d_hits;
-        out.mode = 0;
+        out.mode = PERM_SCORE;
         if (rc == SAFE_OK)
             rc = bits ? launch_counts_bits(ctx, nbr, attr, col0, col1, d_hits)
                       : launch_gather(ctx, nbr, tiles, nullptr, 0, mloc, false, out);   // X = A . B0 (safe.py:593-594)
@@ -3546,29 +3574,15 @@ int safe_outputs_from_counts(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_pe
     SAFE_REQUIRE(enrichment_threshold > 0.0 && enrichment_threshold < 1.0, "safe_outputs_from_counts: enrichment_threshold must be in (0,1)");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t P = num_permutations;
-    std::vector<double> tab(P + 1);
-    if (nes_table_host) {
-        std::copy(nes_table_host, nes_table_host + P + 1, tab.begin());
-    } else {
-        tab[0] = -std::log10(1.0 / static_cast<double>(P));
-        for (int64_t k = 1; k <= P; ++k) tab[k] = -std::log10(static_cast<double>(k) / static_cast<double>(P));
-    }
+    const std::vector<double> tab = nes_table(nes_table_host, P);
     void *small = nullptr;                           // NES table f64 [P + 1] | enriched counters u32 [m + 16]
     SAFE_TRY(ctx_scratch(ctx, 10, static_cast<size_t>(P + 1) * sizeof(double) + static_cast<size_t>(m + 16) * sizeof(unsigned int), &small));
     double *d_tab = static_cast<double *>(small);
     unsigned int *d_enr = reinterpret_cast<unsigned int *>(d_tab + P + 1);
     SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, (m + 16) * sizeof(unsigned int), ctx->stream));
-    PermOut out{};
-    out.pvalues_neg = pvalues_neg_dev;
-    out.pvalues_pos = pvalues_pos_dev;
-    out.nes = nes_dev;
-    out.nes_binary = nes_binary_dev;
+    PermOut out = perm_outputs(PERM_FULL, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
     out.enriched = d_enr;
-    out.nes_table = d_tab;
-    out.nes_threshold = -std::log10(enrichment_threshold);
-    out.sign_mode = sign_mode;
-    out.mode = 2;
     hipLaunchKernelGGL(k_counts_to_outputs, dim3(ceil_div(n * m, 256)), dim3(256), 0, ctx->stream, counts_neg_dev, counts_pos_dev, ns_dev,
                        n * m, m, P, out);
     hipLaunchKernelGGL(k_u32_to_f64, dim3(ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, m);
@@ -3618,25 +3632,11 @@ int safe_outputs_from_packed_counts(safe_ctx *ctx, safe_nbr *nbr, const uint32_t
                  (long long)n_pad, (long long)want_pad);
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t P = num_permutations;
-    std::vector<double> tab(P + 1);
-    if (nes_table_host) {
-        std::copy(nes_table_host, nes_table_host + P + 1, tab.begin());
-    } else {
-        tab[0] = -std::log10(1.0 / static_cast<double>(P));
-        for (int64_t k = 1; k <= P; ++k) tab[k] = -std::log10(static_cast<double>(k) / static_cast<double>(P));
-    }
+    const std::vector<double> tab = nes_table(nes_table_host, P);
     double *d_tab = nullptr;
     SAFE_TRY(ctx_scratch(ctx, 7, (P + 1) * sizeof(double), reinterpret_cast<void **>(&d_tab)));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PermOut out{};
-    out.pvalues_neg = pvalues_neg_dev;
-    out.pvalues_pos = pvalues_pos_dev;
-    out.nes = nes_dev;
-    out.nes_binary = nes_binary_dev;
-    out.nes_table = d_tab;
-    out.nes_threshold = enrichment_threshold > 0.0 ? -std::log10(enrichment_threshold) : 0.0;
-    out.sign_mode = sign_mode;
-    out.mode = 4;
+    const PermOut out = perm_outputs(PERM_SUBSET, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
     int rc = enrich_finalize_counts(ctx, counts_dev, n_pad, rowmap, m, P, out, nullptr);
     if (rc == SAFE_OK && safe_stream_sync(ctx->stream) != hipSuccess) rc = SAFE_E_HIP;   // tab is a host vector
     return rc;
@@ -3666,22 +3666,10 @@ int safe_packed_chunk_info(safe_ctx *ctx, int *chunks, int64_t *bounds, int64_t 
 }
 
 int safe_export_packed_chunk(safe_ctx *ctx, int chunk, uint32_t *dst_dev, int64_t capacity, void *stream) {
-    SAFE_REQUIRE(ctx && dst_dev, "safe_export_packed_chunk: NULL argument");
-    SAFE_REQUIRE(ctx->packed_layout >= 0 && ctx->xc_want >= 1 && chunk >= 0 && chunk < ctx->xc_want,
-                 "safe_export_packed_chunk: chunk %d of %d armed, counters %s", chunk, ctx->xc_want, ctx->packed_layout >= 0 ? "present" : "absent");
-    // the armed grid, whether or not the call ran its tail chunk by chunk (it did not: a kernel form without the tail, too few
-    // stages -- then the call has ended, the counters are final and no event is waited for)
-    const int64_t c0 = std::min<int64_t>(chunk * ctx->xc_cols, ctx->packed_m);
-    const int64_t c1 = chunk + 1 == ctx->xc_want ? ctx->packed_m : std::min<int64_t>((chunk + 1) * ctx->xc_cols, ctx->packed_m);
+    int64_t c0 = 0, c1 = 0;
+    hipStream_t s = nullptr;
+    SAFE_TRY(packed_chunk_prepare(ctx, chunk, dst_dev, capacity, false, stream, &c0, &c1, &s));
     const int64_t cells = (c1 - c0) * ctx->packed_n_pad;
-    SAFE_REQUIRE(capacity >= cells, "safe_export_packed_chunk: buffer holds %lld counters, %lld needed", (long long)capacity, (long long)cells);
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    if (ctx->xc_made > 0) {
-        SAFE_REQUIRE(ctx->xc_made == ctx->xc_want && ctx->xc_bounds[chunk] == c0 && ctx->xc_bounds[chunk + 1] == c1,
-                     "safe_export_packed_chunk: the call's chunks are not the armed ones");
-        SAFE_HIP_CHECK(hipStreamWaitEvent(s, ctx->xc_events[chunk], 0));
-    }
     if (cells)
         SAFE_HIP_CHECK(hipMemcpyAsync(dst_dev, ctx->packed_counts + c0 * ctx->packed_n_pad, static_cast<size_t>(cells) * sizeof(uint32_t),
                                       hipMemcpyDeviceToDevice, s));
@@ -3705,22 +3693,10 @@ __global__ __launch_bounds__(256) void k_pack_counts20(const unsigned int *__res
 }
 
 int safe_export_packed_chunk_narrow(safe_ctx *ctx, int chunk, uint32_t *dst_dev, int64_t capacity_words, void *stream) {
-    SAFE_REQUIRE(ctx && dst_dev, "safe_export_packed_chunk_narrow: NULL argument");
-    SAFE_REQUIRE(ctx->packed_layout >= 0 && ctx->xc_want >= 1 && chunk >= 0 && chunk < ctx->xc_want,
-                 "safe_export_packed_chunk_narrow: chunk %d of %d armed, counters %s", chunk, ctx->xc_want, ctx->packed_layout >= 0 ? "present" : "absent");
-    SAFE_REQUIRE(ctx->packed_perms >= 1 && ctx->packed_perms <= 1023, "safe_export_packed_chunk_narrow: %lld permutations do not fit 10-bit counters",
-                 (long long)ctx->packed_perms);
-    const int64_t c0 = std::min<int64_t>(chunk * ctx->xc_cols, ctx->packed_m);
-    const int64_t c1 = chunk + 1 == ctx->xc_want ? ctx->packed_m : std::min<int64_t>((chunk + 1) * ctx->xc_cols, ctx->packed_m);
+    int64_t c0 = 0, c1 = 0;
+    hipStream_t s = nullptr;
+    SAFE_TRY(packed_chunk_prepare(ctx, chunk, dst_dev, capacity_words, true, stream, &c0, &c1, &s));
     const int64_t words = (c1 - c0) * (ctx->packed_n_pad / 8 * 5);
-    SAFE_REQUIRE(capacity_words >= words, "safe_export_packed_chunk_narrow: buffer holds %lld words, %lld needed", (long long)capacity_words, (long long)words);
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    if (ctx->xc_made > 0) {
-        SAFE_REQUIRE(ctx->xc_made == ctx->xc_want && ctx->xc_bounds[chunk] == c0 && ctx->xc_bounds[chunk + 1] == c1,
-                     "safe_export_packed_chunk_narrow: the call's chunks are not the armed ones");
-        SAFE_HIP_CHECK(hipStreamWaitEvent(s, ctx->xc_events[chunk], 0));
-    }
     if (words) {
         const int64_t pairs = (c1 - c0) * (ctx->packed_n_pad / 2);
         hipLaunchKernelGGL(k_pack_counts20, dim3(static_cast<unsigned int>(ceil_div(pairs, 256))), dim3(256), 0, s,
@@ -3757,13 +3733,7 @@ int safe_outputs_from_packed_slabs(safe_ctx *ctx, safe_nbr *nbr, const uint32_t 
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     const int64_t P = num_permutations;
-    std::vector<double> tab(P + 1);
-    if (nes_table_host) {
-        std::copy(nes_table_host, nes_table_host + P + 1, tab.begin());
-    } else {
-        tab[0] = -std::log10(1.0 / static_cast<double>(P));
-        for (int64_t k = 1; k <= P; ++k) tab[k] = -std::log10(static_cast<double>(k) / static_cast<double>(P));
-    }
+    const std::vector<double> tab = nes_table(nes_table_host, P);
     // the table stays on the device between calls (one call per column chunk of a step: no upload, no sync after the first)
     double *d_tab = nullptr;
     const bool grow = ctx->scratch_bytes[19] < (P + 1) * sizeof(double);
@@ -3775,15 +3745,9 @@ int safe_outputs_from_packed_slabs(safe_ctx *ctx, safe_nbr *nbr, const uint32_t 
     }
     for (int r = 0; r < n_slabs; ++r) {
         if (slab_cols[r] == 0) continue;
-        PermOut out{};
-        out.pvalues_neg = pvalues_neg_dev ? pvalues_neg_dev + out_col0[r] : nullptr;
-        out.pvalues_pos = pvalues_pos_dev ? pvalues_pos_dev + out_col0[r] : nullptr;
-        out.nes = nes_dev ? nes_dev + out_col0[r] : nullptr;
-        out.nes_binary = nes_binary_dev ? nes_binary_dev + out_col0[r] : nullptr;
-        out.nes_table = d_tab;
-        out.nes_threshold = enrichment_threshold > 0.0 ? -std::log10(enrichment_threshold) : 0.0;
-        out.sign_mode = sign_mode;
-        out.mode = 4;
+        const auto at = [&](double *p) { return p ? p + out_col0[r] : nullptr; };
+        PermOut out = perm_outputs(PERM_SUBSET, at(pvalues_neg_dev), at(pvalues_pos_dev), at(nes_dev), at(nes_binary_dev), d_tab,
+                                   enrichment_threshold, sign_mode);
         out.ld = m_total;
         SAFE_TRY(enrich_finalize_counts(ctx, slabs_dev + static_cast<int64_t>(r) * slab_stride, n_pad, rowmap, slab_cols[r], P, out, nullptr, s, pk20));
     }
@@ -3795,7 +3759,7 @@ int safe_randomization_plan(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64
     SAFE_REQUIRE(score_type == SAFE_SCORE_SUM || score_type == SAFE_SCORE_ZSCORE, "safe_randomization_plan: bad score_type %d", score_type);
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     // what safe_randomization would run for this block: only the bit-sliced form is predicted (layout 0); everything else -1
-    *packed_layout = choose_path(ctx, nbr, attr, num_permutations, score_type == SAFE_SCORE_ZSCORE) == PATH_BITS ? 0 : -1;
+    *packed_layout = perm_route(route_switches(), nbr, attr, num_permutations, nullptr, 0, score_type == SAFE_SCORE_ZSCORE) == ROUTE_BITS ? 0 : -1;
     return SAFE_OK;
 }
 

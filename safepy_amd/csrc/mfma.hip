@@ -2632,21 +2632,18 @@ void nbr_free_blocks(safe_nbr *nbr) {
 }
 
 // ---- the switches that steer the permutation test's matrix-core path: read from the environment here and nowhere else (on
-//      every call: a process may change them between calls)
+//      every call: a process may change them between calls) -- but for SAFE_HIP_FORCE_PATH, which the caller parses
 struct MfmaSwitches {
     bool force_mfma = false;       // SAFE_HIP_FORCE_PATH=mfma: whatever the network's size, and even where the column check declines
-    bool force_other = false;      // SAFE_HIP_FORCE_PATH=gather / lds: never
     bool z = true;                 // SAFE_HIP_MFMA_Z=0: z-scores stay on the f64 kernels
     bool filter = true;            // SAFE_HIP_MFMA_FILTER=0: all six slices on the matrix cores
     bool general = false;          // SAFE_HIP_MFMA_FORM=general: the general kernel's FM = 2 where _g / _gz would run (any other value: the default)
     unsigned int filter_cap = 0;   // SAFE_HIP_MFMA_FILTER_CAP: entries of a launch's list of undecided compares (tests: force the fall-back); 0: by size
 };
-static MfmaSwitches mfma_switches() {
+static MfmaSwitches mfma_switches(bool force_mfma) {
     const auto is = [](const char *e, const char *value) { return e && !strcmp(e, value); };
-    const char *force = getenv("SAFE_HIP_FORCE_PATH");
     MfmaSwitches sw;
-    sw.force_mfma = is(force, "mfma");
-    sw.force_other = is(force, "gather") || is(force, "lds");
+    sw.force_mfma = force_mfma;
     sw.z = !is(getenv("SAFE_HIP_MFMA_Z"), "0");
     sw.filter = !is(getenv("SAFE_HIP_MFMA_FILTER"), "0");
     sw.general = is(getenv("SAFE_HIP_MFMA_FORM"), "general");
@@ -2654,11 +2651,9 @@ static MfmaSwitches mfma_switches() {
     return sw;
 }
 
-bool mfma_applicable(const safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const safe_perms *perms, bool z) {
-    (void)ctx;
-    (void)attr;
-    const MfmaSwitches sw = mfma_switches();
-    if (sw.force_other) return false;
+// (SAFE_HIP_FORCE_PATH=gather / lds: the caller, perm_route in enrich.hip, does not ask)
+bool mfma_applicable(const safe_nbr *nbr, const safe_perms *perms, bool z, bool force_mfma) {
+    const MfmaSwitches sw = mfma_switches(force_mfma);
     if (z && !sw.z) return false;
     if (perms->count < 1 || perms->count > 65535) return false;
     // a score is a sum of `members` fixed-point values below 2^46, combined and compared as 64-bit integers: neighborhoods of
@@ -3090,13 +3085,13 @@ int mfma_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, con
 // SAFE_OK) when the attribute values cannot be represented on the fixed-point grid without a
 // rounding that could matter; the caller then uses the f64 kernels.
 static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1, bool z,
-                           const PermOut &out_in, bool *declined, bool allow_filter, bool *overflowed) {
+                           const PermOut &out_in, bool force_mfma, bool *declined, bool allow_filter, bool *overflowed) {
     *declined = false;
     *overflowed = false;
     SAFE_TRY(build_blocks(nbr));
     PermOut out = out_in;
     const int64_t n = nbr->n, mloc = col1 - col0, P = perms->count, n_padr = nbr->bs_groups * MF_R;
-    const MfmaSwitches sw = mfma_switches();
+    const MfmaSwitches sw = mfma_switches(force_mfma);
 #ifdef SAFE_HIP_DIAG
     static const int mfma_dbg = getenv("SAFE_HIP_MFMA_DBG") ? atoi(getenv("SAFE_HIP_MFMA_DBG")) : 0;
     if (mfma_dbg) safe_warn_diagnostic("SAFE_HIP_MFMA_DBG");
@@ -3168,9 +3163,9 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
 }
 
 int launch_mfma(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1, bool z,
-                const PermOut &out_in, bool *declined) {
+                const PermOut &out_in, bool force_mfma, bool *declined) {
     bool overflowed = false;
-    SAFE_TRY(launch_mfma_run(ctx, nbr, attr, perms, col0, col1, z, out_in, declined, true, &overflowed));
+    SAFE_TRY(launch_mfma_run(ctx, nbr, attr, perms, col0, col1, z, out_in, force_mfma, declined, true, &overflowed));
     if (overflowed) {
         // data with many (near-)equal scores: the filter decides too little -- the whole call again with all slices on the
         // matrix cores (counters, scores and outputs are rewritten from scratch)
@@ -3178,7 +3173,7 @@ int launch_mfma(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms
         const int64_t undecided = ctx->last_undecided;
         if (out_in.enriched)                                  // (the abandoned pass may have counted its hits already)
             SAFE_HIP_CHECK(hipMemsetAsync(out_in.enriched, 0, static_cast<size_t>(col1 - col0) * sizeof(unsigned int), ctx->stream));
-        SAFE_TRY(launch_mfma_run(ctx, nbr, attr, perms, col0, col1, z, out_in, declined, false, &overflowed));
+        SAFE_TRY(launch_mfma_run(ctx, nbr, attr, perms, col0, col1, z, out_in, force_mfma, declined, false, &overflowed));
         ctx->last_undecided = -undecided;                // (negative: the filtered pass was abandoned)
     }
     return SAFE_OK;

@@ -24,7 +24,7 @@ def ctx(amd):
 @pytest.fixture(autouse=True)
 def narrow_blocks_stay_on_the_matrix_cores(monkeypatch):
     """These tests exercise the matrix-core kernel at small sizes; the product sends such narrow blocks (n x columns <= 2e5)
-    to the LDS-resident f64 kernel (enrich.hip narrow_block_prefers_lds), which tests/test_gpu_example3.py and the f64-kernel
+    to the LDS-resident f64 kernel (enrich.hip perm_route), which tests/test_gpu_example3.py and the f64-kernel
     tests cover."""
     monkeypatch.setenv('SAFE_HIP_NARROW_LDS', '0')
 

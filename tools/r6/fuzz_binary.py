@@ -2,8 +2,8 @@
 
 Binary 'sum' scores are exact in integers, so every kernel family must leave the same counters for the same seed:
   default (the bit-sliced form of bits_form -- k_permtest_bits_blk, or the sixteen-wave k_permtest_bits_pre / _pre32 -- where
-  one applies, else what choose_path picks), the f64 gather kernel, the sparse scatter kernel and the stream-less blocked
-  bit-sliced kernel (a forced form that does not apply to a shape falls through to what choose_path picks; the summary line says
+  one applies, else what perm_route picks), the f64 gather kernel, the sparse scatter kernel and the stream-less blocked
+  bit-sliced kernel (a forced form that does not apply to a shape falls through to what perm_route picks; the summary line says
   which kernel ran how often).
 The kernels themselves are pinned to the oracle by tests/test_gpu_parity.py; this tool walks shapes those tests do not: random
 sizes up to 32 767 nodes (past the blocked kernel's N <= 8190: the sixteen-wave forms, full and half words), clustered layouts, dense random memberships with rows of every
