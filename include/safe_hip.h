@@ -14,8 +14,25 @@
  *     torch tensor's data_ptr()).  Outputs are always pre-allocated by the caller.
  *   - the library owns device memory only behind its opaque handles.
  *   - work is enqueued on the context's stream (safe_ctx_set_stream; default: a
- *     stream the context owns).  Functions with host outputs synchronise before
- *     returning; functions with only dev outputs are asynchronous.
+ *     stream the context owns).  The library runs further streams of its own behind
+ *     it; every call orders them after what is already queued on the context's stream
+ *     and joins them back before it returns, so a caller orders their own work against
+ *     the context's stream alone.  Functions with host outputs synchronise before
+ *     returning.  Of the functions with only dev outputs these return WITHOUT waiting:
+ *     safe_euclidean_dense_dev, safe_nbr_to_dense_i64_dev, safe_dev_memset,
+ *     safe_attr_create_dev, safe_export_packed_counts, safe_export_packed_chunk(_narrow)
+ *     and safe_outputs_from_packed_slabs (once its NES table is resident: from the
+ *     second call with the same table on).  The others enqueue on the
+ *     context's stream like them but return only once it has drained, because they read
+ *     a flag or a timing event back or keep host memory alive for their kernels:
+ *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
+ *     safe_fdr_adjust, safe_outputs_from_counts, safe_outputs_from_packed_counts,
+ *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
+ *     (tests/test_gpu_stream_order.py measures both lists).
+ *   - safe_ctx_set_stream orders the stream it switches to behind the one it leaves:
+ *     handles created, buffers borrowed and outputs written on the old stream are
+ *     complete for everything enqueued afterwards.  The stream being left must still
+ *     exist at that moment.
  *   - one context per device; a context is not thread-safe.
  *   - there is NO CPU fallback: without a HIP device every compute call fails.
  */
@@ -72,7 +89,8 @@ int safe_ctx_destroy(safe_ctx *ctx);
  * SAFE_HIP_BLOCKING_SYNC=1 in the environment has the same effect. */
 int safe_set_blocking_sync(int on);
 /* Use an existing hipStream_t (passed as void*) for all subsequent work; NULL restores
- * the context's own stream. */
+ * the context's own stream.  When the stream changes, an event is recorded on the old
+ * stream and the new one waits for it (see Conventions). */
 int safe_ctx_set_stream(safe_ctx *ctx, void *hip_stream);
 int safe_ctx_sync(safe_ctx *ctx);
 int safe_ctx_info(safe_ctx *ctx, int *num_cu, int64_t *hbm_bytes, char *arch, size_t arch_len);

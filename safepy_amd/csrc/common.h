@@ -97,6 +97,7 @@ struct safe_ctx {
     char arch[64] = {0};
     hipEvent_t t0 = nullptr, t1 = nullptr;      // safe_timer_*
     hipEvent_t k0 = nullptr, k1 = nullptr;      // dominant-kernel timing
+    hipEvent_t switch_ev = nullptr;             // safe_ctx_set_stream: end of the work on the stream being left (created on first use)
     KernelStat last_kernel;
     int last_slices = 0;                        // i8 slices of the last matrix-core permutation test (2 / 4 / 6)
     void *diag_prof = nullptr;                  // (diagnostic builds) per-phase cycle counters of the matrix-core kernel

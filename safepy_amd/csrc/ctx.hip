@@ -268,6 +268,7 @@ int safe_ctx_destroy(safe_ctx *ctx) {
     if (ctx->t1) (void)hipEventDestroy(ctx->t1);
     if (ctx->k0) (void)hipEventDestroy(ctx->k0);
     if (ctx->k1) (void)hipEventDestroy(ctx->k1);
+    if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
     perms_cache_drop(ctx);
     draw_worker_shutdown(ctx);
     if (ctx->ring) ring_close(ctx->ring);
@@ -299,7 +300,17 @@ int safe_set_blocking_sync(int on) {
 
 int safe_ctx_set_stream(safe_ctx *ctx, void *hip_stream) {
     SAFE_REQUIRE(ctx != nullptr, "safe_ctx_set_stream: ctx is NULL");
-    ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+    hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+    if (next != ctx->stream) {
+        // The new stream continues where the old one stops: handles made, buffers borrowed (safe_attr_create_dev) and outputs
+        // written while the context was on the old stream are complete before anything enqueued from now on touches them.  The
+        // side, aux and further streams fork from ctx->stream with events of their own and inherit the order.
+        SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+        if (!ctx->switch_ev) SAFE_HIP_CHECK(hipEventCreateWithFlags(&ctx->switch_ev, hipEventDisableTiming));
+        SAFE_HIP_CHECK(hipEventRecord(ctx->switch_ev, ctx->stream));
+        SAFE_HIP_CHECK(hipStreamWaitEvent(next, ctx->switch_ev, 0));
+    }
+    ctx->stream = next;
     return SAFE_OK;
 }
 
