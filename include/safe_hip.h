@@ -426,7 +426,8 @@ int safe_packed_chunk_info(safe_ctx *ctx, int *chunks, int64_t *bounds, int64_t 
 int safe_export_packed_chunk(safe_ctx *ctx, int chunk, uint32_t *dst_dev, int64_t capacity, void *stream);
 /* The same slab with the counter pair packed to what the permutation count needs (the concatenated blocks of
  * safepy/safe.py:1355 carry counts of at most num_permutations, safe_extras.py:63-66): for num_permutations <= 1023 a pair is
- * 10 + 10 bits and two outputs travel in five bytes -- a column is n_pad / 2 words (low 32 bits of every 40) followed by
+ * 10 + 10 bits, #(S_p < S_obs) << 10 | #(S_p > S_obs), and two outputs travel in five bytes: positions 2 i (low 20 bits)
+ * and 2 i + 1 (high 20 bits) of a column make 40 bits -- a column is n_pad / 2 words (low 32 bits of every 40) followed by
  * n_pad / 2 bytes (the high 8), 5 * n_pad / 8 words per column, 0.625 of the u32 slab.  capacity_words: u32 words at dst_dev
  * (the rest is zeroed).  safe_outputs_from_packed_slabs takes such slabs with SAFE_PACKED_NARROW added to `layout`
  * (slab_stride stays in u32 words).  More than 1023 permutations: use the u32 form. */
