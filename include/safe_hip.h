@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 6
+#define SAFE_HIP_ABI_VERSION 7
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -369,6 +369,32 @@ int safe_enriched_components(safe_ctx *ctx, int64_t n, int64_t n_edges, const in
  * condensed order; 0 where both profiles are empty. */
 int safe_jaccard_condensed(safe_ctx *ctx, int64_t m_top, int64_t n, const double *x_host, double *out_host);
 
+/* The same two steps on the matrix compute_pvalues left on the device: values_dev is f64 [n, m] row-major (nes_binary), read
+ * in place on the context's stream; the chosen columns are host index lists, each index in [0, m) (SAFE_E_INVALID otherwise,
+ * nothing written), repeats allowed.  Neither makes a dense copy of the chosen columns.  kernel_ms (may be NULL): the
+ * kernels' time, also reported by safe_last_kernel_stats / safe_last_kernel_busy_ms.  Both synchronise.
+ *
+ * safe_enriched_components_dev: labels_host int32 [n_cols, n] as safe_enriched_components gives them for
+ * values[:, cols_host] (> 0 = enriched).  n_cols == 0 writes nothing. */
+int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v, const double *values_dev,
+                                 int64_t n, int64_t m, const int64_t *cols_host, int64_t n_cols, int32_t *labels_host,
+                                 double *kernel_ms);
+/* safe_profile_distances: out_host f64 [m_top (m_top - 1) / 2] = scipy.spatial.distance.pdist(values[:, cols_host].T, metric)
+ * (SciPy 1.15, condensed order) for a boolean metric, bit for bit: the columns are packed into bit words (non-zero = set),
+ * the four contingency counts of a pair come from popcounts and each metric is one division of exact integers; where a
+ * denominator is zero the value is SciPy's (jaccard and yule 0, dice and sokalsneath NaN).  metric: a SAFE_METRIC_* id
+ * (SAFE_E_INVALID otherwise).  SAFE_METRIC_JACCARD gives what safe_jaccard_condensed gives.  m_top < 2 writes nothing. */
+#define SAFE_METRIC_JACCARD 0
+#define SAFE_METRIC_HAMMING 1
+#define SAFE_METRIC_DICE 2
+#define SAFE_METRIC_ROGERSTANIMOTO 3
+#define SAFE_METRIC_RUSSELLRAO 4
+#define SAFE_METRIC_SOKALMICHENER 5
+#define SAFE_METRIC_SOKALSNEATH 6
+#define SAFE_METRIC_YULE 7
+int safe_profile_distances(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
+                           int metric, double *out_host, double *kernel_ms);
+
 /* Counts of a whole call -> outputs (safepy/safe.py:528-554 and 468-472): counts_neg / counts_pos are #(S_p <= S_obs) /
  * #(S_p >= S_obs) as f64 [n, m] on the device (e.g. safe_permtest_counts results summed over the ranks of a
  * permutation-axis split), ns_dev the observed scores (NaN = no test; may be NULL).  Writes p-values, NES
@@ -505,6 +531,18 @@ int safe_kde_grid(safe_ctx *ctx, int64_t n_sets, const int64_t *offsets_host, co
  * values are added in an unspecified order.  kernel_ms (may be NULL): the kernel's time.  Synchronises. */
 int safe_domain_counts(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int32_t *domain_host, int64_t n_domains,
                        double *counts_host, double *kernel_ms);
+
+/* Node-to-domain assignment of define_domains (safepy/safe.py:693-705) in one pass over the two device-resident matrices
+ * nes_binary_dev and nes_dev (f64 [n, m] row-major, read in place): domain_host int32 [m] is the domain id of every attribute
+ * (0 = none), ids_host int32 [n_ids] the sorted distinct ids (SAFE_E_VALUE when they are not, or when a column's id is not
+ * among them).  sums_host f64 [n, n_ids]: safe_domain_counts of nes_binary by id.  primary_host int32 [n]: the id >= 1 with
+ * the first maximum of the node's sums, or 0 when that maximum is 0 (or there is no id >= 1).  primary_nes_host f64 [n]:
+ * the largest non-NaN nes of the node over the attributes of its primary domain (domain 0 included); NaN when all of them
+ * are NaN or no attribute has that id (of -0.0 and +0.0 the larger is +0.0).  1 <= n_ids <= 2048 (SAFE_E_UNSUPPORTED
+ * beyond).  kernel_ms (may be NULL): the kernel's time, also reported by safe_last_kernel_busy_ms.  Synchronises. */
+int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double *nes_dev, int64_t n, int64_t m,
+                      const int32_t *domain_host, const int32_t *ids_host, int64_t n_ids, double *sums_host, int32_t *primary_host,
+                      double *primary_nes_host, double *kernel_ms);
 
 /* The nes / nes_binary columns plot_sample_attributes reads (safepy/safe.py:1081-1187): out_host f64 [n, k] row-major =
  * columns cols_host int64 [k] (each in [0, m)) of the row-major [n, m] f64 device matrix values_dev, without copying the

@@ -10,11 +10,14 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsafe_hip.so')
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
+# metric ids of safe_profile_distances (SAFE_METRIC_*), by SciPy's metric name
+METRIC_IDS = {'jaccard': 0, 'hamming': 1, 'dice': 2, 'rogerstanimoto': 3, 'russellrao': 4, 'sokalmichener': 5, 'sokalsneath': 6,
+              'yule': 7}
 
 
 class SafeHipError(RuntimeError):
@@ -165,6 +168,9 @@ PROTOTYPES = {
     'safe_kde_grid': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(C.c_double)]),
     'safe_domain_counts': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
     'safe_gather_columns': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
+    'safe_enriched_components_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
+    'safe_profile_distances': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, C.POINTER(C.c_double)]),
+    'safe_node_domains': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_double)]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

@@ -353,6 +353,57 @@ class Context:
             if tmp is not None:
                 tmp.free()
 
+    NODE_DOMAINS_MAX = 2048             # domain ids safe_node_domains takes (two 8-byte LDS slots per id)
+
+    def enriched_components_dev(self, values_dev_ptr, n, m, cols, edge_u, edge_v):
+        """int32 [len(cols), n] component labels (smallest node id of the component; -1 = not enriched) of the columns `cols`
+        of the row-major [n, m] f64 device matrix at values_dev_ptr, read in place (safe_enriched_components_dev): what
+        enriched_components gives for the host slice values[:, cols].  Returns (labels, kernel ms)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
+        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
+        if eu.shape != ev.shape or eu.ndim != 1:
+            raise ValueError('enriched_components_dev: edge lists of shapes %s and %s' % (eu.shape, ev.shape))
+        out = np.empty((cols.shape[0], int(n)), dtype=np.int32)
+        ms = C.c_double()
+        check(lib.safe_enriched_components_dev(self.handle, eu.shape[0], _ptr(eu) if eu.size else None, _ptr(ev) if ev.size else None,
+                                               C.c_void_p(values_dev_ptr) if values_dev_ptr else None, int(n), int(m), _ptr(cols),
+                                               cols.shape[0], _ptr(out), C.byref(ms)))
+        return out, ms.value
+
+    def profile_distances(self, values_dev_ptr, n, m, cols, metric):
+        """scipy.spatial.distance.pdist(values[:, cols].T, metric), condensed, for the columns `cols` of the row-major [n, m]
+        f64 device matrix at values_dev_ptr and a metric of _lib.METRIC_IDS (name or id), bit for bit (safe_profile_distances).
+        Returns (distances f64 [k (k - 1) / 2], kernel ms)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        if isinstance(metric, str):
+            if metric not in _lib.METRIC_IDS:
+                raise ValueError('profile_distances: no kernel for metric %r (have: %s)' % (metric, ', '.join(_lib.METRIC_IDS)))
+            metric = _lib.METRIC_IDS[metric]
+        k = cols.shape[0]
+        out = np.empty(k * (k - 1) // 2, dtype=np.float64)
+        ms = C.c_double()
+        check(lib.safe_profile_distances(self.handle, C.c_void_p(values_dev_ptr) if values_dev_ptr else None, int(n), int(m), _ptr(cols),
+                                         k, int(metric), _ptr(out), C.byref(ms)))
+        return out, ms.value
+
+    def node_domains(self, nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids):
+        """define_domains' node table from the two row-major [n, m] f64 device matrices, one pass (safe_node_domains): domain
+        int [m] is every attribute's domain id, ids the sorted distinct ids.  Returns (sums f64 [n, len(ids)], primary int32
+        [n], primary_nes f64 [n], kernel ms)."""
+        dom = np.ascontiguousarray(domain, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if dom.shape != (int(m),):
+            raise ValueError('node_domains: %d domain ids for %d columns' % (dom.size, m))
+        sums = np.empty((int(n), ids.shape[0]), dtype=np.float64)
+        primary = np.empty(int(n), dtype=np.int32)
+        pnes = np.empty(int(n), dtype=np.float64)
+        ms = C.c_double()
+        check(lib.safe_node_domains(self.handle, C.c_void_p(nes_binary_dev_ptr) if nes_binary_dev_ptr else None,
+                                    C.c_void_p(nes_dev_ptr) if nes_dev_ptr else None, int(n), int(m), _ptr(dom), _ptr(ids), ids.shape[0],
+                                    _ptr(sums), _ptr(primary), _ptr(pnes), C.byref(ms)))
+        return sums, primary, pnes, ms.value
+
     def euclidean_dense(self, xy_dev_ptr, n, nr, mask_dev_ptr=None, dist_dev_ptr=None):
         check(lib.safe_euclidean_dense_dev(self.handle, C.c_void_p(xy_dev_ptr), int(n), float(nr),
                                            C.c_void_p(mask_dev_ptr) if mask_dev_ptr else None,
@@ -987,3 +1038,18 @@ def domain_counts(ctx, values, domain, n_domains, n=None, m=None):
 def gather_columns(ctx, values, cols, n=None, m=None):
     """Context.gather_columns: (columns [n, k], kernel ms)."""
     return ctx.gather_columns(values, cols, n, m)
+
+
+def enriched_components_dev(ctx, values_dev_ptr, n, m, cols, edge_u, edge_v):
+    """Context.enriched_components_dev: (labels int32 [len(cols), n], kernel ms)."""
+    return ctx.enriched_components_dev(values_dev_ptr, n, m, cols, edge_u, edge_v)
+
+
+def profile_distances(ctx, values_dev_ptr, n, m, cols, metric):
+    """Context.profile_distances: (condensed distances, kernel ms)."""
+    return ctx.profile_distances(values_dev_ptr, n, m, cols, metric)
+
+
+def node_domains(ctx, nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids):
+    """Context.node_domains: (sums [n, len(ids)], primary int32 [n], primary_nes [n], kernel ms)."""
+    return ctx.node_domains(nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids)

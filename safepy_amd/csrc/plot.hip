@@ -2,7 +2,8 @@
 //   k_kde_grid         domain contours (plot_composite_network_contours, safe.py:822-829): SciPy's gaussian_kde of each
 //                      domain's nodes evaluated on its 100 x 100 grid, every domain in one launch
 //   k_domain_counts    composite colours (plot_composite_network, safe.py:883-886): nes_binary [N, M] summed over each
-//                      domain's attribute columns (the reference's groupby(level='domain', axis=1).sum())
+//                      domain's attribute columns (the reference's groupby(level='domain', axis=1).sum()); its second
+//                      form is the node-to-domain table of define_domains (below)
 //   k_gather_columns   a few columns of a device-resident [N, M] matrix (plot_sample_attributes' nes / nes_binary columns)
 //
 // k_kde_grid restates SciPy 1.15's gaussian_kernel_estimate (scipy/stats/_stats.pyx) operation for operation, for d = 2
@@ -21,6 +22,11 @@
 // Only non-zero, non-NaN values are added (pandas' sum skips NaN).  For whole-number inputs -- nes_binary is 0/1 -- every
 // partial sum is exact, so the order of the adds does not matter and the counts are the same on every run; other inputs
 // are added in an unspecified order.
+//
+// k_domain_counts<true> (safe_node_domains) is the same pass with the row of nes read beside the row of nes_binary: it also
+// keeps each domain's largest non-NaN NES in LDS and ends with the node's primary domain and primary NES (define_domains,
+// safepy/safe.py:693-705), so the node table needs one pass over the two matrices and neither leaves the device.
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -32,6 +38,7 @@ constexpr int64_t KDE_TARGET_BLOCKS = 2048;            // split sets into chunks
 constexpr int64_t KDE_MIN_CHUNK = 1024;                // points; a chunk is never cut shorter
 constexpr int DC_THREADS = 256;
 constexpr int64_t DC_MAX_DOMAINS = 4096;               // f64 LDS bins: at most 32 KB per workgroup
+constexpr int64_t ND_MAX_DOMAINS = 2048;               // safe_node_domains: a sum bin and a maximum key per domain, 32 KB
 constexpr int GC_THREADS = 256;
 
 // One workgroup = one (work item, tile of 256 grid points).  Work item t covers points [p0[t], p1[t]) of set set[t] and
@@ -87,20 +94,73 @@ __global__ __launch_bounds__(KDE_THREADS) void k_kde_sum_chunks(const double *__
     z[t] = s;
 }
 
-__global__ __launch_bounds__(DC_THREADS) void k_domain_counts(const double *__restrict__ values, int64_t m,
-                                                             const int32_t *__restrict__ domain, int64_t n_domains,
-                                                             double *__restrict__ counts) {
+// f64 -> u64 key that orders like the value (-inf < ... < -0.0 < +0.0 < ... < +inf); no non-NaN value has key 0
+__device__ inline unsigned long long nd_key(double v) {
+    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ inline double nd_value(unsigned long long k) {
+    return __longlong_as_double(static_cast<long long>((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// One workgroup per row r.  bins[d] = sum of values[r, c] over the columns with domain[c] == d (domain holds bin indices).
+// NODE form (safe_node_domains) in the same pass over the row: keys[d] = the largest non-NaN nes[r, c] of bin d as an
+// ordered integer key (0 = none seen; LDS integer max), then wave 0 picks the row's primary bin -- the first maximum of the
+// bins from first_real on, or bin 0's role "no domain" (zero_bin, -1 when no column has domain id 0) when that maximum is 0
+// -- and writes the bin index and the primary NES (NaN: no non-NaN value, or no such bin).
+template <bool NODE>
+__global__ __launch_bounds__(DC_THREADS) void k_domain_counts(const double *__restrict__ values, const double *__restrict__ nes,
+                                                             int64_t m, const int32_t *__restrict__ domain, int64_t n_domains,
+                                                             int first_real, int zero_bin, double *__restrict__ counts,
+                                                             int32_t *__restrict__ primary, double *__restrict__ primary_nes) {
     extern __shared__ double bins[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(bins + n_domains);      // NODE form only
     const int64_t r = blockIdx.x;
-    for (int64_t d = threadIdx.x; d < n_domains; d += DC_THREADS) bins[d] = 0;
+    for (int64_t d = threadIdx.x; d < n_domains; d += DC_THREADS) {
+        bins[d] = 0;
+        if (NODE) keys[d] = 0;
+    }
     __syncthreads();
     const double *row = values + r * m;
+    const double *nrow = NODE ? nes + r * m : nullptr;
     for (int64_t c = threadIdx.x; c < m; c += DC_THREADS) {
         const double v = row[c];
-        if (v != 0 && v == v) atomicAdd(&bins[domain[c]], v);
+        const int32_t d = domain[c];
+        if (v != 0 && v == v) atomicAdd(&bins[d], v);
+        if (NODE) {
+            const double x = nrow[c];
+            if (x == x) {
+                const unsigned long long k = nd_key(x);
+                // the bin only grows: a stale read can cost an atomic that changes nothing, never skip one that would
+                if (k > *reinterpret_cast<volatile unsigned long long *>(&keys[d])) atomicMax(&keys[d], k);
+            }
+        }
     }
     __syncthreads();
     for (int64_t d = threadIdx.x; d < n_domains; d += DC_THREADS) counts[r * n_domains + d] = bins[d];
+    if (!NODE || threadIdx.x >= 64) return;
+    // first maximum over the real domains: per lane over its strided bins (ascending, strict >), then across the wave
+    double best = -1;                                                    // sums of 0/1 values are >= 0
+    int best_d = 0x7fffffff;
+    for (int d = first_real + static_cast<int>(threadIdx.x); d < n_domains; d += 64)
+        if (bins[d] > best) {
+            best = bins[d];
+            best_d = d;
+        }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int od = __shfl_xor(best_d, off, 64);
+        if (ob > best || (ob == best && od < best_d)) {
+            best = ob;
+            best_d = od;
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int p = (best_d == 0x7fffffff || best == 0) ? zero_bin : best_d;
+        primary[r] = p;
+        const unsigned long long k = p >= 0 ? keys[p] : 0;
+        primary_nes[r] = k ? nd_value(k) : __longlong_as_double(0x7ff8000000000000ll);
+    }
 }
 
 __global__ __launch_bounds__(GC_THREADS) void k_gather_columns(const double *__restrict__ values, int64_t n, int64_t m,
@@ -255,13 +315,80 @@ int safe_domain_counts(safe_ctx *ctx, const double *values_dev, int64_t n, int64
     if (m) SAFE_HIP_CHECK(hipMemcpyAsync(d_dom, domain_host, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
     PlotTimer tm;
     SAFE_HIP_CHECK(tm.start(s));
-    hipLaunchKernelGGL(k_domain_counts, dim3(static_cast<unsigned>(n)), dim3(DC_THREADS), n_domains * sizeof(double), s, values_dev, m,
-                       d_dom, n_domains, d_counts);
+    hipLaunchKernelGGL(k_domain_counts<false>, dim3(static_cast<unsigned>(n)), dim3(DC_THREADS), n_domains * sizeof(double), s, values_dev,
+                       static_cast<const double *>(nullptr), m, d_dom, n_domains, 0, 0, d_counts, static_cast<int32_t *>(nullptr),
+                       static_cast<double *>(nullptr));
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(tm.stop(s));
     SAFE_HIP_CHECK(hipMemcpyAsync(counts_host, d_counts, n * n_domains * sizeof(double), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));
     if (kernel_ms) SAFE_HIP_CHECK(tm.ms(kernel_ms));
+    return SAFE_OK;
+}
+
+int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double *nes_dev, int64_t n, int64_t m,
+                      const int32_t *domain_host, const int32_t *ids_host, int64_t n_ids, double *sums_host, int32_t *primary_host,
+                      double *primary_nes_host, double *kernel_ms) {
+    SAFE_REQUIRE(ctx && n >= 0 && m >= 0 && n_ids >= 1, "safe_node_domains: bad argument");
+    if (n_ids > ND_MAX_DOMAINS) {
+        safe_set_error("safe_node_domains: %lld domains exceed the kernel's limit of %lld (two 8-byte LDS slots each)", (long long)n_ids,
+                       (long long)ND_MAX_DOMAINS);
+        return SAFE_E_UNSUPPORTED;
+    }
+    if (kernel_ms) *kernel_ms = 0;
+    SAFE_REQUIRE(ids_host, "safe_node_domains: NULL argument");
+    for (int64_t d = 1; d < n_ids; ++d)
+        if (ids_host[d] <= ids_host[d - 1]) {
+            safe_set_error("safe_node_domains: domain ids must be sorted and distinct (position %lld)", (long long)d);
+            return SAFE_E_VALUE;
+        }
+    if (n == 0) return SAFE_OK;
+    SAFE_REQUIRE(sums_host && primary_host && primary_nes_host && (m == 0 || (nes_binary_dev && nes_dev && domain_host)),
+                 "safe_node_domains: NULL argument");
+    std::vector<int32_t> bin(static_cast<size_t>(m));
+    for (int64_t c = 0; c < m; ++c) {
+        const int32_t *at = std::lower_bound(ids_host, ids_host + n_ids, domain_host[c]);
+        if (at == ids_host + n_ids || *at != domain_host[c]) {
+            safe_set_error("safe_node_domains: column %lld: domain %d is not one of the %lld ids", (long long)c, domain_host[c],
+                           (long long)n_ids);
+            return SAFE_E_VALUE;
+        }
+        bin[c] = static_cast<int32_t>(at - ids_host);
+    }
+    // ids >= 1 are the real domains; a node none of them holds an attribute of gets id 0
+    const int first_real = static_cast<int>(std::lower_bound(ids_host, ids_host + n_ids, 1) - ids_host);
+    const int32_t *zero = std::lower_bound(ids_host, ids_host + n_ids, 0);
+    const int zero_bin = (zero != ids_host + n_ids && *zero == 0) ? static_cast<int>(zero - ids_host) : -1;
+    SAFE_REQUIRE(n < (int64_t(1) << 31), "safe_node_domains: too many rows");
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    PlotBufs b;
+    int32_t *d_dom = nullptr, *d_primary = nullptr;
+    double *d_counts = nullptr, *d_pnes = nullptr;
+    SAFE_TRY(b.alloc(&d_dom, static_cast<size_t>(m)));
+    SAFE_TRY(b.alloc(&d_counts, static_cast<size_t>(n * n_ids)));
+    SAFE_TRY(b.alloc(&d_primary, static_cast<size_t>(n)));
+    SAFE_TRY(b.alloc(&d_pnes, static_cast<size_t>(n)));
+    hipStream_t s = ctx->stream;
+    if (m) SAFE_HIP_CHECK(hipMemcpyAsync(d_dom, bin.data(), m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    PlotTimer tm;
+    SAFE_HIP_CHECK(tm.start(s));
+    hipLaunchKernelGGL(k_domain_counts<true>, dim3(static_cast<unsigned>(n)), dim3(DC_THREADS), 2 * n_ids * sizeof(double), s,
+                       nes_binary_dev, nes_dev, m, d_dom, n_ids, first_real, zero_bin, d_counts, d_primary, d_pnes);
+    SAFE_HIP_CHECK(hipGetLastError());
+    SAFE_HIP_CHECK(tm.stop(s));
+    SAFE_HIP_CHECK(hipMemcpyAsync(sums_host, d_counts, n * n_ids * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(hipMemcpyAsync(primary_host, d_primary, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(hipMemcpyAsync(primary_nes_host, d_pnes, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(safe_stream_sync(s));      // (bin is read by the upload until here)
+    double ms = 0;
+    SAFE_HIP_CHECK(tm.ms(&ms));
+    ctx->last_kernel.name = "k_domain_counts<node>";
+    ctx->last_kernel.total_ms = ctx->last_kernel.busy_ms = ms;
+    ctx->last_kernel.launches = 1;
+    ctx->last_kernel.summed = true;
+    if (kernel_ms) *kernel_ms = ms;
+    // bin indices -> ids; a node without a primary bin (no real domain holds an attribute of it and no column has id 0) gets id 0
+    for (int64_t r = 0; r < n; ++r) primary_host[r] = primary_host[r] >= 0 ? ids_host[primary_host[r]] : 0;
     return SAFE_OK;
 }
 

@@ -20,6 +20,7 @@ import pandas as pd        # noqa: F401  at import, like the reference (safepy/s
                            # used to pay for it -- 166 of its 178 ms
 
 from . import backend as be
+from ._lib import METRIC_IDS
 
 _DEFAULTS = {
     # the [DEFAULT] section of safepy/safe_default.ini:1-24, restated (the shipped .ini is not copied):
@@ -756,7 +757,8 @@ class SAFE:
         """safepy/safe.py:610-659.  kwargs: attribute_unimodality_metric, attribute_enrichment_min_size.
         Adds the columns 'top', 'num_connected_components', 'size_connected_components' (object: sizes in
         descending order) and 'num_large_connected_components' to self.attributes.  The connected
-        components of all candidate attributes are found in one device call."""
+        components of all candidate attributes are found in one device call, straight from the
+        device-resident nes_binary while nobody has read it (it stays on the device)."""
         for option in ('attribute_unimodality_metric', 'attribute_enrichment_min_size'):
             if option in kwargs:
                 setattr(self, option, kwargs[option])
@@ -778,8 +780,13 @@ class SAFE:
             cand = attrs.index.values[attrs['top'].values]
             if len(cand):
                 eu, ev = self._graph_edges()
-                n = self.nes_binary.shape[0]
-                labels = be.enriched_components(self._ctx(), n, eu, ev, self.nes_binary[:, cand])
+                src = self.__dict__.get('_r_nes_binary')
+                if isinstance(src, _DeviceResult) and cand.dtype.kind in 'iu' and cand.min() >= 0 and cand.max() < src.shape[1]:
+                    # the candidate columns are read in place on the device: nes_binary stays there
+                    labels, _ = self._ctx().enriched_components_dev(src.buf.ptr, src.shape[0], src.shape[1], cand, eu, ev)
+                else:
+                    n = self.nes_binary.shape[0]
+                    labels = be.enriched_components(self._ctx(), n, eu, ev, self.nes_binary[:, cand])
                 pos_of = {a: i for i, a in enumerate(attrs.index.values)}
                 for row, a in enumerate(cand):
                     lab = labels[row]
@@ -800,7 +807,10 @@ class SAFE:
         """safepy/safe.py:661-713.  Average-linkage clustering of the top attributes on the distance
         between their binarised enrichment profiles (default: Jaccard, computed on the device in
         SciPy's condensed order; the linkage / fcluster calls are SciPy's, as in the reference), then
-        every node's domain sums, primary domain and primary NES."""
+        every node's domain sums, primary domain and primary NES.  While compute_pvalues' nes_binary and
+        nes are still on the device (nobody has read them) both steps read them there -- the boolean
+        metrics of backend.Context.profile_distances, then backend.Context.node_domains -- and they stay
+        there; otherwise the host arrays are used as before."""
         import pandas as pd
         from scipy.cluster.hierarchy import linkage, fcluster
         if 'attribute_distance_threshold' in kwargs:
@@ -808,11 +818,18 @@ class SAFE:
         self.validate_config()
         attrs = self.attributes
         top = attrs['top'].values.astype(bool)
-        m = self.nes_binary[:, top].T
-        if self.attribute_distance_metric == 'jaccard' and m.shape[0] >= 2:
-            z = linkage(be.jaccard_condensed(self._ctx(), m), method='average')
+        metric = self.attribute_distance_metric
+        src_b = self.__dict__.get('_r_nes_binary')
+        if isinstance(src_b, _DeviceResult) and isinstance(metric, str) and metric in METRIC_IDS and np.count_nonzero(top) >= 2:
+            # the top columns are packed and compared in place on the device: nes_binary stays there
+            cond, _ = self._ctx().profile_distances(src_b.buf.ptr, src_b.shape[0], src_b.shape[1], np.flatnonzero(top), metric)
+            z = linkage(cond, method='average')
         else:
-            z = linkage(m, method='average', metric=self.attribute_distance_metric)
+            m = self.nes_binary[:, top].T
+            if metric == 'jaccard' and m.shape[0] >= 2:
+                z = linkage(be.jaccard_condensed(self._ctx(), m), method='average')
+            else:
+                z = linkage(m, method='average', metric=metric)
         max_d = np.max(z[:, 2] * self.attribute_distance_threshold)
         domains = fcluster(z, max_d, criterion='distance')
         attrs['domain'] = 0
@@ -821,29 +838,41 @@ class SAFE:
         # a node belongs to the domain holding most of the attributes it is enriched for (safe.py:693-698)
         dom = attrs['domain'].values
         ids = np.unique(dom)
-        onehot = (dom[:, None] == ids[None, :]).astype(np.float64)
-        sums = self.nes_binary @ onehot
-        node2domain = pd.DataFrame(sums, columns=pd.Index(ids, name='domain'))
-        real = ids >= 1
-        t = sums[:, real]
-        t_max = t.max(axis=1)
-        primary = ids[real][np.argmax(t, axis=1)]                # first maximum, like DataFrame.idxmax
-        primary = np.where(t_max == 0, 0, primary)
-        node2domain['primary_domain'] = primary
-        # the highest NES among the attributes of the primary domain (safe.py:703-705); NaNs are skipped.  Only the
-        # (node, primary domain) pairs are evaluated: a domain's columns for the nodes that have it as primary domain
-        # (all columns of every domain for every node -- domain 0 holds most of the matrix -- took 0.23 s at 3971 x 4373)
-        if np.any(~np.isin(primary, ids)):
-            raise KeyError(0)                                     # the reference's o.loc[row, 0] with no attribute outside the domains
-        primary_nes = np.full(primary.shape[0], np.nan)
-        with np.errstate(invalid='ignore'):
-            for d in ids:
-                rows = np.nonzero(primary == d)[0]
-                if rows.size == 0:
-                    continue
-                block = self.nes[np.ix_(rows, np.nonzero(dom == d)[0])]
-                nan = np.isnan(block)
-                primary_nes[rows] = np.where(nan.all(axis=1), np.nan, np.where(nan, -np.inf, block).max(axis=1))
+        src_b, src_nes = self.__dict__.get('_r_nes_binary'), self.__dict__.get('_r_nes')   # (read again: the slice above may have downloaded)
+        if (isinstance(src_b, _DeviceResult) and isinstance(src_nes, _DeviceResult) and tuple(src_b.shape) == tuple(src_nes.shape)
+                and len(ids) <= be.Context.NODE_DOMAINS_MAX):
+            # sums, primary domain and primary NES in one pass over the two resident matrices (safe_node_domains)
+            sums, primary, primary_nes, _ = self._ctx().node_domains(src_b.buf.ptr, src_nes.buf.ptr, src_b.shape[0], src_b.shape[1],
+                                                                     dom, ids)
+            node2domain = pd.DataFrame(sums, columns=pd.Index(ids, name='domain'))
+            primary = primary.astype(ids.dtype)
+            node2domain['primary_domain'] = primary
+            if np.any(~np.isin(primary, ids)):
+                raise KeyError(0)                                 # as below
+        else:
+            onehot = (dom[:, None] == ids[None, :]).astype(np.float64)
+            sums = self.nes_binary @ onehot
+            node2domain = pd.DataFrame(sums, columns=pd.Index(ids, name='domain'))
+            real = ids >= 1
+            t = sums[:, real]
+            t_max = t.max(axis=1)
+            primary = ids[real][np.argmax(t, axis=1)]                # first maximum, like DataFrame.idxmax
+            primary = np.where(t_max == 0, 0, primary)
+            node2domain['primary_domain'] = primary
+            # the highest NES among the attributes of the primary domain (safe.py:703-705); NaNs are skipped.  Only the
+            # (node, primary domain) pairs are evaluated: a domain's columns for the nodes that have it as primary domain
+            # (all columns of every domain for every node -- domain 0 holds most of the matrix -- took 0.23 s at 3971 x 4373)
+            if np.any(~np.isin(primary, ids)):
+                raise KeyError(0)                                     # the reference's o.loc[row, 0] with no attribute outside the domains
+            primary_nes = np.full(primary.shape[0], np.nan)
+            with np.errstate(invalid='ignore'):
+                for d in ids:
+                    rows = np.nonzero(primary == d)[0]
+                    if rows.size == 0:
+                        continue
+                    block = self.nes[np.ix_(rows, np.nonzero(dom == d)[0])]
+                    nan = np.isnan(block)
+                    primary_nes[rows] = np.where(nan.all(axis=1), np.nan, np.where(nan, -np.inf, block).max(axis=1))
         node2domain['primary_nes'] = primary_nes
         self.node2domain = node2domain
         if self.verbose:
