@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 7
+#define SAFE_HIP_ABI_VERSION 8
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -394,6 +394,28 @@ int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *
 #define SAFE_METRIC_YULE 7
 int safe_profile_distances(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
                            int metric, double *out_host, double *kernel_ms);
+
+/* The clustering of define_domains (safepy/safe.py:672-673, linkage(m, method='average', metric=...)) on the device:
+ * z_host f64 [m_top - 1, 4] = scipy.cluster.hierarchy.linkage(cond, method='average') of SciPy 1.15, bit for bit, tied
+ * distances included (binary profiles give small rationals: ties are the normal case, and the flat clusters fcluster cuts
+ * depend on how they are broken).  SciPy's nn_chain is restated step for step -- the chain starts at the smallest live
+ * index, a scan keeps the chain predecessor unless another live point is strictly closer and then takes the smallest index
+ * of the row minimum, a merge keeps the larger index and averages (nx d_ix + ny d_iy) / (nx + ny) with every operation
+ * rounded -- in one persistent workgroup over a square f64 working matrix; the stable sort of the merges by height and the
+ * union-find relabel run on the host inside the call.  fcluster stays the caller's (O(m_top) on Z).
+ *
+ * safe_linkage_average: cond_dev f64 [m_top (m_top - 1) / 2] in SciPy's condensed order, device memory, read on the
+ * context's stream and never modified.  safe_profile_linkage: the pack and pair kernels of safe_profile_distances (same
+ * arguments, same checks) followed by the linkage, without the condensed vector leaving the device.
+ * Both: m_top < 2 writes nothing and returns SAFE_OK.  A distance that is not finite -- NaN or inf from a direct caller;
+ * dice / sokalsneath of two empty profiles -- returns SAFE_E_VALUE (SciPy's linkage raises on such input), as does an
+ * average that overflows; m_top > SAFE_LINKAGE_MAX_POINTS returns SAFE_E_UNSUPPORTED (the working matrix takes 8 m_top^2
+ * bytes, 2 GiB at the limit, and the chain holds 16-bit ids in LDS).  z_host is written only on success.  kernel_ms (may
+ * be NULL): the kernels' time, also reported by safe_last_kernel_stats / safe_last_kernel_busy_ms.  Both synchronise. */
+#define SAFE_LINKAGE_MAX_POINTS 16384
+int safe_linkage_average(safe_ctx *ctx, const double *cond_dev, int64_t m_top, double *z_host, double *kernel_ms);
+int safe_profile_linkage(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
+                         int metric, double *z_host, double *kernel_ms);
 
 /* Counts of a whole call -> outputs (safepy/safe.py:528-554 and 468-472): counts_neg / counts_pos are #(S_p <= S_obs) /
  * #(S_p >= S_obs) as f64 [n, m] on the device (e.g. safe_permtest_counts results summed over the ranks of a

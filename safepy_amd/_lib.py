@@ -10,11 +10,12 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsafe_hip.so')
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
+LINKAGE_MAX_POINTS = 16384          # SAFE_LINKAGE_MAX_POINTS: points safe_linkage_average / safe_profile_linkage take
 # metric ids of safe_profile_distances (SAFE_METRIC_*), by SciPy's metric name
 METRIC_IDS = {'jaccard': 0, 'hamming': 1, 'dice': 2, 'rogerstanimoto': 3, 'russellrao': 4, 'sokalmichener': 5, 'sokalsneath': 6,
               'yule': 7}
@@ -171,6 +172,8 @@ PROTOTYPES = {
     'safe_enriched_components_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
     'safe_profile_distances': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, C.POINTER(C.c_double)]),
     'safe_node_domains': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    'safe_linkage_average': (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(C.c_double)]),
+    'safe_profile_linkage': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, C.POINTER(C.c_double)]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

@@ -387,6 +387,54 @@ class Context:
                                          k, int(metric), _ptr(out), C.byref(ms)))
         return out, ms.value
 
+    LINKAGE_MAX_POINTS = _lib.LINKAGE_MAX_POINTS   # points the linkage kernel takes (8 n^2 bytes of working matrix, 16-bit chain ids)
+
+    def linkage_average(self, cond, m_top=None):
+        """scipy.cluster.hierarchy.linkage(cond, method='average'), bit for bit (safe_linkage_average): cond is the condensed
+        f64 distance vector of m_top points, as a device pointer (int; m_top required; read on the context's stream, not
+        modified) or as a host array that is uploaded.  Distances that are not all finite raise SafeHipError with code
+        E_VALUE, more than LINKAGE_MAX_POINTS points E_UNSUPPORTED.  Returns (Z f64 [m_top - 1, 4], kernel ms)."""
+        tmp = None
+        if isinstance(cond, (int, np.integer)):
+            if m_top is None:
+                raise ValueError('linkage_average: a device pointer needs m_top')
+            ptr, k = int(cond), int(m_top)
+        else:
+            host = np.ascontiguousarray(cond, dtype=np.float64).reshape(-1)
+            k = int(round((1 + np.sqrt(1 + 8 * host.shape[0])) / 2)) if m_top is None else int(m_top)
+            if k * (k - 1) // 2 != host.shape[0]:
+                raise ValueError('linkage_average: %d distances are not the condensed form of %d points' % (host.shape[0], k))
+            ptr = 0
+            if 2 <= k <= self.LINKAGE_MAX_POINTS:                        # (the library refuses the other sizes before it reads)
+                tmp = self.alloc_f64(host.shape[0])
+                tmp.upload(host)
+                ptr = tmp.ptr
+        try:
+            z = np.empty((max(k - 1, 0), 4), dtype=np.float64)
+            ms = C.c_double()
+            check(lib.safe_linkage_average(self.handle, C.c_void_p(ptr) if ptr else None, k, _ptr(z), C.byref(ms)))
+            return z, ms.value
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def profile_linkage(self, values_dev_ptr, n, m, cols, metric):
+        """linkage(pdist(values[:, cols].T, metric), method='average') of SciPy for the columns `cols` of the row-major [n, m]
+        f64 device matrix at values_dev_ptr and a metric of _lib.METRIC_IDS (name or id): the kernels of profile_distances,
+        then linkage_average's, without the condensed vector leaving the device (safe_profile_linkage).  Raises like
+        linkage_average.  Returns (Z f64 [k - 1, 4], kernel ms)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        if isinstance(metric, str):
+            if metric not in _lib.METRIC_IDS:
+                raise ValueError('profile_linkage: no kernel for metric %r (have: %s)' % (metric, ', '.join(_lib.METRIC_IDS)))
+            metric = _lib.METRIC_IDS[metric]
+        k = cols.shape[0]
+        z = np.empty((max(k - 1, 0), 4), dtype=np.float64)
+        ms = C.c_double()
+        check(lib.safe_profile_linkage(self.handle, C.c_void_p(values_dev_ptr) if values_dev_ptr else None, int(n), int(m), _ptr(cols),
+                                       k, int(metric), _ptr(z), C.byref(ms)))
+        return z, ms.value
+
     def node_domains(self, nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids):
         """define_domains' node table from the two row-major [n, m] f64 device matrices, one pass (safe_node_domains): domain
         int [m] is every attribute's domain id, ids the sorted distinct ids.  Returns (sums f64 [n, len(ids)], primary int32
@@ -1048,6 +1096,16 @@ def enriched_components_dev(ctx, values_dev_ptr, n, m, cols, edge_u, edge_v):
 def profile_distances(ctx, values_dev_ptr, n, m, cols, metric):
     """Context.profile_distances: (condensed distances, kernel ms)."""
     return ctx.profile_distances(values_dev_ptr, n, m, cols, metric)
+
+
+def linkage_average(ctx, cond, m_top=None):
+    """Context.linkage_average: (Z [m_top - 1, 4], kernel ms)."""
+    return ctx.linkage_average(cond, m_top)
+
+
+def profile_linkage(ctx, values_dev_ptr, n, m, cols, metric):
+    """Context.profile_linkage: (Z [len(cols) - 1, 4], kernel ms)."""
+    return ctx.profile_linkage(values_dev_ptr, n, m, cols, metric)
 
 
 def node_domains(ctx, nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids):

@@ -8,7 +8,9 @@
 //  * define_domains (safepy/safe.py:672-673): the condensed Jaccard distance vector between the
 //    binarised enrichment profiles of the top attributes -- scipy's pdist(m, 'jaccard') inside
 //    linkage(): d = #(x != y and (x != 0 or y != 0)) / #(x != 0 or y != 0), 0 when the denominator
-//    is 0 -- from bit-packed columns with popcounts; the linkage itself stays SciPy's.
+//    is 0 -- from bit-packed columns with popcounts.
+//  * the linkage of those distances (safepy/safe.py:672: linkage(m, method='average', metric=...)): SciPy's nn_chain restated
+//    step for step -- k_linkage_expand + k_linkage_nn_chain below -- so that Z equals SciPy 1.15's bit for bit, ties included.
 //
 // Both exist in two forms.  The host forms (safe_enriched_components, safe_jaccard_condensed) take a dense host copy of the
 // chosen columns.  The device forms (safe_enriched_components_dev, safe_profile_distances) read the chosen columns in place
@@ -23,6 +25,9 @@
 //    profile and count for none of the three), then metric_distance, one or two f64 operations on exact integers restating
 //    SciPy 1.15's pdist for the boolean metrics (tests/domain_metrics_ref.py has the table, held to SciPy on the CPU).
 #include <algorithm>
+#include <climits>
+#include <cmath>
+#include <numeric>
 #include <vector>
 
 #include "common.h"
@@ -160,6 +165,209 @@ __global__ __launch_bounds__(256) void k_profile_pairs(const unsigned long long 
     out[k] = metric_distance(metric, ntt, ntf, nft, n);
 }
 
+// ---- average linkage (scipy.cluster.hierarchy.linkage(d, 'average') = _hierarchy.nn_chain + a stable sort + a relabel) ----
+//
+//  * k_linkage_expand: the condensed vector (never modified) becomes a square symmetric f64 working matrix [n, n], so that
+//    every nearest-neighbour scan reads one contiguous row.  A workgroup owns a 32 x 32 tile of the upper triangle: it reads
+//    its rows' segments of the condensed vector, writes them as they are and, through LDS, transposed.  The same pass raises
+//    a flag when a distance is not finite (SciPy refuses such input; `dist < cur` is never true for a NaN).
+//  * k_linkage_nn_chain: all n - 1 merges in ONE workgroup of up to 1024 lanes -- no grid-wide synchronisation and no
+//    assumption about co-residency.  Uniform state (chain length, chain top x and its predecessor p, merge count) lives in
+//    registers of every lane; the chain (16-bit ids) and the live bits are in LDS, the cluster sizes in a small global array.
+//    A scan is a strided read of row x with the dead columns masked, a (value, index) minimum that prefers the smaller index
+//    (wave shuffles, then one LDS slot per wave; the slots alternate between two sets so that one barrier per scan is enough),
+//    and the predecessor compared LAST under SciPy's strict rule: y = p unless the row minimum is < D[x, p].  A merge rewrites
+//    row y and column y with the Lance-Williams average (nx * D[i, x] + ny * D[i, y]) / (nx + ny), every operation rounded on
+//    its own (-ffp-contract=off), and ends in the one barrier that orders its stores before the next scan.  The sizes of x
+//    and p are read with the scan (before its barrier), so the merge that follows may overwrite them without another one.
+//    The scans are bounded by 4 n + 64 (the algorithm needs fewer than 3 n): a kernel that cannot hang.
+//  Roofline: latency.  A scan is one dependent global read of 8 n bytes spread over the workgroup plus a two-level reduction;
+//  the ~3 n scans and n merges run back to back on one CU, the other 255 idle -- the work per step (n values) is too small to
+//  pay for a grid-wide barrier ("Domain stage").
+constexpr int64_t LINKAGE_MAX_POINTS = SAFE_LINKAGE_MAX_POINTS;
+constexpr int LK_THREADS = 1024, LK_UNROLL = 8;
+constexpr int LK_BAD_INPUT = 1, LK_OVERFLOW = 2, LK_INTERNAL = 4;
+static_assert(LINKAGE_MAX_POINTS <= 65536 / 4 && LINKAGE_MAX_POINTS % 32 == 0, "chain ids are 16-bit, the chain is 32 KB of LDS");
+
+__global__ __launch_bounds__(256) void k_linkage_expand(const double *__restrict__ cond, int64_t n, double *__restrict__ sq,
+                                                        int *__restrict__ flag) {
+    __shared__ double tile[32][33];
+    const int64_t bi = blockIdx.y, bj = blockIdx.x;
+    if (bj < bi) return;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    bool bad = false;
+    for (int r = ty; r < 32; r += 8) {
+        const int64_t i = bi * 32 + r, j = bj * 32 + tx;
+        double v = 0.0;                                                  // the diagonal is never read
+        if (i < n && j < n) {
+            if (i != j) {
+                const int64_t a = i < j ? i : j, b = i < j ? j : i;
+                v = cond[a * (2 * n - a - 1) / 2 + (b - a - 1)];       // scipy's condensed index
+                bad |= !std::isfinite(v);
+            }
+            sq[i * n + j] = v;
+        }
+        tile[r][tx] = v;
+    }
+    if (bi != bj) {                                                      // (a diagonal tile has read both of its halves itself)
+        __syncthreads();
+        for (int r = ty; r < 32; r += 8) {
+            const int64_t j = bj * 32 + r, i = bi * 32 + tx;
+            if (i < n && j < n) sq[j * n + i] = tile[tx][r];
+        }
+    }
+    if (bad) atomicOr(flag, LK_BAD_INPUT);
+}
+
+__device__ inline void lk_take_smaller(double &v, int &i, double ov, int oi) {
+    if (ov < v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+    }
+}
+
+// (minimum value, smallest index that attains it) over the workgroup, in every lane; `set` alternates between the two LDS sets
+__device__ inline void lk_block_min(double &v, int &i, double (*part_v)[16], int (*part_i)[16], int &set, int waves) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double ov = __shfl_xor(v, off);
+        const int oi = __shfl_xor(i, off);
+        lk_take_smaller(v, i, ov, oi);
+    }
+    if (waves == 1) return;
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+        part_v[set][threadIdx.x >> 6] = v;
+        part_i[set][threadIdx.x >> 6] = i;
+    }
+    __syncthreads();
+    const int slot = lane & 15;
+    v = slot < waves ? part_v[set][slot] : INFINITY;
+    i = slot < waves ? part_i[set][slot] : INT_MAX;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        const double ov = __shfl_xor(v, off);
+        const int oi = __shfl_xor(i, off);
+        lk_take_smaller(v, i, ov, oi);
+    }
+    set ^= 1;
+}
+
+// sq: the working matrix of k_linkage_expand (modified); size: int32 [n] scratch; merges: f64 [n - 1][3] = (x, y, height) in
+// merge order, x < y; flag: LK_* bits (a flag that is already set ends the kernel at once)
+__global__ __launch_bounds__(LK_THREADS) void k_linkage_nn_chain(double *sq, int n, int *size, double *merges, int *flag) {
+    __shared__ unsigned short chain[LINKAGE_MAX_POINTS];
+    __shared__ unsigned int live[LINKAGE_MAX_POINTS / 32];
+    __shared__ double part_v[2][16];
+    __shared__ int part_i[2][16];
+    __shared__ int stop;
+    const int tid = threadIdx.x, threads = blockDim.x, waves = threads >> 6;
+    const int words = (n + 31) >> 5;
+    if (*flag) return;
+    for (int w = tid; w < words; w += threads) live[w] = (w + 1) * 32 <= n ? 0xffffffffu : (1u << (n & 31)) - 1u;
+    for (int i = tid; i < n; i += threads) size[i] = 1;
+    if (tid == 0) stop = 0;
+    __syncthreads();
+    auto is_live = [&](int i) { return (live[i >> 5] >> (i & 31)) & 1u; };
+
+    int len = 0, x = 0, p = -1, first_word = 0, set = 0;
+    int64_t scans_left = 4ll * n + 64;
+    for (int k = 0; k < n - 1;) {
+        if (len == 0) {                                                  // the chain starts at the smallest live index
+            while (first_word < words && live[first_word] == 0) ++first_word;
+            if (first_word >= words) {
+                if (tid == 0) atomicOr(flag, LK_INTERNAL);
+                return;
+            }
+            x = first_word * 32 + __ffs(live[first_word]) - 1;
+            p = -1;
+            len = 1;
+            if (tid == 0) chain[0] = static_cast<unsigned short>(x);
+        }
+        if (--scans_left < 0) {
+            if (tid == 0) atomicOr(flag, LK_INTERNAL);
+            return;
+        }
+        // ---- nearest neighbour of x: the row minimum over the live columns, smallest index first
+        const double *row = sq + static_cast<int64_t>(x) * n;
+        const double d_xp = p >= 0 ? row[p] : INFINITY;
+        const int size_x = size[x], size_p = p >= 0 ? size[p] : 0;
+        double best = INFINITY;
+        int best_i = INT_MAX;
+        for (int base = tid; base < n; base += threads * LK_UNROLL) {
+            double v[LK_UNROLL];
+#pragma unroll
+            for (int u = 0; u < LK_UNROLL; ++u) {
+                const int i = base + u * threads;
+                v[u] = i < n ? row[i] : INFINITY;
+            }
+#pragma unroll
+            for (int u = 0; u < LK_UNROLL; ++u) {
+                const int i = base + u * threads;
+                if (i < n && i != x && is_live(i) && v[u] < best) {      // ascending i per lane: strict < keeps the smallest
+                    best = v[u];
+                    best_i = i;
+                }
+            }
+        }
+        lk_block_min(best, best_i, part_v, part_i, set, waves);
+        if (best_i == INT_MAX) {                                         // no finite distance left in the row
+            if (tid == 0) atomicOr(flag, LK_OVERFLOW);
+            return;
+        }
+        if (p < 0 || best < d_xp) {                                      // someone is strictly closer than the predecessor: push
+            if (tid == 0) chain[len] = static_cast<unsigned short>(best_i);
+            ++len;
+            p = x;
+            x = best_i;
+            continue;
+        }
+        // ---- x and p are mutual nearest neighbours at height d_xp: merge the smaller index into the larger
+        const int a = x < p ? x : p, b = x < p ? p : x;
+        const int na = x < p ? size_x : size_p, nb = x < p ? size_p : size_x;
+        const double fa = static_cast<double>(na), fb = static_cast<double>(nb), ft = static_cast<double>(na + nb);
+        const double *row_a = sq + static_cast<int64_t>(a) * n;
+        double *row_b = sq + static_cast<int64_t>(b) * n;
+        bool overflow = false;
+        for (int base = tid; base < n; base += threads * LK_UNROLL) {
+            double va[LK_UNROLL], vb[LK_UNROLL];
+#pragma unroll
+            for (int u = 0; u < LK_UNROLL; ++u) {
+                const int i = base + u * threads;
+                va[u] = i < n ? row_a[i] : 0.0;
+                vb[u] = i < n ? row_b[i] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < LK_UNROLL; ++u) {
+                const int i = base + u * threads;
+                if (i < n && i != a && i != b && is_live(i)) {
+                    const double d = (fa * va[u] + fb * vb[u]) / ft;
+                    overflow |= !std::isfinite(d);
+                    row_b[i] = d;
+                    sq[static_cast<int64_t>(i) * n + b] = d;
+                }
+            }
+        }
+        if (overflow) stop = 1;
+        if (tid == 0) {
+            merges[3 * static_cast<int64_t>(k)] = static_cast<double>(a);
+            merges[3 * static_cast<int64_t>(k) + 1] = static_cast<double>(b);
+            merges[3 * static_cast<int64_t>(k) + 2] = d_xp;
+            size[b] = na + nb;
+            live[a >> 5] &= ~(1u << (a & 31));
+        }
+        __syncthreads();                                                 // row b, column b, size, live bit and chain: visible
+        if (stop) {
+            if (tid == 0) atomicOr(flag, LK_OVERFLOW);
+            return;
+        }
+        ++k;
+        len -= 2;
+        x = len >= 1 ? chain[len - 1] : 0;
+        p = len >= 2 ? chain[len - 2] : -1;
+    }
+}
+
 // Device buffers and timing events of one call, released on every return path.
 struct DomBufs {
     std::vector<void *> p;
@@ -217,6 +425,115 @@ hipError_t cc_rounds(hipStream_t s, const int32_t *d_eu, const int32_t *d_ev, in
     }
     if (e == hipSuccess) e = hipGetLastError();
     return e;
+}
+
+// Argument checks shared by safe_profile_distances and safe_profile_linkage (fn names the caller in the messages).
+int profile_check(const char *fn, safe_ctx *ctx, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top, int metric,
+                  double *kernel_ms) {
+    SAFE_REQUIRE(ctx && n >= 1 && m >= 0 && m_top >= 0, "%s: bad argument", fn);
+    SAFE_REQUIRE(metric >= SAFE_METRIC_JACCARD && metric <= SAFE_METRIC_YULE, "%s: unknown metric id %d", fn, metric);
+    if (kernel_ms) *kernel_ms = 0;
+    SAFE_REQUIRE(m_top == 0 || cols_host, "%s: NULL argument", fn);
+    for (int64_t c = 0; c < m_top; ++c)
+        SAFE_REQUIRE(cols_host[c] >= 0 && cols_host[c] < m, "%s: column %lld out of [0, %lld)", fn, (long long)cols_host[c], (long long)m);
+    return SAFE_OK;
+}
+
+// Pack + pair kernels of the checked arguments on the context's stream: *d_out (owned by b) receives the condensed distances.
+// Starts b's timing; the caller stops it behind whatever it enqueues next.
+int profile_condensed(const char *fn, safe_ctx *ctx, DomBufs &b, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host,
+                      int64_t m_top, int metric, double **d_out) {
+    const int64_t words = ceil_div(n, 64), pairs = m_top * (m_top - 1) / 2;
+    SAFE_REQUIRE(m_top < 65536 && ceil_div(words, 4) < (1ll << 31), "%s: too many profiles or rows for one launch", fn);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    int64_t *d_cols = nullptr;
+    unsigned long long *d_bits = nullptr;
+    SAFE_TRY(b.alloc(&d_cols, static_cast<size_t>(m_top)));
+    SAFE_TRY(b.alloc(&d_bits, static_cast<size_t>(m_top) * words));
+    SAFE_TRY(b.alloc(d_out, static_cast<size_t>(pairs)));
+    hipStream_t s = ctx->stream;
+    SAFE_HIP_CHECK(hipMemcpyAsync(d_cols, cols_host, m_top * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    SAFE_HIP_CHECK(b.start(s));
+    hipLaunchKernelGGL(k_profile_pack, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(m_top, 64))), dim3(256),
+                       0, s, values_dev, n, m, d_cols, m_top, words, d_bits);
+    SAFE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_profile_pairs, dim3(static_cast<unsigned>(ceil_div(m_top, 256)), static_cast<unsigned>(m_top)), dim3(256), 0, s,
+                       d_bits, m_top, words, n, metric, *d_out);
+    SAFE_HIP_CHECK(hipGetLastError());
+    return SAFE_OK;
+}
+
+int linkage_check_size(const char *fn, int64_t n) {
+    if (n > LINKAGE_MAX_POINTS) {
+        safe_set_error("%s: %lld points exceed the limit of %lld (an 8 n^2 byte working matrix; 16-bit chain ids in LDS)", fn, (long long)n,
+                       (long long)LINKAGE_MAX_POINTS);
+        return SAFE_E_UNSUPPORTED;
+    }
+    return SAFE_OK;
+}
+
+// Average linkage of the condensed distances d_cond (device, n >= 2 points, read only) into z_host f64 [n - 1, 4]: expand and
+// NN-chain kernels behind what the stream holds (b's timing is running: started by the caller, stopped here), then SciPy's
+// epilogue on the host -- a stable sort of the merges by height and the union-find relabel (linkage() -> label()).  Synchronises.
+// z_host is written only on success.
+int linkage_run(const char *fn, safe_ctx *ctx, DomBufs &b, const double *d_cond, int64_t n, const char *kernels, int64_t launches,
+                double *z_host, double *kernel_ms) {
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    double *d_sq = nullptr, *d_merges = nullptr;
+    int *d_size = nullptr, *d_flag = nullptr;
+    SAFE_TRY(b.alloc(&d_sq, static_cast<size_t>(n) * n));
+    SAFE_TRY(b.alloc(&d_size, static_cast<size_t>(n)));
+    SAFE_TRY(b.alloc(&d_merges, static_cast<size_t>(3 * (n - 1))));
+    SAFE_TRY(b.alloc(&d_flag, 1));
+    hipStream_t s = ctx->stream;
+    SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), s));
+    const unsigned tiles = static_cast<unsigned>(ceil_div(n, 32));
+    hipLaunchKernelGGL(k_linkage_expand, dim3(tiles, tiles), dim3(256), 0, s, d_cond, n, d_sq, d_flag);
+    SAFE_HIP_CHECK(hipGetLastError());
+    const unsigned threads = static_cast<unsigned>(std::min<int64_t>(LK_THREADS, ceil_div(n, 64) * 64));
+    hipLaunchKernelGGL(k_linkage_nn_chain, dim3(1), dim3(threads), 0, s, d_sq, static_cast<int>(n), d_size, d_merges, d_flag);
+    SAFE_HIP_CHECK(hipGetLastError());
+    SAFE_HIP_CHECK(b.stop(s));
+    int flag = 0;
+    std::vector<double> merges(static_cast<size_t>(3 * (n - 1)));
+    SAFE_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(hipMemcpyAsync(merges.data(), d_merges, merges.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(safe_stream_sync(s));
+    SAFE_HIP_CHECK(b.finish(ctx, kernels, launches, kernel_ms));
+    if (flag) {
+        safe_set_error(flag & LK_BAD_INPUT  ? "%s: the distances are not all finite (SciPy's linkage refuses them too)"
+                       : flag & LK_OVERFLOW ? "%s: an averaged distance overflowed"
+                                            : "%s: the chain did not end (internal error)",
+                       fn);
+        return SAFE_E_VALUE;
+    }
+    // np.argsort(Z[:, 2], kind='mergesort'), then label(): row i joins the current clusters of its two points as cluster n + i
+    std::vector<int64_t> order(static_cast<size_t>(n - 1));
+    std::iota(order.begin(), order.end(), int64_t(0));
+    std::stable_sort(order.begin(), order.end(), [&](int64_t u, int64_t v) { return merges[3 * u + 2] < merges[3 * v + 2]; });
+    std::vector<int64_t> parent(static_cast<size_t>(2 * n - 1)), count(static_cast<size_t>(2 * n - 1), 1);
+    std::iota(parent.begin(), parent.end(), int64_t(0));
+    auto find = [&](int64_t v) {
+        int64_t root = v;
+        while (parent[root] != root) root = parent[root];
+        while (parent[v] != root) {
+            const int64_t next = parent[v];
+            parent[v] = root;
+            v = next;
+        }
+        return root;
+    };
+    for (int64_t i = 0; i < n - 1; ++i) {
+        const double *mg = &merges[3 * order[i]];
+        const int64_t u = find(static_cast<int64_t>(mg[0])), v = find(static_cast<int64_t>(mg[1]));
+        parent[u] = parent[v] = n + i;
+        count[n + i] = count[u] + count[v];
+        z_host[4 * i] = static_cast<double>(std::min(u, v));
+        z_host[4 * i + 1] = static_cast<double>(std::max(u, v));
+        z_host[4 * i + 2] = mg[2];
+        z_host[4 * i + 3] = static_cast<double>(count[n + i]);
+    }
+    return SAFE_OK;
 }
 
 }  // namespace
@@ -347,39 +664,45 @@ int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *
 
 int safe_profile_distances(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
                            int metric, double *out_host, double *kernel_ms) {
-    SAFE_REQUIRE(ctx && n >= 1 && m >= 0 && m_top >= 0, "safe_profile_distances: bad argument");
-    SAFE_REQUIRE(metric >= SAFE_METRIC_JACCARD && metric <= SAFE_METRIC_YULE, "safe_profile_distances: unknown metric id %d", metric);
-    if (kernel_ms) *kernel_ms = 0;
-    SAFE_REQUIRE(m_top == 0 || cols_host, "safe_profile_distances: NULL argument");
-    for (int64_t c = 0; c < m_top; ++c)
-        SAFE_REQUIRE(cols_host[c] >= 0 && cols_host[c] < m, "safe_profile_distances: column %lld out of [0, %lld)",
-                     (long long)cols_host[c], (long long)m);
+    const char *fn = "safe_profile_distances";
+    SAFE_TRY(profile_check(fn, ctx, n, m, cols_host, m_top, metric, kernel_ms));
     if (m_top < 2) return SAFE_OK;
-    SAFE_REQUIRE(values_dev && out_host, "safe_profile_distances: NULL argument");
-    const int64_t words = ceil_div(n, 64), pairs = m_top * (m_top - 1) / 2;
-    SAFE_REQUIRE(m_top < 65536 && ceil_div(words, 4) < (1ll << 31), "safe_profile_distances: too many profiles or rows for one launch");
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    SAFE_REQUIRE(values_dev && out_host, "%s: NULL argument", fn);
     DomBufs b;
-    int64_t *d_cols = nullptr;
-    unsigned long long *d_bits = nullptr;
     double *d_out = nullptr;
-    SAFE_TRY(b.alloc(&d_cols, static_cast<size_t>(m_top)));
-    SAFE_TRY(b.alloc(&d_bits, static_cast<size_t>(m_top) * words));
-    SAFE_TRY(b.alloc(&d_out, static_cast<size_t>(pairs)));
+    SAFE_TRY(profile_condensed(fn, ctx, b, values_dev, n, m, cols_host, m_top, metric, &d_out));
     hipStream_t s = ctx->stream;
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_cols, cols_host, m_top * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    SAFE_HIP_CHECK(b.start(s));
-    hipLaunchKernelGGL(k_profile_pack, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(m_top, 64))), dim3(256),
-                       0, s, values_dev, n, m, d_cols, m_top, words, d_bits);
-    SAFE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_profile_pairs, dim3(static_cast<unsigned>(ceil_div(m_top, 256)), static_cast<unsigned>(m_top)), dim3(256), 0, s,
-                       d_bits, m_top, words, n, metric, d_out);
-    SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(b.stop(s));
-    SAFE_HIP_CHECK(hipMemcpyAsync(out_host, d_out, pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(hipMemcpyAsync(out_host, d_out, m_top * (m_top - 1) / 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));
     SAFE_HIP_CHECK(b.finish(ctx, "k_profile_pack+k_profile_pairs", 2, kernel_ms));
     return SAFE_OK;
+}
+
+int safe_linkage_average(safe_ctx *ctx, const double *cond_dev, int64_t m_top, double *z_host, double *kernel_ms) {
+    const char *fn = "safe_linkage_average";
+    SAFE_REQUIRE(ctx && m_top >= 0, "%s: bad argument", fn);
+    if (kernel_ms) *kernel_ms = 0;
+    if (m_top < 2) return SAFE_OK;
+    SAFE_REQUIRE(cond_dev && z_host, "%s: NULL argument", fn);
+    SAFE_TRY(linkage_check_size(fn, m_top));
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    DomBufs b;
+    SAFE_HIP_CHECK(b.start(ctx->stream));
+    return linkage_run(fn, ctx, b, cond_dev, m_top, "k_linkage_expand+k_linkage_nn_chain", 2, z_host, kernel_ms);
+}
+
+int safe_profile_linkage(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
+                         int metric, double *z_host, double *kernel_ms) {
+    const char *fn = "safe_profile_linkage";
+    SAFE_TRY(profile_check(fn, ctx, n, m, cols_host, m_top, metric, kernel_ms));
+    if (m_top < 2) return SAFE_OK;
+    SAFE_REQUIRE(values_dev && z_host, "%s: NULL argument", fn);
+    SAFE_TRY(linkage_check_size(fn, m_top));
+    DomBufs b;
+    double *d_cond = nullptr;
+    SAFE_TRY(profile_condensed(fn, ctx, b, values_dev, n, m, cols_host, m_top, metric, &d_cond));
+    return linkage_run(fn, ctx, b, d_cond, m_top, "k_profile_pack+k_profile_pairs+k_linkage_expand+k_linkage_nn_chain", 4, z_host, kernel_ms);
 }
 
 }  // extern "C"

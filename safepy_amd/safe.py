@@ -20,7 +20,7 @@ import pandas as pd        # noqa: F401  at import, like the reference (safepy/s
                            # used to pay for it -- 166 of its 178 ms
 
 from . import backend as be
-from ._lib import METRIC_IDS
+from ._lib import E_UNSUPPORTED, E_VALUE, METRIC_IDS, SafeHipError
 
 _DEFAULTS = {
     # the [DEFAULT] section of safepy/safe_default.ini:1-24, restated (the shipped .ini is not copied):
@@ -806,11 +806,14 @@ class SAFE:
     def define_domains(self, **kwargs):
         """safepy/safe.py:661-713.  Average-linkage clustering of the top attributes on the distance
         between their binarised enrichment profiles (default: Jaccard, computed on the device in
-        SciPy's condensed order; the linkage / fcluster calls are SciPy's, as in the reference), then
-        every node's domain sums, primary domain and primary NES.  While compute_pvalues' nes_binary and
-        nes are still on the device (nobody has read them) both steps read them there -- the boolean
-        metrics of backend.Context.profile_distances, then backend.Context.node_domains -- and they stay
-        there; otherwise the host arrays are used as before."""
+        SciPy's condensed order; fcluster is SciPy's, as in the reference), then every node's domain
+        sums, primary domain and primary NES.  While compute_pvalues' nes_binary and nes are still on
+        the device (nobody has read them) both steps read them there -- distances of the boolean metrics
+        and their average linkage in backend.Context.profile_linkage (Z equals SciPy's linkage bit for
+        bit; distances SciPy would refuse, or more than Context.LINKAGE_MAX_POINTS top attributes, go
+        through backend.Context.profile_distances and SciPy's linkage), then
+        backend.Context.node_domains -- and they stay there; otherwise the host arrays and SciPy's
+        linkage are used as before."""
         import pandas as pd
         from scipy.cluster.hierarchy import linkage, fcluster
         if 'attribute_distance_threshold' in kwargs:
@@ -821,9 +824,16 @@ class SAFE:
         metric = self.attribute_distance_metric
         src_b = self.__dict__.get('_r_nes_binary')
         if isinstance(src_b, _DeviceResult) and isinstance(metric, str) and metric in METRIC_IDS and np.count_nonzero(top) >= 2:
-            # the top columns are packed and compared in place on the device: nes_binary stays there
-            cond, _ = self._ctx().profile_distances(src_b.buf.ptr, src_b.shape[0], src_b.shape[1], np.flatnonzero(top), metric)
-            z = linkage(cond, method='average')
+            # the top columns are packed, compared and clustered in place on the device: nes_binary stays there and only Z comes back
+            where = (src_b.buf.ptr, src_b.shape[0], src_b.shape[1], np.flatnonzero(top), metric)
+            try:
+                z, _ = self._ctx().profile_linkage(*where)
+            except SafeHipError as err:
+                if err.code not in (E_VALUE, E_UNSUPPORTED):
+                    raise
+                # distances SciPy refuses (it raises below, as before) or more profiles than the linkage kernel takes
+                cond, _ = self._ctx().profile_distances(*where)
+                z = linkage(cond, method='average')
         else:
             m = self.nes_binary[:, top].T
             if metric == 'jaccard' and m.shape[0] >= 2:

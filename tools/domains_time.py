@@ -6,7 +6,8 @@ give no top attribute at all.
 
 Per repeat, one line: host-clock time of each stage (each ends in a device synchronise), the bytes the stage copied from
 the device to the host and uploaded again (DeviceBuffer.download, the host forms' uploads, the small result tables), the
-kernels' busy time of the device forms (ctx.last_kernel_busy_ms after each call; the host forms record none) and whether
+kernels' busy time of the device forms (ctx.last_kernel_busy_ms after each call -- for define_domains that includes the
+linkage kernel of profile_linkage, whose only download is Z; the host forms record none) and whether
 nes / nes_binary are still on the device afterwards.  The script uses the public SAFE interface only, so the same file
 times any commit of the package: `--package DIR` imports safepy_amd from another checkout's root.
 
@@ -104,7 +105,7 @@ class Meter:
         wrap(be.DeviceBuffer, 'download', download)
         wrap(be, 'enriched_components', host_form)
         wrap(be, 'jaccard_condensed', host_form)
-        for name in ('enriched_components_dev', 'profile_distances', 'node_domains'):
+        for name in ('enriched_components_dev', 'profile_distances', 'profile_linkage', 'node_domains'):
             wrap(be.Context, name, device_form)
 
     def take(self):
