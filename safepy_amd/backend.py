@@ -681,13 +681,15 @@ class Permutations:
         self.handle = h
 
     def timing(self):
-        """Host-side timing of the stream (safe_perms_timing), ms, and this rank's role in it."""
+        """Host-side timing of the stream (safe_perms_timing), ms, and this rank's role in it.  'resident': a seeded call that
+        found the complete table of the previous identical call (same seed, n, count and movable rows) still on the device and
+        drew nothing (SAFE_HIP_PERM_REUSE=0 switches that off)."""
         out = (C.c_double * 5)()
         check(lib.safe_perms_timing(self.handle, out))
         tw, ch, won = C.c_int(), C.c_int64(), C.c_int64()
         check(lib.safe_perms_twin_stats(self.handle, C.byref(tw), C.byref(ch), C.byref(won)))
         return {'draw_busy_ms': out[0], 'drawn_all_ms': out[1], 'tables_enqueued_ms': out[2], 'waited_for_producer_ms': out[3],
-                'role': ('own', 'producer', 'consumer', 'device')[int(out[4])],
+                'role': ('own', 'producer', 'consumer', 'device', 'resident')[int(out[4])],
                 'twin_chain': bool(tw.value), 'chunks': ch.value, 'chunks_won_by_twin': won.value}
 
     @classmethod

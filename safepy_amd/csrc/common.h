@@ -393,6 +393,13 @@ struct safe_perms {
     int32_t *d_movpos = nullptr;    // [n] movable rows (first k used) | [n] position of a row in that list (-1: fixed)
     struct PermRing *ring = nullptr;               // the context's ring while this handle takes part in a shared call, else NULL
     bool ring_consumer = false;
+    // Identity of the composed table while the handle is parked in ctx->perm_cache (rng.cpp, perms_create_impl): the stream is a
+    // pure function of (seed, n, count, movable rows), so the next seeded create with the same inputs takes the finished table
+    // as it lies in HBM.  tables_valid is only ever set by safe_perms_destroy and cleared the moment the handle is taken back.
+    bool has_seed = false;          // the caller named the seed (an entropy-seeded stream is never kept)
+    uint32_t seed = 0;
+    bool tables_valid = false;      // parked: table / table16 hold the complete stream of (seed, n, count, h_movable)
+    bool resident = false;          // live: this handle took a parked table instead of drawing (role 4 of safe_perms_timing)
     // host-side timing of the stream (safe_perms_timing), ms since the handle was created
     double t_created_s = 0.0, draw_busy_ms = 0.0, drawn_all_ms = 0.0, enqueued_all_ms = 0.0, ring_wait_ms = 0.0;
 };
@@ -414,7 +421,11 @@ std::vector<int64_t> perms_stage_plan(int64_t count);
 // SAFE_HIP_BITS_SPAN=<n> forces uniform spans.  *span = the longest launch.
 // merge > 1: after the three start-up stages (32, 96, 128 permutations) a launch covers `merge` stages -- fewer,
 // longer launches once the stream is ahead of the kernels.
-static inline std::vector<int64_t> perm_launch_starts(const safe_perms *perms, int64_t *span, int merge = 1) {
+// drawn_spans: a resident table (safe_perms::resident: complete before the first launch, stages = even spans) is consumed in
+// the launches of the drawn stream all the same -- any boundaries are valid for it, every stage event is complete.  For callers
+// whose launch logic is sized by those stages: the matrix-core path (its list of undecided compares holds what a launch of
+// <= 128 permutations leaves) and the column-chunked exchange tail (it needs three launches in front of the tail).
+static inline std::vector<int64_t> perm_launch_starts(const safe_perms *perms, int64_t *span, int merge = 1, bool drawn_spans = false) {
     const int64_t P = perms->count;
     std::vector<int64_t> starts;
     int64_t uniform = 0;
@@ -422,7 +433,8 @@ static inline std::vector<int64_t> perm_launch_starts(const safe_perms *perms, i
     if (uniform > 0) {
         for (int64_t p = 0; p < P; p += uniform) starts.push_back(p);
     } else {
-        const std::vector<int64_t> &plan = perms->stages;          // the handle's own stages (host pipeline, or even spans for device tables)
+        // the handle's own stages (host pipeline, or even spans for device tables and resident tables)
+        const std::vector<int64_t> plan = (drawn_spans && perms->resident) ? perms_stage_plan(P) : perms->stages;
         const int64_t nc = static_cast<int64_t>(plan.size()) - 1;
         for (int64_t c = 0; c < nc; ++c)
             if (c < 3 || merge <= 1 || (c - 3) % merge == 0) starts.push_back(plan[c]);

@@ -2674,7 +2674,9 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     // less per-task fixed cost -- kernel time per 1000 permutations 4.06 -> 3.94 / 3.89 ms at m = 2 / 3 in round 3 -- but the
     // step gets LONGER, 5.2 -> 5.5 / 5.8 ms: a merged launch waits for its last stage's draws)
     int64_t span = 1;
-    const std::vector<int64_t> starts = perm_launch_starts(perms, &span);
+    // (a column-chunked exchange tail, when one is asked for, is cut from the drawn stream's launches whatever the handle's stages)
+    const char *tail_env = ctx->xc_want >= 2 ? getenv("SAFE_HIP_XCHG_TAIL") : nullptr;
+    const std::vector<int64_t> starts = perm_launch_starts(perms, &span, 1, tail_env && atof(tail_env) > 0.0);
     // Exchange overlap of the sharded step (safe_set_exchange_chunks): the LAST permutations -- the tail -- run as one launch per
     // COLUMN chunk over all of the tail instead of one launch per stage over all columns.  A chunk's counters are then final when
     // its launch ends, and its all-gather overlaps the launches of the later chunks (xc_events; sharding.ChunkedExchange).

@@ -2882,7 +2882,7 @@ int mfma_make_plan(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const 
         q_off[qx + 1] = static_cast<int32_t>(tasks.size());
     }
     plan->n_tasks = static_cast<int64_t>(tasks.size());
-    plan->starts = perm_launch_starts(perms, &plan->span);
+    plan->starts = perm_launch_starts(perms, &plan->span, 1, true);       // (amb_cap below is sized for the drawn stream's spans)
     const int64_t span = plan->span, n_launch = plan->n_launch = static_cast<int64_t>(plan->starts.size()) - 1;
     void *ws = nullptr;
     SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + (8 * n_launch + 8 + 16) * sizeof(unsigned int), &ws));
