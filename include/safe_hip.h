@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SAFE_HIP_ABI_VERSION 8
+#define SAFE_HIP_ABI_VERSION 9
 
 #define SAFE_OK 0
 #define SAFE_E_INVALID (-1)   /* bad argument */
@@ -195,6 +195,24 @@ int safe_attr_create_host(safe_ctx *ctx, const void *b_host, int dtype, int64_t 
                           int64_t row_stride, int64_t col_stride, safe_attr **out);
 int safe_attr_create_dev(safe_ctx *ctx, const void *b_dev, int dtype, int64_t n, int64_t m,
                          int64_t row_stride, int64_t col_stride, safe_attr **out);
+/* Additive: self.node2attribute given SPARSE -- the compressed-sparse-column form annotation matrices are built and stored
+ * in (the reference's own GO builder produces a sparse frame before read_attributes densifies it, safepy/safe_io.py:410) --
+ * and expanded on the device: the upload is 8 (m + 1) + 4 nnz bytes (+ the values) instead of n m values.  The handle owns
+ * a dense Fortran-order matrix D of `dtype` (SAFE_DTYPE_F32 when values is NULL: every stored entry is 1) and no later
+ * call can tell it from safe_attr_create_host of D:
+ *   D is 0 everywhere, with values[k] at (indices[k], j) for indptr[j] <= k < indptr[j + 1]; stored zeros and stored NaNs
+ *   are legal and mean 0 and NaN; every row i with missing_rows[i] != 0 (NULL: none) is NaN in every column -- the nodes
+ *   read_attributes fills with fill_value = NaN (safe_io.py:386-390).
+ * Contract on the input: indptr[0] == 0, indptr[m] == nnz, indptr non-decreasing; row indices strictly increasing inside a
+ * column and in [0, n); nnz < 2^31.  A kernel checks it on the device before anything is scattered; a violation returns
+ * SAFE_E_VALUE with a message naming the first rule broken (in the order above) and creates no handle.
+ * When no stored value differs from 1 and no stored entry lies on a missing row, the input already is the list of ones
+ * per column that the scatter form of the permutation test reads, and is kept as such (no scan of D on first use).
+ * Enqueued on the context's stream; synchronises (the verdict is read back, and the staging memory goes back to the
+ * context's pool before the call returns). */
+int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr /*[m+1]*/,
+                              const int32_t *indices /*[nnz]*/, const void *values /*[nnz] or NULL*/, int dtype /*F32|F64*/,
+                              const uint8_t *missing_rows /*[n] or NULL*/, safe_attr **out);
 int safe_attr_destroy(safe_attr *attr);
 /* read_attributes on the device (safepy/safe_io.py:386-390 `node2attribute.reindex(index=
  * node_label_order, fill_value=fill_value)` + `.values` at :410): uploads the file's

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsafe_hip.so')
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
@@ -108,6 +108,7 @@ PROTOTYPES = {
                                      C.POINTER(C.c_int)]),
     'safe_attr_create_host': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _i64, _pp]),
     'safe_attr_create_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _i64, _pp]),
+    'safe_attr_create_csc_host': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _pp]),
     'safe_attr_destroy': (C.c_int, [_vp]),
     'safe_attr_reindex': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _pp]),
     'safe_attr_value_counts': (C.c_int, [_vp, _pi64, _pi64, _pi64, _pi64]),

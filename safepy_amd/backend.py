@@ -538,14 +538,26 @@ class Neighborhoods:
             pass
 
 
+def _is_sparse(a):
+    """scipy.sparse.issparse without importing SciPy for callers that never touch it."""
+    import sys
+    sp = sys.modules.get('scipy.sparse')
+    if sp is None:
+        if not type(a).__module__.startswith('scipy.sparse'):
+            return False
+        import scipy.sparse as sp
+    return sp.issparse(a)
+
+
 class Attributes:
     """Device-resident node x attribute matrix (f32/f64, C or Fortran order, NaN = missing)."""
 
-    def __init__(self, ctx, handle, n, m, keepalive=None):
+    def __init__(self, ctx, handle, n, m, keepalive=None, dtype=None):
         self.ctx = ctx
         self.handle = handle
         self.n, self.m = n, m
         self._keepalive = keepalive
+        self.dtype = None if dtype is None else np.dtype(dtype)      # of the device matrix, where the constructor knows it
 
     @staticmethod
     def _layout(b, allow_u8=False):
@@ -571,8 +583,57 @@ class Attributes:
             rs, cs = 1, n
         return b, dt, n, m, rs, cs
 
+    @staticmethod
+    def canonical_csc(a):
+        """Host side of from_sparse: any scipy.sparse matrix or array as (n, m, indptr int64 [m+1], indices int32 [nnz],
+        values or None, owner), the input form of safe_attr_create_csc_host -- CSC with duplicates summed and row indices sorted,
+        made on a copy this call owns unless the input is in that form already (`owner` keeps the arrays alive; the input is
+        never modified).  values is None when every stored value is 1 (the
+        library then makes an f32 matrix); f32 / f64 data otherwise stays as it is and bool / integer data becomes f64."""
+        import scipy.sparse as sp
+        if not sp.issparse(a):
+            raise TypeError('canonical_csc: expected a scipy.sparse matrix or array, got %s' % type(a).__name__)
+        if a.ndim != 2:
+            raise ValueError('node2attribute must be 2-D, got shape %s' % (a.shape,))
+        if a.format == 'csc' and a.has_canonical_format:
+            c = a                                         # nothing to change, so nothing to copy (16 MB at 2 M stored entries)
+        else:
+            c = a.tocsc(copy=True)
+            c.sum_duplicates()
+            c.sort_indices()
+        if c.dtype not in (np.float32, np.float64):
+            c = c.astype(np.float64)                      # (after the conversion: duplicates meet in the input's own dtype, as in toarray())
+        n, m = c.shape
+        if c.nnz >= 1 << 31 or n >= 1 << 31:
+            raise ValueError('sparse node2attribute: %d stored entries / %d rows do not fit 32-bit row indices' % (c.nnz, n))
+        indptr = np.ascontiguousarray(c.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(c.indices, dtype=np.int32)
+        values = np.ascontiguousarray(c.data)
+        if bool((values == 1).all()):
+            values = None
+        return n, m, indptr, indices, values, c
+
+    @classmethod
+    def from_sparse(cls, ctx, a, missing_rows=None):
+        """A scipy.sparse node x attribute matrix (any format) expanded on the device (safe_attr_create_csc_host): only the
+        stored entries travel.  The handle equals from_host of the dense equivalent -- 0 where nothing is stored, stored
+        zeros and NaNs kept, and NaN across every row i with missing_rows[i] != 0 (the nodes without a row in the file)."""
+        n, m, indptr, indices, values, _keep = cls.canonical_csc(a)
+        mis = None
+        if missing_rows is not None:
+            mis = np.ascontiguousarray(np.asarray(missing_rows) != 0, dtype=np.uint8)
+            if mis.shape != (n,):
+                raise ValueError('missing_rows: expected %d flags, got shape %s' % (n, mis.shape))
+        dt = _lib.DTYPE_F64 if values is not None and values.dtype == np.float64 else _lib.DTYPE_F32
+        h = C.c_void_p()
+        check(lib.safe_attr_create_csc_host(ctx.handle, n, m, indices.shape[0], _ptr(indptr), _ptr(indices) if indices.size else None,
+                                            _ptr(values), dt, _ptr(mis), C.byref(h)))
+        return cls(ctx, h, n, m, dtype=np.float64 if dt == _lib.DTYPE_F64 else np.float32)
+
     @classmethod
     def from_host(cls, ctx, b):
+        if _is_sparse(b):
+            return cls.from_sparse(ctx, b)
         b, dt, n, m, rs, cs = cls._layout(np.asarray(b), allow_u8=True)
         h = C.c_void_p()
         check(lib.safe_attr_create_host(ctx.handle, _ptr(b), dt, n, m, rs, cs, C.byref(h)))

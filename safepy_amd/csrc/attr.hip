@@ -293,6 +293,18 @@ __global__ __launch_bounds__(256) void k_nan_to_zero(T *__restrict__ raw, int64_
     }
 }
 
+// the support lists go back where they came from: the context's pool (installed from a CSC input) or the driver
+static void attr_free_support(safe_attr *attr) {
+    if (attr->sup_ptr_pool_bytes) ctx_block_free(attr->ctx, attr->sup_ptr, attr->sup_ptr_pool_bytes);
+    else (void)hipFree(attr->sup_ptr);
+    if (attr->sup_row_pool_bytes) ctx_block_free(attr->ctx, attr->sup_row, attr->sup_row_pool_bytes);
+    else (void)hipFree(attr->sup_row);
+    attr->sup_ptr = nullptr;
+    attr->sup_row = nullptr;
+    attr->sup_ptr_pool_bytes = attr->sup_row_pool_bytes = 0;
+    attr->h_sup_ptr.clear();
+}
+
 int attr_build_support(safe_attr *attr) {
     if (attr->sup_ptr) return SAFE_OK;
     SAFE_TRY(safe_attr_prepare(attr));
@@ -404,6 +416,90 @@ int safe_attr_prepare(safe_attr *attr) {
     return SAFE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// A sparse node x attribute matrix (CSC: the form GO-style annotation matrices are built and stored in) expanded on the
+// device into the dense Fortran-order matrix every other entry point reads (safe_attr_create_csc_host)
+// ---------------------------------------------------------------------------------------------
+// what k_csc_validate reports: the rules of the input contract in the order the header states them, then two facts
+enum : unsigned int {
+    CSC_PTR_FIRST = 1u,       // indptr[0] != 0
+    CSC_PTR_LAST = 2u,        // indptr[m] != nnz
+    CSC_PTR_DECREASES = 4u,   // indptr[j + 1] < indptr[j]
+    CSC_ROW_EQUAL = 8u,       // two neighbours of a column name the same row
+    CSC_ROW_DESCENDS = 16u,   // ... or descend
+    CSC_ROW_RANGE = 32u,      // a row index outside [0, n)
+    CSC_RULES = 63u,
+    CSC_NOT_ONE = 256u,       // a stored value that is not 1 (a stored zero and a stored NaN included)
+    CSC_ON_MISSING = 512u,    // a stored entry in a row of missing_rows
+};
+
+// One lane per stored entry and one per column boundary (a thread plays both roles).  Every read is inside the three arrays
+// whatever they hold: an entry looks at indices[k - 1 .. k] and, where the row does not ascend, searches indptr[0 .. m] for a
+// column that starts at k (a non-monotone indptr makes that search meaningless, not unsafe -- the boundary lanes report it).
+// The boundary lanes also leave indptr as the int32 offsets of the support lists.
+template <typename T>
+__global__ __launch_bounds__(256) void k_csc_validate(int64_t n, int64_t m, int64_t nnz, const int64_t *__restrict__ indptr,
+                                                      const int32_t *__restrict__ indices, const T *__restrict__ values,
+                                                      const uint8_t *__restrict__ missing, int32_t *__restrict__ sup_ptr,
+                                                      unsigned int *__restrict__ flag) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned int bad = 0;
+    if (t < nnz) {
+        const int32_t r = indices[t];
+        if (r < 0 || r >= n) bad |= CSC_ROW_RANGE;
+        else if (missing && missing[r]) bad |= CSC_ON_MISSING;
+        if (values && !(values[t] == static_cast<T>(1))) bad |= CSC_NOT_ONE;
+        if (t > 0) {
+            const int32_t prev = indices[t - 1];
+            if (r <= prev) {
+                int64_t lo = 0, hi = m + 1;                    // first j in [0, m] with indptr[j] >= t
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (indptr[mid] < t) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (!(lo <= m && indptr[lo] == t)) bad |= r == prev ? CSC_ROW_EQUAL : CSC_ROW_DESCENDS;
+            }
+        }
+    }
+    if (t <= m) {
+        const int64_t p = indptr[t];
+        if (t == 0 && p != 0) bad |= CSC_PTR_FIRST;
+        if (t == m && p != nnz) bad |= CSC_PTR_LAST;
+        if (t < m && indptr[t + 1] < p) bad |= CSC_PTR_DECREASES;
+        sup_ptr[t] = static_cast<int32_t>(p);
+    }
+    for (int off = 32; off; off >>= 1) bad |= __shfl_xor(bad, off);
+    if ((threadIdx.x & 63) == 0 && bad) atomicOr(flag, bad);
+}
+
+// one wave per column, lanes along its stored entries (indices and values are read coalesced); the 4- or 8-byte writes fall
+// inside the column's contiguous span of the zeroed Fortran-order matrix.  Runs only on validated input, and guards its
+// reads and writes all the same.
+template <typename T>
+__global__ __launch_bounds__(256) void k_csc_scatter(int64_t n, int64_t m, int64_t nnz, const int64_t *__restrict__ indptr,
+                                                     const int32_t *__restrict__ indices, const T *__restrict__ values,
+                                                     T *__restrict__ out) {
+    const int64_t j = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (j >= m) return;
+    const int64_t p0 = std::max<int64_t>(indptr[j], 0), p1 = std::min<int64_t>(indptr[j + 1], nnz);
+    T *col = out + j * n;
+    for (int64_t k = p0 + lane; k < p1; k += 64) {
+        const int64_t r = indices[k];
+        if (r >= 0 && r < n) col[r] = values ? values[k] : static_cast<T>(1);
+    }
+}
+
+// rows of missing_rows are NaN in every column (the nodes read_attributes fills with fill_value = NaN): lanes along the rows
+// of a column, a thread keeps its row and walks the columns
+template <typename T>
+__global__ __launch_bounds__(256) void k_csc_missing_rows(const uint8_t *__restrict__ missing, int64_t n, int64_t m, T *__restrict__ out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n || !missing[i]) return;
+    for (int64_t j = blockIdx.y; j < m; j += gridDim.y) out[j * n + i] = static_cast<T>(__builtin_nan(""));
+}
+
 static int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out) {
     SAFE_REQUIRE(ctx && out, "safe_attr_create: NULL argument");
     SAFE_REQUIRE(dtype == SAFE_DTYPE_F32 || dtype == SAFE_DTYPE_F64, "safe_attr_create: dtype must be f32 or f64 (u8: host form only)");
@@ -481,6 +577,134 @@ int safe_attr_create_host(safe_ctx *ctx, const void *b_host, int dtype, int64_t 
     }
     a->raw = d;
     a->owns_raw = true;
+    *out = a;
+    return SAFE_OK;
+}
+
+int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                              const void *values, int dtype, const uint8_t *missing_rows, safe_attr **out) {
+    SAFE_REQUIRE(ctx && out && indptr, "safe_attr_create_csc_host: NULL argument");
+    SAFE_REQUIRE(nnz >= 0 && (indices || nnz == 0), "safe_attr_create_csc_host: %lld stored entries without indices", (long long)nnz);
+    if (nnz >= (1ll << 31)) {
+        safe_set_error("safe_attr_create_csc_host: nnz = %lld, must be below 2^31", (long long)nnz);
+        return SAFE_E_VALUE;
+    }
+    if (!values) dtype = SAFE_DTYPE_F32;                    // every stored entry is 1
+    safe_attr *a = nullptr;
+    SAFE_TRY(attr_new(ctx, dtype, n, m, 1, n, &a));         // (checks ctx, dtype, n, m)
+    *out = nullptr;                                         // (set once the handle is complete: a refusal leaves none)
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t esz = dtype == SAFE_DTYPE_F64 ? 8 : 4;
+    const size_t dense_bytes = static_cast<size_t>(n) * m * esz;
+    // staging, one block of the context's pool: indptr | values | missing_rows | flag word; the row indices and the int32
+    // offsets in blocks of their own, because they stay as the support lists when the input is one
+    const size_t off_val = static_cast<size_t>(m + 1) * 8;
+    const size_t off_mis = off_val + (values ? (static_cast<size_t>(nnz) * esz + 7) / 8 * 8 : 0);
+    const size_t off_flag = off_mis + (missing_rows ? (static_cast<size_t>(n) + 7) / 8 * 8 : 0);
+    const size_t stage_bytes = off_flag + 8, idx_bytes = static_cast<size_t>(nnz) * 4, ptr_bytes = static_cast<size_t>(m + 1) * 4;
+    void *stage = nullptr, *d_idx = nullptr, *d_ptr = nullptr, *dense = nullptr;
+    auto give_back = [&](bool lists, bool matrix) {         // (after a sync of the context's stream)
+        ctx_block_free(ctx, stage, stage_bytes);
+        if (lists) ctx_block_free(ctx, d_idx, idx_bytes), ctx_block_free(ctx, d_ptr, ptr_bytes);
+        if (matrix) ctx_block_free(ctx, dense, dense_bytes);
+    };
+    int rc = ctx_block_alloc(ctx, stage_bytes, &stage);
+    if (rc == SAFE_OK) rc = ctx_block_alloc(ctx, idx_bytes, &d_idx);
+    if (rc == SAFE_OK) rc = ctx_block_alloc(ctx, ptr_bytes, &d_ptr);
+    if (rc == SAFE_OK) rc = ctx_block_alloc(ctx, dense_bytes, &dense);
+    void *pinned = nullptr;
+    if (rc == SAFE_OK) rc = ctx_pinned(ctx, 64, &pinned);
+    if (rc != SAFE_OK) {
+        give_back(true, true);
+        delete a;
+        return rc;
+    }
+    uint8_t *sb = static_cast<uint8_t *>(stage);
+    const int64_t *d_indptr = reinterpret_cast<const int64_t *>(sb);
+    const void *d_val = values ? sb + off_val : nullptr;
+    const uint8_t *d_mis = missing_rows ? sb + off_mis : nullptr;
+    unsigned int *d_flag = reinterpret_cast<unsigned int *>(sb + off_flag);
+    const int32_t *d_rows = static_cast<const int32_t *>(d_idx);
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemcpyAsync(sb, indptr, static_cast<size_t>(m + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, indices, idx_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && values && nnz) e = hipMemcpyAsync(sb + off_val, values, static_cast<size_t>(nnz) * esz, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && missing_rows) e = hipMemcpyAsync(sb + off_mis, missing_rows, static_cast<size_t>(n), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 8, st);
+    if (e == hipSuccess) {
+        const dim3 grid(static_cast<unsigned int>(ceil_div(std::max<int64_t>(nnz, m + 1), 256)));
+        if (dtype == SAFE_DTYPE_F64)
+            hipLaunchKernelGGL(k_csc_validate<double>, grid, dim3(256), 0, st, n, m, nnz, d_indptr, d_rows, static_cast<const double *>(d_val),
+                               d_mis, static_cast<int32_t *>(d_ptr), d_flag);
+        else
+            hipLaunchKernelGGL(k_csc_validate<float>, grid, dim3(256), 0, st, n, m, nnz, d_indptr, d_rows, static_cast<const float *>(d_val),
+                               d_mis, static_cast<int32_t *>(d_ptr), d_flag);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+    // (the matrix is the handle's own: zeroing it needs no verdict, and runs while the host waits for the flag)
+    if (e == hipSuccess) e = hipMemsetAsync(dense, 0, dense_bytes, st);
+    if (e == hipSuccess) e = safe_stream_sync(st);
+    unsigned int flag = 0;
+    if (e == hipSuccess) {
+        memcpy(&flag, pinned, sizeof(flag));
+        if (flag & CSC_RULES) {
+            const unsigned int first = flag & CSC_RULES & (~(flag & CSC_RULES) + 1u);
+            const char *rule = first == CSC_PTR_FIRST       ? "indptr[0] is not 0"
+                               : first == CSC_PTR_LAST      ? "indptr[m] is not nnz"
+                               : first == CSC_PTR_DECREASES ? "indptr decreases"
+                               : first == CSC_ROW_EQUAL     ? "a row index is repeated inside a column (duplicates must be summed)"
+                               : first == CSC_ROW_DESCENDS  ? "row indices descend inside a column (indices must be sorted)"
+                                                            : "a row index lies outside [0, n)";
+            safe_set_error("safe_attr_create_csc_host: %s (%lld x %lld, %lld stored entries)", rule, (long long)n, (long long)m, (long long)nnz);
+            give_back(true, true);
+            delete a;
+            return SAFE_E_VALUE;
+        }
+        // the check passed: scatter the stored entries, then the missing rows on top of them
+        if (nnz) {
+            const dim3 grid(static_cast<unsigned int>(ceil_div(m * 64, 256)));
+            if (dtype == SAFE_DTYPE_F64)
+                hipLaunchKernelGGL(k_csc_scatter<double>, grid, dim3(256), 0, st, n, m, nnz, d_indptr, d_rows, static_cast<const double *>(d_val),
+                                   static_cast<double *>(dense));
+            else
+                hipLaunchKernelGGL(k_csc_scatter<float>, grid, dim3(256), 0, st, n, m, nnz, d_indptr, d_rows, static_cast<const float *>(d_val),
+                                   static_cast<float *>(dense));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && missing_rows) {
+            const dim3 grid(static_cast<unsigned int>(ceil_div(n, 256)), static_cast<unsigned int>(std::min<int64_t>(m, 1024)));
+            if (dtype == SAFE_DTYPE_F64)
+                hipLaunchKernelGGL(k_csc_missing_rows<double>, grid, dim3(256), 0, st, d_mis, n, m, static_cast<double *>(dense));
+            else
+                hipLaunchKernelGGL(k_csc_missing_rows<float>, grid, dim3(256), 0, st, d_mis, n, m, static_cast<float *>(dense));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = safe_stream_sync(st);       // the staging block goes back to the pool: nothing may still read it
+    }
+    if (e != hipSuccess) {
+        safe_set_error("safe_attr_create_csc_host: %s", hipGetErrorString(e));
+        (void)safe_stream_sync(st);
+        give_back(true, true);
+        delete a;
+        return SAFE_E_HIP;
+    }
+    a->raw = dense;
+    a->owns_raw = true;
+    a->raw_pool_bytes = dense_bytes;
+    // No stored value other than 1 and no entry on a missing row: the input IS the CSC of the ones, what k_fill_support would
+    // find by scanning the dense matrix (a stored zero or an entry under a NaN row would not be in its lists).
+    const bool is_support = !(flag & (CSC_NOT_ONE | CSC_ON_MISSING));
+    if (is_support) {
+        a->sup_ptr = static_cast<int32_t *>(d_ptr);
+        a->sup_row = static_cast<int32_t *>(d_idx);
+        a->sup_ptr_pool_bytes = ptr_bytes;
+        a->sup_row_pool_bytes = idx_bytes;
+        a->n_ones = nnz;
+        a->h_sup_ptr.resize(static_cast<size_t>(m + 1));
+        for (int64_t j = 0; j <= m; ++j) a->h_sup_ptr[static_cast<size_t>(j)] = static_cast<int32_t>(indptr[j]);
+    }
+    give_back(!is_support, false);
     *out = a;
     return SAFE_OK;
 }
@@ -593,11 +817,7 @@ int safe_attr_nan_to_zero(safe_attr *attr) {
     // every derived fact is stale now
     attr->stats_ready = false;
     attr->flags_ready = false;
-    (void)hipFree(attr->sup_ptr);
-    (void)hipFree(attr->sup_row);
-    attr->sup_ptr = nullptr;
-    attr->sup_row = nullptr;
-    attr->h_sup_ptr.clear();
+    attr_free_support(attr);
     return SAFE_OK;
 }
 
@@ -615,11 +835,11 @@ int safe_attr_destroy(safe_attr *attr) {
     if (!attr) return SAFE_OK;
     (void)hipSetDevice(attr->ctx->device);
     (void)safe_stream_sync(attr->ctx->stream);
-    if (attr->owns_raw) (void)hipFree(const_cast<void *>(attr->raw));
+    if (attr->owns_raw && attr->raw_pool_bytes) ctx_block_free(attr->ctx, const_cast<void *>(attr->raw), attr->raw_pool_bytes);
+    else if (attr->owns_raw) (void)hipFree(const_cast<void *>(attr->raw));
     ctx_block_free(attr->ctx, attr->row_flags, flags_block_bytes(attr->n));
     ctx_block_free(attr->ctx, attr->col_sum, static_cast<size_t>(attr->m) * sizeof(double));
-    (void)hipFree(attr->sup_ptr);
-    (void)hipFree(attr->sup_row);
+    attr_free_support(attr);
     delete attr;
     return SAFE_OK;
 }

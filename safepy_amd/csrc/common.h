@@ -310,6 +310,7 @@ struct safe_attr {
     int64_t row_stride = 0, col_stride = 0;
     const void *raw = nullptr;      // device
     bool owns_raw = false;
+    size_t raw_pool_bytes = 0;      // owns_raw and > 0: raw is a block of the context's pool (ctx_block_alloc) of that size
     uint8_t *row_flags = nullptr;   // [n] device, 1 = row has >= 1 non-NaN value
     std::vector<uint8_t> h_row_flags;   // host copy of row_flags (kept in step: safe_attr_row_flags answers without a device sync)
     bool flags_ready = false;
@@ -322,6 +323,7 @@ struct safe_attr {
     int32_t *sup_row = nullptr;     // [n_ones]
     int64_t n_ones = 0;
     std::vector<int32_t> h_sup_ptr; // host copy
+    size_t sup_ptr_pool_bytes = 0, sup_row_pool_bytes = 0;   // > 0: the lists are blocks of the context's pool (installed from a CSC input)
 };
 
 struct DrawStream;   // host MT19937 draw stream (rng.cpp)

@@ -112,9 +112,13 @@ int ctx_block_alloc(safe_ctx *ctx, size_t bytes, void **out) {
 void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes) {
     if (!p) return;
     const size_t have = block_class(bytes);
-    if (have > (8u << 20) || ctx->block_cache.size() >= 32) {
+    if (have > (8u << 20)) {
         (void)hipFree(p);
         return;
+    }
+    if (ctx->block_cache.size() >= 32) {                   // full: the block that has waited longest makes room (the shapes in use stay)
+        (void)hipFree(ctx->block_cache.front().second);
+        ctx->block_cache.erase(ctx->block_cache.begin());
     }
     ctx->block_cache.emplace_back(have, p);
 }

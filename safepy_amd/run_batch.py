@@ -23,6 +23,14 @@ import time
 import numpy as np
 
 
+def _column_block(node2attribute, c0, c1):
+    """This rank's columns: a contiguous copy of a dense matrix, a sparse slice of a sparse one (it stays sparse)."""
+    from safepy_amd import backend
+    if backend._is_sparse(node2attribute):
+        return node2attribute.tocsc()[:, c0:c1]
+    return np.ascontiguousarray(node2attribute[:, c0:c1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Run SAFE on the columns of an attribute file, sharded across the GPUs of a node')
     ap.add_argument('path_to_attribute_file', type=str, help='label-to-attribute annotations (.txt / .gz)')
@@ -82,7 +90,7 @@ def main(argv=None):
         if rank == 0:
             logging.info('Running SAFE on %d shards of about %d attributes...' % (world, -(-m_total // world)))
         out = sharding.sharded_compute_pvalues(
-            sf._ctx(), sf._device_neighborhoods(), np.ascontiguousarray(sf.node2attribute[:, c0:c1]), m_total,
+            sf._ctx(), sf._device_neighborhoods(), _column_block(sf.node2attribute, c0, c1), m_total,
             enrichment_type=args.how, num_permutations=args.permutations, random_seed=sf.random_seed,
             neighborhood_score_type=args.score, attribute_sign=sf.attribute_sign,
             enrichment_threshold=sf.enrichment_threshold, gather=('nes',), multiple_testing=args.multiple_testing)

@@ -228,6 +228,7 @@ class SAFE:
         self._pending_binary = None
         self._attr_dev = None            # resident node2attribute (load_attributes(keep_on_device=True))
         self._attr_dev_host = None
+        self._missing_rows = None        # sparse node2attribute only: uint8 [N], 1 = the node's whole row is missing (NaN)
 
         self.read_config(path_to_ini_file, path_to_safe_data=self.path_to_safe_data)
         self.validate_config()
@@ -412,17 +413,23 @@ class SAFE:
     def load_attributes(self, **kwargs):
         """safepy/safe.py:334-367 over `read_attributes` (safe_io.py:336-430): `attribute_file=` a
         `.txt` / `.gz` path, a pandas DataFrame indexed by node key, or (additive) a ready [N,M]
-        ndarray in node order; other kwargs (`mask_duplicates`, `fill_value`) are forwarded.
+        ndarray in node order, or (additive) a scipy.sparse [N,M] matrix in node order, which stays sparse:
+        `self.node2attribute` is that object, only its stored entries are uploaded and the dense matrix exists on
+        the device alone; `missing_rows=` (bool / 0-1 [N], sparse input only) marks the nodes whose whole row is
+        missing (NaN), what `fill_value=NaN` gives the nodes a file does not list.  Other kwargs
+        (`mask_duplicates`, `fill_value`) are forwarded.
         The alignment to node order runs on the device.  `keep_on_device=True` (additive) keeps the
         aligned matrix resident for compute_pvalues(), which then skips the upload; the host
         `self.node2attribute` is made read-only in exchange (assign a new array to replace it)."""
         import pandas as pd
         from . import safe_io
         keep = bool(kwargs.pop('keep_on_device', False))
+        missing_rows = kwargs.pop('missing_rows', None)
         self._drop_device_attributes()
+        self._missing_rows = None
         if 'attribute_file' in kwargs:
             src = kwargs.pop('attribute_file')
-            if self.path_to_safe_data is None or isinstance(src, (pd.DataFrame, np.ndarray)):
+            if self.path_to_safe_data is None or isinstance(src, (pd.DataFrame, np.ndarray)) or be._is_sparse(src):
                 self.path_to_attribute_file = src
             elif isinstance(src, str):
                 self.path_to_attribute_file = os.path.join(self.path_to_safe_data, src)
@@ -432,6 +439,23 @@ class SAFE:
         if isinstance(src, str):
             assert os.path.exists(src), src
         self.validate_config()
+        if missing_rows is not None and not be._is_sparse(src):
+            raise TypeError('missing_rows goes with a scipy.sparse attribute_file; a dense matrix carries its missing values as NaN')
+        if be._is_sparse(src):
+            if missing_rows is not None:
+                missing_rows = np.ascontiguousarray(np.asarray(missing_rows) != 0, dtype=np.uint8)
+                if missing_rows.shape != (src.shape[0],):
+                    raise ValueError('missing_rows: expected %d flags, got shape %s' % (src.shape[0], missing_rows.shape))
+            self.node2attribute = src
+            self._missing_rows = missing_rows
+            self._missing_rows_of = src          # (the flags belong to this object: a matrix assigned later has none)
+            self.attributes = pd.DataFrame({'id': np.arange(src.shape[1]),
+                                            'name': [str(j) for j in range(src.shape[1])]})
+            if keep:
+                self._attr_dev = be.Attributes.from_sparse(self._ctx(), src, missing_rows)
+                self._attr_dev_host = src
+                self._attr_dev_sig = (src.shape, src.nnz)
+            return
         if isinstance(src, np.ndarray):
             self.node2attribute = src
             self.attributes = pd.DataFrame({'id': np.arange(src.shape[1]),
@@ -468,8 +492,20 @@ class SAFE:
         host = self.node2attribute
         if host is self._attr_dev_host and isinstance(host, np.ndarray) and not host.flags.writeable:
             return attr
+        if host is self._attr_dev_host and be._is_sparse(host) and (host.shape, host.nnz) == self.__dict__.get('_attr_dev_sig'):
+            return attr                  # (a sparse object cannot be made read-only: same object, same shape and entry count)
         self._drop_device_attributes()
         return None
+
+    def _missing_rows_for(self, a):
+        """The missing-row flags load_attributes recorded for the sparse matrix `a`, or None."""
+        return self.__dict__.get('_missing_rows') if self.__dict__.get('_missing_rows_of') is a else None
+
+    def _upload_attributes(self):
+        """A device handle of self.node2attribute: a dense array as it is, a sparse matrix by its stored entries."""
+        if be._is_sparse(self.node2attribute):
+            return be.Attributes.from_sparse(self._ctx(), self.node2attribute, self._missing_rows_for(self.node2attribute))
+        return be.Attributes.from_host(self._ctx(), self.node2attribute)
 
     def _node_keys(self):
         if isinstance(self.graph, LayoutGraph):
@@ -625,15 +661,33 @@ class SAFE:
         resident = self._resident_attributes()
         if self.background == 'network':
             logging.info('Setting all null attribute values to 0. Using the network as background for enrichment.')
-            if resident is not None:                                       # both copies, the host one stays read-only
-                resident.nan_to_zero()
-                self.node2attribute.flags.writeable = True
-            if np.issubdtype(self.node2attribute.dtype, np.floating):      # (a uint8 / bool matrix has no missing values)
-                self.node2attribute[np.isnan(self.node2attribute)] = 0     # in place, like safe.py:451
-            if resident is not None:
-                self.node2attribute.flags.writeable = False
+            if be._is_sparse(self.node2attribute):
+                # the sparse form of the same step: the missing rows become rows of zeros (nothing stored), stored NaNs
+                # become stored zeros -- on the host object and on the resident handle; never densified
+                if resident is not None:
+                    resident.nan_to_zero()
+                a = self.node2attribute
+                if a.format not in ('csc', 'csr', 'coo'):
+                    raise TypeError("background='network' edits the stored values of the sparse node2attribute in place and knows "
+                                    "the CSC, CSR and COO layouts; convert this %s with .tocsc()" % type(a).__name__)
+                missing = self._missing_rows_for(a)
+                if missing is not None and missing.any():                 # what a missing row stores is missing too: NaN -> 0
+                    rows = {'csc': lambda: a.indices, 'coo': lambda: a.row,
+                            'csr': lambda: np.repeat(np.arange(a.shape[0]), np.diff(a.indptr))}[a.format]()
+                    a.data[missing[rows] != 0] = 0
+                self._missing_rows = None
+                if np.issubdtype(a.data.dtype, np.floating):
+                    a.data[np.isnan(a.data)] = 0
+            else:
+                if resident is not None:                                       # both copies, the host one stays read-only
+                    resident.nan_to_zero()
+                    self.node2attribute.flags.writeable = True
+                if np.issubdtype(self.node2attribute.dtype, np.floating):      # (a uint8 / bool matrix has no missing values)
+                    self.node2attribute[np.isnan(self.node2attribute)] = 0     # in place, like safe.py:451
+                if resident is not None:
+                    self.node2attribute.flags.writeable = False
 
-        attr = resident if resident is not None else be.Attributes.from_host(self._ctx(), self.node2attribute)
+        attr = resident if resident is not None else self._upload_attributes()
         try:
             stats = attr.stats()
             if stats['max_nan_col'] / self.node2attribute.shape[0] > 0.5:
@@ -677,7 +731,7 @@ class SAFE:
 
         ctx = self._ctx()
         nbr = self._device_neighborhoods()
-        attr = _attr if _attr is not None else be.Attributes.from_host(ctx, self.node2attribute)
+        attr = _attr if _attr is not None else self._upload_attributes()
         n, m = attr.n, attr.m
         # random_seed=None (the default, like the reference's): the tables are generated on the device (backend.Permutations);
         # `device_stream_key` (None = OS entropy) makes such a run repeatable for tests and debugging
@@ -717,7 +771,7 @@ class SAFE:
             logging.info('Using the hypergeometric test to calculate enrichment...')
         ctx = self._ctx()
         nbr = self._device_neighborhoods()
-        attr = _attr if _attr is not None else be.Attributes.from_host(ctx, self.node2attribute)
+        attr = _attr if _attr is not None else self._upload_attributes()
         n, m = attr.n, attr.m
         bufs = [ctx.alloc_f64(n, m) for _ in range(3)] + [ctx.alloc_f64(m)]
         try:
@@ -1209,7 +1263,14 @@ class SAFE:
         from .safe_io import _legend
         with np.errstate(divide='ignore', invalid='ignore'):
             s_zero, s_min, s_max = 5, 5, 55
-            values = self.node2attribute[:, attribute]
+            if be._is_sparse(self.node2attribute):                            # one column of a sparse matrix, never the whole of it
+                a = self.node2attribute if self.node2attribute.format in ('csc', 'csr', 'lil', 'dok') else self.node2attribute.tocsc()
+                values = np.asarray(a[:, [int(attribute)]].toarray()).reshape(-1).astype(np.float64)
+                mis = self._missing_rows_for(self.node2attribute)
+                if mis is not None:
+                    values[mis != 0] = np.nan
+            else:
+                values = self.node2attribute[:, attribute]
             mag = np.abs(values)
             if set(np.unique(mag[~np.isnan(mag)])).issubset([0, 1]):          # binary attribute
                 s = np.zeros(len(mag))
