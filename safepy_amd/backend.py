@@ -262,7 +262,8 @@ class Context:
         w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
         if rp.shape[0] != n + 1 or cl.shape[0] != rp[-1] or (w is not None and w.shape[0] != cl.shape[0]):
             raise ValueError('layout_spring: CSR arrays do not match %d nodes' % n)
-        code = {np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.float64): _lib.DTYPE_F64}[np.dtype(dtype)]
+        # any other dtype goes to the library as a code it refuses (SafeHipError), like every other bad argument
+        code = {np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.float64): _lib.DTYPE_F64}.get(np.dtype(dtype), -1)
         out = np.empty((n, 2), dtype=np.float64)
         ran = C.c_int(0)
         check(lib.safe_layout_spring(self.handle, n, _ptr(rp), _ptr(cl) if cl.size else None,

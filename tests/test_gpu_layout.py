@@ -167,12 +167,26 @@ def test_layout_graph_and_iterations_run(golden):
 
 
 def test_live_networkx_cross_check():
+    """apply_network_layout against the installed networkx, rescale and f32 weight rounding included: two random geometric
+    graphs (120 and 600 nodes), a dense graph (140 nodes, half of all pairs: more neighbour entries per 16 x 128 block
+    than one round of the kernel's scatter) and one whose size is a whole number of 128-column chunks (512 nodes, f32
+    form), the last two with weights that are not f32 numbers.  networkx's f32 form takes 80 - 190 us per row per iteration
+    on the host: N = 600 costs this test 5 - 12 s of networkx time and N = 512 another 4 - 10 s."""
     nx = pytest.importorskip('networkx')
     from safepy_amd import safe_io
+    graphs = []
     for n, seed in ((120, 3), (600, 4)):
         G = nx.random_geometric_graph(n, 0.12, seed=seed)
         for u, v in list(G.edges())[::3]:
             G[u][v]['weight'] = 0.5 + (u % 7) / 4
+        graphs.append((n, seed, G))
+    for n, p, seed in ((140, 0.5, 5), (512, 0.05, 6)):
+        G = nx.gnp_random_graph(n, p, seed=seed)
+        for u, v in list(G.edges())[::3]:
+            G[u][v]['weight'] = 0.1 * (1 + (u + v) % 9)
+        assert any(float(np.float32(d['weight'])) != d['weight'] for _, _, d in G.edges(data=True) if 'weight' in d)
+        graphs.append((n, seed, G))
+    for n, seed, G in graphs:
         want = nx.spring_layout(G, k=0.2, iterations=100, seed=seed)
         H = G.copy()
         safe_io.apply_network_layout(H, layout='spring_embedded', seed=seed, verbose=False)
