@@ -351,7 +351,7 @@ int safe_attr_prepare(safe_attr *attr) {
     SAFE_REQUIRE(n_words * sizeof(unsigned int) <= 150 * 1024, "safe_attr_stats: too many rows for the LDS row bitmap");
     void *tmp = nullptr;
     const size_t tmp_bytes = 132 * sizeof(unsigned long long) + static_cast<size_t>(n_words + m) * sizeof(unsigned int);
-    SAFE_TRY(ctx_scratch(ctx, 11, tmp_bytes, &tmp));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_ATTR_STATS, tmp_bytes, &tmp));
     unsigned long long *d_acc = static_cast<unsigned long long *>(tmp);
     unsigned int *d_rowbits = reinterpret_cast<unsigned int *>(d_acc + 132);
     unsigned int *d_colnan = d_rowbits + n_words;
@@ -553,7 +553,7 @@ int safe_attr_create_host(safe_ctx *ctx, const void *b_host, int dtype, int64_t 
     hipError_t e = hipSuccess;
     if (u8) {
         void *staged = nullptr;                               // the bytes as they came (16-byte loads: padded)
-        rc = ctx_scratch(ctx, 20, (count + 15) / 16 * 16, &staged);
+        rc = ctx_scratch(ctx, SCRATCH_ATTR_STAGED, (count + 15) / 16 * 16, &staged);
         if (rc != SAFE_OK) {
             (void)hipFree(d);
             delete a;

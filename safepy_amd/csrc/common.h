@@ -84,6 +84,49 @@ struct DrawWorker {
 };
 void draw_worker_shutdown(safe_ctx *ctx);
 
+// The context's grow-only scratch buffers (ctx_scratch): one line per slot -- what lives there | who takes it | how long the
+// contents must survive.  A slot with several users holds one ROLE: those users never run at the same time, and sharing keeps a
+// single allocation of the largest size.  A new buffer gets a new enumerator in front of N_SCRATCH, not a free-looking old one.
+enum ScratchSlot {
+    SCRATCH_COUNTERS,       // packed u32 counters [mloc][n_pad] | every integer-counter route: launch_bits, launch_lds_f64 (enrich.hip),
+                            //   mfma_make_plan (mfma.hip) | until the next integer-counter call: ctx->packed_counts points here
+    SCRATCH_OPERANDS,       // the attribute operand: bit planes (uint2), f64 tiles, block-sparse i8 planes (d_bs) | launch_bits,
+                            //   launch_counts_bits, launch_lds_f64, hypergeom_fused (enrich.hip), counts_setup, mfma_prepare_columns
+                            //   (mfma.hip) | within the call
+    SCRATCH_F64_MATRIX,     // one f64 [n][mloc] matrix -- observed scores nobody asked for (launch_lds_f64, launch_mfma_run), the hits of
+                            //   safe_hypergeom's per-element form -- or hypergeom_fused's (p, -log10 p) table | within the call
+    SCRATCH_TASKS,          // task lists + queue offsets and counters | launch_bits (enrich.hip), counts_setup, mfma_make_plan (mfma.hip) |
+                            //   within the call
+    SCRATCH_STREAM_A,       // double buffer, even launches: permuted member ids (launch_bits), permuted source rows (mfma_make_plan);
+                            //   or counts_setup's one source-row list | within the call
+    SCRATCH_STREAM_B,       // ... odd launches; or the split count form's u16 counts (mfma_counts_split_begin) | within the call
+    SCRATCH_COLUMN_META,    // per-column side data: hypergeom_fused's distinct (n, K) values and ids (enrich.hip), mfma_prepare_columns'
+                            //   column statistics (mfma.hip) | within the call
+    SCRATCH_BITS_OBSERVED,  // observed sums of every (word group, slice) of the blocked bit-sliced kernel | launch_bits | within the call
+    SCRATCH_SPLIT_ROWS,     // row lists + tasks of the split count form's second half | mfma_counts_split_rows | within the call
+    SCRATCH_HYP_SMALL,      // neighborhood sizes f64 [n] | enriched counters u32 [mloc + 64] | safe_hypergeom | within the call
+    SCRATCH_ENRICHED,       // enriched counters u32 [m + 16] | safe_randomization, safe_outputs_from_counts | within the call
+    SCRATCH_ATTR_STATS,     // accumulators | row bitmap | column counts of the statistics sweep | safe_attr_prepare (attr.hip) | within the call
+    SCRATCH_MFMA_OBS64,     // filtered 'sum' form: exact fixed-point observed scores i64 [n_pad][mloc] | mfma_make_plan | within the call
+    SCRATCH_MFMA_AMB_A,     // double buffer, even launches: the filtered form's undecided compares | mfma_make_plan | within the call
+    SCRATCH_MFMA_AMB_B,     // ... odd launches
+    SCRATCH_MFMA_FILTER,    // source-row ids | per-launch counts of undecided compares | mfma_make_plan | within the call
+    SCRATCH_MFMA_Q64,       // filtered 'sum' form: the fixed-point values as i64 [n + 1][mloc] | mfma_prepare_columns | within the call
+    SCRATCH_MFMA_Z64,       // filtered z form: value | square + not-NaN flag [n + 1][mloc] | mfma_prepare_columns | within the call
+    SCRATCH_BITS_TAIL_IDS,  // permuted member ids of the column-chunked exchange tail | launch_bits | within the call
+    SCRATCH_NES_TABLE,      // the NES table f64 [P + 1] | ctx_nes_table alone, for safe_randomization and every safe_outputs_from_* entry
+                            //   point | ACROSS calls: the device copy of ctx->nes_tab_host, uploaded again only when the table changes
+    SCRATCH_ATTR_STAGED,    // the bytes of a u8 attribute matrix as they came | safe_attr_create_host (attr.hip) | within the call
+    SCRATCH_HYP_DUMMY,      // 64 write-only f64 for the padding rows / columns of branch-free epilogues (HypLookup::dummy) |
+                            //   hypergeom_fused | within the call
+    SCRATCH_FDR_FLAG,       // one u32 flag | safe_fdr_adjust's count-ratio check and fdr_matrix's histogram form (fdr.hip) | within the call
+    N_SCRATCH
+};
+static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,
+              "the two halves of a double buffer are adjacent slots (scratch_pair)");
+// half b (0 / 1) of the double buffer whose first slot is `first`
+static inline ScratchSlot scratch_pair(ScratchSlot first, int b) { return static_cast<ScratchSlot>(first + b); }
+
 struct safe_ctx {
     int device = 0;
     DrawWorker *draw_worker = nullptr, *draw_worker2 = nullptr;    // (the second one runs the twin chain: safe_perms::twin)
@@ -106,7 +149,7 @@ struct safe_ctx {
     // grow-only scratch buffers reused across calls (hipMalloc of >100 MB costs milliseconds)
     struct safe_perms *perm_cache = nullptr;    // buffers of the last destroyed permutation handle, reused by the next
     struct PermRing *ring = nullptr;            // node-shared permutation stream (safe_ctx_share_stream), or NULL
-    // packed <= / >= counters of the last integer-counter permutation kernel (scratch slot 0):
+    // packed <= / >= counters of the last integer-counter permutation kernel (SCRATCH_COUNTERS):
     // u32 [packed_m][packed_n_pad] = (#less << 16 | #greater); layout 0 = SELL positions,
     // 1 = block order of the MFMA kernel, -1 = none (safe_export_packed_counts)
     const unsigned int *packed_counts = nullptr;
@@ -124,7 +167,7 @@ struct safe_ctx {
     int64_t xc_bounds[XC_MAX + 1] = {};         // column boundaries of the chunks (this rank's columns: clipped to packed_m)
     int64_t xc_tail_perms = 0;                  // permutations the column-chunked launches covered
     hipEvent_t xc_events[XC_MAX] = {};          // chunk k's counters are final
-    std::vector<double> nes_tab_host;           // safe_outputs_from_packed_slabs: the table it uploaded last (no sync per call)
+    std::vector<double> nes_tab_host;           // ctx_nes_table: the table SCRATCH_NES_TABLE holds (empty: none)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     // large device-to-host copies into pageable memory (safe_memcpy_d2h): a ring of pinned slots the DMA engine fills while host
@@ -136,14 +179,21 @@ struct safe_ctx {
     hipEvent_t d2h_events[D2H_SLOTS] = {};
     std::vector<hipEvent_t> ev_timing, ev_plain;   // reused per-launch events (creating 20 per call costs ~0.1 ms)
     std::vector<std::pair<size_t, void *>> block_cache;   // small device blocks of destroyed handles (ctx_block_alloc)
-    static constexpr int N_SCRATCH = 21;
     void *scratch[N_SCRATCH] = {};
     size_t scratch_bytes[N_SCRATCH] = {};
 };
 
-// returns a device buffer of at least `bytes` from slot `slot`, valid until the next request
-// for the same slot; contents are undefined
-int ctx_scratch(safe_ctx *ctx, int slot, size_t bytes, void **out);
+// Returns a device buffer of at least `bytes` from slot `slot`; its contents are undefined.  The buffer is valid until the next
+// request for the same slot: a larger request frees it and allocates anew.  Before it frees, ctx_scratch synchronises the
+// context's two enrichment streams (ctx->stream, ctx->side_stream) and NO other: a caller that uses the buffer on any other
+// stream -- the aux stream, a stream of the application's -- must itself have synchronised that stream before it asks again.
+int ctx_scratch(safe_ctx *ctx, ScratchSlot slot, size_t bytes, void **out);
+// The NES look-up table tab[k] = -log10(k / P), k = 0 .. P (k = 0 as k = 1) -- `host_or_null` [P + 1], or computed here -- on the
+// device, for work on stream s (enrich.hip).  The table stays resident in SCRATCH_NES_TABLE: a call with the table of the call
+// before costs no upload and no synchronisation; another table synchronises s before the old one is released or overwritten
+// (whatever still reads it on s finishes first), is uploaded on s, and s is synchronised again (the source is host memory).
+// As with ctx_scratch, work that reads the table on yet another stream is the caller's to finish before the table changes.
+int ctx_nes_table(safe_ctx *ctx, const double *host_or_null, int64_t P, hipStream_t s, const double **d_tab);
 // grow-only pinned host buffer (device-to-host copies into it go through the DMA engines: no copy kernel
 // that would have to wait for a CU while a persistent kernel holds all of them)
 int ctx_pinned(safe_ctx *ctx, size_t bytes, void **out);

@@ -66,7 +66,7 @@ hipError_t safe_stream_sync(hipStream_t s) {
     return hipEventSynchronize(ev);
 }
 
-int ctx_scratch(safe_ctx *ctx, int slot, size_t bytes, void **out) {
+int ctx_scratch(safe_ctx *ctx, ScratchSlot slot, size_t bytes, void **out) {
     if (bytes == 0) bytes = 1;
     if (ctx->scratch_bytes[slot] < bytes) {
         if (ctx->scratch[slot]) {
@@ -285,7 +285,7 @@ int safe_ctx_destroy(safe_ctx *ctx) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_timing) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_plain) (void)hipEventDestroy(e);
-    for (int i = 0; i < safe_ctx::N_SCRATCH; ++i)
+    for (int i = 0; i < N_SCRATCH; ++i)
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     for (auto &b : ctx->block_cache) (void)hipFree(b.second);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);

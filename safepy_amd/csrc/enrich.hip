@@ -2663,7 +2663,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     const int64_t n_wgt = half ? 2 * n_wg : n_wg;        // column units of the tasks: word groups, or their halves
     safe_trace("launch_bits: enter");
     uint2 *d_bits = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
     launch_bits_prep(ctx, attr, col0, mloc, n_wg, d_bits);
     safe_trace("launch_bits: prep launched");
     // The permutations are consumed in launches of `span` permutations so that the host's draw
@@ -2748,12 +2748,12 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     unsigned int *d_gl = nullptr;
     {
         void *ws = nullptr;       // tasks + queue words in one scratch buffer
-        SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int4) + (8 * n_launch + 4) * sizeof(unsigned int), &ws));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, tasks.size() * sizeof(int4) + (8 * n_launch + 4) * sizeof(unsigned int), &ws));
         d_tasks = static_cast<int4 *>(ws);
         d_queue = reinterpret_cast<unsigned int *>(d_tasks + tasks.size());
     }
     const int64_t n_pad = nbr->n_slices * 64;
-    SAFE_TRY(ctx_scratch(ctx, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_gl)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_gl)));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_tasks, nbr->bits_plan_pinned, tasks.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_queue, 0, 8 * n_launch * sizeof(unsigned int), ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_gl, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), ctx->stream));
@@ -2766,10 +2766,10 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     constexpr int NS = 2;
     uint16_t *d_ids[NS] = {nullptr, nullptr};
     for (int b = 0; b < NS; ++b)
-        SAFE_TRY(ctx_scratch(ctx, 4 + b, static_cast<size_t>(span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids[b])));
+        SAFE_TRY(ctx_scratch(ctx, scratch_pair(SCRATCH_STREAM_A, b), static_cast<size_t>(span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids[b])));
     uint16_t *d_ids_tail = nullptr;                   // the tail's permuted member lists: built once, read by every column chunk's launch
     if (n_tail)
-        SAFE_TRY(ctx_scratch(ctx, 18, static_cast<size_t>(tail_span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids_tail)));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_TAIL_IDS, static_cast<size_t>(tail_span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids_tail)));
     hipStream_t kstreams[NS] = {ctx->stream, ctx->side_stream};
     const size_t lds_T = half ? bits_half_lds_bytes(n) : bits_pre_lds_bytes(n);     // the kernel's word column and queue slot
     // SAFE_HIP_BITS_DBG: variants of the blocked kernel.  32 / 128 / 256 / 384 / 512 / 640 give correct results (A/B: one-stage carry
@@ -2820,7 +2820,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     uint32_t *d_obs = nullptr;
     if (blk) {
         // observed sums of every (word group, slice), once: the compare operand of every task, and `ns`
-        SAFE_TRY(ctx_scratch(ctx, 7, static_cast<size_t>(n_wg) * nbr->n_slices * 2 * BT_LV * 64 * sizeof(uint32_t),
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_OBSERVED, static_cast<size_t>(n_wg) * nbr->n_slices * 2 * BT_LV * 64 * sizeof(uint32_t),
                              reinterpret_cast<void **>(&d_obs)));
         const size_t lds_obs = lds_T + (out.ns ? 4 * 64 * 66 * sizeof(uint16_t) : 0);            // + the waves' transposition tiles
         SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bits_observed), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2954,7 +2954,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
 static int launch_counts_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, int64_t col1, double *out_dev) {
     const int64_t n = nbr->n, mloc = col1 - col0, n_wg = ceil_div(mloc, 64);
     uint2 *d_bits = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
     launch_bits_prep(ctx, attr, col0, mloc, n_wg, d_bits);
     SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
     hipLaunchKernelGGL(k_counts_bits<false>, dim3(nbr->n_slices, n_wg), dim3(64), 0, ctx->stream, nbr->sell_row, nbr->slice_off,
@@ -2976,8 +2976,8 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     const int64_t n_tiles = z ? mloc : ceil_div(mloc, 4);
     PermOut out = out_in;
     double *d_tiles = nullptr, *d_ns = out.ns;
-    SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n_tiles) * (n + 1) * 4 * sizeof(double), reinterpret_cast<void **>(&d_tiles)));
-    if (!d_ns) SAFE_TRY(ctx_scratch(ctx, 2, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_ns)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_tiles) * (n + 1) * 4 * sizeof(double), reinterpret_cast<void **>(&d_tiles)));
+    if (!d_ns) SAFE_TRY(ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_ns)));
     {
         const dim3 grid(ceil_div(n_tiles * (n + 1), 256)), block(256);
         const bool f32 = attr->dtype == SAFE_DTYPE_F32;
@@ -3006,7 +3006,7 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     unsigned int *d_queue = nullptr, *d_counts = nullptr;
     SAFE_TRY(dev_alloc(&d_tasks, tasks.size()));
     SAFE_TRY(dev_alloc(&d_queue, n_launch));
-    SAFE_TRY(ctx_scratch(ctx, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_counts)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_counts)));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_queue, 0, n_launch * sizeof(unsigned int), ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_counts, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), ctx->stream));
@@ -3113,8 +3113,8 @@ static int hypergeom_fused(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_
 
     double2 *d_tab = nullptr;
     int32_t *d_ids = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 2, static_cast<size_t>(n_nid) * n_kid * xs * sizeof(double2), reinterpret_cast<void **>(&d_tab)));
-    SAFE_TRY(ctx_scratch(ctx, 6, static_cast<size_t>(n_nid + n_kid + n + mloc) * sizeof(int32_t), reinterpret_cast<void **>(&d_ids)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n_nid) * n_kid * xs * sizeof(double2), reinterpret_cast<void **>(&d_tab)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COLUMN_META, static_cast<size_t>(n_nid + n_kid + n + mloc) * sizeof(int32_t), reinterpret_cast<void **>(&d_ids)));
     int32_t *d_nvals = d_ids, *d_kvals = d_nvals + n_nid, *d_nid = d_kvals + n_kid, *d_kid = d_nid + n;
     // d_ids = [nvals | kvals | nid | kid]: one copy out of the pinned block
     memcpy(up, nvals.data(), n_nid * sizeof(int32_t));
@@ -3143,7 +3143,7 @@ static int hypergeom_fused(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_
     hl.n_kid = n_kid;
     hl.xs = xs;
     hl.p_cut = p_cut;
-    SAFE_TRY(ctx_scratch(ctx, 7, 64 * sizeof(double), reinterpret_cast<void **>(&hl.dummy)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_HYP_DUMMY, 64 * sizeof(double), reinterpret_cast<void **>(&hl.dummy)));
     hl.pvalues_pos = p_dev;
     hl.nes = nes_dev;
     hl.nes_binary = nb_dev;
@@ -3161,7 +3161,7 @@ static int hypergeom_fused(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_
         SAFE_TRY(launch_mfma_counts(ctx, nbr, attr, col0, col1, hl));   // records its own timing events
     } else {
         uint2 *d_bits = nullptr;                                       // bit-packed attributes: only the bit-sliced form reads them
-        SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
         launch_bits_prep(ctx, attr, col0, mloc, n_wg, d_bits);
         SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
         hipLaunchKernelGGL(k_counts_bits<true>, dim3(nbr->n_slices, n_wg), dim3(64), 0, ctx->stream, nbr->sell_row, nbr->slice_off,
@@ -3339,6 +3339,23 @@ static std::vector<double> nes_table(const double *host, int64_t P) {
     return tab;
 }
 
+int ctx_nes_table(safe_ctx *ctx, const double *host_or_null, int64_t P, hipStream_t s, const double **d_tab) {
+    std::vector<double> tab = nes_table(host_or_null, P);
+    if (ctx->nes_tab_host != tab) {                      // (a table that needs a larger buffer is a different table)
+        const size_t bytes = tab.size() * sizeof(double);
+        void *d = nullptr;
+        // an earlier call's kernel may still read the resident table on s, a stream ctx_scratch does not wait for
+        SAFE_HIP_CHECK(safe_stream_sync(s));
+        ctx->nes_tab_host.clear();                       // (nothing is resident until the upload below has succeeded)
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_NES_TABLE, bytes, &d));
+        SAFE_HIP_CHECK(hipMemcpyAsync(d, tab.data(), bytes, hipMemcpyHostToDevice, s));
+        SAFE_HIP_CHECK(safe_stream_sync(s));             // (tab is a host vector)
+        ctx->nes_tab_host = std::move(tab);
+    }
+    *d_tab = static_cast<const double *>(ctx->scratch[SCRATCH_NES_TABLE]);
+    return SAFE_OK;
+}
+
 // the p-value / NES outputs of PERM_FULL or PERM_SUBSET (NULL: not wanted) against the NES table d_tab on the device
 static PermOut perm_outputs(int mode, double *pvalues_neg, double *pvalues_pos, double *nes, double *nes_binary, const double *d_tab,
                             double enrichment_threshold, int sign_mode) {
@@ -3376,6 +3393,47 @@ static int packed_chunk_prepare(safe_ctx *ctx, int chunk, const uint32_t *dst_de
         SAFE_REQUIRE(ctx->xc_made == ctx->xc_want && ctx->xc_bounds[chunk] == *c0 && ctx->xc_bounds[chunk + 1] == *c1,
                      "%s: the call's chunks are not the armed ones", fn);
         SAFE_HIP_CHECK(hipStreamWaitEvent(*s, ctx->xc_events[chunk], 0));
+    }
+    return SAFE_OK;
+}
+
+// The packed epilogue: counters of `n_slabs` column slabs (u32 pairs, or 20-bit pairs where `narrow_ok` and the layout says so)
+// -> any subset of the output matrices, on stream `stream` (NULL: the context's), nothing synchronised once the NES table is
+// resident.  `fn`: the entry point's name for the messages.
+static int outputs_from_packed(const char *fn, bool narrow_ok, safe_ctx *ctx, safe_nbr *nbr, const uint32_t *slabs_dev, int layout,
+                               int64_t n_pad, int n_slabs, int64_t slab_stride, const int64_t *slab_cols, const int64_t *out_col0,
+                               int64_t m_total, int64_t num_permutations, int sign_mode, double enrichment_threshold,
+                               const double *nes_table_host, double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev,
+                               double *nes_binary_dev, void *stream) {
+    SAFE_REQUIRE(ctx && nbr && slabs_dev && slab_cols && out_col0 && n_slabs >= 1, "%s: NULL argument", fn);
+    SAFE_REQUIRE(pvalues_neg_dev || pvalues_pos_dev || nes_dev || nes_binary_dev, "%s: no output requested", fn);
+    const bool pk20 = narrow_ok && (layout & SAFE_PACKED_NARROW) != 0;   // slabs of 20-bit pairs (safe_export_packed_chunk_narrow)
+    if (narrow_ok) layout &= ~SAFE_PACKED_NARROW;
+    SAFE_REQUIRE(layout == 0 || layout == 1, "%s: bad layout %d", fn, layout);
+    SAFE_REQUIRE(!pk20 || num_permutations <= 1023, "%s: 20-bit pairs hold at most 1023 permutations", fn);
+    SAFE_REQUIRE(sign_mode >= SAFE_SIGN_HIGHEST && sign_mode <= SAFE_SIGN_BOTH, "%s: bad sign_mode %d", fn, sign_mode);
+    SAFE_REQUIRE(num_permutations >= 1 && num_permutations <= 65535 && m_total >= 1, "%s: bad sizes", fn);
+    SAFE_REQUIRE(enrichment_threshold > 0.0 || !nes_binary_dev, "%s: enrichment_threshold must be positive", fn);
+    const int32_t *rowmap = layout == 0 ? nbr->sell_row : nbr->bs_rowmap;
+    const int64_t want_pad = layout == 0 ? nbr->n_slices * 64 : nbr->bs_groups * 256;
+    SAFE_REQUIRE(rowmap && n_pad == want_pad, "%s: counters are for %lld positions, the membership has %lld", fn, (long long)n_pad,
+                 (long long)want_pad);
+    for (int r = 0; r < n_slabs; ++r)
+        SAFE_REQUIRE(slab_cols[r] >= 0 && slab_cols[r] * (pk20 ? n_pad / 8 * 5 : n_pad) <= slab_stride && out_col0[r] >= 0 && out_col0[r] + slab_cols[r] <= m_total,
+                     "%s: slab %d (%lld columns at column %lld) does not fit", fn, r, (long long)slab_cols[r], (long long)out_col0[r]);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int64_t P = num_permutations;
+    // the table stays on the device between calls (one call per column chunk of a step: no upload, no sync after the first)
+    const double *d_tab = nullptr;
+    SAFE_TRY(ctx_nes_table(ctx, nes_table_host, P, s, &d_tab));
+    for (int r = 0; r < n_slabs; ++r) {
+        if (slab_cols[r] == 0) continue;
+        const auto at = [&](double *p) { return p ? p + out_col0[r] : nullptr; };
+        PermOut out = perm_outputs(PERM_SUBSET, at(pvalues_neg_dev), at(pvalues_pos_dev), at(nes_dev), at(nes_binary_dev), d_tab,
+                                   enrichment_threshold, sign_mode);
+        out.ld = m_total;
+        SAFE_TRY(enrich_finalize_counts(ctx, slabs_dev + static_cast<int64_t>(r) * slab_stride, n_pad, rowmap, slab_cols[r], P, out, nullptr, s, pk20));
     }
     return SAFE_OK;
 }
@@ -3450,12 +3508,10 @@ int safe_randomization(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     const int64_t mloc = col1 - col0, P = perms->count;
     const RouteSwitches sw = route_switches();
     const PermRoute route = perm_route(sw, nbr, attr, P, perms, mloc, z);
-    const std::vector<double> tab = nes_table(nes_table_host, P);
-    void *small = nullptr;                           // NES table f64 [P + 1] | enriched counters u32 [mloc + 16] (grow-only scratch)
-    SAFE_TRY(ctx_scratch(ctx, 10, static_cast<size_t>(P + 1) * sizeof(double) + static_cast<size_t>(mloc + 16) * sizeof(unsigned int), &small));
-    double *d_tab = static_cast<double *>(small);
-    unsigned int *d_enr = reinterpret_cast<unsigned int *>(d_tab + P + 1);
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const double *d_tab = nullptr;
+    SAFE_TRY(ctx_nes_table(ctx, nes_table_host, P, ctx->stream, &d_tab));
+    unsigned int *d_enr = nullptr;                   // enriched counters u32 [mloc + 16]
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_ENRICHED, static_cast<size_t>(mloc + 16) * sizeof(unsigned int), reinterpret_cast<void **>(&d_enr)));
     SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, (mloc + 16) * sizeof(unsigned int), ctx->stream));
     PermOut out = perm_outputs(PERM_FULL, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
     out.ns = ns_dev;
@@ -3464,7 +3520,7 @@ int safe_randomization(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     hipLaunchKernelGGL(k_u32_to_f64, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, mloc);
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_TRY(finish_kernel_timing(ctx));
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));   // tab (host) + temporaries
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));   // temporaries; the call has finished when it returns
     return SAFE_OK;
 }
 
@@ -3485,7 +3541,7 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
     const CountsRoute route = counts_route(sw, nbr, attr);
     const bool bits = route.bits, table = bits && sw.hyper_table, use_mfma = route.mfma;
     void *small = nullptr;                                                  // d_size f64 [n] | d_enr u32 [mloc + 64]
-    int rc = ctx_scratch(ctx, 9, static_cast<size_t>(n) * sizeof(double) + static_cast<size_t>(mloc + 64) * sizeof(unsigned int), &small);
+    int rc = ctx_scratch(ctx, SCRATCH_HYP_SMALL, static_cast<size_t>(n) * sizeof(double) + static_cast<size_t>(mloc + 64) * sizeof(unsigned int), &small);
     if (rc == SAFE_OK) {
         d_size = static_cast<double *>(small);
         d_enr = reinterpret_cast<unsigned int *>(d_size + n);
@@ -3523,7 +3579,7 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
         std::vector<double> lf(n + 2);
         for (int64_t k = 0; k <= n + 1; ++k) lf[k] = std::lgamma(static_cast<double>(k) + 1.0);
         rc = dev_alloc(&d_lf, n + 2);
-        if (rc == SAFE_OK) rc = ctx_scratch(ctx, 2, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_hits));
+        if (rc == SAFE_OK) rc = ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_hits));
         if (rc == SAFE_OK && !bits) rc = build_tiles(ctx, attr, col0, col1, false, &tiles);
         if (rc == SAFE_OK && hipMemcpyAsync(d_lf, lf.data(), (n + 2) * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
             safe_set_error("safe_hypergeom: hipMemcpyAsync failed");
@@ -3576,12 +3632,10 @@ int safe_outputs_from_counts(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_pe
     SAFE_REQUIRE(enrichment_threshold > 0.0 && enrichment_threshold < 1.0, "safe_outputs_from_counts: enrichment_threshold must be in (0,1)");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     const int64_t P = num_permutations;
-    const std::vector<double> tab = nes_table(nes_table_host, P);
-    void *small = nullptr;                           // NES table f64 [P + 1] | enriched counters u32 [m + 16]
-    SAFE_TRY(ctx_scratch(ctx, 10, static_cast<size_t>(P + 1) * sizeof(double) + static_cast<size_t>(m + 16) * sizeof(unsigned int), &small));
-    double *d_tab = static_cast<double *>(small);
-    unsigned int *d_enr = reinterpret_cast<unsigned int *>(d_tab + P + 1);
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const double *d_tab = nullptr;
+    SAFE_TRY(ctx_nes_table(ctx, nes_table_host, P, ctx->stream, &d_tab));
+    unsigned int *d_enr = nullptr;                   // enriched counters u32 [m + 16] (d_enr[m]: a count was out of range)
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_ENRICHED, static_cast<size_t>(m + 16) * sizeof(unsigned int), reinterpret_cast<void **>(&d_enr)));
     SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, (m + 16) * sizeof(unsigned int), ctx->stream));
     PermOut out = perm_outputs(PERM_FULL, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
     out.enriched = d_enr;
@@ -3592,7 +3646,7 @@ int safe_outputs_from_counts(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_pe
     unsigned int *bad = nullptr;
     SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), reinterpret_cast<void **>(&bad)));
     SAFE_HIP_CHECK(hipMemcpyAsync(bad, d_enr + m, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));                 // tab is a host vector
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));                 // `bad` is read below; the call has finished when it returns
     if (*bad) {
         safe_set_error("safe_outputs_from_counts: a count lies outside [0, num_permutations = %lld] (or is NaN where the observed "
                        "score is not): the counts of a permutation-axis split must add up to ONE run of num_permutations",
@@ -3618,29 +3672,16 @@ int safe_export_packed_counts(safe_ctx *ctx, uint32_t *dst_dev, int64_t capacity
     return SAFE_OK;
 }
 
+// one slab of full counters at column 0, on the context's stream, finished when the call returns
 int safe_outputs_from_packed_counts(safe_ctx *ctx, safe_nbr *nbr, const uint32_t *counts_dev, int layout, int64_t n_pad, int64_t m,
                                     int64_t num_permutations, int sign_mode, double enrichment_threshold,
                                     const double *nes_table_host, double *pvalues_neg_dev, double *pvalues_pos_dev,
                                     double *nes_dev, double *nes_binary_dev) {
-    SAFE_REQUIRE(ctx && nbr && counts_dev, "safe_outputs_from_packed_counts: NULL argument");
-    SAFE_REQUIRE(pvalues_neg_dev || pvalues_pos_dev || nes_dev || nes_binary_dev, "safe_outputs_from_packed_counts: no output requested");
-    SAFE_REQUIRE(layout == 0 || layout == 1, "safe_outputs_from_packed_counts: bad layout %d", layout);
-    SAFE_REQUIRE(sign_mode >= SAFE_SIGN_HIGHEST && sign_mode <= SAFE_SIGN_BOTH, "safe_outputs_from_packed_counts: bad sign_mode %d", sign_mode);
-    SAFE_REQUIRE(num_permutations >= 1 && num_permutations <= 65535 && m >= 1, "safe_outputs_from_packed_counts: bad sizes");
-    SAFE_REQUIRE(enrichment_threshold > 0.0 || !nes_binary_dev, "safe_outputs_from_packed_counts: enrichment_threshold must be positive");
-    const int32_t *rowmap = layout == 0 ? nbr->sell_row : nbr->bs_rowmap;
-    const int64_t want_pad = layout == 0 ? nbr->n_slices * 64 : nbr->bs_groups * 256;
-    SAFE_REQUIRE(rowmap && n_pad == want_pad, "safe_outputs_from_packed_counts: counters are for %lld positions, the membership has %lld",
-                 (long long)n_pad, (long long)want_pad);
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t P = num_permutations;
-    const std::vector<double> tab = nes_table(nes_table_host, P);
-    double *d_tab = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 7, (P + 1) * sizeof(double), reinterpret_cast<void **>(&d_tab)));
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const PermOut out = perm_outputs(PERM_SUBSET, pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, d_tab, enrichment_threshold, sign_mode);
-    int rc = enrich_finalize_counts(ctx, counts_dev, n_pad, rowmap, m, P, out, nullptr);
-    if (rc == SAFE_OK && safe_stream_sync(ctx->stream) != hipSuccess) rc = SAFE_E_HIP;   // tab is a host vector
+    const int64_t slab_cols = m, out_col0 = 0;
+    int rc = outputs_from_packed("safe_outputs_from_packed_counts", false, ctx, nbr, counts_dev, layout, n_pad, 1, m * n_pad, &slab_cols,
+                                 &out_col0, m, num_permutations, sign_mode, enrichment_threshold, nes_table_host, pvalues_neg_dev,
+                                 pvalues_pos_dev, nes_dev, nes_binary_dev, nullptr);
+    if (rc == SAFE_OK && safe_stream_sync(ctx->stream) != hipSuccess) rc = SAFE_E_HIP;
     return rc;
 }
 
@@ -3715,45 +3756,9 @@ int safe_outputs_from_packed_slabs(safe_ctx *ctx, safe_nbr *nbr, const uint32_t 
                                    int64_t num_permutations, int sign_mode, double enrichment_threshold, const double *nes_table_host,
                                    double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev, double *nes_binary_dev,
                                    void *stream) {
-    SAFE_REQUIRE(ctx && nbr && slabs_dev && slab_cols && out_col0 && n_slabs >= 1, "safe_outputs_from_packed_slabs: NULL argument");
-    SAFE_REQUIRE(pvalues_neg_dev || pvalues_pos_dev || nes_dev || nes_binary_dev, "safe_outputs_from_packed_slabs: no output requested");
-    const bool pk20 = (layout & SAFE_PACKED_NARROW) != 0;   // slabs of 20-bit pairs (safe_export_packed_chunk_narrow)
-    layout &= ~SAFE_PACKED_NARROW;
-    SAFE_REQUIRE(layout == 0 || layout == 1, "safe_outputs_from_packed_slabs: bad layout %d", layout);
-    SAFE_REQUIRE(!pk20 || num_permutations <= 1023, "safe_outputs_from_packed_slabs: 20-bit pairs hold at most 1023 permutations");
-    SAFE_REQUIRE(sign_mode >= SAFE_SIGN_HIGHEST && sign_mode <= SAFE_SIGN_BOTH, "safe_outputs_from_packed_slabs: bad sign_mode %d", sign_mode);
-    SAFE_REQUIRE(num_permutations >= 1 && num_permutations <= 65535 && m_total >= 1, "safe_outputs_from_packed_slabs: bad sizes");
-    SAFE_REQUIRE(enrichment_threshold > 0.0 || !nes_binary_dev, "safe_outputs_from_packed_slabs: enrichment_threshold must be positive");
-    const int32_t *rowmap = layout == 0 ? nbr->sell_row : nbr->bs_rowmap;
-    const int64_t want_pad = layout == 0 ? nbr->n_slices * 64 : nbr->bs_groups * 256;
-    SAFE_REQUIRE(rowmap && n_pad == want_pad, "safe_outputs_from_packed_slabs: counters are for %lld positions, the membership has %lld",
-                 (long long)n_pad, (long long)want_pad);
-    for (int r = 0; r < n_slabs; ++r)
-        SAFE_REQUIRE(slab_cols[r] >= 0 && slab_cols[r] * (pk20 ? n_pad / 8 * 5 : n_pad) <= slab_stride && out_col0[r] >= 0 && out_col0[r] + slab_cols[r] <= m_total,
-                     "safe_outputs_from_packed_slabs: slab %d (%lld columns at column %lld) does not fit", r, (long long)slab_cols[r],
-                     (long long)out_col0[r]);
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    const int64_t P = num_permutations;
-    const std::vector<double> tab = nes_table(nes_table_host, P);
-    // the table stays on the device between calls (one call per column chunk of a step: no upload, no sync after the first)
-    double *d_tab = nullptr;
-    const bool grow = ctx->scratch_bytes[19] < (P + 1) * sizeof(double);
-    SAFE_TRY(ctx_scratch(ctx, 19, (P + 1) * sizeof(double), reinterpret_cast<void **>(&d_tab)));
-    if (grow || ctx->nes_tab_host != tab) {
-        SAFE_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), (P + 1) * sizeof(double), hipMemcpyHostToDevice, s));
-        SAFE_HIP_CHECK(safe_stream_sync(s));                                                  // (tab is a host vector)
-        ctx->nes_tab_host = tab;
-    }
-    for (int r = 0; r < n_slabs; ++r) {
-        if (slab_cols[r] == 0) continue;
-        const auto at = [&](double *p) { return p ? p + out_col0[r] : nullptr; };
-        PermOut out = perm_outputs(PERM_SUBSET, at(pvalues_neg_dev), at(pvalues_pos_dev), at(nes_dev), at(nes_binary_dev), d_tab,
-                                   enrichment_threshold, sign_mode);
-        out.ld = m_total;
-        SAFE_TRY(enrich_finalize_counts(ctx, slabs_dev + static_cast<int64_t>(r) * slab_stride, n_pad, rowmap, slab_cols[r], P, out, nullptr, s, pk20));
-    }
-    return SAFE_OK;
+    return outputs_from_packed("safe_outputs_from_packed_slabs", true, ctx, nbr, slabs_dev, layout, n_pad, n_slabs, slab_stride, slab_cols,
+                               out_col0, m_total, num_permutations, sign_mode, enrichment_threshold, nes_table_host, pvalues_neg_dev,
+                               pvalues_pos_dev, nes_dev, nes_binary_dev, stream);
 }
 
 int safe_randomization_plan(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t num_permutations, int score_type, int *packed_layout) {

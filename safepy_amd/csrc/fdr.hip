@@ -261,7 +261,7 @@ int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_per
     // randomization form: p-values are counts / n_perm -- no sort needed (k_fdr_row_counts); table + histogram must fit LDS
     if (n_perm > 0 && (n_perm + 1) * 12 <= 60 * 1024 && !sort_env) {
         unsigned int *d_flag = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, 10, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
         SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
         const size_t lds = static_cast<size_t>(n_perm + 1) * 12;
         SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_row_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -358,7 +358,7 @@ extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_
     int64_t hist_perm = 0;
     if (num_permutations > 0 && (num_permutations + 1) * 12 <= 60 * 1024 && !getenv("SAFE_HIP_FDR_SORT")) {
         unsigned int *d_flag = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, 10, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
         SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
         const int64_t total = n * m;
         for (const double *mat : {static_cast<const double *>(pvalues_neg_dev), static_cast<const double *>(pvalues_pos_dev)})

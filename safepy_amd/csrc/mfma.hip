@@ -2297,17 +2297,17 @@ int counts_setup(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, in
     cs->tasks = &nbr->counts_tasks;
     memcpy(cs->q_off, nbr->counts_qoff, sizeof(cs->q_off));
     void *ws = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + 16 * sizeof(unsigned int), &ws));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + 16 * sizeof(unsigned int), &ws));
     cs->d_tasks = static_cast<int2 *>(ws);
     cs->d_qoff = reinterpret_cast<int32_t *>(cs->d_tasks + tasks.size());
     cs->d_qctr = reinterpret_cast<unsigned int *>(cs->d_qoff + 16);
-    SAFE_TRY(ctx_scratch(ctx, 4, static_cast<size_t>(n_src) * sizeof(int32_t), reinterpret_cast<void **>(&cs->d_src)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_STREAM_A, static_cast<size_t>(n_src) * sizeof(int32_t), reinterpret_cast<void **>(&cs->d_src)));
     SAFE_HIP_CHECK(hipMemcpyAsync(cs->d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(cs->d_qoff, nbr->counts_qoff, sizeof(cs->q_off), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(cs->d_qctr, 0, 16 * sizeof(unsigned int), ctx->stream));
     hipLaunchKernelGGL(k_mfma_src, dim3(ceil_div(n_src, 256), 1), dim3(256), 0, ctx->stream, nbr->bs_order, n_src, n,
                        static_cast<const int32_t *>(nullptr), 0, cs->d_src);
-    SAFE_TRY(ctx_scratch(ctx, 1, static_cast<size_t>(n + 1) * row_bytes, reinterpret_cast<void **>(&cs->d_bs)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n + 1) * row_bytes, reinterpret_cast<void **>(&cs->d_bs)));
     if (attr->col_stride == 1) {                                          // C order: straight through
         const dim3 grid(ceil_div(row_bytes / 4, 256), ceil_div(n + 1, 8));
         const bool f32 = attr->dtype == SAFE_DTYPE_F32;
@@ -2395,7 +2395,7 @@ int mfma_counts_split_begin(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64
     *out = st;
     SAFE_TRY(counts_setup(ctx, nbr, attr, col0, col1, &st->cs));
     const int64_t n_padr = nbr->bs_groups * MF_R;
-    SAFE_TRY(ctx_scratch(ctx, 5, static_cast<size_t>(st->cs.n_grp) * n_padr * 32 * 3 * sizeof(unsigned int), reinterpret_cast<void **>(&st->cnt16)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_STREAM_B, static_cast<size_t>(st->cs.n_grp) * n_padr * 32 * 3 * sizeof(unsigned int), reinterpret_cast<void **>(&st->cnt16)));
     SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
     // The count kernel is persistent and takes a CU whole (256 VGPRs x 2 waves per SIMD): with one workgroup
     // per CU nothing else runs until it ends -- not even the copy kernels of the side stream.
@@ -2437,7 +2437,7 @@ int mfma_counts_split_rows(safe_ctx *ctx, safe_nbr *nbr, MfmaCountsSplit *st, co
     }
     std::stable_sort(st->tasks.begin(), st->tasks.end(), [](const int2 &a, const int2 &b) { return a.y - a.x > b.y - b.x; });
     void *ws = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 8, st->rows.size() * sizeof(int4) + st->tasks.size() * sizeof(int2), &ws));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_SPLIT_ROWS, st->rows.size() * sizeof(int4) + st->tasks.size() * sizeof(int2), &ws));
     st->d_rows = static_cast<int4 *>(ws);
     st->d_tasks = reinterpret_cast<int2 *>(st->d_rows + st->rows.size());
     const size_t bytes = st->rows.size() * sizeof(int4) + st->tasks.size() * sizeof(int2);
@@ -2792,12 +2792,12 @@ int mfma_prepare_columns(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *at
     const int64_t n = nbr->n, n_ct = ceil_div(mloc, z ? 16 : 32);
     const bool f32 = attr->dtype == SAFE_DTYPE_F32;
     const MfmaLayout lay = cols->lay = mfma_layout(z, want_filter, n, n_ct);
-    if (lay.split_off) SAFE_TRY(ctx_scratch(ctx, 16, static_cast<size_t>(n + 1) * mloc * sizeof(long long), reinterpret_cast<void **>(&cols->d_q64)));
-    if (lay.zf_hi_off) SAFE_TRY(ctx_scratch(ctx, 17, static_cast<size_t>(n + 1) * mloc * sizeof(longlong2), reinterpret_cast<void **>(&cols->d_z64)));
-    SAFE_TRY(ctx_scratch(ctx, 1, lay.bytes, reinterpret_cast<void **>(&cols->d_bs)));
+    if (lay.split_off) SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_Q64, static_cast<size_t>(n + 1) * mloc * sizeof(long long), reinterpret_cast<void **>(&cols->d_q64)));
+    if (lay.zf_hi_off) SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_Z64, static_cast<size_t>(n + 1) * mloc * sizeof(longlong2), reinterpret_cast<void **>(&cols->d_z64)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, lay.bytes, reinterpret_cast<void **>(&cols->d_bs)));
     void *d_colbuf = nullptr;                    // maxbits u64 | sumsq f64 | scale, scale2 f64 | cnt, small, rounded, neg_lowbit u32 | shift, shift2 i32 | bad, need i32
     const size_t colbuf_bytes = static_cast<size_t>(mloc) * (8 + 8 + 16 + 4 + 4 + 4 + 4 + 4 + 4 + 8) + 64;   // (+ zeros, inexact u32)
-    SAFE_TRY(ctx_scratch(ctx, 6, colbuf_bytes, &d_colbuf));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COLUMN_META, colbuf_bytes, &d_colbuf));
     unsigned long long *d_max = static_cast<unsigned long long *>(d_colbuf);
     double *d_sumsq = reinterpret_cast<double *>(d_max + mloc);
     double *d_scale = cols->d_scale = d_sumsq + mloc;
@@ -2885,25 +2885,25 @@ int mfma_make_plan(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const 
     plan->starts = perm_launch_starts(perms, &plan->span, 1, true);       // (amb_cap below is sized for the drawn stream's spans)
     const int64_t span = plan->span, n_launch = plan->n_launch = static_cast<int64_t>(plan->starts.size()) - 1;
     void *ws = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, 3, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + (8 * n_launch + 8 + 16) * sizeof(unsigned int), &ws));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, tasks.size() * sizeof(int2) + 16 * sizeof(int32_t) + (8 * n_launch + 8 + 16) * sizeof(unsigned int), &ws));
     plan->d_tasks = static_cast<int2 *>(ws);
     plan->d_qoff = reinterpret_cast<int32_t *>(plan->d_tasks + tasks.size());
     plan->d_qctr = reinterpret_cast<unsigned int *>(plan->d_qoff + 16);
-    SAFE_TRY(ctx_scratch(ctx, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&plan->d_counts)));
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&plan->d_counts)));
     for (int b = 0; b < 2; ++b)
-        SAFE_TRY(ctx_scratch(ctx, 4 + b, static_cast<size_t>(span + 1) * n_src * sizeof(int32_t), reinterpret_cast<void **>(&plan->d_src[b])));
+        SAFE_TRY(ctx_scratch(ctx, scratch_pair(SCRATCH_STREAM_A, b), static_cast<size_t>(span + 1) * n_src * sizeof(int32_t), reinterpret_cast<void **>(&plan->d_src[b])));
     SAFE_HIP_CHECK(hipMemcpyAsync(plan->d_tasks, tasks.data(), tasks.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(plan->d_qoff, q_off, sizeof(q_off), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(plan->d_qctr, 0, (8 * n_launch + 8 + 16) * sizeof(unsigned int), ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(plan->d_counts, 0, static_cast<size_t>(n_padr) * mloc * sizeof(unsigned int), ctx->stream));
     if (form.filtered()) {
-        if (!form.z) SAFE_TRY(ctx_scratch(ctx, 12, static_cast<size_t>(n_padr) * mloc * sizeof(long long), reinterpret_cast<void **>(&plan->d_obs64)));
+        if (!form.z) SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_OBS64, static_cast<size_t>(n_padr) * mloc * sizeof(long long), reinterpret_cast<void **>(&plan->d_obs64)));
         const double per_launch = static_cast<double>(n) * static_cast<double>(mloc) * static_cast<double>(span);
         plan->amb_cap = sw.filter_cap ? sw.filter_cap : static_cast<unsigned int>(std::min(67108864.0, std::max(1048576.0, per_launch / 512.0)));
         for (int b = 0; b < 2; ++b)
-            SAFE_TRY(ctx_scratch(ctx, 13 + b, static_cast<size_t>(plan->amb_cap) * sizeof(ulonglong2), reinterpret_cast<void **>(&plan->d_amb[b])));
+            SAFE_TRY(ctx_scratch(ctx, scratch_pair(SCRATCH_MFMA_AMB_A, b), static_cast<size_t>(plan->amb_cap) * sizeof(ulonglong2), reinterpret_cast<void **>(&plan->d_amb[b])));
         void *small = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, 15, static_cast<size_t>(n_src) * sizeof(int32_t) + static_cast<size_t>(n_launch) * sizeof(unsigned int), &small));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_FILTER, static_cast<size_t>(n_src) * sizeof(int32_t) + static_cast<size_t>(n_launch) * sizeof(unsigned int), &small));
         plan->d_src_id = static_cast<int32_t *>(small);
         plan->d_amb_cnt = reinterpret_cast<unsigned int *>(plan->d_src_id + n_src);
         SAFE_HIP_CHECK(hipMemsetAsync(plan->d_amb_cnt, 0, static_cast<size_t>(n_launch) * sizeof(unsigned int), ctx->stream));
@@ -3113,7 +3113,7 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
     ctx->last_core_slices = form.core_slices;
     ctx->last_undecided = 0;
     // z-scores: the counters compare against the observed score itself, which may be NaN (k_counts_finalize<true> reads it)
-    if (z && !out.ns) SAFE_TRY(ctx_scratch(ctx, 2, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&out.ns)));
+    if (z && !out.ns) SAFE_TRY(ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&out.ns)));
     ctx->last_kernel.name = "k_permtest_mfma";
     ctx->last_kernel.total_ms = 0.0;
     ctx->last_kernel.busy_ms = 0.0;

@@ -480,6 +480,92 @@ def test_refusals_leave_the_outputs_alone(world):
     _check(w.results(m), want['both', 0.05], m, ('nes',), 'nes after the refusals')
 
 
+def _want_from_table(less, greater, P, sign, thr, table):
+    """outputs_from_pairs with the NES looked up in `table` (the nes_table_host of a call) instead of evaluated: what the
+    consumers do with a table that is not -log10(k / P)."""
+    want = dict(cr.outputs_from_pairs(less, greater, P, sign, thr))
+    ep, en = table[P - less], table[P - greater]
+    want['nes'] = {'highest': ep, 'lowest': en, 'both': ep - en}[sign]
+    want['nes_binary'] = (np.abs(want['nes']) > -np.log10(thr)).astype(np.float64)
+    return want
+
+
+def test_the_nes_table_follows_the_call_across_entry_points(world, monkeypatch):
+    """One context keeps ONE NES table on the device for all its entry points and uploads it only when a call names another.
+    Six calls in a row, each with another permutation count or table than the call before it -- slabs P = 37, packed counts
+    P = 1000, f64 counts P = 37, a real safe_randomization P = 1000, slabs P = 37 again, slabs P = 37 with a table that
+    differs in one entry -- each bit-equal to the reference for ITS count and table: the table of the call before never
+    shows through.  70 columns: more than one 64-column word group; the membership spans more than one 64-row slice."""
+    w, be, ctx = world, world.be, world.ctx
+    layout, sign, thr, m = 0, 'both', 0.05, 70
+    n_pad, pos = w.maps[layout]
+    assert n_pad > 64 and m > 64
+    tables = {P: cr.nes_table(P) for P in (37, 1000)}
+    design = {}
+    for P in (37, 1000):
+        less, greater = cr.designed_matrix(P, N, m, pos & 1, np.random.default_rng(50 + P))
+        design[P] = (less, greater, cr.outputs_from_pairs(less, greater, P, sign, thr))
+        lookup = _want_from_table(less, greater, P, sign, thr, tables[P])     # (the look-up restatement is the evaluated one)
+        for k in cr.NAMES:
+            np.testing.assert_array_equal(lookup[k], design[P][2][k], err_msg='table look-up, P=%d %s' % (P, k))
+    one_slab = (n_pad, m * n_pad, (m,), (0,), m)
+
+    def slabs(P, table, want, what):
+        less, greater, _ = design[P]
+        w.slab.upload(cr.slab_u32(less, greater, pos, n_pad))
+        w.prefill(m)
+        assert w.packed_slabs(layout, *one_slab, P, sign, thr, cr.NAMES, table) == 0, what
+        _check(w.results(m), want, m, cr.NAMES, what)
+
+    # 1. slabs, P = 37
+    slabs(37, tables[37], design[37][2], '1: slabs P=37')
+    # 2. packed counts, P = 1000
+    less, greater, want = design[1000]
+    w.slab.upload(cr.slab_u32(less, greater, pos, n_pad))
+    w.prefill(m)
+    assert w.packed_counts(layout, n_pad, m, 1000, sign, thr, cr.NAMES, tables[1000]) == 0
+    _check(w.results(m), want, m, cr.NAMES, '2: packed counts P=1000')
+    # 3. f64 counts, P = 37 (no NaN scores: the same four matrices, and the column sums of nes_binary)
+    less, greater, want = design[37]
+    d = [ctx.alloc_f64(N, m) for _ in range(3)] + [ctx.alloc_f64(m)]
+    try:
+        for x, host in zip(d, ((37 - greater).astype(np.float64), (37 - less).astype(np.float64), np.zeros((N, m)))):
+            x.upload(host)
+        d[3].upload(np.full(m, SENTINEL))
+        w.prefill(m)
+        rc = w.lib.safe_outputs_from_counts(ctx.handle, N, m, 37, w.sign[sign], thr, w.table_ptr(tables[37]),
+                                            *[C.c_void_p(x.ptr) for x in d[:3]], *w.ptrs(cr.NAMES), C.c_void_p(d[3].ptr))
+        assert rc == 0
+        _check(w.results(m), want, m, cr.NAMES, '3: f64 counts P=37')
+        np.testing.assert_array_equal(d[3].download((m,)), want['nes_binary'].sum(axis=0), err_msg='3: num_enriched')
+    finally:
+        for x in d:
+            x.free()
+    # 4. a real safe_randomization on the bit-sliced kernel, P = 1000: its matrices against the counters it leaves
+    for var in SWITCHES:
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv('SAFE_HIP_FORCE_PATH', 'bits')
+    ns, pn, pp, nes, nb, ne = _randomization(be, ctx, w.nbr, _data('binary', 40, 5), 1000, 3, sign, thr)
+    left, left_pad, left_layout = _exported(be, ctx)
+    assert (left_layout, left_pad) == (layout, n_pad) and not np.isnan(ns).any()
+    less, greater = (left[:, pos] >> 16).T.astype(np.int64), (left[:, pos] & 0xFFFF).T.astype(np.int64)
+    assert (less + greater <= 1000).all() and (less + greater).max() > 37          # (counts a table of 38 entries cannot serve)
+    want = cr.outputs_from_pairs(less, greater, 1000, sign, thr)
+    for k, got in zip(cr.NAMES, (pn, pp, nes, nb)):
+        np.testing.assert_array_equal(got, want[k], err_msg='4: randomization P=1000 %s' % k)
+    np.testing.assert_array_equal(ne, want['nes_binary'].sum(axis=0), err_msg='4: num_enriched')
+    # 5. slabs again, P = 37
+    slabs(37, tables[37], design[37][2], '5: slabs P=37 after P=1000')
+    # 6. ... and once more with a table of the same length that differs in ONE entry, one the counters use
+    less, greater, want5 = design[37]
+    other = tables[37].copy()
+    other[37] = 0.25                                                           # (count 37 of 37: the pair (0, 0) is designed in)
+    assert ((37 - less) == 37).any() and (other != tables[37]).sum() == 1
+    want6 = _want_from_table(less, greater, 37, sign, thr, other)
+    assert not np.array_equal(want6['nes'], want5['nes'])
+    slabs(37, other, want6, '6: slabs P=37, another table')
+
+
 # ---- f64 counts (k_counts_to_outputs) ---------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('P', P_COUNTS)

@@ -60,14 +60,14 @@ THRESHOLD = 0.05
 
 # entry point -> why it returns only after the context's stream has drained (safepy_amd/csrc, file:line of the wait)
 SYNCHRONISES = {
-    'safe_score': 'enrich.hip:3208 finish_kernel_timing reads the dominant kernel\'s event pair (hipEventSynchronize)',
-    'safe_permtest_counts': 'enrich.hip:3208 finish_kernel_timing; the launchers also wait for their host task lists (enrich.hip:2436, 2944, 3043)',
-    'safe_randomization': 'enrich.hip:3465 the NES table is a host vector of the call',
-    'safe_hypergeom': 'enrich.hip:3556 host id vectors and temporaries of the call (and enrich.hip:3079, 3172, 3549)',
+    'safe_score': 'enrich.hip:3210 finish_kernel_timing reads the dominant kernel\'s event pair (hipEventSynchronize)',
+    'safe_permtest_counts': 'enrich.hip:3210 finish_kernel_timing; the launchers also wait for their host task lists (enrich.hip:2436, 2946, 3045)',
+    'safe_randomization': 'enrich.hip:3523 temporaries of the call; its callers rely on the call having finished when it returns',
+    'safe_hypergeom': 'enrich.hip:3614 host id vectors and temporaries of the call (and enrich.hip:3174, 3607)',
     'safe_fdr_adjust': 'fdr.hip:371 reads back the count-ratio flag; fdr.hip:384 frees the enriched counters',
-    'safe_outputs_from_counts': 'enrich.hip:3593 reads back the out-of-range flag (SAFE_E_VALUE)',
-    'safe_outputs_from_packed_counts': 'enrich.hip:3641 the NES table is a host vector of the call',
-    'safe_nes_from_packed_counts': 'enrich.hip:3641 (it is safe_outputs_from_packed_counts with one output)',
+    'safe_outputs_from_counts': 'enrich.hip:3649 reads back the out-of-range flag (SAFE_E_VALUE)',
+    'safe_outputs_from_packed_counts': 'enrich.hip:3684 the slab epilogue followed by a wait: the call has finished when it returns',
+    'safe_nes_from_packed_counts': 'enrich.hip:3684 (it is safe_outputs_from_packed_counts with one output)',
     'safe_attr_nan_to_zero': 'attr.hip:592 frees the support lists derived from the old values',
 }
 
@@ -888,3 +888,82 @@ def test_call_on_one_stream_read_on_the_contexts_own(lab):
     PENDING['stream switch s1 -> own: euclidean_dense_dev, memcpy_d2h'] = (('safe_euclidean_dense_dev', 'safe_ctx_set_stream'), pending)
     assert pending, 'safe_euclidean_dense_dev returned only after the caller\'s stream had drained'
     assert np.array_equal(bits(got), bits(orc.euclidean_distances(xy)))
+
+
+# ------------------------------------------------------------------------------------------------------- case 6 ----
+
+def test_nes_table_grows_behind_a_call_still_queued_on_the_callers_stream(lab, switches):
+    """safe_outputs_from_packed_slabs on a stream the caller passes in while the context stays on its own: the call at
+    P = 37 finds its table resident and returns at once, its kernel queued behind the delay; the call straight after it at
+    P = 65535 needs a table 1700 times as large, so the context's table buffer is released and allocated anew.  The first
+    call's kernel must have read the old table before that happens: both calls' outputs equal the reference bit for bit.
+    (The wait for growth of a scratch buffer covers the context's streams only; the caller's stream is the table helper's to
+    wait for.)  A context of the test's own: in the shared one an earlier module may have left a table buffer that is
+    large enough already.  The counters are those a real run of NPERM = 20 permutations leaves (both fields <= 20, valid
+    for either count); the reference is tests/counter_ref.py on the oracle's counts of that run."""
+    import counter_ref as cr
+    torch, be = lab.torch, lab.be
+    _, a, b64, n, m = lab.kind('bin')
+    ref = perm_reference(lab, 'bin', 'float64', a, b64, 'sum', False)
+    assert not (np.isnan(ref['counts_pos']).any() or np.isnan(ref['counts_neg']).any())
+    less, greater = (NPERM - ref['counts_pos']).astype(np.int64), (NPERM - ref['counts_neg']).astype(np.int64)
+    counts = (37, 65535)
+    want = {P: cr.outputs_from_pairs(less, greater, P, 'both', THRESHOLD) for P in counts}
+    tables = {P: cr.nes_table(P) for P in counts}
+    ctx = be.Context(0)
+    nbr = be.Neighborhoods.from_dense(ctx, a.astype(np.int64))
+    attr = be.Attributes.from_host(ctx, b64)
+    perms = be.Permutations(ctx, n, (~np.isnan(b64)).any(axis=1).astype(np.uint8), NPERM, SEED)
+    s = lab.s
+    try:
+        scratch = [torch.empty((n, m), dtype=torch.float64, device='cuda') for _ in range(5)] + [torch.empty((m,), dtype=torch.float64, device='cuda')]
+        be.randomization(ctx, nbr, attr, perms, 'sum', 'both', THRESHOLD, [t.data_ptr() for t in scratch])
+        n_pad, m_loc, layout = be.packed_counts_info(ctx)
+        assert (layout, m_loc) == (0, m)
+        staging = torch.empty(m * n_pad, dtype=torch.int32, device='cuda')
+        be.export_packed_counts(ctx, staging.data_ptr(), m * n_pad)
+        ctx.sync()
+        slab = torch.empty_like(staging)
+        outs = {P: [torch.empty((n, m), dtype=torch.float64, device='cuda') for _ in range(4)] for P in counts}
+        snaps = {P: [torch.empty_like(o) for o in outs[P]] for P in counts}
+
+        def call(P):
+            be.outputs_from_packed_slabs(ctx, nbr, slab.data_ptr(), layout, n_pad, m * n_pad, [m], [0], m, P, 'both', THRESHOLD,
+                                         [o.data_ptr() for o in outs[P]], table=tables[P], stream=s.cuda_stream)
+
+        slab.copy_(staging)
+        torch.cuda.synchronize()
+        call(37)                                       # the quiet way first: the table of P = 37 is resident from here on
+        s.synchronize()
+        for k, o in zip(cr.NAMES, outs[37]):
+            same(numpy_of(o), want[37][k], 'quiet P=37 ' + k)
+        with torch.cuda.stream(s):
+            for P in counts:
+                for o in outs[P]:
+                    poison(o)
+            poison(slab)
+        delay_done = lab.delay(s, 1.0)
+        with torch.cuda.stream(s):
+            slab.copy_(staging)
+        assert not delay_done.query(), 'the harness drained the busy stream before the calls'
+        call(37)
+        pending = not delay_done.query()
+        call(65535)                                    # the table buffer grows here
+        with torch.cuda.stream(s):
+            for P in counts:
+                for snap, o in zip(snaps[P], outs[P]):
+                    snap.copy_(o)
+                for o in outs[P]:
+                    poison(o)
+            poison(slab)
+        s.synchronize()
+    finally:
+        torch.cuda.synchronize()
+        perms.close()
+        attr.close()
+        nbr.close()
+    PENDING['outputs_from_packed_slabs P=37 then P=65535 (table grows)'] = (('safe_outputs_from_packed_slabs',), pending)
+    assert pending, 'safe_outputs_from_packed_slabs with its table resident returned only after the caller\'s stream had drained'
+    for P in counts:
+        for k, snap in zip(cr.NAMES, snaps[P]):
+            same(numpy_of(snap), want[P][k], 'busy P=%d %s' % (P, k))
