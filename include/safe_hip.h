@@ -71,6 +71,7 @@ typedef struct safe_nbr safe_nbr;       /* neighborhood membership, device resid
 typedef struct safe_attr safe_attr;     /* node x attribute matrix, device resident     */
 typedef struct safe_perms safe_perms;   /* composed row-permutation tables, device res. */
 typedef struct safe_comm safe_comm;     /* RCCL communicator of the attribute-sharded path */
+typedef struct safe_kk safe_kk;         /* Kamada-Kawai cost function of one distance matrix, device res. */
 typedef struct PermRing safe_ring;      /* node-shared permutation stream (shared memory)    */
 
 /* ------------------------------------------------------------------ context ---- */
@@ -183,6 +184,31 @@ int safe_edge_lengths(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t n
 int safe_layout_spring(safe_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const double *weight,
                        int dtype, const double *pos0_f64, double k, int iterations, double threshold,
                        double *pos_out, int *iterations_run);
+
+/* Kamada-Kawai layout: the nx.kamada_kawai_layout(G) of apply_network_layout (safepy/safe_io.py:288-308; networkx 3.4.2
+ * kamada_kawai_layout -> _kamada_kawai_solve -> _kamada_kawai_costfn, dim = 2).  A handle holds what _kamada_kawai_solve
+ * prepares once -- invdist = 1 / (dist_mtx + eye * 1e-3) and its transpose, 16 n^2 bytes of device memory -- and
+ * safe_kk_eval is _kamada_kawai_costfn: cost and gradient at a position vector, every operation rounded as NumPy rounds
+ * it and every sum taken in NumPy's order (each node's two einsum sums over the other nodes in node order; np.sum(offset**2)
+ * in 8192-element buffers, each summed pairwise), so both equal networkx's bit for bit, NaN entries for coincident nodes
+ * included (their payloads are not specified).  The minimiser stays the caller's (scipy.optimize.minimize, L-BFGS-B).
+ *
+ * safe_kk_create_host (safe_io.py:288-308; kamada_kawai_layout's dist_mtx): dist_host f64 [n, n] row-major,
+ *   dist[i][j] = preferred distance from node i to node j, read as given ([i][j] and [j][i] are two values); +inf counts
+ *   as networkx's 1e6 for an unreached node.
+ * safe_kk_create_nbr (safe_io.py:288-308; kamada_kawai_layout's dict(nx.shortest_path_length(G, weight=weight))): the
+ *   distances a safe_nbr_shortpath handle of the same context kept (keep_distances != 0; cutoff = +inf for all pairs),
+ *   read on the device -- no n^2 transfer.  SAFE_E_INVALID if the handle kept none.  The membership handle may be destroyed
+ *   afterwards.
+ * Both: a NaN or negative distance is SAFE_E_VALUE, n > SAFE_KK_MAX_NODES is SAFE_E_UNSUPPORTED (64 GiB of matrices at the
+ *   limit), n >= 1.  Enqueued on the context's stream; synchronise.
+ * safe_kk_eval (safe_io.py:288-308; _kamada_kawai_costfn): pos_host f64 [n, 2] row-major in, *cost and grad_host f64 [n, 2]
+ *   out.  Synchronous on the context's stream.  No atomics: repeated calls give identical bits. */
+#define SAFE_KK_MAX_NODES 65536
+int safe_kk_create_host(safe_ctx *ctx, const double *dist_host, int64_t n, safe_kk **out);
+int safe_kk_create_nbr(safe_ctx *ctx, safe_nbr *nbr, safe_kk **out);
+int safe_kk_eval(safe_kk *kk, const double *pos_host, double *cost, double *grad_host);
+int safe_kk_destroy(safe_kk *kk);
 
 /* --------------------------------------------------------------- attributes ---- */
 /* self.node2attribute (safepy/safe_io.py:410): [n,m], f32 or f64, NaN = missing, with

@@ -15,6 +15,7 @@ DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
+KK_MAX_NODES = 65536                # SAFE_KK_MAX_NODES: nodes safe_kk_create_host / safe_kk_create_nbr take
 LINKAGE_MAX_POINTS = 16384          # SAFE_LINKAGE_MAX_POINTS: points safe_linkage_average / safe_profile_linkage take
 # metric ids of safe_profile_distances (SAFE_METRIC_*), by SciPy's metric name
 METRIC_IDS = {'jaccard': 0, 'hamming': 1, 'dice': 2, 'rogerstanimoto': 3, 'russellrao': 4, 'sokalmichener': 5, 'sokalsneath': 6,
@@ -106,6 +107,10 @@ PROTOTYPES = {
     'safe_edge_lengths': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'safe_layout_spring': (C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, C.c_double, _vp,
                                      C.POINTER(C.c_int)]),
+    'safe_kk_create_host': (C.c_int, [_vp, _vp, _i64, _pp]),
+    'safe_kk_create_nbr': (C.c_int, [_vp, _vp, _pp]),
+    'safe_kk_eval': (C.c_int, [_vp, _vp, C.POINTER(C.c_double), _vp]),
+    'safe_kk_destroy': (C.c_int, [_vp]),
     'safe_attr_create_host': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _i64, _pp]),
     'safe_attr_create_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _i64, _pp]),
     'safe_attr_create_csc_host': (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _pp]),

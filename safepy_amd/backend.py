@@ -539,6 +539,60 @@ class Neighborhoods:
             pass
 
 
+class KamadaKawai:
+    """networkx's Kamada-Kawai cost function for one matrix of preferred distances, device resident (safe_kk_*): what
+    _kamada_kawai_solve prepares once -- 1 / (dist_mtx + eye * 1e-3) and its transpose, 16 n^2 bytes -- behind
+    `evaluate`, the _kamada_kawai_costfn a minimiser calls."""
+
+    MAX_NODES = _lib.KK_MAX_NODES
+
+    def __init__(self, ctx, handle, n):
+        self.ctx = ctx
+        self.handle = handle
+        self.n = int(n)
+        self.evaluations = 0
+
+    @classmethod
+    def from_distances(cls, ctx, dist):
+        """dist: [n, n] f64, dist[i][j] = preferred distance from node i to node j (inf counts as networkx's 1e6)."""
+        d = np.ascontiguousarray(dist, dtype=np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1] or d.shape[0] < 1:
+            raise ValueError('the distance matrix must be square, got shape %s' % (d.shape,))
+        h = C.c_void_p()
+        check(lib.safe_kk_create_host(ctx.handle, _ptr(d), d.shape[0], C.byref(h)))
+        return cls(ctx, h, d.shape[0])
+
+    @classmethod
+    def from_neighborhoods(cls, ctx, nbr):
+        """From the all-pairs distances a Neighborhoods.shortpath(..., cutoff=inf, keep_distances=True) handle kept: they stay
+        on the device."""
+        h = C.c_void_p()
+        check(lib.safe_kk_create_nbr(ctx.handle, nbr.handle, C.byref(h)))
+        return cls(ctx, h, nbr.n)
+
+    def evaluate(self, pos):
+        """(cost, gradient [2n]) at the positions pos ([n, 2] or flat [2n]), as _kamada_kawai_costfn returns them."""
+        x = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
+        if x.shape[0] != 2 * self.n:
+            raise ValueError('evaluate: expected %d coordinates, got %d' % (2 * self.n, x.shape[0]))
+        grad = np.empty(2 * self.n, dtype=np.float64)
+        cost = C.c_double()
+        check(lib.safe_kk_eval(self.handle, _ptr(x), C.byref(cost), _ptr(grad)))
+        self.evaluations += 1
+        return np.float64(cost.value), grad
+
+    def close(self):
+        if self.handle:
+            check(lib.safe_kk_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _is_sparse(a):
     """scipy.sparse.issparse without importing SciPy for callers that never touch it."""
     import sys

@@ -348,8 +348,8 @@ class SAFE:
         """safepy/safe.py:244-324 for in-memory graphs (`graph=` / `network_file=` a networkx.Graph
         with node attributes x, y -- and edge attribute 'length' for the default metric -- or a
         `LayoutGraph`), `.gpickle` files, edge lists (`.txt` / `.tsv`, optionally `.gz`: parsed, laid
-        out with the spring-embedded layout on the device from self.random_seed, edge lengths added;
-        safe.py:289-293, safe_io.py:30-121) and `.scatter` files (with their Euclidean pseudo-network,
+        out with the spring-embedded layout on the device from self.random_seed -- or, additive, with `layout='kamada_kawai'`
+        passed here -- edge lengths added; safe.py:289-293, safe_io.py:30-121) and `.scatter` files (with their Euclidean pseudo-network,
         safe.py:296-309, built on the device).  The MATLAB and Cytoscape loaders (safe_io.py:124-268)
         are out of scope.  Sets self.graph, self.graph_euclidean (for .scatter) and self.nodes
         (safe.py:311-324)."""
@@ -382,7 +382,8 @@ class SAFE:
             if ext == '.gpickle':
                 graph = safe_io.load_network_from_gpickle(path, verbose=self.verbose)
             elif ext in ('.txt', '.tsv'):
-                graph = safe_io.load_network_from_txt(path, node_key_attribute=self.node_key_attribute,
+                graph = safe_io.load_network_from_txt(path, layout=kwargs.get('layout', 'spring_embedded'),
+                                                      node_key_attribute=self.node_key_attribute,
                                                       seed=self.random_seed, verbose=self.verbose, device=self.device)
             elif ext == '.scatter':
                 graph = safe_io.load_network_from_scatter(path, node_key_attribute=self.node_key_attribute,

@@ -11,6 +11,11 @@ Host-side mirror of the pieces of `safepy/safe_io.py` that feed `define_neighbor
   apply_network_layout        safe_io.py:288-308   'spring_embedded': networkx 3.4.2's spring_layout(k=0.2,
                                                    iterations=100) on the device (layout.hip), coordinates equal
                                                    to networkx's bit for bit
+  kamada_kawai_layout         safe_io.py:288-308   the other layout, nx.kamada_kawai_layout: all-pairs distances and
+                                                   the cost function + gradient on the device (kk.hip), SciPy's
+                                                   L-BFGS-B on the host as in networkx; coordinates equal to
+                                                   networkx's bit for bit.  load_network_from_txt(layout=
+                                                   'kamada_kawai') uses it
   euclidean_pseudo_network    safe.py:302-309      the `.scatter` pseudo-network: all-pairs distance +
                                                    threshold kernel, edges read back from the device CSR
   read_attributes             safe_io.py:336-430   parse with pandas like the reference; the alignment to
@@ -28,8 +33,7 @@ not load it):
   get_node_coordinates        safe_io.py:649-691   both branches (labels=[] and the label lookup)
 
 The plot methods of SAFE put their data-parallel parts on the device (plot.hip: domain density grids, domain counts,
-column reads of the device-resident results).  The Kamada-Kawai layout and the Cytoscape / MATLAB loaders stay out of
-scope.
+column reads of the device-resident results).  The Cytoscape / MATLAB loaders stay out of scope.
 There is no CPU fallback: every function that computes needs a HIP device.
 """
 import logging
@@ -238,13 +242,13 @@ def _random_state(seed):
     raise ValueError('%r cannot be used to create a numpy.random.RandomState instance' % (seed,))
 
 
-def _rescale_layout(pos):
-    """networkx rescale_layout(pos, scale=1) (drawing/layout.py), in the array's dtype, then `+ center`."""
+def _rescale_layout(pos, scale=1, center=None):
+    """networkx rescale_layout(pos, scale=scale) (drawing/layout.py), in the array's dtype, then `+ center`."""
     pos -= pos.mean(axis=0)
     lim = np.abs(pos).max()
     if lim > 0:
-        pos *= 1 / lim
-    return pos + np.zeros(2)
+        pos *= scale / lim
+    return pos + (np.zeros(2) if center is None else center)
 
 
 def _spring_layout(n, row_ptr, col, weight, seed, device):
@@ -262,15 +266,88 @@ def _spring_layout(n, row_ptr, col, weight, seed, device):
     return _rescale_layout(np.ascontiguousarray(pos))
 
 
+def kamada_kawai_layout(G, dist=None, pos=None, weight='weight', scale=1, center=None, device=0):
+    """nx.kamada_kawai_layout(G, dist, pos, weight, scale, center) for dim = 2 (the layout safepy/safe_io.py:288-308 applies by
+    default), coordinates equal to networkx 3.4.2's bit for bit: the cost function and its gradient are evaluated on
+    the device (kk.hip) in NumPy's rounding and summation order, and SciPy's L-BFGS-B drives them from the host exactly as
+    _kamada_kawai_solve does.
+
+    G: an undirected networkx graph -- returns {node: position} like networkx -- or a `LayoutGraph` -- sets its `.xy` and
+    returns it.  dist: None = all-pairs shortest path lengths over edge attribute `weight` (missing = 1; None = every edge
+    1; a LayoutGraph: its `.weight`), computed and kept on the device; or networkx's two-level dict {node: {node: distance}}
+    (missing pairs count as 1e6).  pos: None = nx.circular_layout, or {node: (x, y)}.  No nodes: {}."""
+    import networkx as nx
+    import scipy.optimize
+    from .safe import LayoutGraph
+    center = np.zeros(2) if center is None else np.asarray(center)
+    if len(center) != 2:
+        raise ValueError('length of center coordinates must match dimension of layout')
+    is_layout = isinstance(G, LayoutGraph)
+    if not is_layout and (G.is_directed() or G.is_multigraph()):
+        raise NotImplementedError('kamada_kawai_layout: directed graphs and multigraphs are not supported')
+    nodes = list(range(G.number_of_nodes())) if is_layout else list(G)
+    n = len(nodes)
+    if n == 0:
+        if is_layout:
+            G.xy = np.zeros((0, 2))
+            return G
+        return {}
+    if n > be.KamadaKawai.MAX_NODES:
+        raise be._lib.SafeHipError(be._lib.E_UNSUPPORTED, 'kamada_kawai_layout: %d nodes exceed the limit of %d'
+                              % (n, be.KamadaKawai.MAX_NODES))
+    ctx = be.Context.default(device)
+    if dist is None:
+        if is_layout:
+            eu, ev = G.edge_u, G.edge_v
+            ew = None if weight is None or G.weight is None else G.weight
+        else:
+            index = {node: i for i, node in enumerate(nodes)}
+            edges = list(G.edges(data=True))
+            eu = np.fromiter((index[e[0]] for e in edges), dtype=np.int64, count=len(edges))
+            ev = np.fromiter((index[e[1]] for e in edges), dtype=np.int64, count=len(edges))
+            ew = None
+            if weight is not None and any(weight in e[2] for e in edges):
+                ew = np.array([e[2].get(weight, 1) for e in edges], dtype=np.float64)
+        nbr = be.Neighborhoods.shortpath(ctx, n, eu, ev, ew, np.inf, keep_distances=True)
+        try:
+            kk = be.KamadaKawai.from_neighborhoods(ctx, nbr)
+        finally:
+            nbr.close()
+    else:
+        dist_mtx = 1e6 * np.ones((n, n))
+        for row, nr in enumerate(nodes):
+            if nr not in dist:
+                continue
+            rdist = dist[nr]
+            for col, nc in enumerate(nodes):
+                if nc in rdist:
+                    dist_mtx[row][col] = rdist[nc]
+        kk = be.KamadaKawai.from_distances(ctx, dist_mtx)
+    try:
+        if pos is None:
+            pos = nx.circular_layout(nodes)
+        pos_arr = np.array([pos[node] for node in nodes], dtype=np.float64)
+        result = scipy.optimize.minimize(kk.evaluate, pos_arr.ravel(), method='L-BFGS-B', jac=True)
+    finally:
+        kk.close()
+    xy = _rescale_layout(result.x.reshape((-1, 2)), scale=scale, center=center)
+    if is_layout:
+        G.xy = np.ascontiguousarray(xy)
+        return G
+    return dict(zip(nodes, xy))
+
+
 def apply_network_layout(G, layout='kamada_kawai', seed=None, verbose=True, device=0):
     """safepy/safe_io.py:288-308.  'spring_embedded' runs nx.spring_layout(G, k=0.2, iterations=100,
     seed=seed) on the device: the adjacency is the graph's, in node order, with edge attribute 'weight'
     (default 1); the initial positions are drawn with NumPy from `seed` (None = the global stream, an int,
     or a RandomState).  Sets node attributes 'x' / 'y' (a `LayoutGraph`: its `.xy`) and returns G.
-    'kamada_kawai' is not implemented (no path of SAFE reaches it)."""
+    'kamada_kawai' still raises here: the layout itself is `kamada_kawai_layout` (which load_network_from_txt calls for
+    layout='kamada_kawai'); routing this function's own default to it is left to a later change."""
     from .safe import LayoutGraph
     if layout == 'kamada_kawai':
-        raise NotImplementedError("the Kamada-Kawai layout is not implemented; use layout='spring_embedded'")
+        raise NotImplementedError("apply_network_layout does not run the Kamada-Kawai layout; call "
+                                  "safe_io.kamada_kawai_layout(G), or use layout='spring_embedded'")
     if layout != 'spring_embedded':
         raise ValueError("unknown layout %r (supported: 'spring_embedded')" % (layout,))
     if verbose:
@@ -344,8 +421,8 @@ def load_network_from_txt(filename, layout='spring_embedded', node_key_attribute
                           device=0):
     """safepy/safe_io.py:30-121: a tab-separated edge list -> networkx graph with nodes 0..N-1 numbered in order
     of first appearance, node attributes 'label' and `node_key_attribute`, unweighted edges (the file's weight
-    column is read but not attached, as in the reference), the layout (apply_network_layout: spring-embedded
-    on the device) and edge 'length' (calculate_edge_lengths)."""
+    column is read but not attached, as in the reference), the layout ('spring_embedded': apply_network_layout;
+    'kamada_kawai': kamada_kawai_layout; both on the device) and edge 'length' (calculate_edge_lengths)."""
     import networkx as nx
     data, nodes = _read_edge_list(filename)
     G = nx.Graph()
@@ -354,7 +431,13 @@ def load_network_from_txt(filename, layout='spring_embedded', node_key_attribute
     nx.set_node_attributes(G, dict(zip(range(n), nodes['node_label1'].to_numpy())), 'label')
     nx.set_node_attributes(G, dict(zip(range(n), nodes['node_key1'].to_numpy())), node_key_attribute)
     G.add_edges_from(zip(data['node_index1'].tolist(), data['node_index2'].tolist()))
-    G = apply_network_layout(G, layout=layout, seed=seed, verbose=verbose, device=device)
+    if layout == 'kamada_kawai':
+        if verbose:
+            logging.info('Applying the Kamada-Kawai network layout...')
+        for node, xy in kamada_kawai_layout(G, device=device).items():
+            G.nodes[node]['x'], G.nodes[node]['y'] = xy[0], xy[1]
+    else:
+        G = apply_network_layout(G, layout=layout, seed=seed, verbose=verbose, device=device)
     return calculate_edge_lengths(G, verbose=verbose, device=device)
 
 
