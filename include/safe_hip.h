@@ -560,6 +560,12 @@ int safe_last_mfma_filter(safe_ctx *ctx, int *core_slices, int64_t *undecided);
  * Buffers are cached per context and per handle shape, so a repeated call of the same shape is expected to add none
  * (the reference allocates every [N, M] temporary anew on each pass: safe_extras.py:50-66). */
 int safe_alloc_count(int64_t *calls);
+/* Diagnostics: the device blocks the library holds in this process right now -- every hipMalloc it has made whose hipFree it has
+ * not (safe_dev_alloc / safe_dev_free included; pinned host memory is not counted).  A call that returns no handle leaves the
+ * count as it found it once the context's scratch and pooled blocks have grown to the call's shape; creating and destroying a
+ * handle does too.  Unlike hipMemGetInfo the count sees nothing of other processes on the device.  safe_dev_free counts down
+ * for whatever pointer it is given: handing it memory that did not come from safe_dev_alloc skews the count. */
+int safe_live_alloc_count(int64_t *blocks);
 /* Host placement of the seeded stream's sequential part (np.random.seed / np.random.permutation, safepy/safe_extras.py:46,58):
  * the CPUs the library's draw threads may run on (count = 0: wherever the process may).  For LAUNCHERS that place their own
  * threads (bench.py, run_batch): keeping the draw thread off the hardware threads that share a core with the launcher's

@@ -950,6 +950,14 @@ def device_alloc_count():
     return v.value
 
 
+def device_live_alloc_count():
+    """Device blocks the library holds in this process right now (safe_live_alloc_count): the same before and after a call
+    that returns no handle, once the context's scratch has grown to the call's shape."""
+    v = C.c_int64()
+    check(lib.safe_live_alloc_count(C.byref(v)))
+    return v.value
+
+
 def last_mfma_slices(ctx):
     """i8 slices the last matrix-core permutation test ran with (2 / 4 / 6; 0 = it has not run)."""
     v = C.c_int()

@@ -296,9 +296,9 @@ __global__ __launch_bounds__(256) void k_nan_to_zero(T *__restrict__ raw, int64_
 // the support lists go back where they came from: the context's pool (installed from a CSC input) or the driver
 static void attr_free_support(safe_attr *attr) {
     if (attr->sup_ptr_pool_bytes) ctx_block_free(attr->ctx, attr->sup_ptr, attr->sup_ptr_pool_bytes);
-    else (void)hipFree(attr->sup_ptr);
+    else (void)dev_free(attr->sup_ptr);
     if (attr->sup_row_pool_bytes) ctx_block_free(attr->ctx, attr->sup_row, attr->sup_row_pool_bytes);
-    else (void)hipFree(attr->sup_row);
+    else (void)dev_free(attr->sup_row);
     attr->sup_ptr = nullptr;
     attr->sup_row = nullptr;
     attr->sup_ptr_pool_bytes = attr->sup_row_pool_bytes = 0;
@@ -539,45 +539,30 @@ int safe_attr_create_host(safe_ctx *ctx, const void *b_host, int dtype, int64_t 
                           int64_t col_stride, safe_attr **out) {
     SAFE_REQUIRE(b_host != nullptr, "safe_attr_create_host: b_host is NULL");
     const bool u8 = dtype == SAFE_DTYPE_U8;                 // (a 0/1 matrix as bytes: a quarter of the f32 upload; f32 from here on)
-    safe_attr *a = nullptr;
-    SAFE_TRY(attr_new(ctx, u8 ? SAFE_DTYPE_F32 : dtype, n, m, row_stride, col_stride, &a));
+    const char *fn = "safe_attr_create_host";
+    safe_attr *made = nullptr;
+    SAFE_TRY(attr_new(ctx, u8 ? SAFE_DTYPE_F32 : dtype, n, m, row_stride, col_stride, &made));
+    std::unique_ptr<safe_attr> a(made);                       // (owns nothing on the device until the matrix is complete)
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t count = static_cast<size_t>(n) * m;
     const size_t bytes = count * (dtype == SAFE_DTYPE_F64 ? 8 : 4);
+    CallBufs b;
     uint8_t *d = nullptr;
-    int rc = dev_alloc(&d, bytes);
-    if (rc != SAFE_OK) {
-        delete a;
-        return rc;
-    }
-    hipError_t e = hipSuccess;
+    SAFE_TRY(b.alloc(&d, bytes));
     if (u8) {
         void *staged = nullptr;                               // the bytes as they came (16-byte loads: padded)
-        rc = ctx_scratch(ctx, SCRATCH_ATTR_STAGED, (count + 15) / 16 * 16, &staged);
-        if (rc != SAFE_OK) {
-            (void)hipFree(d);
-            delete a;
-            return rc;
-        }
-        e = hipMemcpyAsync(staged, b_host, count, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_u8_to_f32, dim3(static_cast<unsigned int>(ceil_div(static_cast<int64_t>(count), 256 * 16))), dim3(256), 0, ctx->stream,
-                               static_cast<const uint8_t *>(staged), static_cast<int64_t>(count), reinterpret_cast<float *>(d));
-            e = hipGetLastError();
-        }
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_ATTR_STAGED, (count + 15) / 16 * 16, &staged));
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(staged, b_host, count, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_u8_to_f32, dim3(static_cast<unsigned int>(ceil_div(static_cast<int64_t>(count), 256 * 16))), dim3(256), 0, ctx->stream,
+                           static_cast<const uint8_t *>(staged), static_cast<int64_t>(count), reinterpret_cast<float *>(d));
+        SAFE_HIP_CHECK_AS(fn, hipGetLastError());
     } else {
-        e = hipMemcpyAsync(d, b_host, bytes, hipMemcpyHostToDevice, ctx->stream);
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d, b_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-    if (e != hipSuccess) {
-        safe_set_error("safe_attr_create_host: %s", hipGetErrorString(e));
-        (void)hipFree(d);
-        delete a;
-        return SAFE_E_HIP;
-    }
-    a->raw = d;
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
+    a->raw = b.release(d);
     a->owns_raw = true;
-    *out = a;
+    *out = a.release();
     return SAFE_OK;
 }
 
@@ -738,42 +723,30 @@ int safe_attr_reindex(safe_ctx *ctx, const void *table_host, int dtype, int64_t 
     const size_t in_bytes = static_cast<size_t>(n_labels) * m * esz, out_bytes = static_cast<size_t>(n) * m * esz;
     uint8_t *d_in = nullptr, *d_out = nullptr;
     int64_t *d_map = nullptr;
-    SAFE_TRY(dev_alloc(&d_in, in_bytes));
-    int rc = dev_alloc(&d_out, out_bytes);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_map, n);
+    const char *fn = "safe_attr_reindex";
+    CallBufs b;
+    SAFE_TRY(b.alloc(&d_in, in_bytes));
+    SAFE_TRY(b.alloc(&d_out, out_bytes));
+    SAFE_TRY(b.alloc(&d_map, n));
     const int64_t ors = out_order == 0 ? m : 1, ocs = out_order == 0 ? 1 : n;
-    safe_attr *a = nullptr;
-    if (rc == SAFE_OK) rc = attr_new(ctx, dtype, n, m, ors, ocs, &a);
-    hipError_t e = hipSuccess;
-    if (rc == SAFE_OK) {
-        e = hipMemcpyAsync(d_in, table_host, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_map, row_map_host, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            const dim3 grid(static_cast<unsigned>(ceil_div(m, 64)), static_cast<unsigned>(ceil_div(n, 64)));
-            if (dtype == SAFE_DTYPE_F32)
-                hipLaunchKernelGGL(k_reindex_rows<float>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const float *>(d_in),
-                                   n_labels, m, row_stride, col_stride, d_map, reinterpret_cast<float *>(d_out), n, ors, ocs,
-                                   static_cast<float>(fill_value));
-            else
-                hipLaunchKernelGGL(k_reindex_rows<double>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const double *>(d_in),
-                                   n_labels, m, row_stride, col_stride, d_map, reinterpret_cast<double *>(d_out), n, ors, ocs,
-                                   fill_value);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && out_host) e = hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_map);
-    if (rc != SAFE_OK || e != hipSuccess) {
-        if (e != hipSuccess) safe_set_error("safe_attr_reindex: %s", hipGetErrorString(e));
-        (void)hipFree(d_out);
-        delete a;
-        return rc != SAFE_OK ? rc : SAFE_E_HIP;
-    }
-    a->raw = d_out;
+    safe_attr *made = nullptr;
+    SAFE_TRY(attr_new(ctx, dtype, n, m, ors, ocs, &made));
+    std::unique_ptr<safe_attr> a(made);                       // (owns nothing on the device until the matrix is complete)
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_in, table_host, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_map, row_map_host, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grid(static_cast<unsigned>(ceil_div(m, 64)), static_cast<unsigned>(ceil_div(n, 64)));
+    if (dtype == SAFE_DTYPE_F32)
+        hipLaunchKernelGGL(k_reindex_rows<float>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const float *>(d_in), n_labels, m,
+                           row_stride, col_stride, d_map, reinterpret_cast<float *>(d_out), n, ors, ocs, static_cast<float>(fill_value));
+    else
+        hipLaunchKernelGGL(k_reindex_rows<double>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const double *>(d_in), n_labels, m,
+                           row_stride, col_stride, d_map, reinterpret_cast<double *>(d_out), n, ors, ocs, fill_value);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    if (out_host) SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
+    a->raw = b.release(d_out);
     a->owns_raw = true;
-    *out = a;
+    *out = a.release();
     return SAFE_OK;
 }
 
@@ -781,8 +754,9 @@ int safe_attr_value_counts(safe_attr *attr, int64_t *n_nan, int64_t *n_zero, int
     SAFE_REQUIRE(attr != nullptr, "safe_attr_value_counts: attr is NULL");
     safe_ctx *ctx = attr->ctx;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    CallBufs b;
     unsigned long long *d_acc = nullptr, h_acc[4];
-    SAFE_TRY(dev_alloc(&d_acc, 4));
+    SAFE_TRY(b.alloc(&d_acc, 4));
     SAFE_HIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(h_acc), ctx->stream));
     const int64_t count = attr->n * attr->m;
     const unsigned blocks = static_cast<unsigned>(std::min<int64_t>(ceil_div(count, 256), 8192));
@@ -793,7 +767,6 @@ int safe_attr_value_counts(safe_attr *attr, int64_t *n_nan, int64_t *n_zero, int
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(hipMemcpyAsync(h_acc, d_acc, sizeof(h_acc), hipMemcpyDeviceToHost, ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    (void)hipFree(d_acc);
     if (n_nan) *n_nan = static_cast<int64_t>(h_acc[0]);
     if (n_zero) *n_zero = static_cast<int64_t>(h_acc[1]);
     if (n_positive) *n_positive = static_cast<int64_t>(h_acc[2]);
@@ -836,7 +809,7 @@ int safe_attr_destroy(safe_attr *attr) {
     (void)hipSetDevice(attr->ctx->device);
     (void)safe_stream_sync(attr->ctx->stream);
     if (attr->owns_raw && attr->raw_pool_bytes) ctx_block_free(attr->ctx, const_cast<void *>(attr->raw), attr->raw_pool_bytes);
-    else if (attr->owns_raw) (void)hipFree(const_cast<void *>(attr->raw));
+    else if (attr->owns_raw) (void)dev_free(attr->raw);
     ctx_block_free(attr->ctx, attr->row_flags, flags_block_bytes(attr->n));
     ctx_block_free(attr->ctx, attr->col_sum, static_cast<size_t>(attr->m) * sizeof(double));
     attr_free_support(attr);

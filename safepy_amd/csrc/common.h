@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <atomic>
 #include <string>
@@ -206,22 +207,114 @@ int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch);   
 int ctx_block_alloc(safe_ctx *ctx, size_t bytes, void **out);
 void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes);
 
-// RAII-less device buffer helper: all frees go through the owning handle's destroy.
+// as SAFE_HIP_CHECK, with the message "<who>: <hip error string>" of the entry points that name themselves
+#define SAFE_HIP_CHECK_AS(who, expr)                                                           \
+    do {                                                                                       \
+        hipError_t _e = (expr);                                                                \
+        if (_e != hipSuccess) {                                                                \
+            safe_set_error("%s: %s", who, hipGetErrorString(_e));                              \
+            return SAFE_E_HIP;                                                                 \
+        }                                                                                      \
+    } while (0)
+
+// Device memory of the library: every block comes from dev_alloc and goes back through dev_free.  Who owns a block:
+//   * the context: its scratch slots (ctx_scratch) and pooled small blocks (ctx_block_alloc), until safe_ctx_destroy;
+//   * a handle (safe_nbr, safe_attr, safe_perms, safe_kk): its members, plain pointers, until the handle's destroy;
+//   * a call: a CallBufs (below) on the stack of the entry point, until it returns -- on whatever path.
 // calls of hipMalloc / hipHostMalloc made by the library so far (safe_alloc_count): a timed step is expected to make none
 extern std::atomic<long long> g_alloc_calls;
+// device blocks from dev_alloc that dev_free has not seen yet (safe_live_alloc_count): the same before and after any call
+// that returns no handle
+extern std::atomic<long long> g_live_blocks;
+
+static inline int dev_alloc_bytes(void **p, size_t bytes) {
+    *p = nullptr;
+    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        safe_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return SAFE_E_NOMEM;
+    }
+    g_live_blocks.fetch_add(1, std::memory_order_relaxed);
+    return SAFE_OK;
+}
 
 template <typename T>
 static inline int dev_alloc(T **p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-    if (e != hipSuccess) {
-        safe_set_error("hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return SAFE_E_NOMEM;
-    }
-    return SAFE_OK;
+    return dev_alloc_bytes(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T));
 }
+
+// NULL is fine.  hipFree waits until the device is idle: work that still uses the block has ended before it is released.
+static inline hipError_t dev_free(const void *p) {
+    if (!p) return hipSuccess;
+    g_live_blocks.fetch_sub(1, std::memory_order_relaxed);
+    return hipFree(const_cast<void *>(p));
+}
+
+// The device buffers of one call, released when the call returns on any path.  The destructor may run while work of the call
+// is still enqueued (an early return behind a launch): dev_free waits for the device, so the kernels and copies that use the
+// buffers have ended before they go.  Host memory has no such wait -- declare a CallBufs AFTER every host std::vector an
+// asynchronous copy of the call reads, so that it is destroyed (and the device idle) before the vector is.
+struct CallBufs {
+    std::vector<void *> p;
+    CallBufs() = default;
+    CallBufs(const CallBufs &) = delete;
+    CallBufs &operator=(const CallBufs &) = delete;
+    ~CallBufs() {
+        for (void *q : p) (void)dev_free(q);
+    }
+    template <typename T>
+    int alloc(T **q, size_t count) {
+        const int rc = dev_alloc(q, count);
+        if (rc == SAFE_OK) p.push_back(*q);
+        return rc;
+    }
+    // the block now belongs to a handle: it stays when the call ends
+    template <typename T>
+    T *release(T *q) {
+        p.erase(std::remove(p.begin(), p.end(), static_cast<void *>(q)), p.end());
+        return q;
+    }
+};
+
+// Kernel time of a call between two events on a stream; the events are destroyed on every return path.
+struct CallTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    CallTimer() = default;
+    CallTimer(const CallTimer &) = delete;
+    CallTimer &operator=(const CallTimer &) = delete;
+    ~CallTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t start(hipStream_t s) {
+        for (hipEvent_t &e : ev) {
+            const hipError_t err = hipEventCreateWithFlags(&e, safe_event_flags(hipEventDefault));
+            if (err != hipSuccess) return err;
+        }
+        return hipEventRecord(ev[0], s);
+    }
+    hipError_t stop(hipStream_t s) { return hipEventRecord(ev[1], s); }
+    // after the stream has been synchronised
+    hipError_t ms(double *out) {
+        float f = 0;
+        const hipError_t err = hipEventElapsedTime(&f, ev[0], ev[1]);
+        *out = f;
+        return err;
+    }
+    // ... the time also recorded as the context's last kernel
+    hipError_t finish(safe_ctx *ctx, const char *name, int64_t launches, double *kernel_ms) {
+        double t = 0;
+        const hipError_t err = ms(&t);
+        if (err != hipSuccess) return err;
+        ctx->last_kernel.name = name;
+        ctx->last_kernel.total_ms = ctx->last_kernel.busy_ms = t;
+        ctx->last_kernel.launches = launches;
+        ctx->last_kernel.summed = true;
+        if (kernel_ms) *kernel_ms = t;
+        return hipSuccess;
+    }
+};
 
 struct BitsQueues {
     int off[9];                                                           // tasks [off[q], off[q+1]) belong to queue q

@@ -38,7 +38,7 @@ void safe_set_error(const char *fmt, ...) {
 // blocking waits switched on (safe_set_blocking_sync / SAFE_HIP_BLOCKING_SYNC=1: several ranks sharing few host cores) the
 // thread sleeps on an interrupt-backed event instead -- a few tens of microseconds later, no CPU meanwhile.
 static std::atomic<int> g_blocking_sync{-1};
-std::atomic<long long> g_alloc_calls{0};
+std::atomic<long long> g_alloc_calls{0}, g_live_blocks{0};
 
 static bool blocking_sync_on() {
     int v = g_blocking_sync.load(std::memory_order_relaxed);
@@ -72,17 +72,12 @@ int ctx_scratch(safe_ctx *ctx, ScratchSlot slot, size_t bytes, void **out) {
         if (ctx->scratch[slot]) {
             SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
             SAFE_HIP_CHECK(safe_stream_sync(ctx->side_stream));
-            SAFE_HIP_CHECK(hipFree(ctx->scratch[slot]));
+            SAFE_HIP_CHECK(dev_free(ctx->scratch[slot]));
             ctx->scratch[slot] = nullptr;
             ctx->scratch_bytes[slot] = 0;
         }
         const size_t want = bytes + bytes / 8;
-        g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-        hipError_t e = hipMalloc(&ctx->scratch[slot], want);
-        if (e != hipSuccess) {
-            safe_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-            return SAFE_E_NOMEM;
-        }
+        SAFE_TRY(dev_alloc_bytes(&ctx->scratch[slot], want));
         ctx->scratch_bytes[slot] = want;
     }
     *out = ctx->scratch[slot];
@@ -99,13 +94,7 @@ int ctx_block_alloc(safe_ctx *ctx, size_t bytes, void **out) {
             ctx->block_cache.erase(ctx->block_cache.begin() + static_cast<std::ptrdiff_t>(i));
             return SAFE_OK;
         }
-    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-    hipError_t e = hipMalloc(out, want);
-    if (e != hipSuccess) {
-        safe_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-        return SAFE_E_NOMEM;
-    }
-    return SAFE_OK;
+    return dev_alloc_bytes(out, want);
 }
 
 // the caller has synchronised every stream that may still touch the block
@@ -113,11 +102,11 @@ void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes) {
     if (!p) return;
     const size_t have = block_class(bytes);
     if (have > (8u << 20)) {
-        (void)hipFree(p);
+        (void)dev_free(p);
         return;
     }
     if (ctx->block_cache.size() >= 32) {                   // full: the block that has waited longest makes room (the shapes in use stay)
-        (void)hipFree(ctx->block_cache.front().second);
+        (void)dev_free(ctx->block_cache.front().second);
         ctx->block_cache.erase(ctx->block_cache.begin());
     }
     ctx->block_cache.emplace_back(have, p);
@@ -195,8 +184,9 @@ static void ctx_open_copy_queue(safe_ctx *ctx) {
     const int n_streams = 4;
     const size_t bytes = size_t(8) << 20;
     void *host = nullptr, *dev = nullptr;
-    if (hipHostMalloc(&host, 2 * n_streams * bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&dev, 2 * n_streams * bytes) != hipSuccess) {
+    if (hipHostMalloc(&host, 2 * n_streams * bytes, hipHostMallocDefault) != hipSuccess || dev_alloc_bytes(&dev, 2 * n_streams * bytes) != SAFE_OK) {
         (void)hipGetLastError();
+        safe_set_error("%s", "");                              // (best effort: a failed allocation here is no error of the call)
         if (host) (void)hipHostFree(host);
         return;
     }
@@ -215,7 +205,7 @@ static void ctx_open_copy_queue(safe_ctx *ctx) {
         if (s) (void)hipStreamSynchronize(s);
     for (hipStream_t s : streams)
         if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(dev);
+    (void)dev_free(dev);
     (void)hipHostFree(host);
     (void)hipGetLastError();
     (void)ctx;
@@ -285,9 +275,9 @@ int safe_ctx_destroy(safe_ctx *ctx) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_timing) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_plain) (void)hipEventDestroy(e);
-    for (int i = 0; i < N_SCRATCH; ++i)
-        if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
-    for (auto &b : ctx->block_cache) (void)hipFree(b.second);
+    for (void *p : ctx->scratch) (void)dev_free(p);
+    for (auto &b : ctx->block_cache) (void)dev_free(b.second);
+    (void)dev_free(ctx->diag_prof);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     for (hipStream_t ms : ctx->more_streams)
@@ -347,7 +337,7 @@ int safe_dev_free(safe_ctx *ctx, void *dev) {
     if (!dev) return SAFE_OK;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    SAFE_HIP_CHECK(hipFree(dev));
+    SAFE_HIP_CHECK(dev_free(dev));
     return SAFE_OK;
 }
 
@@ -497,6 +487,12 @@ int safe_timer_stop_ms(safe_ctx *ctx, double *elapsed_ms) {
 int safe_alloc_count(int64_t *calls) {
     SAFE_REQUIRE(calls, "safe_alloc_count: NULL argument");
     *calls = g_alloc_calls.load(std::memory_order_relaxed);
+    return SAFE_OK;
+}
+
+int safe_live_alloc_count(int64_t *blocks) {
+    SAFE_REQUIRE(blocks, "safe_live_alloc_count: NULL argument");
+    *blocks = g_live_blocks.load(std::memory_order_relaxed);
     return SAFE_OK;
 }
 

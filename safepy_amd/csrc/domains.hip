@@ -368,44 +368,6 @@ __global__ __launch_bounds__(LK_THREADS) void k_linkage_nn_chain(double *sq, int
     }
 }
 
-// Device buffers and timing events of one call, released on every return path.
-struct DomBufs {
-    std::vector<void *> p;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~DomBufs() {
-        for (void *q : p) (void)hipFree(q);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T **q, size_t count) {
-        const int rc = dev_alloc(q, count);
-        if (rc == SAFE_OK) p.push_back(*q);
-        return rc;
-    }
-    hipError_t start(hipStream_t s) {
-        for (hipEvent_t &e : ev) {
-            const hipError_t err = hipEventCreateWithFlags(&e, safe_event_flags(hipEventDefault));
-            if (err != hipSuccess) return err;
-        }
-        return hipEventRecord(ev[0], s);
-    }
-    hipError_t stop(hipStream_t s) { return hipEventRecord(ev[1], s); }
-    // after the stream has been synchronised: the kernels' time, also recorded as the context's last kernel
-    hipError_t finish(safe_ctx *ctx, const char *name, int64_t launches, double *kernel_ms) {
-        float f = 0;
-        const hipError_t err = hipEventElapsedTime(&f, ev[0], ev[1]);
-        if (err != hipSuccess) return err;
-        ctx->last_kernel.name = name;
-        ctx->last_kernel.total_ms = f;
-        ctx->last_kernel.launches = launches;
-        ctx->last_kernel.busy_ms = f;
-        ctx->last_kernel.summed = true;
-        if (kernel_ms) *kernel_ms = f;
-        return hipSuccess;
-    }
-};
-
 // Hook + compress rounds over parent [n_cols][n] until no edge joins two labels (both forms of safe_enriched_components).
 // Synchronises the stream once per round (the changed flag).
 hipError_t cc_rounds(hipStream_t s, const int32_t *d_eu, const int32_t *d_ev, int64_t n_edges, int64_t n, int64_t n_cols,
@@ -440,8 +402,8 @@ int profile_check(const char *fn, safe_ctx *ctx, int64_t n, int64_t m, const int
 }
 
 // Pack + pair kernels of the checked arguments on the context's stream: *d_out (owned by b) receives the condensed distances.
-// Starts b's timing; the caller stops it behind whatever it enqueues next.
-int profile_condensed(const char *fn, safe_ctx *ctx, DomBufs &b, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host,
+// Starts the timer; the caller stops it behind whatever it enqueues next.
+int profile_condensed(const char *fn, safe_ctx *ctx, CallBufs &b, CallTimer &tm, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host,
                       int64_t m_top, int metric, double **d_out) {
     const int64_t words = ceil_div(n, 64), pairs = m_top * (m_top - 1) / 2;
     SAFE_REQUIRE(m_top < 65536 && ceil_div(words, 4) < (1ll << 31), "%s: too many profiles or rows for one launch", fn);
@@ -453,7 +415,7 @@ int profile_condensed(const char *fn, safe_ctx *ctx, DomBufs &b, const double *v
     SAFE_TRY(b.alloc(d_out, static_cast<size_t>(pairs)));
     hipStream_t s = ctx->stream;
     SAFE_HIP_CHECK(hipMemcpyAsync(d_cols, cols_host, m_top * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    SAFE_HIP_CHECK(b.start(s));
+    SAFE_HIP_CHECK(tm.start(s));
     hipLaunchKernelGGL(k_profile_pack, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(m_top, 64))), dim3(256),
                        0, s, values_dev, n, m, d_cols, m_top, words, d_bits);
     SAFE_HIP_CHECK(hipGetLastError());
@@ -473,10 +435,10 @@ int linkage_check_size(const char *fn, int64_t n) {
 }
 
 // Average linkage of the condensed distances d_cond (device, n >= 2 points, read only) into z_host f64 [n - 1, 4]: expand and
-// NN-chain kernels behind what the stream holds (b's timing is running: started by the caller, stopped here), then SciPy's
+// NN-chain kernels behind what the stream holds (the timer is running: started by the caller, stopped here), then SciPy's
 // epilogue on the host -- a stable sort of the merges by height and the union-find relabel (linkage() -> label()).  Synchronises.
 // z_host is written only on success.
-int linkage_run(const char *fn, safe_ctx *ctx, DomBufs &b, const double *d_cond, int64_t n, const char *kernels, int64_t launches,
+int linkage_run(const char *fn, safe_ctx *ctx, CallBufs &b, CallTimer &tm, const double *d_cond, int64_t n, const char *kernels, int64_t launches,
                 double *z_host, double *kernel_ms) {
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     double *d_sq = nullptr, *d_merges = nullptr;
@@ -493,13 +455,13 @@ int linkage_run(const char *fn, safe_ctx *ctx, DomBufs &b, const double *d_cond,
     const unsigned threads = static_cast<unsigned>(std::min<int64_t>(LK_THREADS, ceil_div(n, 64) * 64));
     hipLaunchKernelGGL(k_linkage_nn_chain, dim3(1), dim3(threads), 0, s, d_sq, static_cast<int>(n), d_size, d_merges, d_flag);
     SAFE_HIP_CHECK(hipGetLastError());
-    SAFE_HIP_CHECK(b.stop(s));
+    SAFE_HIP_CHECK(tm.stop(s));
     int flag = 0;
     std::vector<double> merges(static_cast<size_t>(3 * (n - 1)));
     SAFE_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(hipMemcpyAsync(merges.data(), d_merges, merges.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));
-    SAFE_HIP_CHECK(b.finish(ctx, kernels, launches, kernel_ms));
+    SAFE_HIP_CHECK(tm.finish(ctx, kernels, launches, kernel_ms));
     if (flag) {
         safe_set_error(flag & LK_BAD_INPUT  ? "%s: the distances are not all finite (SciPy's linkage refuses them too)"
                        : flag & LK_OVERFLOW ? "%s: an averaged distance overflowed"
@@ -553,37 +515,25 @@ int safe_enriched_components(safe_ctx *ctx, int64_t n, int64_t n_edges, const in
     double *d_member = nullptr;
     int32_t *d_parent = nullptr, *d_eu = nullptr, *d_ev = nullptr;
     int *d_changed = nullptr;
-    int rc = dev_alloc(&d_member, static_cast<size_t>(n) * n_cols);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_parent, static_cast<size_t>(n) * n_cols);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_eu, std::max<int64_t>(n_edges, 1));
-    if (rc == SAFE_OK) rc = dev_alloc(&d_ev, std::max<int64_t>(n_edges, 1));
-    if (rc == SAFE_OK) rc = dev_alloc(&d_changed, 1);
-    hipError_t e = hipSuccess;
-    if (rc == SAFE_OK) {
-        e = hipMemcpyAsync(d_member, member_host, static_cast<size_t>(n) * n_cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && n_edges)
-            e = hipMemcpyAsync(d_eu, edge_u, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && n_edges)
-            e = hipMemcpyAsync(d_ev, edge_v, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    const char *fn = "safe_enriched_components";
+    const int64_t total = n * n_cols;
+    hipStream_t s = ctx->stream;
+    CallBufs b;
+    SAFE_TRY(b.alloc(&d_member, static_cast<size_t>(total)));
+    SAFE_TRY(b.alloc(&d_parent, static_cast<size_t>(total)));
+    SAFE_TRY(b.alloc(&d_eu, std::max<int64_t>(n_edges, 1)));
+    SAFE_TRY(b.alloc(&d_ev, std::max<int64_t>(n_edges, 1)));
+    SAFE_TRY(b.alloc(&d_changed, 1));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_member, member_host, static_cast<size_t>(total) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_edges) {
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_eu, edge_u, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_ev, edge_v, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
-    if (rc == SAFE_OK && e == hipSuccess) {
-        const int64_t total = n * n_cols;
-        hipLaunchKernelGGL(k_cc_init, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_member, n, n_cols, d_parent);
-        e = cc_rounds(ctx->stream, d_eu, d_ev, n_edges, n, n_cols, d_parent, d_changed, nullptr);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(labels_host, d_parent, static_cast<size_t>(total) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-    }
-    if (rc == SAFE_OK && e != hipSuccess) {
-        safe_set_error("safe_enriched_components: %s", hipGetErrorString(e));
-        rc = SAFE_E_HIP;
-    }
-    (void)hipFree(d_member);
-    (void)hipFree(d_parent);
-    (void)hipFree(d_eu);
-    (void)hipFree(d_ev);
-    (void)hipFree(d_changed);
-    return rc;
+    hipLaunchKernelGGL(k_cc_init, dim3(ceil_div(total, 256)), dim3(256), 0, s, d_member, n, n_cols, d_parent);
+    SAFE_HIP_CHECK_AS(fn, cc_rounds(s, d_eu, d_ev, n_edges, n, n_cols, d_parent, d_changed, nullptr));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(labels_host, d_parent, static_cast<size_t>(total) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
+    return SAFE_OK;
 }
 
 int safe_jaccard_condensed(safe_ctx *ctx, int64_t m_top, int64_t n, const double *x_host, double *out_host) {
@@ -594,28 +544,19 @@ int safe_jaccard_condensed(safe_ctx *ctx, int64_t m_top, int64_t n, const double
     const int64_t words = ceil_div(n, 64), pairs = m_top * (m_top - 1) / 2;
     double *d_x = nullptr, *d_out = nullptr;
     unsigned long long *d_bits = nullptr;
-    int rc = dev_alloc(&d_x, static_cast<size_t>(m_top) * n);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_bits, static_cast<size_t>(m_top) * words);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_out, pairs);
-    hipError_t e = hipSuccess;
-    if (rc == SAFE_OK) {
-        e = hipMemcpyAsync(d_x, x_host, static_cast<size_t>(m_top) * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_jaccard_pack, dim3(ceil_div(words, 4), m_top), dim3(256), 0, ctx->stream, d_x, m_top, n, words, d_bits);
-            hipLaunchKernelGGL(k_jaccard_pairs, dim3(ceil_div(m_top, 256), m_top), dim3(256), 0, ctx->stream, d_bits, m_top, words, d_out);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out_host, d_out, pairs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-        if (e != hipSuccess) {
-            safe_set_error("safe_jaccard_condensed: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-        }
-    }
-    (void)hipFree(d_x);
-    (void)hipFree(d_bits);
-    (void)hipFree(d_out);
-    return rc;
+    const char *fn = "safe_jaccard_condensed";
+    hipStream_t s = ctx->stream;
+    CallBufs b;
+    SAFE_TRY(b.alloc(&d_x, static_cast<size_t>(m_top) * n));
+    SAFE_TRY(b.alloc(&d_bits, static_cast<size_t>(m_top) * words));
+    SAFE_TRY(b.alloc(&d_out, pairs));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_x, x_host, static_cast<size_t>(m_top) * n * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_jaccard_pack, dim3(ceil_div(words, 4), m_top), dim3(256), 0, s, d_x, m_top, n, words, d_bits);
+    hipLaunchKernelGGL(k_jaccard_pairs, dim3(ceil_div(m_top, 256), m_top), dim3(256), 0, s, d_bits, m_top, words, d_out);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(out_host, d_out, pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
+    return SAFE_OK;
 }
 
 int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v, const double *values_dev,
@@ -634,7 +575,8 @@ int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *
                      "safe_enriched_components_dev: edge %lld out of range", (long long)e);
     SAFE_REQUIRE(n_cols < 65536 && ceil_div(n * n_cols, 256) < (1ll << 31), "safe_enriched_components_dev: too many labels for one launch");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    DomBufs b;
+    CallBufs b;
+    CallTimer tm;
     int64_t *d_cols = nullptr;
     int32_t *d_parent = nullptr, *d_eu = nullptr, *d_ev = nullptr;
     int *d_changed = nullptr;
@@ -649,16 +591,16 @@ int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *
         SAFE_HIP_CHECK(hipMemcpyAsync(d_eu, edge_u, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, s));
         SAFE_HIP_CHECK(hipMemcpyAsync(d_ev, edge_v, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
-    SAFE_HIP_CHECK(b.start(s));
+    SAFE_HIP_CHECK(tm.start(s));
     int64_t launches = 1;
     hipLaunchKernelGGL(k_cc_init_cols, dim3(static_cast<unsigned>(ceil_div(n, 64)), static_cast<unsigned>(ceil_div(n_cols, 64))), dim3(256),
                        0, s, values_dev, n, m, d_cols, n_cols, d_parent);
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(cc_rounds(s, d_eu, d_ev, n_edges, n, n_cols, d_parent, d_changed, &launches));
-    SAFE_HIP_CHECK(b.stop(s));
+    SAFE_HIP_CHECK(tm.stop(s));
     SAFE_HIP_CHECK(hipMemcpyAsync(labels_host, d_parent, static_cast<size_t>(n) * n_cols * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));
-    SAFE_HIP_CHECK(b.finish(ctx, "k_cc_init_cols+k_cc_hook+k_cc_compress", launches, kernel_ms));
+    SAFE_HIP_CHECK(tm.finish(ctx, "k_cc_init_cols+k_cc_hook+k_cc_compress", launches, kernel_ms));
     return SAFE_OK;
 }
 
@@ -668,14 +610,15 @@ int safe_profile_distances(safe_ctx *ctx, const double *values_dev, int64_t n, i
     SAFE_TRY(profile_check(fn, ctx, n, m, cols_host, m_top, metric, kernel_ms));
     if (m_top < 2) return SAFE_OK;
     SAFE_REQUIRE(values_dev && out_host, "%s: NULL argument", fn);
-    DomBufs b;
+    CallBufs b;
+    CallTimer tm;
     double *d_out = nullptr;
-    SAFE_TRY(profile_condensed(fn, ctx, b, values_dev, n, m, cols_host, m_top, metric, &d_out));
+    SAFE_TRY(profile_condensed(fn, ctx, b, tm, values_dev, n, m, cols_host, m_top, metric, &d_out));
     hipStream_t s = ctx->stream;
-    SAFE_HIP_CHECK(b.stop(s));
+    SAFE_HIP_CHECK(tm.stop(s));
     SAFE_HIP_CHECK(hipMemcpyAsync(out_host, d_out, m_top * (m_top - 1) / 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));
-    SAFE_HIP_CHECK(b.finish(ctx, "k_profile_pack+k_profile_pairs", 2, kernel_ms));
+    SAFE_HIP_CHECK(tm.finish(ctx, "k_profile_pack+k_profile_pairs", 2, kernel_ms));
     return SAFE_OK;
 }
 
@@ -687,9 +630,10 @@ int safe_linkage_average(safe_ctx *ctx, const double *cond_dev, int64_t m_top, d
     SAFE_REQUIRE(cond_dev && z_host, "%s: NULL argument", fn);
     SAFE_TRY(linkage_check_size(fn, m_top));
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    DomBufs b;
-    SAFE_HIP_CHECK(b.start(ctx->stream));
-    return linkage_run(fn, ctx, b, cond_dev, m_top, "k_linkage_expand+k_linkage_nn_chain", 2, z_host, kernel_ms);
+    CallBufs b;
+    CallTimer tm;
+    SAFE_HIP_CHECK(tm.start(ctx->stream));
+    return linkage_run(fn, ctx, b, tm, cond_dev, m_top, "k_linkage_expand+k_linkage_nn_chain", 2, z_host, kernel_ms);
 }
 
 int safe_profile_linkage(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t m_top,
@@ -699,10 +643,11 @@ int safe_profile_linkage(safe_ctx *ctx, const double *values_dev, int64_t n, int
     if (m_top < 2) return SAFE_OK;
     SAFE_REQUIRE(values_dev && z_host, "%s: NULL argument", fn);
     SAFE_TRY(linkage_check_size(fn, m_top));
-    DomBufs b;
+    CallBufs b;
+    CallTimer tm;
     double *d_cond = nullptr;
-    SAFE_TRY(profile_condensed(fn, ctx, b, values_dev, n, m, cols_host, m_top, metric, &d_cond));
-    return linkage_run(fn, ctx, b, d_cond, m_top, "k_profile_pack+k_profile_pairs+k_linkage_expand+k_linkage_nn_chain", 4, z_host, kernel_ms);
+    SAFE_TRY(profile_condensed(fn, ctx, b, tm, values_dev, n, m, cols_host, m_top, metric, &d_cond));
+    return linkage_run(fn, ctx, b, tm, d_cond, m_top, "k_profile_pack+k_profile_pairs+k_linkage_expand+k_linkage_nn_chain", 4, z_host, kernel_ms);
 }
 
 }  // extern "C"

@@ -2329,10 +2329,14 @@ __global__ __launch_bounds__(256) void k_hypergeom_tail(const double *__restrict
 // host side
 // --------------------------------------------------------------------------------------
 struct Tiles {
-    double *bt = nullptr;
+    double *bt = nullptr;           // owned: released when the call that built the tiles returns (dev_free waits for the device)
     int64_t n_tiles = 0;
     int bn = 0;
     int planes = 1;
+    Tiles() = default;
+    Tiles(const Tiles &) = delete;
+    Tiles &operator=(const Tiles &) = delete;
+    ~Tiles() { (void)dev_free(bt); }
 };
 
 static int build_tiles(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col1, bool z, Tiles *tiles) {
@@ -2408,10 +2412,11 @@ static int launch_scatter(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     for (int64_t j = 0; j < mloc; ++j) order[j] = static_cast<int32_t>(j);
     const int32_t *sp = attr->h_sup_ptr.data() + col0;
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return sp[a + 1] - sp[a] > sp[b + 1] - sp[b]; });
+    CallBufs b;
     int32_t *d_order = nullptr;
     unsigned int *d_queue = nullptr;
-    SAFE_TRY(dev_alloc(&d_order, mloc));
-    SAFE_TRY(dev_alloc(&d_queue, 1));
+    SAFE_TRY(b.alloc(&d_order, mloc));
+    SAFE_TRY(b.alloc(&d_queue, 1));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_order, order.data(), mloc * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_queue, 0, sizeof(unsigned int), ctx->stream));
     const size_t lds_bytes = scatter_lds_bytes(n);
@@ -2434,8 +2439,6 @@ static int launch_scatter(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
     ctx->last_kernel.name = "k_permtest_scatter";
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));    // order (host vector) and temporaries
-    (void)hipFree(d_order);
-    (void)hipFree(d_queue);
     return SAFE_OK;
 }
 
@@ -3002,10 +3005,11 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     const std::vector<int4> tasks = cost_sorted_tasks(slice_group_blocks(nbr->h_slice_width, nbr->n_slices, NW), span, 0, n_tiles,
                                                       tasks_per_tile, INT64_MAX, false, mloc);
     const int64_t n_launch = static_cast<int64_t>(starts.size()) - 1, n_pad = nbr->n_slices * 64;
+    CallBufs b;
     int4 *d_tasks = nullptr;
     unsigned int *d_queue = nullptr, *d_counts = nullptr;
-    SAFE_TRY(dev_alloc(&d_tasks, tasks.size()));
-    SAFE_TRY(dev_alloc(&d_queue, n_launch));
+    SAFE_TRY(b.alloc(&d_tasks, tasks.size()));
+    SAFE_TRY(b.alloc(&d_queue, n_launch));
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_counts)));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemsetAsync(d_queue, 0, n_launch * sizeof(unsigned int), ctx->stream));
@@ -3043,10 +3047,7 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
     SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    SAFE_TRY(kernel_stat_from_events(ctx, ev, n_launch));
-    (void)hipFree(d_tasks);
-    (void)hipFree(d_queue);
-    return SAFE_OK;
+    return kernel_stat_from_events(ctx, ev, n_launch);
 }
 
 // Hypergeometric path for binary attributes with the tail looked up instead of evaluated per
@@ -3312,10 +3313,8 @@ static int run_perm_route(safe_ctx *ctx, const RouteSwitches &sw, PermRoute rout
     if (route == ROUTE_LDS_F64) return launch_lds_f64(ctx, nbr, attr, perms, col0, col1, z, out);
     Tiles tiles;
     SAFE_TRY(build_tiles(ctx, attr, col0, col1, z, &tiles));
-    int rc = perms_wait(perms, perms->count, ctx->stream);          // (rc from here on: the tile buffer is freed on every path)
-    if (rc == SAFE_OK) rc = launch_gather(ctx, nbr, tiles, perms->table, perms->count, col1 - col0, z, out);
-    (void)hipFree(tiles.bt);
-    return rc;
+    SAFE_TRY(perms_wait(perms, perms->count, ctx->stream));
+    return launch_gather(ctx, nbr, tiles, perms->table, perms->count, col1 - col0, z, out);
 }
 
 // The counts X = A . B0 of a binary 'sum' block: through the bit-sliced count kernel (F is not gather, the attribute is binary,
@@ -3438,6 +3437,36 @@ static int outputs_from_packed(const char *fn, bool narrow_ok, safe_ctx *ctx, sa
     return SAFE_OK;
 }
 
+// The side-stream fork of safe_hypergeom.  Its destructor joins the side stream back into ctx->stream and waits for both, then
+// lets go of the split state and the event: whatever return path the call takes, none of its work is under way when the
+// owners declared BEFORE the fork (tiles, buffers, host vectors) are destroyed after it.
+struct HypFork {
+    safe_ctx *ctx;
+    hipStream_t hs;                     // where the ids and the table are prepared: ctx->stream, or ctx->side_stream once forked
+    hipEvent_t ev = nullptr;            // fork and join
+    MfmaCountsSplit *split = nullptr;
+    bool joined = false, idle = false;
+    explicit HypFork(safe_ctx *c) : ctx(c), hs(c->stream) {}
+    HypFork(const HypFork &) = delete;
+    HypFork &operator=(const HypFork &) = delete;
+    void join() {                       // ctx->stream continues behind what hs holds
+        if (!joined && hs != ctx->stream && ev && hipEventRecord(ev, hs) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ev, 0);
+        joined = true;
+    }
+    hipError_t wait() {
+        join();
+        const hipError_t e = safe_stream_sync(ctx->stream);
+        if (hs != ctx->stream) (void)safe_stream_sync(hs);
+        idle = true;
+        return e;
+    }
+    ~HypFork() {
+        if (!idle) (void)wait();
+        if (split) mfma_counts_split_free(split);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 extern "C" {
 
 int safe_score(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int score_type, int64_t col0, int64_t col1,
@@ -3463,10 +3492,8 @@ int safe_score(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int score_type, in
     PermOut out{};
     out.ns = out_dev;
     out.mode = PERM_SCORE;
-    int rc = launch_gather(ctx, nbr, tiles, nullptr, 0, col1 - col0, z, out);
-    if (rc == SAFE_OK) rc = finish_kernel_timing(ctx);
-    (void)hipFree(tiles.bt);
-    return rc;
+    SAFE_TRY(launch_gather(ctx, nbr, tiles, nullptr, 0, col1 - col0, z, out));
+    return finish_kernel_timing(ctx);
 }
 
 int safe_permtest_counts(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int score_type,
@@ -3534,90 +3561,74 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
     SAFE_TRY(safe_attr_prepare(attr));
     const int64_t n = nbr->n, mloc = col1 - col0;
     const int64_t pop = attr->n_rows_with_value;
-    double *d_lf = nullptr, *d_hits = nullptr, *d_size = nullptr;
-    unsigned int *d_enr = nullptr;
-    Tiles tiles;
     const RouteSwitches sw = route_switches();
     const CountsRoute route = counts_route(sw, nbr, attr);
     const bool bits = route.bits, table = bits && sw.hyper_table, use_mfma = route.mfma;
+    // Destroyed from the bottom up: the fork first (join, wait for both streams), then the device memory the kernels used,
+    // then the host table an upload reads.
+    std::vector<double> lf;
+    Tiles tiles;
+    CallBufs bufs;
+    HypFork fork(ctx);
     void *small = nullptr;                                                  // d_size f64 [n] | d_enr u32 [mloc + 64]
-    int rc = ctx_scratch(ctx, SCRATCH_HYP_SMALL, static_cast<size_t>(n) * sizeof(double) + static_cast<size_t>(mloc + 64) * sizeof(unsigned int), &small);
-    if (rc == SAFE_OK) {
-        d_size = static_cast<double *>(small);
-        d_enr = reinterpret_cast<unsigned int *>(d_size + n);
-        if (hipMemsetAsync(d_enr, 0, (mloc + 64) * sizeof(unsigned int), ctx->stream) != hipSuccess) {
-            safe_set_error("safe_hypergeom: hipMemsetAsync failed");
-            rc = SAFE_E_HIP;
-        }
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_HYP_SMALL, static_cast<size_t>(n) * sizeof(double) + static_cast<size_t>(mloc + 64) * sizeof(unsigned int), &small));
+    double *d_size = static_cast<double *>(small);
+    unsigned int *d_enr = reinterpret_cast<unsigned int *>(d_size + n);
+    if (hipMemsetAsync(d_enr, 0, (mloc + 64) * sizeof(unsigned int), ctx->stream) != hipSuccess) {
+        safe_set_error("safe_hypergeom: hipMemsetAsync failed");
+        return SAFE_E_HIP;
     }
     // Split matrix-core form: bit planes and counts start on ctx->stream right away; neighborhood sizes,
     // the distinct (n, K) ids and the table are prepared on the side stream meanwhile (hypergeom_fused)
-    MfmaCountsSplit *split = nullptr;
-    hipStream_t hs = ctx->stream;
-    hipEvent_t ev = nullptr;
-    if (rc == SAFE_OK && table && use_mfma && mfma_counts_split_applicable(nbr)) {
-        hs = ctx->side_stream;
-        if (hipEventCreateWithFlags(&ev, safe_event_flags(hipEventDisableTiming)) != hipSuccess || hipEventRecord(ev, ctx->stream) != hipSuccess ||
-            hipStreamWaitEvent(hs, ev, 0) != hipSuccess) {
+    if (table && use_mfma && mfma_counts_split_applicable(nbr)) {
+        fork.hs = ctx->side_stream;
+        if (hipEventCreateWithFlags(&fork.ev, safe_event_flags(hipEventDisableTiming)) != hipSuccess ||
+            hipEventRecord(fork.ev, ctx->stream) != hipSuccess || hipStreamWaitEvent(fork.hs, fork.ev, 0) != hipSuccess) {
             safe_set_error("safe_hypergeom: stream fork failed");
-            rc = SAFE_E_HIP;
+            return SAFE_E_HIP;
         }
-        if (rc == SAFE_OK) rc = mfma_counts_split_begin(ctx, nbr, attr, col0, col1, &split);
+        SAFE_TRY(mfma_counts_split_begin(ctx, nbr, attr, col0, col1, &fork.split));
     }
     bool fused = false, enriched_done = false;
-    if (rc == SAFE_OK) {
-        hipLaunchKernelGGL(k_nbr_size, dim3(ceil_div(n, 4)), dim3(256), 0, hs, nbr->row_ptr, nbr->col, attr->row_flags, n, d_size);
-        if (table) rc = hypergeom_fused(ctx, nbr, attr, col0, col1, pop, d_size, nes_p_cut(enrichment_threshold),
-                                        pvalues_pos_dev, nes_dev, nes_binary_dev, d_enr, use_mfma, hs, split, &fused, num_enriched_dev,
-                                        &enriched_done);
-    }
-    if (hs != ctx->stream) {                                                // join (the fallback below reads d_size)
-        if (ev && hipEventRecord(ev, hs) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ev, 0);
-    }
-    if (rc == SAFE_OK && !fused) {
+    hipLaunchKernelGGL(k_nbr_size, dim3(ceil_div(n, 4)), dim3(256), 0, fork.hs, nbr->row_ptr, nbr->col, attr->row_flags, n, d_size);
+    if (table)
+        SAFE_TRY(hypergeom_fused(ctx, nbr, attr, col0, col1, pop, d_size, nes_p_cut(enrichment_threshold), pvalues_pos_dev, nes_dev,
+                                 nes_binary_dev, d_enr, use_mfma, fork.hs, fork.split, &fused, num_enriched_dev, &enriched_done));
+    fork.join();                                                            // (the fallback below reads d_size)
+    if (!fused) {
         // per-element evaluation: counts through memory, pmf from a log-factorial table lf[k] = log(k!), k = 0..n
-        std::vector<double> lf(n + 2);
+        lf.resize(n + 2);
         for (int64_t k = 0; k <= n + 1; ++k) lf[k] = std::lgamma(static_cast<double>(k) + 1.0);
-        rc = dev_alloc(&d_lf, n + 2);
-        if (rc == SAFE_OK) rc = ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_hits));
-        if (rc == SAFE_OK && !bits) rc = build_tiles(ctx, attr, col0, col1, false, &tiles);
-        if (rc == SAFE_OK && hipMemcpyAsync(d_lf, lf.data(), (n + 2) * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        double *d_lf = nullptr, *d_hits = nullptr;
+        SAFE_TRY(bufs.alloc(&d_lf, n + 2));
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&d_hits)));
+        if (!bits) SAFE_TRY(build_tiles(ctx, attr, col0, col1, false, &tiles));
+        if (hipMemcpyAsync(d_lf, lf.data(), (n + 2) * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
             safe_set_error("safe_hypergeom: hipMemcpyAsync failed");
-            rc = SAFE_E_HIP;
+            return SAFE_E_HIP;
         }
         PermOut out{};
         out.ns = d_hits;
         out.mode = PERM_SCORE;
-        if (rc == SAFE_OK)
-            rc = bits ? launch_counts_bits(ctx, nbr, attr, col0, col1, d_hits)
-                      : launch_gather(ctx, nbr, tiles, nullptr, 0, mloc, false, out);   // X = A . B0 (safe.py:593-594)
-        if (rc == SAFE_OK) {                                                // (no early return: the join and the frees below must run)
-            hipError_t e = hipEventRecord(ctx->k0, ctx->stream);
-            hipLaunchKernelGGL(k_hypergeom_tail, dim3(ceil_div(mloc, 64), ceil_div(n, 4)), dim3(256), 0, ctx->stream, d_hits,
-                               d_size, attr->col_sum, col0, n, mloc, static_cast<double>(pop), d_lf,
-                               nes_p_cut(enrichment_threshold), pvalues_pos_dev, nes_dev, nes_binary_dev, d_enr);
-            if (e == hipSuccess) e = hipGetLastError();
-            if (e == hipSuccess) e = hipEventRecord(ctx->k1, ctx->stream);
-            if (e != hipSuccess) {
-                safe_set_error("safe_hypergeom: %s", hipGetErrorString(e));
-                rc = SAFE_E_HIP;
-            }
-            ctx->last_kernel.name = "k_hypergeom_tail";
-        }
-        if (rc == SAFE_OK && safe_stream_sync(ctx->stream) != hipSuccess) rc = SAFE_E_HIP;   // lf is host memory
+        SAFE_TRY(bits ? launch_counts_bits(ctx, nbr, attr, col0, col1, d_hits)
+                      : launch_gather(ctx, nbr, tiles, nullptr, 0, mloc, false, out));   // X = A . B0 (safe.py:593-594)
+        hipError_t e = hipEventRecord(ctx->k0, ctx->stream);
+        hipLaunchKernelGGL(k_hypergeom_tail, dim3(ceil_div(mloc, 64), ceil_div(n, 4)), dim3(256), 0, ctx->stream, d_hits, d_size,
+                           attr->col_sum, col0, n, mloc, static_cast<double>(pop), d_lf, nes_p_cut(enrichment_threshold),
+                           pvalues_pos_dev, nes_dev, nes_binary_dev, d_enr);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->k1, ctx->stream);
+        ctx->last_kernel.name = "k_hypergeom_tail";
+        SAFE_HIP_CHECK_AS("safe_hypergeom", e);
+        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
     }
-    if (rc == SAFE_OK && !enriched_done) {
+    if (!enriched_done) {
         hipLaunchKernelGGL(k_u32_to_f64, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, mloc);
-        if (hipGetLastError() != hipSuccess) rc = SAFE_E_HIP;
+        SAFE_HIP_CHECK(hipGetLastError());
     }
-    if (rc == SAFE_OK) rc = finish_kernel_timing(ctx);
-    if (safe_stream_sync(ctx->stream) != hipSuccess && rc == SAFE_OK) rc = SAFE_E_HIP;
-    if (hs != ctx->stream) (void)safe_stream_sync(hs);
-    if (split) mfma_counts_split_free(split);
-    if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(d_lf);
-    (void)hipFree(tiles.bt);
-    return rc;
+    SAFE_TRY(finish_kernel_timing(ctx));
+    SAFE_HIP_CHECK(fork.wait());
+    return SAFE_OK;
 }
 
 int safe_outputs_from_counts(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,

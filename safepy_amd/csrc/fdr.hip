@@ -302,43 +302,31 @@ int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_per
     double *keys_out = nullptr;
     int32_t *vals_in = nullptr, *vals_out = nullptr;
     int64_t *offsets = nullptr;
-    void *temp = nullptr;
+    uint8_t *temp = nullptr;
     size_t temp_bytes = 0;
-    int rc = dev_alloc(&keys_out, batch_items);
-    if (rc == SAFE_OK) rc = dev_alloc(&vals_in, batch_items);
-    if (rc == SAFE_OK) rc = dev_alloc(&vals_out, batch_items);
-    if (rc == SAFE_OK) rc = dev_alloc(&offsets, batch_rows + 1);
-    hipError_t e = hipSuccess;
-    if (rc == SAFE_OK) {
-        hipLaunchKernelGGL(k_fdr_cols, dim3(ceil_div(batch_items, 256)), dim3(256), 0, ctx->stream, vals_in, batch_items, m);
-        hipLaunchKernelGGL(k_fdr_offsets, dim3(ceil_div(batch_rows + 1, 256)), dim3(256), 0, ctx->stream, offsets, batch_rows, m);
-        e = hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, p_dev, keys_out, vals_in, vals_out,
-                                                        static_cast<int>(batch_items), static_cast<int>(batch_rows), offsets,
-                                                        offsets + 1, 0, 64, ctx->stream);
-        g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-        if (e == hipSuccess) e = hipMalloc(&temp, std::max<size_t>(temp_bytes, 16));
-    }
-    for (int64_t r0 = 0; rc == SAFE_OK && e == hipSuccess && r0 < n; r0 += batch_rows) {
+    const char *fn = "safe_fdr_adjust";
+    CallBufs b;
+    SAFE_TRY(b.alloc(&keys_out, batch_items));
+    SAFE_TRY(b.alloc(&vals_in, batch_items));
+    SAFE_TRY(b.alloc(&vals_out, batch_items));
+    SAFE_TRY(b.alloc(&offsets, batch_rows + 1));
+    hipLaunchKernelGGL(k_fdr_cols, dim3(ceil_div(batch_items, 256)), dim3(256), 0, ctx->stream, vals_in, batch_items, m);
+    hipLaunchKernelGGL(k_fdr_offsets, dim3(ceil_div(batch_rows + 1, 256)), dim3(256), 0, ctx->stream, offsets, batch_rows, m);
+    SAFE_HIP_CHECK_AS(fn, hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, p_dev, keys_out, vals_in, vals_out,
+                                                                      static_cast<int>(batch_items), static_cast<int>(batch_rows),
+                                                                      offsets, offsets + 1, 0, 64, ctx->stream));
+    SAFE_TRY(b.alloc(&temp, std::max<size_t>(temp_bytes, 16)));
+    for (int64_t r0 = 0; r0 < n; r0 += batch_rows) {
         const int64_t rows = std::min<int64_t>(batch_rows, n - r0);
         double *block = p_dev + r0 * m;
-        e = hipcub::DeviceSegmentedRadixSort::SortPairs(temp, temp_bytes, block, keys_out, vals_in, vals_out,
-                                                        static_cast<int>(rows * m), static_cast<int>(rows), offsets, offsets + 1, 0,
-                                                        64, ctx->stream);
-        if (e != hipSuccess) break;
+        SAFE_HIP_CHECK_AS(fn, hipcub::DeviceSegmentedRadixSort::SortPairs(temp, temp_bytes, block, keys_out, vals_in, vals_out,
+                                                                          static_cast<int>(rows * m), static_cast<int>(rows), offsets,
+                                                                          offsets + 1, 0, 64, ctx->stream));
         hipLaunchKernelGGL(k_fdr_row, dim3(rows), dim3(256), 0, ctx->stream, keys_out, vals_out, m, block);
-        e = hipGetLastError();
+        SAFE_HIP_CHECK_AS(fn, hipGetLastError());
     }
-    if (rc == SAFE_OK && e == hipSuccess) e = safe_stream_sync(ctx->stream);
-    if (e != hipSuccess) {
-        safe_set_error("safe_fdr_adjust: %s", hipGetErrorString(e));
-        rc = SAFE_E_HIP;
-    }
-    (void)hipFree(keys_out);
-    (void)hipFree(vals_in);
-    (void)hipFree(vals_out);
-    (void)hipFree(offsets);
-    (void)hipFree(temp);
-    return rc;
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
+    return SAFE_OK;
 }
 
 }  // namespace
@@ -373,19 +361,15 @@ extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_
     }
     if (num_permutations > 0) SAFE_TRY(fdr_matrix(ctx, pvalues_neg_dev, n, m, hist_perm));
     SAFE_TRY(fdr_matrix(ctx, pvalues_pos_dev, n, m, hist_perm));
+    CallBufs b;
     unsigned int *d_enr = nullptr;
-    SAFE_TRY(dev_alloc(&d_enr, m));
+    SAFE_TRY(b.alloc(&d_enr, m));
     SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, m * sizeof(unsigned int), ctx->stream));
     hipLaunchKernelGGL(k_nes_from_pvalues, dim3(ceil_div(m, 64), ceil_div(n, 64)), dim3(256), 0, ctx->stream, pvalues_neg_dev,
                        pvalues_pos_dev, n, m, num_permutations > 0 ? 1.0 / static_cast<double>(num_permutations) : 0.0, sign_mode,
                        -std::log10(enrichment_threshold), nes_p_cut(enrichment_threshold), nes_dev, nes_binary_dev, d_enr);
     hipLaunchKernelGGL(k_fdr_u32_to_f64, dim3(ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, m);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-    (void)hipFree(d_enr);
-    if (e != hipSuccess) {
-        safe_set_error("safe_fdr_adjust: %s", hipGetErrorString(e));
-        return SAFE_E_HIP;
-    }
+    SAFE_HIP_CHECK_AS("safe_fdr_adjust", hipGetLastError());
+    SAFE_HIP_CHECK_AS("safe_fdr_adjust", safe_stream_sync(ctx->stream));
     return SAFE_OK;
 }

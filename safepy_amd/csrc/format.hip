@@ -133,7 +133,7 @@ struct FmtState {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
         for (void *p : {(void *)d_prefix, (void *)d_prefix_off, (void *)d_len, (void *)d_end, d_tmp, (void *)d_out[0], (void *)d_out[1]})
-            if (p) (void)hipFree(p);
+            (void)dev_free(p);
         for (void *p : {(void *)h_out[0], (void *)h_out[1], (void *)h_total})
             if (p) (void)hipHostFree(p);
     }
@@ -155,13 +155,12 @@ int fmt_write_all(int fd, const char *p, size_t bytes) {
 
 template <typename T>
 int fmt_alloc(T **p, size_t bytes) {
-    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) {
-        safe_set_error("safe_format_tsv: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return SAFE_E_NOMEM;
+    const int rc = dev_alloc_bytes(reinterpret_cast<void **>(p), std::max<size_t>(bytes, 16));
+    if (rc != SAFE_OK) {
+        const std::string why = safe_last_error();              // (the entry point names itself in its messages)
+        safe_set_error("safe_format_tsv: %s", why.c_str());
     }
-    return SAFE_OK;
+    return rc;
 }
 
 template <typename T>

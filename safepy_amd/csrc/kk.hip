@@ -248,12 +248,9 @@ struct safe_kk {
 
 static void kk_free(safe_kk *kk) {
     if (!kk) return;
-    (void)hipFree(kk->inv);
-    (void)hipFree(kk->inv_t);
-    (void)hipFree(kk->d_pos);
-    (void)hipFree(kk->d_grad);
-    (void)hipFree(kk->d_sums);
-    (void)hipFree(kk->d_blocks);
+    for (const void *q : {(const void *)kk->inv, (const void *)kk->inv_t, (const void *)kk->d_pos, (const void *)kk->d_grad,
+                          (const void *)kk->d_sums, (const void *)kk->d_blocks})
+        (void)dev_free(q);
     if (kk->h_stage) (void)hipHostFree(kk->h_stage);
     delete kk;
 }
@@ -266,64 +263,50 @@ static int kk_create(safe_ctx *ctx, int64_t n, const double *dist_host, const do
         return SAFE_E_UNSUPPORTED;
     }
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    safe_kk *kk = new safe_kk;
+    std::unique_ptr<safe_kk, void (*)(safe_kk *)> kk(new safe_kk, kk_free);   // (half built until it is released into *out)
     kk->ctx = ctx;
     kk->n = n;
     kk->n_full = n * n / KK_BUF;
     kk->ragged = static_cast<int>(n * n % KK_BUF);
     if (kk->ragged) kk_list_blocks(0, kk->ragged, kk->blocks);
     const size_t n_sums = static_cast<size_t>(kk->n_full) + kk->blocks.size();
+    const char *fn = "safe_kk_create";
+    hipStream_t s = ctx->stream;
+    CallBufs b;
     int *d_flag = nullptr;
     int flag = 0;
-    int rc = SAFE_OK;
-    hipStream_t s = ctx->stream;
-    do {
-        if ((rc = dev_alloc(&kk->inv, n * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&kk->inv_t, n * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&kk->d_pos, 2 * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&kk->d_grad, 2 * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&kk->d_sums, n_sums)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&kk->d_blocks, kk->blocks.size())) != SAFE_OK) break;
-        if ((rc = dev_alloc(&d_flag, 1)) != SAFE_OK) break;
-        g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&kk->h_stage), (4 * n + n_sums) * sizeof(double), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            safe_set_error("hipHostMalloc(%zu bytes) failed: %s", (4 * n + n_sums) * sizeof(double), hipGetErrorString(e));
-            rc = SAFE_E_NOMEM;
-            break;
-        }
-        if (dist_host) {
-            e = hipMemcpyAsync(kk->inv, dist_host, n * n * sizeof(double), hipMemcpyHostToDevice, s);
-            dist_dev = kk->inv;
-        }
-        if (e == hipSuccess && !kk->blocks.empty())
-            e = hipMemcpyAsync(kk->d_blocks, kk->blocks.data(), kk->blocks.size() * sizeof(int2), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int), s);
-        if (e == hipSuccess) {
-            const int grid = static_cast<int>(std::min<int64_t>(ceil_div(n * n, 256), 65536));
-            hipLaunchKernelGGL(k_kk_invdist, dim3(grid), dim3(256), 0, s, dist_dev, n, kk->inv, d_flag);
-            const unsigned tiles = static_cast<unsigned>(ceil_div(n, 32));
-            hipLaunchKernelGGL(k_kk_transpose, dim3(tiles, tiles), dim3(256), 0, s, kk->inv, n, kk->inv_t);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = safe_stream_sync(s);
-        if (e != hipSuccess) {
-            safe_set_error("safe_kk_create: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-            break;
-        }
-        if (flag) {
-            safe_set_error("safe_kk_create: the distance matrix holds a NaN or a negative distance");
-            rc = SAFE_E_VALUE;
-        }
-    } while (0);
-    (void)hipFree(d_flag);
-    if (rc != SAFE_OK) {
-        kk_free(kk);
-        return rc;
+    SAFE_TRY(dev_alloc(&kk->inv, n * n));
+    SAFE_TRY(dev_alloc(&kk->inv_t, n * n));
+    SAFE_TRY(dev_alloc(&kk->d_pos, 2 * n));
+    SAFE_TRY(dev_alloc(&kk->d_grad, 2 * n));
+    SAFE_TRY(dev_alloc(&kk->d_sums, n_sums));
+    SAFE_TRY(dev_alloc(&kk->d_blocks, kk->blocks.size()));
+    SAFE_TRY(b.alloc(&d_flag, 1));
+    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&kk->h_stage), (4 * n + n_sums) * sizeof(double), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        safe_set_error("hipHostMalloc(%zu bytes) failed: %s", (4 * n + n_sums) * sizeof(double), hipGetErrorString(e));
+        return SAFE_E_NOMEM;
     }
-    *out = kk;
+    if (dist_host) {
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(kk->inv, dist_host, n * n * sizeof(double), hipMemcpyHostToDevice, s));
+        dist_dev = kk->inv;
+    }
+    if (!kk->blocks.empty())
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(kk->d_blocks, kk->blocks.data(), kk->blocks.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    SAFE_HIP_CHECK_AS(fn, hipMemsetAsync(d_flag, 0, sizeof(int), s));
+    const int grid = static_cast<int>(std::min<int64_t>(ceil_div(n * n, 256), 65536));
+    hipLaunchKernelGGL(k_kk_invdist, dim3(grid), dim3(256), 0, s, dist_dev, n, kk->inv, d_flag);
+    const unsigned tiles = static_cast<unsigned>(ceil_div(n, 32));
+    hipLaunchKernelGGL(k_kk_transpose, dim3(tiles, tiles), dim3(256), 0, s, kk->inv, n, kk->inv_t);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
+    if (flag) {
+        safe_set_error("safe_kk_create: the distance matrix holds a NaN or a negative distance");
+        return SAFE_E_VALUE;
+    }
+    *out = kk.release();
     return SAFE_OK;
 }
 

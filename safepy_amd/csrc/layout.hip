@@ -154,14 +154,6 @@ __global__ __launch_bounds__(LT_THREADS) void k_spring_step(const T *__restrict_
     }
 }
 
-struct LayoutBuffers {
-    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~LayoutBuffers() {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-    }
-};
-
 template <typename T>
 int layout_run(safe_ctx *ctx, int n, const int32_t *row_ptr, const int32_t *col, const double *weight, const double *pos0,
                double k, int iterations, double threshold, double *pos_out, int *iterations_run) {
@@ -194,22 +186,16 @@ int layout_run(safe_ctx *ctx, int n, const int32_t *row_ptr, const int32_t *col,
     const T dt = t / static_cast<T>(iterations + 1);
     const T kk = static_cast<T>(k * k), kt = static_cast<T>(k), dmin = static_cast<T>(0.01);
 
-    LayoutBuffers bufs;
+    CallBufs bufs;
     T *d_pos = nullptr, *d_w = nullptr;
     int *d_off = nullptr, *d_slot = nullptr, *d_state = nullptr;
     double *d_sumsq = nullptr;
-    SAFE_TRY(dev_alloc(&d_pos, 4 * static_cast<size_t>(n)));
-    bufs.p[0] = d_pos;
-    SAFE_TRY(dev_alloc(&d_off, off.size()));
-    bufs.p[1] = d_off;
-    SAFE_TRY(dev_alloc(&d_slot, slot.size()));
-    bufs.p[2] = d_slot;
-    SAFE_TRY(dev_alloc(&d_w, w.size()));
-    bufs.p[3] = d_w;
-    SAFE_TRY(dev_alloc(&d_sumsq, std::max(iterations, 1)));
-    bufs.p[4] = d_sumsq;
-    SAFE_TRY(dev_alloc(&d_state, 2));
-    bufs.p[5] = d_state;
+    SAFE_TRY(bufs.alloc(&d_pos, 4 * static_cast<size_t>(n)));
+    SAFE_TRY(bufs.alloc(&d_off, off.size()));
+    SAFE_TRY(bufs.alloc(&d_slot, slot.size()));
+    SAFE_TRY(bufs.alloc(&d_w, w.size()));
+    SAFE_TRY(bufs.alloc(&d_sumsq, std::max(iterations, 1)));
+    SAFE_TRY(bufs.alloc(&d_state, 2));
     hipStream_t s = ctx->stream;
     SAFE_HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * sizeof(T), hipMemcpyHostToDevice, s));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s));

@@ -2615,16 +2615,12 @@ __global__ __launch_bounds__(256) void k_mfma_obs_ns(const long long *__restrict
 }  // namespace
 
 void nbr_free_blocks(safe_nbr *nbr) {
-    (void)hipFree(nbr->bs_order);
-    (void)hipFree(nbr->bs_rowmap);
-    (void)hipFree(nbr->bs_rowcnt);
-    (void)hipFree(nbr->bs_grpmax);
-    (void)hipFree(nbr->bs_bits4p);
+    for (const void *q : {(const void *)nbr->bs_order, (const void *)nbr->bs_rowmap, (const void *)nbr->bs_rowcnt,
+                          (const void *)nbr->bs_grpmax, (const void *)nbr->bs_bits4p, (const void *)nbr->bs_ptr,
+                          (const void *)nbr->bs_kb, (const void *)nbr->bs_bits})
+        (void)dev_free(q);
     nbr->bs_rowcnt = nbr->bs_grpmax = nullptr;
     nbr->bs_bits4p = nullptr;
-    (void)hipFree(nbr->bs_ptr);
-    (void)hipFree(nbr->bs_kb);
-    (void)hipFree(nbr->bs_bits);
     nbr->bs_order = nbr->bs_rowmap = nbr->bs_ptr = nbr->bs_kb = nullptr;
     nbr->bs_bits = nullptr;
     nbr->blocks_ready = false;
@@ -3020,7 +3016,7 @@ int mfma_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, con
             fa.p_base = static_cast<int>(p_base);
 #ifdef SAFE_HIP_DIAG
             if (dbg == 512) {
-                if (!ctx->diag_prof) SAFE_HIP_CHECK(hipMalloc(&ctx->diag_prof, 64 * sizeof(unsigned long long)));
+                if (!ctx->diag_prof) SAFE_TRY(dev_alloc_bytes(&ctx->diag_prof, 64 * sizeof(unsigned long long)));
                 if (c == 0) SAFE_HIP_CHECK(hipMemsetAsync(ctx->diag_prof, 0, 64 * sizeof(unsigned long long), ks));
                 fa.prof = static_cast<unsigned long long *>(ctx->diag_prof);
             }

@@ -358,51 +358,50 @@ __global__ void k_fill_u64(unsigned long long *p, unsigned long long v, int64_t 
 // --------------------------------------------------------------------------------------
 static void nbr_free(safe_nbr *nbr) {
     if (!nbr) return;
-    (void)hipFree(nbr->bits);
-    (void)hipFree(nbr->row_ptr);
-    (void)hipFree(nbr->col);
-    (void)hipFree(nbr->sell_row);
-    (void)hipFree(nbr->sell_pos);
-    (void)hipFree(nbr->slice_off);
-    (void)hipFree(nbr->slice_width);
-    (void)hipFree(nbr->sell_col);
-    (void)hipFree(nbr->sell_col2);
-    (void)hipFree(nbr->sell_col2b);
-    (void)hipFree(nbr->dist);
-    (void)hipFree(nbr->at_ptr);
-    (void)hipFree(nbr->at_col);
+    for (const void *q : {(const void *)nbr->bits, (const void *)nbr->row_ptr, (const void *)nbr->col, (const void *)nbr->sell_row,
+                          (const void *)nbr->sell_pos, (const void *)nbr->slice_off, (const void *)nbr->slice_width,
+                          (const void *)nbr->sell_col, (const void *)nbr->sell_col2, (const void *)nbr->sell_col2b,
+                          (const void *)nbr->dist, (const void *)nbr->at_ptr, (const void *)nbr->at_col})
+        (void)dev_free(q);
     nbr_free_blocks(nbr);
     if (nbr->bits_plan_pinned) (void)hipHostFree(nbr->bits_plan_pinned);
     delete nbr;
 }
 
-static int nbr_new(safe_ctx *ctx, int64_t n, safe_nbr **out) {
+// a handle under construction: freed on every return path until it is released into the caller's *out
+using NbrPtr = std::unique_ptr<safe_nbr, void (*)(safe_nbr *)>;
+
+static int nbr_new(safe_ctx *ctx, int64_t n, NbrPtr *out) {
     SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 64, "neighborhood size n=%lld out of range", (long long)n);
-    safe_nbr *nbr = new safe_nbr();
+    NbrPtr nbr(new safe_nbr(), nbr_free);
     nbr->ctx = ctx;
     nbr->n = n;
     nbr->words = ceil_div(n, 64);
-    int rc = dev_alloc(&nbr->bits, static_cast<size_t>(n) * nbr->words);
-    if (rc != SAFE_OK) {
-        nbr_free(nbr);
-        return rc;
-    }
-    *out = nbr;
+    SAFE_TRY(dev_alloc(&nbr->bits, static_cast<size_t>(n) * nbr->words));
+    *out = std::move(nbr);
     return SAFE_OK;
 }
 
-int nbr_finalize_from_bits(safe_nbr *nbr) {
+// per-row member counts of the bit matrix into nbr->h_row_count
+static int nbr_row_counts(safe_nbr *nbr) {
     safe_ctx *ctx = nbr->ctx;
     const int64_t n = nbr->n;
+    CallBufs b;
     int32_t *d_count = nullptr;
-    SAFE_TRY(dev_alloc(&d_count, n));
+    SAFE_TRY(b.alloc(&d_count, n));
     hipLaunchKernelGGL(k_row_popcount, dim3(ceil_div(n * 64, 256)), dim3(256), 0, ctx->stream, nbr->bits, n,
                        nbr->words, d_count);
     nbr->h_row_count.resize(n);
     SAFE_HIP_CHECK(hipMemcpyAsync(nbr->h_row_count.data(), d_count, n * sizeof(int32_t), hipMemcpyDeviceToHost,
                                   ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    (void)hipFree(d_count);
+    return SAFE_OK;
+}
+
+int nbr_finalize_from_bits(safe_nbr *nbr) {
+    safe_ctx *ctx = nbr->ctx;
+    const int64_t n = nbr->n;
+    SAFE_TRY(nbr_row_counts(nbr));
 
     std::vector<int32_t> row_ptr(n + 1, 0);
     int64_t nnz = 0, max_count = 0;
@@ -476,11 +475,12 @@ int nbr_build_transpose(safe_nbr *nbr) {
     if (nbr->at_ptr) return SAFE_OK;
     safe_ctx *ctx = nbr->ctx;
     const int64_t n = nbr->n, nnz = nbr->nnz;
+    std::vector<int32_t> cnt(n), ptr(n + 1, 0);
+    CallBufs b;
     int32_t *d_cnt = nullptr;
-    SAFE_TRY(dev_alloc(&d_cnt, n));
+    SAFE_TRY(b.alloc(&d_cnt, n));
     SAFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, n * sizeof(int32_t), ctx->stream));
     if (nnz) hipLaunchKernelGGL(k_count_cols, dim3(ceil_div(nnz, 256)), dim3(256), 0, ctx->stream, nbr->col, nnz, d_cnt);
-    std::vector<int32_t> cnt(n), ptr(n + 1, 0);
     SAFE_HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
     for (int64_t k = 0; k < n; ++k) ptr[k + 1] = ptr[k] + cnt[k];
@@ -492,7 +492,6 @@ int nbr_build_transpose(safe_nbr *nbr) {
                        nbr->at_ptr, d_cnt, nbr->at_col);
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    (void)hipFree(d_cnt);
     return SAFE_OK;
 }
 
@@ -502,34 +501,18 @@ int safe_nbr_euclidean(safe_ctx *ctx, const double *xy_host, int64_t n, double n
     SAFE_REQUIRE(ctx && xy_host && out, "safe_nbr_euclidean: NULL argument");
     *out = nullptr;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    safe_nbr *nbr = nullptr;
+    NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
+    CallBufs b;
     double *d_xy = nullptr;
-    int rc = dev_alloc(&d_xy, 2 * n);
-    if (rc != SAFE_OK) {
-        nbr_free(nbr);
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_euclid_bits, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n,
-                           squared_threshold(nr), nbr->bits, nbr->words);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        safe_set_error("safe_nbr_euclidean: %s", hipGetErrorString(e));
-        (void)hipFree(d_xy);
-        nbr_free(nbr);
-        return SAFE_E_HIP;
-    }
-    rc = nbr_finalize_from_bits(nbr);
-    (void)hipFree(d_xy);
-    if (rc != SAFE_OK) {
-        nbr_free(nbr);
-        return rc;
-    }
+    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_HIP_CHECK_AS("safe_nbr_euclidean", hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_euclid_bits, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n,
+                       squared_threshold(nr), nbr->bits, nbr->words);
+    SAFE_HIP_CHECK_AS("safe_nbr_euclidean", hipGetLastError());
+    SAFE_TRY(nbr_finalize_from_bits(nbr.get()));
     nbr->h_xy.assign(xy_host, xy_host + 2 * n);       // node order of the block-sparse form (mfma.hip)
-    *out = nbr;
+    *out = nbr.release();
     return SAFE_OK;
 }
 
@@ -591,10 +574,11 @@ int safe_edge_lengths(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t n
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
     double *d_xy = nullptr, *d_out = nullptr;
     int32_t *d_u = nullptr, *d_v = nullptr;
-    SAFE_TRY(dev_alloc(&d_xy, 2 * n));
-    SAFE_TRY(dev_alloc(&d_out, n_edges));
-    SAFE_TRY(dev_alloc(&d_u, n_edges));
-    SAFE_TRY(dev_alloc(&d_v, n_edges));
+    CallBufs b;
+    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_TRY(b.alloc(&d_out, n_edges));
+    SAFE_TRY(b.alloc(&d_u, n_edges));
+    SAFE_TRY(b.alloc(&d_v, n_edges));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_u, edge_u, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_v, edge_v, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -603,10 +587,6 @@ int safe_edge_lengths(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t n
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(hipMemcpyAsync(out_host, d_out, n_edges * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    (void)hipFree(d_xy);
-    (void)hipFree(d_out);
-    (void)hipFree(d_u);
-    (void)hipFree(d_v);
     return SAFE_OK;
 }
 
@@ -641,61 +621,39 @@ int safe_nbr_shortpath(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t 
             adj_w[fill[v]++] = w;
         }
     }
-    safe_nbr *nbr = nullptr;
+    const char *fn = "safe_nbr_shortpath";
+    hipStream_t s = ctx->stream;
+    NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
     const int64_t n_workers = std::min<int64_t>(n, static_cast<int64_t>(ctx->num_cu) * 8);
+    CallBufs b;                                         // (behind deg, adj_col, adj_w: the uploads read them)
     int32_t *d_ptr = nullptr, *d_col = nullptr;
     double *d_w = nullptr;
     SpScratch sc{};
-    int rc = SAFE_OK;
-    do {
-        if ((rc = dev_alloc(&d_ptr, n + 1)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&d_col, n_adj)) != SAFE_OK) break;
-        if (edge_w && (rc = dev_alloc(&d_w, n_adj)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&sc.dist, n_workers * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&sc.qa, n_workers * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&sc.qb, n_workers * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&sc.reached, n_workers * n)) != SAFE_OK) break;
-        if ((rc = dev_alloc(&sc.flag, n_workers * n)) != SAFE_OK) break;
-        if (keep_distances && (rc = dev_alloc(&nbr->dist, n * n)) != SAFE_OK) break;
-        hipError_t e = hipMemcpyAsync(d_ptr, deg.data(), (n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && n_adj)
-            e = hipMemcpyAsync(d_col, adj_col.data(), n_adj * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && d_w && n_adj)
-            e = hipMemcpyAsync(d_w, adj_w.data(), n_adj * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(nbr->bits, 0, n * nbr->words * sizeof(uint64_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(sc.flag, 0, n_workers * n * sizeof(int32_t), ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, ctx->stream, sc.dist, 0x7FF0000000000000ull,
-                               n_workers * n);
-            if (nbr->dist)
-                hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, ctx->stream,
-                                   reinterpret_cast<unsigned long long *>(nbr->dist), 0x7FF0000000000000ull, n * n);
-            hipLaunchKernelGGL(k_shortpath, dim3(n_workers), dim3(64), 0, ctx->stream, n, d_ptr, d_col, d_w, cutoff, sc,
-                               n_workers, nbr->bits, nbr->words, nbr->dist);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-        if (e != hipSuccess) {
-            safe_set_error("safe_nbr_shortpath: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-            break;
-        }
-        rc = nbr_finalize_from_bits(nbr);
-    } while (0);
-    (void)hipFree(d_ptr);
-    (void)hipFree(d_col);
-    (void)hipFree(d_w);
-    (void)hipFree(sc.dist);
-    (void)hipFree(sc.qa);
-    (void)hipFree(sc.qb);
-    (void)hipFree(sc.reached);
-    (void)hipFree(sc.flag);
-    if (rc != SAFE_OK) {
-        nbr_free(nbr);
-        return rc;
-    }
-    *out = nbr;
+    SAFE_TRY(b.alloc(&d_ptr, n + 1));
+    SAFE_TRY(b.alloc(&d_col, n_adj));
+    if (edge_w) SAFE_TRY(b.alloc(&d_w, n_adj));
+    SAFE_TRY(b.alloc(&sc.dist, n_workers * n));
+    SAFE_TRY(b.alloc(&sc.qa, n_workers * n));
+    SAFE_TRY(b.alloc(&sc.qb, n_workers * n));
+    SAFE_TRY(b.alloc(&sc.reached, n_workers * n));
+    SAFE_TRY(b.alloc(&sc.flag, n_workers * n));
+    if (keep_distances) SAFE_TRY(dev_alloc(&nbr->dist, n * n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_ptr, deg.data(), (n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n_adj) SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_col, adj_col.data(), n_adj * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (d_w && n_adj) SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_w, adj_w.data(), n_adj * sizeof(double), hipMemcpyHostToDevice, s));
+    SAFE_HIP_CHECK_AS(fn, hipMemsetAsync(nbr->bits, 0, n * nbr->words * sizeof(uint64_t), s));
+    SAFE_HIP_CHECK_AS(fn, hipMemsetAsync(sc.flag, 0, n_workers * n * sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, s, sc.dist, 0x7FF0000000000000ull, n_workers * n);
+    if (nbr->dist)
+        hipLaunchKernelGGL(k_fill_u64, dim3(2048), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(nbr->dist),
+                           0x7FF0000000000000ull, n * n);
+    hipLaunchKernelGGL(k_shortpath, dim3(n_workers), dim3(64), 0, s, n, d_ptr, d_col, d_w, cutoff, sc, n_workers, nbr->bits,
+                       nbr->words, nbr->dist);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
+    SAFE_TRY(nbr_finalize_from_bits(nbr.get()));
+    *out = nbr.release();
     return SAFE_OK;
 }
 
@@ -703,40 +661,31 @@ int safe_nbr_from_dense_i64(safe_ctx *ctx, const int64_t *a_host, int64_t n, saf
     SAFE_REQUIRE(ctx && a_host && out, "safe_nbr_from_dense_i64: NULL argument");
     *out = nullptr;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    safe_nbr *nbr = nullptr;
+    const char *fn = "safe_nbr_from_dense_i64";
+    hipStream_t s = ctx->stream;
+    NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
-    int64_t *d_a = nullptr;
-    int *d_bad = nullptr;
-    int rc = dev_alloc(&d_a, n * n);
-    if (rc == SAFE_OK) rc = dev_alloc(&d_bad, 1);
     int bad = 0;
-    if (rc == SAFE_OK) {
-        hipError_t e = hipMemcpyAsync(d_a, a_host, n * n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_dense_to_bits, dim3(ceil_div(n * nbr->words * 64, 256)), dim3(256), 0, ctx->stream, d_a,
-                               n, nbr->words, nbr->bits, d_bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-        if (e != hipSuccess) {
-            safe_set_error("safe_nbr_from_dense_i64: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-        }
+    {
+        CallBufs b;                                     // (the 8 n^2 byte copy of the matrix goes before the derived forms are built)
+        int64_t *d_a = nullptr;
+        int *d_bad = nullptr;
+        SAFE_TRY(b.alloc(&d_a, n * n));
+        SAFE_TRY(b.alloc(&d_bad, 1));
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_a, a_host, n * n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        SAFE_HIP_CHECK_AS(fn, hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_dense_to_bits, dim3(ceil_div(n * nbr->words * 64, 256)), dim3(256), 0, s, d_a, n, nbr->words, nbr->bits,
+                           d_bad);
+        SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+        SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
     }
-    (void)hipFree(d_a);
-    (void)hipFree(d_bad);
-    if (rc == SAFE_OK && bad) {
+    if (bad) {
         safe_set_error("safe_nbr_from_dense_i64: membership matrix has entries outside {0,1}");
-        rc = SAFE_E_VALUE;
+        return SAFE_E_VALUE;
     }
-    if (rc == SAFE_OK) rc = nbr_finalize_from_bits(nbr);
-    if (rc != SAFE_OK) {
-        nbr_free(nbr);
-        return rc;
-    }
-    *out = nbr;
+    SAFE_TRY(nbr_finalize_from_bits(nbr.get()));
+    *out = nbr.release();
     return SAFE_OK;
 }
 
@@ -770,19 +719,13 @@ int safe_nbr_to_dense_i64(safe_nbr *nbr, int64_t *out_host) {
     SAFE_REQUIRE(nbr && out_host, "safe_nbr_to_dense_i64: NULL argument");
     safe_ctx *ctx = nbr->ctx;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    CallBufs b;
     int64_t *d = nullptr;
-    SAFE_TRY(dev_alloc(&d, nbr->n * nbr->n));
-    int rc = safe_nbr_to_dense_i64_dev(nbr, d);
-    if (rc == SAFE_OK) {
-        hipError_t e = hipMemcpyAsync(out_host, d, nbr->n * nbr->n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
-        if (e != hipSuccess) {
-            safe_set_error("safe_nbr_to_dense_i64: %s", hipGetErrorString(e));
-            rc = SAFE_E_HIP;
-        }
-    }
-    (void)hipFree(d);
-    return rc;
+    SAFE_TRY(b.alloc(&d, nbr->n * nbr->n));
+    SAFE_TRY(safe_nbr_to_dense_i64_dev(nbr, d));
+    SAFE_HIP_CHECK_AS("safe_nbr_to_dense_i64", hipMemcpyAsync(out_host, d, nbr->n * nbr->n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_HIP_CHECK_AS("safe_nbr_to_dense_i64", safe_stream_sync(ctx->stream));
+    return SAFE_OK;
 }
 
 int safe_nbr_row_counts(safe_nbr *nbr, int64_t *out_host) {

@@ -171,43 +171,6 @@ __global__ __launch_bounds__(GC_THREADS) void k_gather_columns(const double *__r
     out[t] = values[r * m + cols[c]];
 }
 
-// Device buffers of one call, freed on every return path.
-struct PlotBufs {
-    std::vector<void *> p;
-    ~PlotBufs() {
-        for (void *q : p) (void)hipFree(q);
-    }
-    template <typename T>
-    int alloc(T **q, size_t count) {
-        const int rc = dev_alloc(q, count);
-        if (rc == SAFE_OK) p.push_back(*q);
-        return rc;
-    }
-};
-
-// Kernel time of a call (ms) between two events on the context stream; the events are destroyed on every return path.
-struct PlotTimer {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PlotTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t start(hipStream_t s) {
-        for (hipEvent_t &e : ev) {
-            const hipError_t err = hipEventCreateWithFlags(&e, safe_event_flags(hipEventDefault));
-            if (err != hipSuccess) return err;
-        }
-        return hipEventRecord(ev[0], s);
-    }
-    hipError_t stop(hipStream_t s) { return hipEventRecord(ev[1], s); }
-    hipError_t ms(double *out) {
-        float f = 0;
-        const hipError_t err = hipEventElapsedTime(&f, ev[0], ev[1]);
-        *out = f;
-        return err;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -250,7 +213,7 @@ int safe_kde_grid(safe_ctx *ctx, int64_t n_sets, const int64_t *offsets_host, co
                  "safe_kde_grid: too many sets or grid points for one launch");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
 
-    PlotBufs b;
+    CallBufs b;
     double *d_pts = nullptr, *d_w = nullptr, *d_norm = nullptr, *d_xi = nullptr, *d_part = nullptr, *d_z = nullptr;
     int64_t *d_item = nullptr, *d_set_item0 = nullptr;
     SAFE_TRY(b.alloc(&d_pts, static_cast<size_t>(2 * total)));
@@ -272,7 +235,7 @@ int safe_kde_grid(safe_ctx *ctx, int64_t n_sets, const int64_t *offsets_host, co
     SAFE_HIP_CHECK(hipMemcpyAsync(d_item + items, item_p0.data(), items * sizeof(int64_t), hipMemcpyHostToDevice, s));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_item + 2 * items, item_p1.data(), items * sizeof(int64_t), hipMemcpyHostToDevice, s));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_set_item0, set_item0.data(), (n_sets + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    PlotTimer tm;
+    CallTimer tm;
     SAFE_HIP_CHECK(tm.start(s));
     hipLaunchKernelGGL(k_kde_grid, dim3(static_cast<unsigned>(items * tiles)), dim3(KDE_THREADS), 0, s, d_pts, d_w, d_norm, d_xi,
                        d_item, d_item + items, d_item + 2 * items, g, tiles, d_part);
@@ -306,14 +269,14 @@ int safe_domain_counts(safe_ctx *ctx, const double *values_dev, int64_t n, int64
         }
     SAFE_REQUIRE(n < (int64_t(1) << 31), "safe_domain_counts: too many rows");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    PlotBufs b;
+    CallBufs b;
     int32_t *d_dom = nullptr;
     double *d_counts = nullptr;
     SAFE_TRY(b.alloc(&d_dom, static_cast<size_t>(m)));
     SAFE_TRY(b.alloc(&d_counts, static_cast<size_t>(n * n_domains)));
     hipStream_t s = ctx->stream;
     if (m) SAFE_HIP_CHECK(hipMemcpyAsync(d_dom, domain_host, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PlotTimer tm;
+    CallTimer tm;
     SAFE_HIP_CHECK(tm.start(s));
     hipLaunchKernelGGL(k_domain_counts<false>, dim3(static_cast<unsigned>(n)), dim3(DC_THREADS), n_domains * sizeof(double), s, values_dev,
                        static_cast<const double *>(nullptr), m, d_dom, n_domains, 0, 0, d_counts, static_cast<int32_t *>(nullptr),
@@ -361,7 +324,7 @@ int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double 
     const int zero_bin = (zero != ids_host + n_ids && *zero == 0) ? static_cast<int>(zero - ids_host) : -1;
     SAFE_REQUIRE(n < (int64_t(1) << 31), "safe_node_domains: too many rows");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    PlotBufs b;
+    CallBufs b;
     int32_t *d_dom = nullptr, *d_primary = nullptr;
     double *d_counts = nullptr, *d_pnes = nullptr;
     SAFE_TRY(b.alloc(&d_dom, static_cast<size_t>(m)));
@@ -370,7 +333,7 @@ int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double 
     SAFE_TRY(b.alloc(&d_pnes, static_cast<size_t>(n)));
     hipStream_t s = ctx->stream;
     if (m) SAFE_HIP_CHECK(hipMemcpyAsync(d_dom, bin.data(), m * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PlotTimer tm;
+    CallTimer tm;
     SAFE_HIP_CHECK(tm.start(s));
     hipLaunchKernelGGL(k_domain_counts<true>, dim3(static_cast<unsigned>(n)), dim3(DC_THREADS), 2 * n_ids * sizeof(double), s,
                        nes_binary_dev, nes_dev, m, d_dom, n_ids, first_real, zero_bin, d_counts, d_primary, d_pnes);
@@ -380,13 +343,7 @@ int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double 
     SAFE_HIP_CHECK(hipMemcpyAsync(primary_host, d_primary, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(hipMemcpyAsync(primary_nes_host, d_pnes, n * sizeof(double), hipMemcpyDeviceToHost, s));
     SAFE_HIP_CHECK(safe_stream_sync(s));      // (bin is read by the upload until here)
-    double ms = 0;
-    SAFE_HIP_CHECK(tm.ms(&ms));
-    ctx->last_kernel.name = "k_domain_counts<node>";
-    ctx->last_kernel.total_ms = ctx->last_kernel.busy_ms = ms;
-    ctx->last_kernel.launches = 1;
-    ctx->last_kernel.summed = true;
-    if (kernel_ms) *kernel_ms = ms;
+    SAFE_HIP_CHECK(tm.finish(ctx, "k_domain_counts<node>", 1, kernel_ms));
     // bin indices -> ids; a node without a primary bin (no real domain holds an attribute of it and no column has id 0) gets id 0
     for (int64_t r = 0; r < n; ++r) primary_host[r] = primary_host[r] >= 0 ? ids_host[primary_host[r]] : 0;
     return SAFE_OK;
@@ -403,14 +360,14 @@ int safe_gather_columns(safe_ctx *ctx, const double *values_dev, int64_t n, int6
                      (long long)cols_host[c], (long long)m);
     SAFE_REQUIRE(ceil_div(n * k, GC_THREADS) < (int64_t(1) << 31), "safe_gather_columns: too many values");
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    PlotBufs b;
+    CallBufs b;
     int64_t *d_cols = nullptr;
     double *d_out = nullptr;
     SAFE_TRY(b.alloc(&d_cols, static_cast<size_t>(k)));
     SAFE_TRY(b.alloc(&d_out, static_cast<size_t>(n * k)));
     hipStream_t s = ctx->stream;
     SAFE_HIP_CHECK(hipMemcpyAsync(d_cols, cols_host, k * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    PlotTimer tm;
+    CallTimer tm;
     SAFE_HIP_CHECK(tm.start(s));
     hipLaunchKernelGGL(k_gather_columns, dim3(static_cast<unsigned>(ceil_div(n * k, GC_THREADS))), dim3(GC_THREADS), 0, s, values_dev,
                        n, m, d_cols, k, d_out);

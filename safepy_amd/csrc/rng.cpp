@@ -856,22 +856,17 @@ static void perms_free(safe_perms *p) {
         if (p->staged2[b]) (void)hipEventDestroy(p->staged2[b]);
     }
     for (int b = 0; b < 2; ++b) {
-        (void)hipFree(p->d_maps[b]);
-        (void)hipFree(p->d_maps_odd[b]);
+        (void)dev_free(p->d_maps[b]);
+        (void)dev_free(p->d_maps_odd[b]);
         if (p->replayed[b]) (void)hipEventDestroy(p->replayed[b]);
     }
     if (p->movpos_ready) (void)hipEventDestroy(p->movpos_ready);
-    (void)hipFree(p->d_targets_odd);
     if (p->h_movpos) (void)hipHostFree(p->h_movpos);
-    (void)hipFree(p->d_targets);
-    (void)hipFree(p->d_big);
     for (hipEvent_t e : p->chunk_done)
         if (e) (void)hipEventDestroy(e);
-    (void)hipFree(p->d_cur);
-    (void)hipFree(p->d_movpos);
-    (void)hipFree(p->table);
-    (void)hipFree(p->table16);
-    (void)hipFree(p->inverse_t);
+    for (const void *q : {(const void *)p->d_targets_odd, (const void *)p->d_targets, (const void *)p->d_big, (const void *)p->d_cur,
+                          (const void *)p->d_movpos, (const void *)p->table, (const void *)p->table16, (const void *)p->inverse_t})
+        (void)dev_free(q);
     if (p->stream) draw_stream_free(p->stream);
     if (p->stream2) draw_stream_free(p->stream2);
     delete p;
@@ -1321,7 +1316,7 @@ int safe_perms_destroy(safe_perms *perms) {
     perms->stream = nullptr;
     if (perms->stream2) draw_stream_free(perms->stream2);
     perms->stream2 = nullptr;
-    (void)hipFree(perms->inverse_t);
+    (void)dev_free(perms->inverse_t);
     perms->inverse_t = nullptr;
     ctx->perm_cache = perms;
     return rc;
