@@ -159,6 +159,27 @@ int safe_nbr_csr(safe_nbr *nbr, int32_t *row_ptr_host, int32_t *col_host);
  * (inf where unreached).  SAFE_E_INVALID if distances were not kept. */
 int safe_nbr_distances(safe_nbr *nbr, double *out_host);
 
+/* Order statistics of the pairwise node distances, for the radius types the reference reads and then ignores
+ * (neighborhood_radius_type 'percentile': safepy/safe.py:377-381, 389-410; safe_default.ini:13).  The multiset is the
+ * distances of the unordered node pairs i < j, never stored: exact radix selection over the f64 bit patterns, recomputed
+ * (or re-read) in every pass.  out_host[t] = the element of rank ranks[t] (0-based) of the ascending multiset; ranks need
+ * not be sorted and may repeat; any number of ranks (they are served SAFE_SELECT_SLOTS distinct prefixes per sweep);
+ * n_ranks = 0 only counts.  A rank outside [0, count) is SAFE_E_INVALID (the count is still delivered), n above
+ * SAFE_SELECT_MAX_NODES is SAFE_E_UNSUPPORTED (a call sees fewer than 2^32 pairs).  Synchronous on the context's stream.
+ *
+ * safe_pair_distance_select_xy (safepy/safe.py:377-381, 389-410; safe_default.ini:13): 'euclidean' -- the multiset is
+ *   scipy.spatial.distance.pdist(xy), sqrt(dx*dx + dy*dy) with every operation rounded to f64, bit for bit; xy_host is
+ *   [n,2] row-major, every coordinate finite (SAFE_E_VALUE otherwise); *n_pairs = n (n - 1) / 2.
+ * safe_nbr_distance_select (safepy/safe.py:377-381, 389-410; safe_default.ini:13): the shortest-path metrics -- the
+ *   multiset is D[i][j], i < j, D[i][j] finite, of the matrix a safe_nbr_shortpath handle kept (row i = the search from
+ *   source i), read in place on the device; *n_finite_pairs = their number.  SAFE_E_INVALID if the handle kept none. */
+#define SAFE_SELECT_MAX_NODES 65536
+#define SAFE_SELECT_SLOTS 4
+int safe_pair_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n, const int64_t *ranks, int64_t n_ranks,
+                                 double *out_host, int64_t *n_pairs);
+int safe_nbr_distance_select(safe_nbr *nbr, const int64_t *ranks, int64_t n_ranks, double *out_host,
+                             int64_t *n_finite_pairs);
+
 /* The fused all-pairs kernel on its own (compute_node_distances for 'euclidean', and
  * the K1 roofline bench): xy_dev [n,2]; mask_out_dev int64 [n,n] and/or dist_out_dev
  * f64 [n,n]; either may be NULL.  Same arithmetic as safe_nbr_euclidean

@@ -15,6 +15,7 @@ DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
+SELECT_MAX_NODES = 65536            # SAFE_SELECT_MAX_NODES: nodes safe_pair_distance_select_xy / safe_nbr_distance_select take
 KK_MAX_NODES = 65536                # SAFE_KK_MAX_NODES: nodes safe_kk_create_host / safe_kk_create_nbr take
 LINKAGE_MAX_POINTS = 16384          # SAFE_LINKAGE_MAX_POINTS: points safe_linkage_average / safe_profile_linkage take
 # metric ids of safe_profile_distances (SAFE_METRIC_*), by SciPy's metric name
@@ -103,6 +104,8 @@ PROTOTYPES = {
     'safe_nbr_row_counts': (C.c_int, [_vp, _vp]),
     'safe_nbr_csr': (C.c_int, [_vp, _vp, _vp]),
     'safe_nbr_distances': (C.c_int, [_vp, _vp]),
+    'safe_pair_distance_select_xy': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _pi64]),
+    'safe_nbr_distance_select': (C.c_int, [_vp, _vp, _i64, _vp, _pi64]),
     'safe_euclidean_dense_dev': (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _vp]),
     'safe_edge_lengths': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'safe_layout_spring': (C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, C.c_double, _vp,

@@ -251,6 +251,20 @@ class Context:
         check(lib.safe_edge_lengths(self.handle, _ptr(xy), xy.shape[0], eu.shape[0], _ptr(eu), _ptr(ev), _ptr(out)))
         return out
 
+    def pair_distance_select(self, xy, ranks):
+        """Order statistics of scipy's pdist(xy) without the N (N - 1) / 2 distances (safe_pair_distance_select_xy): the
+        elements of the 0-based `ranks` of the ascending multiset, bit for bit.  Returns (values f64 [len(ranks)], number
+        of pairs); no ranks = the count alone."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError('pair_distance_select: xy must be [n, 2], got shape %s' % (xy.shape,))
+        rk = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64)
+        out = np.empty(rk.shape[0], dtype=np.float64)
+        count = C.c_int64(0)
+        check(lib.safe_pair_distance_select_xy(self.handle, _ptr(xy), xy.shape[0], _ptr(rk) if rk.size else None, rk.shape[0],
+                                               _ptr(out) if rk.size else None, C.byref(count)))
+        return out, count.value
+
     def layout_spring(self, row_ptr, col, weight, pos0, k, iterations, threshold, dtype):
         """networkx's Fruchterman-Reingold iterations on the device (safe_layout_spring): CSR adjacency with
         strictly increasing columns per row (weight None = 1), pos0 [n,2] f64, dtype np.float32 (the sparse
@@ -526,6 +540,16 @@ class Neighborhoods:
         out = np.empty((self.n, self.n), dtype=np.float64)
         check(lib.safe_nbr_distances(self.handle, _ptr(out)))
         return out
+
+    def distance_select(self, ranks):
+        """Order statistics of the kept distances D[i, j], i < j, finite (safe_nbr_distance_select), read on the device:
+        (values f64 [len(ranks)], number of finite pairs); no ranks = the count alone."""
+        rk = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64)
+        out = np.empty(rk.shape[0], dtype=np.float64)
+        count = C.c_int64(0)
+        check(lib.safe_nbr_distance_select(self.handle, _ptr(rk) if rk.size else None, rk.shape[0],
+                                           _ptr(out) if rk.size else None, C.byref(count)))
+        return out, count.value
 
     def close(self):
         if self.handle:
@@ -1197,6 +1221,16 @@ def jaccard_condensed(ctx, x):
     out = np.empty(m_top * (m_top - 1) // 2, dtype=np.float64)
     check(lib.safe_jaccard_condensed(ctx.handle, m_top, n, _ptr(x), _ptr(out)))
     return out
+
+
+def pair_distance_select(ctx, xy, ranks):
+    """Context.pair_distance_select: (values [len(ranks)], number of pairs)."""
+    return ctx.pair_distance_select(xy, ranks)
+
+
+def nbr_distance_select(nbr, ranks):
+    """Neighborhoods.distance_select: (values [len(ranks)], number of finite pairs)."""
+    return nbr.distance_select(ranks)
 
 
 def kde_grid(ctx, offsets, pts, weights, norm, xi):

@@ -354,8 +354,215 @@ __global__ void k_fill_u64(unsigned long long *p, unsigned long long v, int64_t 
 }
 
 // --------------------------------------------------------------------------------------
+// K3: exact order statistics of the pairwise node distances (neighborhood_radius_type
+// 'percentile': the radius is np.percentile of the distances of all pairs i < j), without
+// ever holding the N (N - 1) / 2 distances.
+//
+// Keys are the f64 bit patterns of non-negative values, which order like unsigned integers
+// (as in K2).  Bit 63 is never set; the other 63 bits are taken most significant digit first
+// in six digits of 11, 11, 11, 10, 10, 10 bits -- the first is exactly the exponent field.  A
+// pass sweeps every key once: a key whose bits above the digit equal one of up to SEL_SLOTS
+// prefixes adds one to that prefix's histogram of the digit.  The host then finds, for every
+// requested rank, the bin that holds it and appends the bin's digit to the rank's prefix; after
+// the sixth pass the prefix is the key.  All counts are integers, so the result does not depend
+// on the order of the atomics.
+//
+// Histograms are private to a workgroup (u32 in LDS: a call sees fewer than 2^32 keys, see
+// SAFE_SELECT_MAX_NODES) and go to the 64-bit global counters once, when the workgroup ends.
+// Real inputs put most keys of a pass into a few bins (one exponent; whole runs of tied
+// distances), so a wave first settles the bins of its two leading lanes with one LDS atomic each,
+// carrying the number of lanes that share the bin; only the lanes left over add singly.
+// --------------------------------------------------------------------------------------
+#define SEL_SLOTS SAFE_SELECT_SLOTS   // 4 x 2048 u32 = 32 KiB of LDS per workgroup
+#define SEL_BINS 2048
+static const int kSelPasses = 6;
+static const int kSelShift[kSelPasses] = {52, 41, 30, 20, 10, 0};
+static const int kSelBits[kSelPasses] = {11, 11, 11, 10, 10, 10};
+
+struct SelPass {
+    unsigned long long pre[SEL_SLOTS];   // bits above the digit that select slot q; ~0 = slot unused (bit 63 of a key is 0)
+    int shift, hshift;                   // digit = (key >> shift) & mask; prefix = key >> hshift
+    unsigned int mask;
+};
+
+// bin (slot * SEL_BINS + digit) the key counts in, -1 = none
+__device__ __forceinline__ int sel_bin(unsigned long long key, bool valid, const SelPass &ps) {
+    const unsigned long long hi = key >> ps.hshift;
+    int slot = -1;
+#pragma unroll
+    for (int q = 0; q < SEL_SLOTS; ++q) slot = (hi == ps.pre[q]) ? q : slot;
+    const int digit = static_cast<int>((key >> ps.shift) & ps.mask);
+    return (valid && slot >= 0) ? slot * SEL_BINS + digit : -1;
+}
+
+// every lane of the wave calls this together
+__device__ __forceinline__ void sel_count(uint32_t *hist, int bin, int lane) {
+    unsigned long long todo = __ballot(bin >= 0);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        if (!todo) return;                                           // wave-uniform
+        const int leader = __ffsll(todo) - 1;
+        const int b = __shfl(bin, leader);                           // >= 0: lanes without a key never match
+        const unsigned long long same = __ballot(bin == b);
+        if (lane == leader) atomicAdd(&hist[b], static_cast<uint32_t>(__popcll(same)));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1) atomicAdd(&hist[bin], 1u);
+}
+
+__device__ __forceinline__ void sel_flush(const uint32_t *hist, unsigned long long *__restrict__ ghist) {
+    for (int b = threadIdx.x; b < SEL_SLOTS * SEL_BINS; b += 256)
+        if (hist[b]) atomicAdd(&ghist[b], static_cast<unsigned long long>(hist[b]));
+}
+
+// Keys from coordinates: the SQUARED distance dx*dx + dy*dy of every pair i < j, recomputed in each pass with the operand
+// order of k_euclid_dense (each operation rounded, no FMA: -ffp-contract=off).  Selecting on the square is valid because sqrt
+// is correctly rounded and monotone: the sorted distances are the square roots of the sorted squares, element by element, so
+// the r-th smallest distance is sqrt of the r-th smallest square (the caller takes that one root per rank on the host).
+// A workgroup takes tiles of 64 rows x 256 columns: a lane keeps its column's coordinates in registers, the rows' are LDS
+// broadcasts.  Tiles without a pair i < j are skipped.
+__global__ __launch_bounds__(256) void k_select_xy(const double *__restrict__ xy, int64_t n, int64_t tiles_j, int64_t tiles,
+                                                   SelPass ps, unsigned long long *__restrict__ ghist) {
+    __shared__ uint32_t hist[SEL_SLOTS * SEL_BINS];
+    __shared__ double sx[64], sy[64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int b = tid; b < SEL_SLOTS * SEL_BINS; b += 256) hist[b] = 0;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t i0 = (t / tiles_j) * 64, j0 = (t % tiles_j) * 256;
+        if (i0 >= j0 + 255) continue;                                // (same for the whole workgroup)
+        __syncthreads();                                             // the tile before is done with sx, sy (first tile: hist is zero)
+        if (tid < 64) {
+            const int64_t i = i0 + tid;
+            sx[tid] = i < n ? xy[2 * i] : 0.0;
+            sy[tid] = i < n ? xy[2 * i + 1] : 0.0;
+        }
+        __syncthreads();
+        const int64_t j = j0 + tid;
+        const bool jin = j < n;
+        const double xj = jin ? xy[2 * j] : 0.0, yj = jin ? xy[2 * j + 1] : 0.0;
+        const int tn = static_cast<int>(n - i0 < 64 ? n - i0 : 64);
+        for (int u = 0; u < tn; ++u) {
+            const double dx = sx[u] - xj;
+            const double dy = sy[u] - yj;
+            const double s = dx * dx + dy * dy;                      // no FMA (-ffp-contract=off)
+            sel_count(hist, sel_bin(static_cast<unsigned long long>(__double_as_longlong(s)), jin && i0 + u < j, ps), lane);
+        }
+    }
+    __syncthreads();
+    sel_flush(hist, ghist);
+}
+
+// Keys from the distance matrix a shortest-path handle kept (f64 [n][n], +inf where unreached), read in place: the entries
+// above the diagonal, row i = the search from source i; +inf is no key.  Workgroups take rows round-robin.
+__global__ __launch_bounds__(256) void k_select_dist(const double *__restrict__ dist, int64_t n, SelPass ps,
+                                                     unsigned long long *__restrict__ ghist) {
+    __shared__ uint32_t hist[SEL_SLOTS * SEL_BINS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const unsigned long long INF_BITS = 0x7FF0000000000000ull;
+    for (int b = tid; b < SEL_SLOTS * SEL_BINS; b += 256) hist[b] = 0;
+    __syncthreads();
+    for (int64_t i = blockIdx.x; i < n - 1; i += gridDim.x) {
+        const unsigned long long *row = reinterpret_cast<const unsigned long long *>(dist) + i * n;
+        for (int64_t jb = i + 1; jb < n; jb += 256) {
+            const int64_t j = jb + tid;
+            const unsigned long long key = j < n ? row[j] : INF_BITS;
+            sel_count(hist, sel_bin(key, key < INF_BITS, ps), lane);
+        }
+    }
+    __syncthreads();
+    sel_flush(hist, ghist);
+}
+
+// --------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------
+// where K3's keys come from: coordinates on the device (xy) or a kept distance matrix (dist)
+struct SelSource {
+    const double *xy = nullptr, *dist = nullptr;
+    int64_t n = 0;
+};
+
+// one pass for up to SEL_SLOTS prefixes: the histograms, on the host
+static int sel_pass(safe_ctx *ctx, const SelSource &src, const SelPass &ps, unsigned long long *d_hist,
+                    std::vector<unsigned long long> &h_hist) {
+    hipStream_t s = ctx->stream;
+    const size_t bytes = static_cast<size_t>(SEL_SLOTS) * SEL_BINS * sizeof(unsigned long long);
+    const int64_t n = src.n, wgs = 4 * static_cast<int64_t>(ctx->num_cu);   // 33 KiB of LDS each: four fit a CU
+    SAFE_HIP_CHECK(hipMemsetAsync(d_hist, 0, bytes, s));
+    if (src.xy) {
+        const int64_t tiles_j = ceil_div(n, 256), tiles = ceil_div(n, 64) * tiles_j;
+        hipLaunchKernelGGL(k_select_xy, dim3(std::min(tiles, wgs)), dim3(256), 0, s, src.xy, n, tiles_j, tiles, ps, d_hist);
+    } else {
+        hipLaunchKernelGGL(k_select_dist, dim3(std::min(n - 1, wgs)), dim3(256), 0, s, src.dist, n, ps, d_hist);
+    }
+    SAFE_HIP_CHECK(hipGetLastError());
+    SAFE_HIP_CHECK(hipMemcpyAsync(h_hist.data(), d_hist, bytes, hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK(safe_stream_sync(s));
+    return SAFE_OK;
+}
+
+// keys[t] = the key of rank ranks[t] (0-based, ascending multiset) among the source's keys; *count = how many keys there are.
+// Ranks are checked against the count, which the first pass delivers.
+static int sel_keys(safe_ctx *ctx, const SelSource &src, const char *who, const int64_t *ranks, int64_t n_ranks,
+                    std::vector<unsigned long long> *keys, int64_t *count) {
+    *count = 0;
+    keys->assign(n_ranks, 0);
+    std::vector<unsigned long long> h_hist(static_cast<size_t>(SEL_SLOTS) * SEL_BINS), pre(n_ranks, 0), next(n_ranks, 0), distinct;
+    std::vector<int64_t> rem(ranks, ranks + n_ranks);
+    CallBufs b;                                         // (behind h_hist: the read-backs write it)
+    unsigned long long *d_hist = nullptr;
+    SAFE_TRY(b.alloc(&d_hist, h_hist.size()));
+    for (int pass = 0; pass < kSelPasses && src.n >= 2; ++pass) {
+        distinct.assign(pre.begin(), pre.end());
+        if (pass == 0) distinct.assign(1, 0ull);        // one empty prefix: every key, whether or not a rank was asked for
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        const int bins = 1 << kSelBits[pass];
+        for (size_t g = 0; g < distinct.size(); g += SEL_SLOTS) {
+            const int used = static_cast<int>(std::min<size_t>(SEL_SLOTS, distinct.size() - g));
+            SelPass ps;
+            for (int q = 0; q < SEL_SLOTS; ++q) ps.pre[q] = q < used ? distinct[g + q] : ~0ull;
+            ps.shift = kSelShift[pass];
+            ps.hshift = kSelShift[pass] + kSelBits[pass];
+            ps.mask = static_cast<unsigned int>(bins - 1);
+            SAFE_TRY(sel_pass(ctx, src, ps, d_hist, h_hist));
+            if (pass == 0) {
+                unsigned long long total = 0;
+                for (int d = 0; d < bins; ++d) total += h_hist[d];
+                *count = static_cast<int64_t>(total);
+                break;                                  // (the ranks are resolved below, once they are known to be inside)
+            }
+            for (int64_t t = 0; t < n_ranks; ++t) {
+                int q = 0;
+                while (q < used && ps.pre[q] != pre[t]) ++q;
+                if (q == used) continue;                // this rank's prefix is in another group
+                const unsigned long long *h = &h_hist[static_cast<size_t>(q) * SEL_BINS];
+                int d = 0;
+                while (d < bins && static_cast<unsigned long long>(rem[t]) >= h[d]) rem[t] -= static_cast<int64_t>(h[d++]);
+                if (d == bins) {
+                    safe_set_error("%s: the histograms of pass %d do not hold rank %lld", who, pass, (long long)ranks[t]);
+                    return SAFE_E_HIP;
+                }
+                next[t] = (pre[t] << kSelBits[pass]) | static_cast<unsigned long long>(d);
+            }
+        }
+        if (pass == 0) {
+            for (int64_t t = 0; t < n_ranks; ++t) {
+                SAFE_REQUIRE(ranks[t] >= 0 && ranks[t] < *count, "%s: rank %lld is outside [0, %lld)", who, (long long)ranks[t],
+                             (long long)*count);
+                int d = 0;
+                while (static_cast<unsigned long long>(rem[t]) >= h_hist[d]) rem[t] -= static_cast<int64_t>(h_hist[d++]);
+                next[t] = static_cast<unsigned long long>(d);
+            }
+            if (n_ranks == 0) return SAFE_OK;
+        }
+        pre.swap(next);
+    }
+    SAFE_REQUIRE(src.n >= 2 || n_ranks == 0, "%s: rank %lld is outside [0, 0): one node has no pair", who, (long long)ranks[0]);
+    *keys = pre;
+    return SAFE_OK;
+}
+
 static void nbr_free(safe_nbr *nbr) {
     if (!nbr) return;
     for (const void *q : {(const void *)nbr->bits, (const void *)nbr->row_ptr, (const void *)nbr->col, (const void *)nbr->sell_row,
@@ -754,6 +961,67 @@ int safe_nbr_distances(safe_nbr *nbr, double *out_host) {
     SAFE_HIP_CHECK(hipMemcpyAsync(out_host, nbr->dist, nbr->n * nbr->n * sizeof(double), hipMemcpyDeviceToHost,
                                   ctx->stream));
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    return SAFE_OK;
+}
+
+int safe_pair_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n, const int64_t *ranks, int64_t n_ranks,
+                                 double *out_host, int64_t *n_pairs) {
+    const char *fn = "safe_pair_distance_select_xy";
+    SAFE_REQUIRE(ctx && xy_host && n >= 1 && n_ranks >= 0, "%s: bad argument", fn);
+    SAFE_REQUIRE(n_ranks == 0 || (ranks && out_host), "%s: NULL rank or output array", fn);
+    if (n_pairs) *n_pairs = 0;
+    if (n > SAFE_SELECT_MAX_NODES) {
+        safe_set_error("%s: n=%lld is above the %d nodes the selection takes", fn, (long long)n, SAFE_SELECT_MAX_NODES);
+        return SAFE_E_UNSUPPORTED;
+    }
+    for (int64_t i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy_host[i])) {
+            safe_set_error("%s: node %lld has a coordinate that is not finite", fn, (long long)(i / 2));
+            return SAFE_E_VALUE;
+        }
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    CallBufs b;
+    double *d_xy = nullptr;
+    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SelSource src;
+    src.xy = d_xy;
+    src.n = n;
+    int64_t count = 0;
+    const int rc = sel_keys(ctx, src, fn, ranks, n_ranks, &keys, &count);
+    if (n_pairs) *n_pairs = count;                                    // (known even where a rank is refused)
+    SAFE_TRY(rc);
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));             // (n = 1 launches nothing: the upload still reads xy_host)
+    for (int64_t t = 0; t < n_ranks; ++t) {
+        double s;
+        std::memcpy(&s, &keys[t], sizeof s);
+        out_host[t] = std::sqrt(s);                                   // the one root per rank (k_select_xy)
+    }
+    return SAFE_OK;
+}
+
+int safe_nbr_distance_select(safe_nbr *nbr, const int64_t *ranks, int64_t n_ranks, double *out_host, int64_t *n_finite_pairs) {
+    const char *fn = "safe_nbr_distance_select";
+    SAFE_REQUIRE(nbr && n_ranks >= 0, "%s: bad argument", fn);
+    SAFE_REQUIRE(n_ranks == 0 || (ranks && out_host), "%s: NULL rank or output array", fn);
+    SAFE_REQUIRE(nbr->dist != nullptr, "%s: handle was built without keep_distances", fn);
+    if (n_finite_pairs) *n_finite_pairs = 0;
+    if (nbr->n > SAFE_SELECT_MAX_NODES) {
+        safe_set_error("%s: n=%lld is above the %d nodes the selection takes", fn, (long long)nbr->n, SAFE_SELECT_MAX_NODES);
+        return SAFE_E_UNSUPPORTED;
+    }
+    safe_ctx *ctx = nbr->ctx;
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    SelSource src;
+    src.dist = nbr->dist;
+    src.n = nbr->n;
+    int64_t count = 0;
+    const int rc = sel_keys(ctx, src, fn, ranks, n_ranks, &keys, &count);
+    if (n_finite_pairs) *n_finite_pairs = count;                      // (known even where a rank is refused)
+    SAFE_TRY(rc);
+    for (int64_t t = 0; t < n_ranks; ++t) std::memcpy(&out_host[t], &keys[t], sizeof(double));
     return SAFE_OK;
 }
 

@@ -2,8 +2,10 @@
 
 Same constructor signature, attribute names, method names, kwargs, array layouts and
 error behaviour as `safepy.safe.SAFE` (safepy/safe.py:37-608) for
-`define_neighborhoods()` / `compute_pvalues()` (+ the additive `compute_node_distances()`);
-the arithmetic runs in libsafe_hip.so on an MI355X.  `print_output_files()` writes the reference's
+`define_neighborhoods()` / `compute_pvalues()` (+ the additive `compute_node_distances()` and
+`node_distance_percentile()`); the arithmetic runs in libsafe_hip.so on an MI355X.  One departure:
+`neighborhood_radius_type`, which the reference reads and ignores, acts here ('absolute' and 'percentile'
+radii; 'diameter' is the reference's rule).  `print_output_files()` writes the reference's
 three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The plot methods
 (`plot_network`, `plot_sample_attributes`, `plot_composite_network`, `plot_composite_network_contours`) draw with
 matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  The MATLAB / Cytoscape
@@ -38,6 +40,43 @@ _DEFAULTS = {
     'groupDistanceType': 'jaccard',
     'groupDistanceThreshold': '0.75',
 }
+
+
+def _is_percentage(q):
+    return isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool) and 0 <= q <= 100
+
+
+def _percentile_ranks(count, q):
+    """The two order statistics np.percentile(v, q) -- NumPy 2.2, method 'linear' -- interpolates between for len(v) = count,
+    and the weight: (previous, next, gamma), 0-based ranks of sorted v.  As numpy.lib._function_base_impl does it: the
+    virtual index (count - 1) * (q / 100) in f64, its floor and the rank after it, gamma the difference; an index at or
+    above count - 1 takes the last element twice (NumPy's index -1, whence its gamma = index + 1 there)."""
+    if count < 1:
+        raise ValueError('no pair of nodes has a distance: the percentile of an empty set is undefined')
+    h = float((count - 1) * np.true_divide(q, 100))
+    if h >= count - 1:
+        return count - 1, count - 1, h + 1.0
+    k = int(np.floor(h))
+    return k, k + 1, h - k
+
+
+def _lerp(a, b, t):
+    """numpy.lib._function_base_impl._lerp for f64 scalars: a + (b - a) * t, and b - (b - a) * (1 - t) where t >= 0.5."""
+    a, b, t = float(a), float(b), float(t)
+    d = b - a
+    return b - d * (1 - t) if t >= 0.5 else a + d * t
+
+
+def _percentile_plan(count, qs):
+    """(the distinct ranks to select, ascending; per q: (position of previous, position of next, gamma))."""
+    triples = [_percentile_ranks(count, q) for q in qs]
+    ranks = sorted({r for k, k1, _ in triples for r in (k, k1)})
+    pos = {r: i for i, r in enumerate(ranks)}
+    return ranks, [(pos[k], pos[k1], g) for k, k1, g in triples]
+
+
+def _percentile_values(plan, values):
+    return [_lerp(values[i], values[i1], g) for i, i1, g in plan[1]]
 
 
 class LayoutGraph:
@@ -192,6 +231,7 @@ class SAFE:
         self.node_distance_metric = 'shortpath_weighted_layout'
         self.neighborhood_radius_type = None
         self.neighborhood_radius = None
+        self.neighborhood_radius_resolved = None     # the radius the last define_neighborhoods / compute_node_distances used (float)
 
         self.background = 'attribute_file'
         self.num_permutations = 1000
@@ -289,6 +329,15 @@ class SAFE:
             bad, self.node_distance_metric = self.node_distance_metric, self.default_config.get('nodeDistanceType')
             raise ValueError('%s is not a valid setting for node_distance_metric. '
                              'Valid options are: euclidean, shortpath, shortpath_weighted_layout' % bad)
+        if self.neighborhood_radius_type not in [None, 'diameter', 'absolute', 'percentile']:
+            bad, self.neighborhood_radius_type = self.neighborhood_radius_type, self.default_config.get('neighborhoodRadiusType')
+            raise ValueError('%s is not a valid setting for neighborhood_radius_type. '
+                             'Valid options are: diameter, absolute, percentile' % bad)
+        if self.neighborhood_radius_type == 'percentile' and not _is_percentage(self.neighborhood_radius):
+            bad, self.neighborhood_radius = self.neighborhood_radius, float(self.default_config.get('neighborhoodRadius'))
+            self.neighborhood_radius_type = self.default_config.get('neighborhoodRadiusType')
+            raise ValueError('neighborhood_radius = %r is not a percentile: with neighborhood_radius_type = percentile '
+                             'it must be a number in the [0, 100] range.' % (bad,))
         if self.attribute_sign not in ['highest', 'lowest', 'both']:
             bad, self.attribute_sign = self.attribute_sign, self.default_config.get('annotationsign')
             raise ValueError('%s is not a valid setting for attribute_sign. '
@@ -585,17 +634,55 @@ class SAFE:
             self.neighborhood_radius = kwargs['neighborhood_radius']
         self.validate_config()
 
-    def _shortpath_inputs(self, xy, eu, ev, length, weight):
+    def _shortpath_weights(self, xy, eu, ev, length, weight):
         n = xy.shape[0]
         if eu.size and (eu.min() < 0 or ev.min() < 0 or eu.max() >= n or ev.max() >= n):
             raise ValueError('shortest-path metrics index the neighborhood matrix by node id: ids must be 0..N-1')
         if self.node_distance_metric == 'shortpath_weighted_layout':
-            w = length                                  # weight='length', missing -> 1 (networkx)
-            cutoff = self._radius(xy)
+            return length                               # weight='length', missing -> 1 (networkx)
+        return weight                                   # default weight attr 'weight', missing -> 1
+
+    def _distance_percentiles(self, ctx, arrays, qs):
+        """np.percentile(v, q), bit for bit, for every q of `qs`.  v is the multiset of node distances of the pairs i < j
+        under the current metric: pdist(xy), or the finite D[i, j] of the all-pairs shortest paths (row i = the search
+        from i: one unbounded search whose matrix stays on the device).  v is never stored: the device counts it, then
+        selects the order statistics the interpolations need."""
+        xy, eu, ev, length, weight = arrays
+        if self.node_distance_metric == 'euclidean':
+            plan = _percentile_plan(ctx.pair_distance_select(xy, [])[1], qs)
+            return _percentile_values(plan, ctx.pair_distance_select(xy, plan[0])[0])
+        w = self._shortpath_weights(xy, eu, ev, length, weight)
+        nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, np.inf, keep_distances=True)
+        try:
+            plan = _percentile_plan(nbr.distance_select([])[1], qs)
+            return _percentile_values(plan, nbr.distance_select(plan[0])[0])
+        finally:
+            nbr.close()
+
+    def _resolve_radius(self, ctx, arrays):
+        """The radius in distance units (the hop cutoff for 'shortpath') that neighborhood_radius stands for under
+        neighborhood_radius_type; kept as self.neighborhood_radius_resolved."""
+        kind = self.neighborhood_radius_type
+        if kind == 'percentile':
+            r = self._distance_percentiles(ctx, arrays, [self.neighborhood_radius])[0]
+        elif kind == 'absolute' or self.node_distance_metric == 'shortpath':
+            r = self.neighborhood_radius                # 'shortpath' + 'diameter': the reference's hop cutoff, safe.py:409
         else:
-            w = weight                                  # default weight attr 'weight', missing -> 1
-            cutoff = self.neighborhood_radius          # safe.py:409
-        return w, cutoff
+            r = self._radius(arrays[0])
+        self.neighborhood_radius_resolved = float(r)
+        return r
+
+    def node_distance_percentile(self, q):
+        """Additive: np.percentile(v, q) (linear method, bit for bit) of the distances v of all node pairs i < j under the
+        current node_distance_metric -- scipy's pdist(xy) for 'euclidean', the finite all-pairs shortest-path lengths
+        D[i, j] otherwise -- computed on the device without storing v.  q: a number or a sequence in [0, 100]; returns a
+        float or an array.  What neighborhood_radius_type = 'percentile' resolves its radius with; touches neither
+        neighborhoods nor node_distances nor any setting."""
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        if qs.ndim != 1 or not all(_is_percentage(v) for v in qs.tolist()):
+            raise ValueError('Percentiles must be in the range [0, 100]')
+        out = np.array(self._distance_percentiles(self._ctx(), _graph_arrays(self.graph), qs.tolist()), dtype=np.float64)
+        return float(out[0]) if np.ndim(q) == 0 else out
 
     def define_neighborhoods(self, **kwargs):
         """safepy/safe.py:369-430.  kwargs: node_distance_metric, neighborhood_radius_type,
@@ -607,17 +694,20 @@ class SAFE:
         if self.node_distance_metric != 'euclidean':
             self._node_distances = None          # replaced below (a copy still on the device is not fetched first)
         self._invalidate_neighborhoods()
+        radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
         if self.node_distance_metric == 'euclidean':
-            self._nbr = be.Neighborhoods.euclidean(ctx, xy, self._radius(xy))
+            self._nbr = be.Neighborhoods.euclidean(ctx, xy, radius)
         else:
-            w, cutoff = self._shortpath_inputs(xy, eu, ev, length, weight)
-            self._nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, cutoff, keep_distances=True)
+            w = self._shortpath_weights(xy, eu, ev, length, weight)
+            self._nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, radius, keep_distances=True)
             self._nbr.set_layout(xy)
             self._node_distances = ('device-shortpath', self._nbr)
         if self.verbose:
             num_neighbors = self._nbr.row_counts()
             logging.info('Node distance metric: %s' % self.node_distance_metric)
             logging.info('Neighborhood definition: %.2f x %s' % (self.neighborhood_radius, self.neighborhood_radius_type))
+            if self.neighborhood_radius_type not in (None, 'diameter'):
+                logging.info('Neighborhood radius in distance units: %r' % self.neighborhood_radius_resolved)
             logging.info('Number of nodes per neighborhood (mean +/- std): %.2f +/- %.2f'
                          % (np.mean(num_neighbors), np.std(num_neighbors)))
 
@@ -630,19 +720,20 @@ class SAFE:
         xy, eu, ev, length, weight = _graph_arrays(self.graph)
         ctx = self._ctx()
         n = xy.shape[0]
+        radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
         if self.node_distance_metric == 'euclidean':
             d_xy = ctx.alloc(xy.nbytes)
             d_out = ctx.alloc_f64(n, n)
             try:
                 d_xy.upload(xy)
-                ctx.euclidean_dense(d_xy.ptr, n, self._radius(xy), None, d_out.ptr)
+                ctx.euclidean_dense(d_xy.ptr, n, radius, None, d_out.ptr)
                 self._node_distances = d_out.download((n, n))
             finally:
                 d_xy.free()
                 d_out.free()
         else:
-            w, cutoff = self._shortpath_inputs(xy, eu, ev, length, weight)
-            nbr = be.Neighborhoods.shortpath(ctx, n, eu, ev, w, cutoff, keep_distances=True)
+            w = self._shortpath_weights(xy, eu, ev, length, weight)
+            nbr = be.Neighborhoods.shortpath(ctx, n, eu, ev, w, radius, keep_distances=True)
             self._node_distances = ('dense-shortpath', nbr.distances())
             nbr.close()
 
