@@ -72,6 +72,7 @@ typedef struct safe_attr safe_attr;     /* node x attribute matrix, device resid
 typedef struct safe_perms safe_perms;   /* composed row-permutation tables, device res. */
 typedef struct safe_comm safe_comm;     /* RCCL communicator of the attribute-sharded path */
 typedef struct safe_kk safe_kk;         /* Kamada-Kawai cost function of one distance matrix, device res. */
+typedef struct safe_pairs safe_pairs;   /* one selection of a result matrix, counted and scanned, device res. */
 typedef struct PermRing safe_ring;      /* node-shared permutation stream (shared memory)    */
 
 /* ------------------------------------------------------------------ context ---- */
@@ -642,6 +643,39 @@ int safe_node_domains(safe_ctx *ctx, const double *nes_binary_dev, const double 
  * rest of it.  kernel_ms (may be NULL): the kernel's time.  Synchronises. */
 int safe_gather_columns(safe_ctx *ctx, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host, int64_t k,
                         double *out_host, double *kernel_ms);
+
+/* The enriched (node, attribute) pairs of a device-resident result matrix as the three arrays of a scipy.sparse CSR or CSC
+ * matrix, compacted on the device: what np.nonzero(nes_binary) and nes[rows, cols] give on the host after both [n, m] matrices
+ * have been read (the selection of safepy/safe.py:468-472), without moving the other cells across the link.
+ *
+ * safe_pairs_create (safepy/safe.py:470, the comparison): selector_dev is a row-major f64 [n, m] device matrix, read in place.
+ * A cell x is selected when   mode 0: x > 0   mode 1: |x| > threshold   mode 2: x > threshold   mode 3: x < -threshold.
+ * The comparison is strict, NaN is never selected, -0.0 is not selected at threshold 0, +-inf are.  The threshold is a number
+ * >= 0 or +inf (SAFE_E_VALUE for NaN or a negative one; mode 0 ignores it).  axis 0 counts the selected cells per row (CSR),
+ * axis 1 per column (CSC); the counts are scanned on the device and the handle keeps the pointer array (and, for axis 1, the
+ * offsets of every 64-row block inside its column) there.  *nnz = the number of selected cells.  kernel_ms (may be NULL):
+ * the count and scan kernels' time, also reported by safe_last_kernel_stats.  Synchronises (nnz is a host output).
+ * SAFE_E_INVALID: a NULL or negative argument, a mode outside 0..3, an axis outside 0..1.  SAFE_E_UNSUPPORTED, the number in
+ * the message: n or m >= 2^31, or nnz >= 2^31 (the indices are int32, what SciPy picks below that).  n == 0 or m == 0 gives
+ * an empty selection without a launch (selector_dev may then be NULL).  A refusal leaves *nnz alone and *out NULL.
+ *
+ * safe_pairs_read (safepy/safe.py:470-472, the cells the comparison picked): evaluates the same comparison over
+ * selector_dev once more and writes indptr_host int32 [n + 1] (axis 0) or [m + 1] (axis 1), indices_host int32 [nnz] -- the
+ * column indices of every row in ascending order, or the row indices of every column in ascending order -- and data_host
+ * f64 [nnz]: the cells of values_dev (row-major f64 [n, m] on the device; may be selector_dev itself) at those places, copied
+ * bit for bit (NaN payloads, signed zeros, denormals).  values_dev NULL: the pattern only, data_host is not touched and may be
+ * NULL.  Indices and values are gathered into device buffers of the call and copied out; it has host outputs, so it
+ * synchronises.  May be called again (other values).  kernel_ms (may be NULL): the emit kernel's time.
+ * selector_dev is the caller's memory and must hold what safe_pairs_create saw.  If it does not, nothing is stored outside
+ * the range the scan gave each row or column, and the call fails with SAFE_E_VALUE ("selection changed between create and
+ * read").  A refusal writes nothing to indptr_host, indices_host or data_host.
+ *
+ * safe_pairs_destroy waits for the context's stream and frees the handle's device arrays.  NULL is fine. */
+int safe_pairs_create(safe_ctx *ctx, const double *selector_dev, int64_t n, int64_t m, int mode, double threshold, int axis,
+                      safe_pairs **out, int64_t *nnz, double *kernel_ms);
+int safe_pairs_read(safe_pairs *pairs, const double *selector_dev, const double *values_dev, int32_t *indptr_host,
+                    int32_t *indices_host, double *data_host, double *kernel_ms);
+int safe_pairs_destroy(safe_pairs *pairs);
 
 /* Name and average duration (ms) of the dominant kernel of the last enrichment call,
  * measured with HIP events on the context stream (bench.py's roofline object). */

@@ -184,6 +184,9 @@ PROTOTYPES = {
     'safe_node_domains': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     'safe_linkage_average': (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(C.c_double)]),
     'safe_profile_linkage': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, C.POINTER(C.c_double)]),
+    'safe_pairs_create': (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_int, _pp, _pi64, C.POINTER(C.c_double)]),
+    'safe_pairs_read': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    'safe_pairs_destroy': (C.c_int, [_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

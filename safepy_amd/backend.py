@@ -467,6 +467,19 @@ class Context:
                                     _ptr(sums), _ptr(primary), _ptr(pnes), C.byref(ms)))
         return sums, primary, pnes, ms.value
 
+    def enriched_pairs(self, selector_ptr, values_ptr, n, m, mode, threshold, axis):
+        """The selected cells of the row-major [n, m] f64 device matrix at selector_ptr as the arrays of a scipy.sparse CSR
+        (axis 0) or CSC (axis 1) matrix, compacted on the device (safe_pairs_create / _read / _destroy; modes: Pairs.MODES).
+        values_ptr: the [n, m] device matrix whose cells become `data` (may be selector_ptr), or None for the pattern alone
+        (data is then None).  Neither matrix is written, freed or copied whole.  Returns (indptr int32 [n + 1] or [m + 1],
+        indices int32 [nnz], data f64 [nnz] or None, (count kernels ms, emit kernel ms))."""
+        pairs = Pairs(self, selector_ptr, n, m, mode, threshold, axis)
+        try:
+            indptr, indices, data, read_ms = pairs.read(selector_ptr, values_ptr)
+            return indptr, indices, data, (pairs.create_ms, read_ms)
+        finally:
+            pairs.close()
+
     def euclidean_dense(self, xy_dev_ptr, n, nr, mask_dev_ptr=None, dist_dev_ptr=None):
         check(lib.safe_euclidean_dense_dev(self.handle, C.c_void_p(xy_dev_ptr), int(n), float(nr),
                                            C.c_void_p(mask_dev_ptr) if mask_dev_ptr else None,
@@ -608,6 +621,56 @@ class KamadaKawai:
     def close(self):
         if self.handle:
             check(lib.safe_kk_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pairs:
+    """One selection of a device-resident [n, m] f64 matrix, counted and scanned on the device (safe_pairs_create): `nnz`
+    is known, `read` emits the indices and gathers values.  mode: 0 x > 0, 1 |x| > threshold, 2 x > threshold,
+    3 x < -threshold (strict; NaN never); axis 0 by row (CSR), 1 by column (CSC).  Raises SafeHipError: E_INVALID for a bad
+    mode or axis, E_VALUE for a NaN or negative threshold, E_UNSUPPORTED when a side or nnz reaches 2**31."""
+
+    MODES = {'positive_nonzero': 0, 'both': 1, 'positive': 2, 'negative': 3}
+
+    def __init__(self, ctx, selector_ptr, n, m, mode, threshold, axis):
+        self.ctx = ctx
+        self.handle = None
+        self.n, self.m, self.axis = int(n), int(m), int(axis)
+        h = C.c_void_p()
+        nnz = C.c_int64()
+        ms = C.c_double()
+        check(lib.safe_pairs_create(ctx.handle, C.c_void_p(selector_ptr) if selector_ptr else None, self.n, self.m, int(mode),
+                                    float(threshold), self.axis, C.byref(h), C.byref(nnz), C.byref(ms)))
+        self.handle = h
+        self.nnz = nnz.value
+        self.create_ms = ms.value
+
+    def read(self, selector_ptr, values_ptr=None, out=None):
+        """(indptr, indices, data or None, emit kernel ms).  selector_ptr must hold what the constructor saw: SafeHipError
+        E_VALUE otherwise, and nothing is written.  out: (indptr, indices, data) arrays to fill instead of fresh ones."""
+        dim = self.n if self.axis == 0 else self.m
+        if out is None:
+            out = (np.empty(dim + 1, dtype=np.int32), np.empty(self.nnz, dtype=np.int32),
+                   np.empty(self.nnz, dtype=np.float64) if values_ptr else None)
+        indptr, indices, data = out
+        if (indptr.shape, indptr.dtype) != ((dim + 1,), np.int32) or (indices.shape, indices.dtype) != ((self.nnz,), np.int32) or (
+                values_ptr and (data.shape, data.dtype) != ((self.nnz,), np.float64)):
+            raise ValueError('Pairs.read: output arrays of the wrong shape or type')
+        ms = C.c_double()
+        check(lib.safe_pairs_read(self.handle, C.c_void_p(selector_ptr) if selector_ptr else None,
+                                  C.c_void_p(values_ptr) if values_ptr else None, _ptr(indptr), _ptr(indices),
+                                  _ptr(data) if values_ptr else None, C.byref(ms)))
+        return indptr, indices, data if values_ptr else None, ms.value
+
+    def close(self):
+        if self.handle:
+            check(lib.safe_pairs_destroy(self.handle))
             self.handle = None
 
     def __del__(self):
@@ -1271,3 +1334,8 @@ def profile_linkage(ctx, values_dev_ptr, n, m, cols, metric):
 def node_domains(ctx, nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids):
     """Context.node_domains: (sums [n, len(ids)], primary int32 [n], primary_nes [n], kernel ms)."""
     return ctx.node_domains(nes_binary_dev_ptr, nes_dev_ptr, n, m, domain, ids)
+
+
+def enriched_pairs(ctx, selector_ptr, values_ptr, n, m, mode, threshold, axis):
+    """Context.enriched_pairs: (indptr int32, indices int32 [nnz], data f64 [nnz] or None, (count ms, emit ms))."""
+    return ctx.enriched_pairs(selector_ptr, values_ptr, n, m, mode, threshold, axis)

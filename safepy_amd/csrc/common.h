@@ -219,7 +219,7 @@ void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes);
 
 // Device memory of the library: every block comes from dev_alloc and goes back through dev_free.  Who owns a block:
 //   * the context: its scratch slots (ctx_scratch) and pooled small blocks (ctx_block_alloc), until safe_ctx_destroy;
-//   * a handle (safe_nbr, safe_attr, safe_perms, safe_kk): its members, plain pointers, until the handle's destroy;
+//   * a handle (safe_nbr, safe_attr, safe_perms, safe_kk, safe_pairs): its members, plain pointers, until the handle's destroy;
 //   * a call: a CallBufs (below) on the stack of the entry point, until it returns -- on whatever path.
 // calls of hipMalloc / hipHostMalloc made by the library so far (safe_alloc_count): a timed step is expected to make none
 extern std::atomic<long long> g_alloc_calls;

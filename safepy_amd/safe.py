@@ -8,7 +8,9 @@ error behaviour as `safepy.safe.SAFE` (safepy/safe.py:37-608) for
 radii; 'diameter' is the reference's rule).  `print_output_files()` writes the reference's
 three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The plot methods
 (`plot_network`, `plot_sample_attributes`, `plot_composite_network`, `plot_composite_network_contours`) draw with
-matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  The MATLAB / Cytoscape
+matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  Additive:
+`enriched_pairs()` / `enriched_table()` return the enriched (node, attribute) pairs as a scipy.sparse array / a long
+DataFrame, compacted on the device while the result matrices are still there (pairs.hip).  The MATLAB / Cytoscape
 loaders are out of scope.
 """
 import configparser
@@ -1062,6 +1064,103 @@ class SAFE:
         if self.verbose:
             logging.info('Removed %d domains because they were the top choice for less than %d neighborhoods.'
                          % (len(small), min_nodes))
+
+    # ------------------------------------------------------------------ sparse results ----
+    PAIR_VALUES = ('nes', 'pvalues_pos', 'pvalues_neg', 'ns', 'nes_binary')
+
+    def enriched_pairs(self, values='nes', format='csr', threshold=None, side='both'):
+        """The enriched (node, attribute) pairs as a scipy.sparse array of shape [N, M] (no counterpart in the reference,
+        whose users run np.nonzero(nes_binary) and nes[rows, cols] on the dense matrices; the comparison is that of
+        safepy/safe.py:470).
+
+        Selection.  threshold=None: the cells where nes_binary > 0.  threshold=t (a float >= 0, or inf): the cells of nes
+        with |nes| > t (side='both'), nes > t ('positive') or nes < -t ('negative').  The comparison is strict; NaN is never
+        selected, -0.0 is not selected at t = 0, +-inf are.
+
+        values names the result matrix whose cells become `data` ('nes', 'pvalues_pos', 'pvalues_neg', 'ns', 'nes_binary'),
+        copied bit for bit, as float64.  values=None gives the pattern alone: data is int8 ones.  The stored entries are
+        exactly the selected cells: a selected cell whose value is 0 is still stored, as an explicit zero (so `.nnz` counts
+        the selection; `.eliminate_zeros()` would drop such cells).
+
+        format: 'csr' (csr_array), 'csc' (csc_array) or 'coo' (coo_array, row-major order).  Indices are sorted inside every
+        row / column and int32.
+
+        While every matrix the call needs -- nes_binary or nes for the selection, and the values matrix -- is still on the
+        device (nobody has read it), the pairs are compacted there (backend.Context.enriched_pairs) and only they cross the
+        link; the matrices stay on the device.  Otherwise the host arrays are indexed with NumPy."""
+        import scipy.sparse as sp
+        if values is not None and values not in self.PAIR_VALUES:
+            raise ValueError('enriched_pairs: values=%r is not None or one of %s' % (values, ', '.join(self.PAIR_VALUES)))
+        if format not in ('csr', 'csc', 'coo'):
+            raise ValueError("enriched_pairs: format=%r is not 'csr', 'csc' or 'coo'" % (format,))
+        if side not in ('both', 'positive', 'negative'):
+            raise ValueError("enriched_pairs: side=%r is not 'both', 'positive' or 'negative'" % (side,))
+        if threshold is None:
+            selector, mode, t = 'nes_binary', be.Pairs.MODES['positive_nonzero'], 0.0
+        else:
+            t = float(threshold)
+            if not t >= 0.0:
+                raise ValueError('enriched_pairs: threshold=%r is not a number >= 0' % (threshold,))
+            selector, mode = 'nes', be.Pairs.MODES[side]
+        needed = [selector] + ([values] if values is not None and values != selector else [])
+        slots = [self.__dict__.get('_r_' + name) for name in needed]
+        for name, slot in zip(needed, slots):
+            if slot is None:
+                raise ValueError('enriched_pairs: %s is not set (run compute_pvalues first; the hypergeometric test leaves '
+                                 'ns and pvalues_neg unset)' % name)
+        shape = tuple(int(d) for d in slots[0].shape)
+        if len(shape) != 2 or any(tuple(s.shape) != shape for s in slots):
+            raise ValueError('enriched_pairs: %s do not share one [N, M] shape' % ' and '.join(needed))
+
+        axis = 1 if format == 'csc' else 0
+        if all(isinstance(s, _DeviceResult) for s in slots):
+            sel_ptr = slots[0].buf.ptr
+            val_ptr = None if values is None else slots[-1].buf.ptr
+            indptr, indices, data, _ = self._ctx().enriched_pairs(sel_ptr, val_ptr, shape[0], shape[1], mode, t, axis)
+        else:
+            sel = np.asarray(getattr(self, selector))
+            with np.errstate(invalid='ignore'):
+                mask = (sel > 0, np.abs(sel) > t, sel > t, sel < -t)[mode]
+            major, minor = np.nonzero(mask.T if axis else mask)
+            indptr = np.zeros(shape[1 if axis else 0] + 1, dtype=np.int32)
+            np.cumsum(np.bincount(major, minlength=indptr.shape[0] - 1), out=indptr[1:])
+            indices = minor.astype(np.int32)
+            data = None
+            if values is not None:
+                rows, cols = (minor, major) if axis else (major, minor)
+                data = np.ascontiguousarray(np.asarray(getattr(self, values), dtype=np.float64)[rows, cols])
+        if data is None:
+            data = np.ones(indices.shape[0], dtype=np.int8)
+        if format == 'coo':
+            row = np.repeat(np.arange(shape[0], dtype=np.int32), np.diff(indptr))
+            out = sp.coo_array((data, (row, indices)), shape=shape)
+            out.has_canonical_format = True                        # row-major, no duplicates: by construction
+            return out
+        return (sp.csc_array if axis else sp.csr_array)((data, indices, indptr), shape=shape)
+
+    def enriched_table(self, values='nes', threshold=None, side='both'):
+        """enriched_pairs as a long pandas.DataFrame, one row per pair in row-major order: 'node' (row index), 'key' and
+        'label' (of self.nodes), 'attribute' (column index), 'name' (of self.attributes), a column named after `values`
+        (none for values=None) and, when self.attributes has it, 'domain'.  Built on the host from the COO form."""
+        pairs = self.enriched_pairs(values=values, format='coo', threshold=threshold, side=side)
+        row, col = pairs.row, pairs.col
+        nodes = self.nodes
+        if nodes is not None and 'key' in nodes and 'label' in nodes and len(nodes) == pairs.shape[0]:
+            keys, labels = nodes['key'].to_numpy(), nodes['label'].to_numpy()
+        elif self.graph is not None:
+            _, keys, labels = self._graph_keys_labels()
+            keys, labels = np.asarray(keys, dtype=object), np.asarray(labels, dtype=object)
+        else:
+            raise ValueError('enriched_table: neither self.nodes nor self.graph names the %d nodes' % pairs.shape[0])
+        attrs = self.attributes
+        if attrs is None or 'name' not in attrs or len(attrs) != pairs.shape[1]:
+            raise ValueError('enriched_table: self.attributes does not name the %d attributes' % pairs.shape[1])
+        table = {'node': row, 'key': keys[row], 'label': labels[row], 'attribute': col, 'name': attrs['name'].to_numpy()[col]}
+        if values is not None:
+            table[values] = pairs.data
+        if 'domain' in attrs:
+            table['domain'] = attrs['domain'].to_numpy()[col]
+        return pd.DataFrame(table)
 
     # ------------------------------------------------------------------ plots ----
     def _columns(self, name, cols):
