@@ -291,6 +291,10 @@ int safe_attr_stats(safe_attr *attr, int64_t *n_other, int64_t *max_nan_col,
 /* row_has_value[i] = 1 iff row i has >= 1 non-NaN value: indx_vals of
  * safepy/safe_extras.py:51 and nodes_not_nan of safepy/safe.py:574. */
 int safe_attr_row_flags(safe_attr *attr, uint8_t *out_host);
+/* nansum of every column in f64 (np.nansum(node2attribute, axis=0), safepy/safe.py:583: the hypergeometric N_in_group): the sums the
+ * statistics pass left on the device, out_host f64 [m].  Integer-valued columns are exact; other values add in an order
+ * that depends on the layout.  Host output: synchronises. */
+int safe_attr_column_sums(safe_attr *attr, double *out_host);
 /* Override the row flags (attribute-sharded multi-GPU runs must use the flags of the
  * FULL matrix, not of the local column shard). */
 int safe_attr_set_row_flags(safe_attr *attr, const uint8_t *flags_host);

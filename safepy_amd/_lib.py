@@ -124,6 +124,7 @@ PROTOTYPES = {
     'safe_attr_download': (C.c_int, [_vp, _vp]),
     'safe_attr_stats': (C.c_int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     'safe_attr_row_flags': (C.c_int, [_vp, _vp]),
+    'safe_attr_column_sums': (C.c_int, [_vp, _vp]),
     'safe_attr_set_row_flags': (C.c_int, [_vp, _vp]),
     'safe_perms_create': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_uint32, _pp]),
     'safe_perms_destroy': (C.c_int, [_vp]),

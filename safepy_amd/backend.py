@@ -829,6 +829,12 @@ class Attributes:
         check(lib.safe_attr_row_flags(self.handle, _ptr(out)))
         return out
 
+    def column_sums(self):
+        """nansum of every column, f64 [m], as the statistics pass left it on the device (exact for integer-valued data)."""
+        out = np.empty(self.m, dtype=np.float64)
+        check(lib.safe_attr_column_sums(self.handle, _ptr(out)))
+        return out
+
     def set_row_flags(self, flags):
         flags = np.ascontiguousarray(flags, dtype=np.uint8)
         assert flags.shape == (self.n,)

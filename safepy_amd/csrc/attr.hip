@@ -841,6 +841,17 @@ int safe_attr_row_flags(safe_attr *attr, uint8_t *out_host) {
     return SAFE_OK;
 }
 
+int safe_attr_column_sums(safe_attr *attr, double *out_host) {
+    SAFE_REQUIRE(attr && out_host, "safe_attr_column_sums: NULL argument");
+    SAFE_TRY(safe_attr_prepare(attr));
+    safe_ctx *ctx = attr->ctx;
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    SAFE_HIP_CHECK(hipMemcpyAsync(out_host, attr->col_sum, static_cast<size_t>(attr->m) * sizeof(double), hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    return SAFE_OK;
+}
+
 int safe_attr_set_row_flags(safe_attr *attr, const uint8_t *flags_host) {
     SAFE_REQUIRE(attr && flags_host, "safe_attr_set_row_flags: NULL argument");
     safe_ctx *ctx = attr->ctx;

@@ -130,6 +130,11 @@ def test_to_dense(be, net, dev):
     assert np.array_equal(dev['nbr'].to_dense(), net['member'])
 
 
+def test_attr_column_sums(be, net, dev):
+    assert_steady(be, dev['attr'].column_sums)
+    assert np.array_equal(dev['attr'].column_sums(), net['binary'].sum(axis=0))
+
+
 def test_score_and_randomization_gather(be, ctx, dev, monkeypatch):
     monkeypatch.setenv('SAFE_HIP_FORCE_PATH', 'gather')                  # the f64 tiles of build_tiles
     ptrs = [b.ptr for b in dev['bufs'][:5]] + [dev['enr'].ptr]
