@@ -26,7 +26,8 @@
  *     context's stream like them but return only once it has drained, because they read
  *     a flag or a timing event back or keep host memory alive for their kernels:
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
- *     safe_fdr_adjust, safe_outputs_from_counts, safe_outputs_from_packed_counts,
+ *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_fdr_adjust, safe_fdr_adjust_rows,
+ *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
  *     (tests/test_gpu_stream_order.py measures both lists).
  *   - safe_ctx_set_stream orders the stream it switches to behind the one it leaves:
@@ -425,6 +426,35 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
 int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
                     double enrichment_threshold, double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev,
                     double *nes_binary_dev, double *num_enriched_dev);
+
+/* Benjamini-Hochberg adjustment of every row of ONE matrix (f64 [n,m] row-major), in place: what safe_fdr_adjust with
+ * num_permutations = 0 does to pvalues_pos_dev, without the NES epilogue (the rows are sorted; no histogram form). */
+int safe_fdr_adjust_rows(safe_ctx *ctx, int64_t n, int64_t m, double *p_dev);
+
+/* The hypergeometric test with BOTH tails, for 0/1 attributes (NaN allowed): what compute_pvalues_by_hypergeom would set if it
+ * followed attribute_sign the way the randomization route does (safepy/safe.py:546-554; the reference computes the upper tail
+ * only, safe.py:596).  All outputs f64 [n, col1 - col0] row-major, num_enriched_dev f64 [col1 - col0]:
+ *   ns          x = A . nan_to_num(B)  (safe.py:593-594; safe_score 'sum')
+ *   pvalues_pos P[H >= x] = hypergeom.sf(x - 1, N, K, n), N / K / n as at safe.py:574-590
+ *   pvalues_neg P[H <= x] = hypergeom.cdf(x, N, K, n): 0 below the support, 1 at or above its top
+ *   nes         -log10 pvalues_pos (SAFE_SIGN_HIGHEST), -log10 pvalues_neg (SAFE_SIGN_LOWEST), the first minus the second
+ *               (SAFE_SIGN_BOTH); no 1 / P substitution: p = 0 gives +-inf (safe.py:608)
+ *   nes_binary  |nes| > -log10(enrichment_threshold) (safe.py:468-472): decided on p itself for one side, on the difference of the
+ *               logarithms in doubles for SAFE_SIGN_BOTH; NaN -> 0.  num_enriched = its column sums.
+ * evaluator: 0 = the library chooses, 1 = the table evaluator (one thread per distinct (n, K) pair, both tails in double-double,
+ * correctly rounded but for ties; SAFE_E_UNSUPPORTED when the table would exceed 512 MB or the call has fewer than 4 cells per
+ * pair), 2 = the per-element evaluator (relative error <= 1e-6 for p >= 1e-290).  A matrix that holds anything but 0, 1 and NaN is
+ * SAFE_E_VALUE, reported before anything is launched.  safe_last_kernel_stats names the evaluator: k_hyp_tails_emit<table> or
+ * k_hyp_tails_emit<element>. */
+int safe_hypergeom_tails(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int sign_mode, double enrichment_threshold,
+                         int evaluator, int64_t col0, int64_t col1, double *ns_dev, double *pvalues_neg_dev,
+                         double *pvalues_pos_dev, double *nes_dev, double *nes_binary_dev, double *num_enriched_dev);
+
+/* NES, nes_binary and the per-attribute counts from two p matrices (f64 [n,m] row-major, read only) under the rules of
+ * safe_hypergeom_tails: what follows safe_fdr_adjust_rows on both matrices when multiple_testing is on. */
+int safe_hypergeom_outputs(safe_ctx *ctx, int64_t n, int64_t m, int sign_mode, double enrichment_threshold,
+                           const double *pvalues_neg_dev, const double *pvalues_pos_dev, double *nes_dev,
+                           double *nes_binary_dev, double *num_enriched_dev);
 
 /* ---- consumers of nes_binary (SAFE.define_top_attributes / define_domains) ---------------- */
 /* Connected components of the subgraph induced by the enriched nodes of each candidate

@@ -138,6 +138,9 @@ PROTOTYPES = {
     'safe_enriched_components': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     'safe_jaccard_condensed': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     'safe_fdr_adjust': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'safe_fdr_adjust_rows': (C.c_int, [_vp, _i64, _i64, _vp]),
+    'safe_hypergeom_tails': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'safe_hypergeom_outputs': (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'safe_export_packed_counts': (C.c_int, [_vp, _vp, _i64, _pi64, _pi64, C.POINTER(C.c_int)]),
     'safe_nes_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, _vp, _vp]),
     'safe_outputs_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),

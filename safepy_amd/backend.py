@@ -1136,6 +1136,28 @@ def hypergeom(ctx, nbr, attr, enrichment_threshold, out_ptrs, col0=0, col1=None)
                              C.c_void_p(pp), C.c_void_p(nes), C.c_void_p(nb), C.c_void_p(ne)))
 
 
+HYP_EVALUATORS = {None: 0, 'auto': 0, 'table': 1, 'element': 2}
+
+
+def hypergeom_tails(ctx, nbr, attr, attribute_sign, enrichment_threshold, out_ptrs, col0=0, col1=None, evaluator=None):
+    """Both hypergeometric tails of 0/1 attributes: out_ptrs = (ns, pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched)
+    device pointers.  evaluator: None / 'auto' (the library chooses), 'table', 'element'."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_hypergeom_tails(ctx.handle, nbr.handle, attr.handle, _SIGN[attribute_sign], float(enrichment_threshold),
+                                   HYP_EVALUATORS[evaluator], col0, col1, *[C.c_void_p(p) if p else None for p in out_ptrs]))
+
+
+def hypergeom_outputs(ctx, n, m, attribute_sign, enrichment_threshold, pvalues_neg_ptr, pvalues_pos_ptr, out_ptrs):
+    """NES, nes_binary and the enriched counts from two p matrices: out_ptrs = (nes, nes_binary, num_enriched)."""
+    check(lib.safe_hypergeom_outputs(ctx.handle, int(n), int(m), _SIGN[attribute_sign], float(enrichment_threshold),
+                                     *[C.c_void_p(p) if p else None for p in (pvalues_neg_ptr, pvalues_pos_ptr) + tuple(out_ptrs)]))
+
+
+def fdr_adjust_rows(ctx, n, m, p_ptr):
+    """Benjamini-Hochberg on every row of one f64 [n, m] device matrix, in place."""
+    check(lib.safe_fdr_adjust_rows(ctx.handle, int(n), int(m), C.c_void_p(p_ptr) if p_ptr else None))
+
+
 def packed_counts_info(ctx):
     """(n_pad, m, layout) of the integer counters the last randomization call left on the device;
     layout -1 = none (f64 kernels)."""

@@ -121,6 +121,11 @@ enum ScratchSlot {
     SCRATCH_HYP_DUMMY,      // 64 write-only f64 for the padding rows / columns of branch-free epilogues (HypLookup::dummy) |
                             //   hypergeom_fused | within the call
     SCRATCH_FDR_FLAG,       // one u32 flag | safe_fdr_adjust's count-ratio check and fdr_matrix's histogram form (fdr.hip) | within the call
+    SCRATCH_TAILS_SMALL,    // neighborhood sizes f64 [n] | enriched counters u32 [mloc] | largest count u32 | safe_hypergeom_tails,
+                            //   safe_hypergeom_outputs (hyptails.hip) | within the call
+    SCRATCH_TAILS_TABLE,    // the (p_pos, p_neg) table [sizes][x][counts] | safe_hypergeom_tails | within the call
+    SCRATCH_TAILS_TERMS,    // the relative pmf (hi, lo) of the same shape between the passes of k_hyp_tails_table | within the call
+    SCRATCH_TAILS_IDS,      // distinct (n, K) values, row / column ids, rows sorted by size id | safe_hypergeom_tails | within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,

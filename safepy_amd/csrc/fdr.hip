@@ -373,3 +373,12 @@ extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_
     SAFE_HIP_CHECK_AS("safe_fdr_adjust", safe_stream_sync(ctx->stream));
     return SAFE_OK;
 }
+
+// Benjamini-Hochberg on every row of one matrix, in place: fdr_matrix's sort form (what safe_fdr_adjust with
+// num_permutations = 0 does to pvalues_pos), without the NES epilogue
+extern "C" int safe_fdr_adjust_rows(safe_ctx *ctx, int64_t n, int64_t m, double *p_dev) {
+    SAFE_REQUIRE(ctx && p_dev, "safe_fdr_adjust_rows: NULL argument");
+    SAFE_REQUIRE(n >= 1 && m >= 1, "safe_fdr_adjust_rows: bad sizes");
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    return fdr_matrix(ctx, p_dev, n, m);
+}

@@ -240,6 +240,7 @@ class SAFE:
         self.multiple_testing = False
         self.neighborhood_score_type = 'sum'
         self.enrichment_type = 'auto'
+        self.hypergeom_tails = 'upper'   # 'attribute_sign': the hypergeometric test follows attribute_sign (both tails, ns, signed nes)
         self.enrichment_threshold = 0.05
         self.enrichment_max_log10 = 16
         self.attribute_enrichment_min_size = 10
@@ -344,6 +345,10 @@ class SAFE:
             bad, self.attribute_sign = self.attribute_sign, self.default_config.get('annotationsign')
             raise ValueError('%s is not a valid setting for attribute_sign. '
                              'Valid options are: highest, lowest, both' % bad)
+        if getattr(self, 'hypergeom_tails', 'upper') not in ['upper', 'attribute_sign']:
+            bad, self.hypergeom_tails = self.hypergeom_tails, 'upper'
+            raise ValueError('%s is not a valid setting for hypergeom_tails. '
+                             'Valid options are: upper, attribute_sign' % (bad,))
         if not isinstance(self.num_permutations, int) or (self.num_permutations < 10):
             self.num_permutations = 1000
             raise ValueError('num_permutations must be an integer equal or greater than 10.')
@@ -389,6 +394,7 @@ class SAFE:
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('hypergeom_tails', 'upper')     # (objects pickled before the setting existed)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -750,6 +756,8 @@ class SAFE:
             self.multiple_testing = kwargs['multiple_testing']
         if 'background' in kwargs:
             self.background = kwargs['background']
+        if 'hypergeom_tails' in kwargs:
+            self.hypergeom_tails = kwargs['hypergeom_tails']
         self.validate_config()
 
         resident = self._resident_attributes()
@@ -852,10 +860,15 @@ class SAFE:
                 attr.close()
 
     def compute_pvalues_by_hypergeom(self, _attr=None, **kwargs):
-        """safepy/safe.py:556-608.  Sets pvalues_pos and nes only (ns / pvalues_neg untouched)."""
+        """safepy/safe.py:556-608.  Sets pvalues_pos and nes only (ns / pvalues_neg untouched) -- the reference's behaviour,
+        hypergeom_tails = 'upper' (the default).  hypergeom_tails = 'attribute_sign' (additive; 0/1 data, NaN allowed) makes the
+        test follow attribute_sign the way the randomization route does: ns, pvalues_pos = P[H >= x], pvalues_neg = P[H <= x],
+        nes = -log10 of the side the sign names ('both': the difference), multiple_testing adjusts both matrices."""
         if kwargs:
             if 'verbose' in kwargs:
                 self.verbose = kwargs['verbose']
+            if 'hypergeom_tails' in kwargs:
+                self.hypergeom_tails = kwargs['hypergeom_tails']
             if self.verbose:
                 logging.warning('Overwriting global settings:')
                 for k in kwargs:
@@ -867,6 +880,13 @@ class SAFE:
         nbr = self._device_neighborhoods()
         attr = _attr if _attr is not None else self._upload_attributes()
         n, m = attr.n, attr.m
+        if self.hypergeom_tails == 'attribute_sign':
+            try:
+                self._hypergeom_both_tails(ctx, nbr, attr)
+            finally:
+                if _attr is None:
+                    attr.close()
+            return
         bufs = [ctx.alloc_f64(n, m) for _ in range(3)] + [ctx.alloc_f64(m)]
         try:
             be.hypergeom(ctx, nbr, attr, self.enrichment_threshold, [b.ptr for b in bufs])
@@ -885,6 +905,33 @@ class SAFE:
                 b.free()
             if _attr is None:
                 attr.close()
+
+    def _hypergeom_both_tails(self, ctx, nbr, attr):
+        """hypergeom_tails = 'attribute_sign': ns, both p matrices, the signed nes and its binarisation from one device call
+        (backend.hypergeom_tails); multiple_testing adjusts every row of both p matrices (fdrcorrection(row)[1], as safe.py:538-542
+        does for randomization) and recomputes nes, nes_binary and the counts from the adjusted values."""
+        n, m = attr.n, attr.m
+        if attr.stats()['n_other'] != 0:                   # before anything is launched
+            raise ValueError("hypergeom_tails = 'attribute_sign' needs 0/1 attribute values (NaN allowed): the matrix holds "
+                             "%d other values" % attr.stats()['n_other'])
+        bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
+        try:
+            be.hypergeom_tails(ctx, nbr, attr, self.attribute_sign, self.enrichment_threshold, [b.ptr for b in bufs])
+            if self.multiple_testing:
+                if self.verbose:
+                    logging.info('Running FDR-adjustment of p-values...')
+                be.fdr_adjust_rows(ctx, n, m, bufs[1].ptr)
+                be.fdr_adjust_rows(ctx, n, m, bufs[2].ptr)
+                be.hypergeom_outputs(ctx, n, m, self.attribute_sign, self.enrichment_threshold, bufs[1].ptr, bufs[2].ptr,
+                                     [b.ptr for b in bufs[3:]])
+            enriched = bufs[5].download((m,))
+            res = [self._result(b, (n, m)) for b in bufs[:5]]
+            bufs = bufs[5:] if self.lazy_outputs else bufs       # handed over: the results own their buffers now
+            self.ns, self.pvalues_neg, self.pvalues_pos, self.nes = res[:4]
+            self._pending_binary = (res[4], enriched)
+        finally:
+            for b in bufs:
+                b.free()
 
     # ------------------------------------------------------------------------------------
     # consumers of nes_binary (SURVEY section 8f, row 2)
