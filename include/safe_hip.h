@@ -26,7 +26,7 @@
  *     context's stream like them but return only once it has drained, because they read
  *     a flag or a timing event back or keep host memory alive for their kernels:
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
- *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_fdr_adjust, safe_fdr_adjust_rows,
+ *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_fdr_adjust, safe_fdr_adjust_rows,
  *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
  *     (tests/test_gpu_stream_order.py measures both lists).
@@ -296,6 +296,13 @@ int safe_attr_row_flags(safe_attr *attr, uint8_t *out_host);
  * statistics pass left on the device, out_host f64 [m].  Integer-valued columns are exact; other values add in an order
  * that depends on the layout.  Host output: synchronises. */
 int safe_attr_column_sums(safe_attr *attr, double *out_host);
+/* Exact first and second moments of columns [col0, col1) over the rows the randomization route permutes (row_has_value = 1:
+ * indx_vals of safepy/safe_extras.py:51; a NaN cell inside them counts as 0, safe_extras.py:10), host f64 [col1 - col0] each:
+ *   mean = column_sum / n_rows_with_value (0 when no row has a value)
+ *   css  = sum over those rows of (b - mean)^2, centred, in a second pass; exactly 0 when the column's min equals its max
+ * Values are widened to f64 before any arithmetic; the summation order is fixed (no floating-point atomics), so two calls
+ * give the same bits.  Runs on the context's stream; host outputs: synchronises. */
+int safe_attr_column_moments(safe_attr *attr, int64_t col0, int64_t col1, double *mean_host, double *css_host);
 /* Override the row flags (attribute-sharded multi-GPU runs must use the flags of the
  * FULL matrix, not of the local column shard). */
 int safe_attr_set_row_flags(safe_attr *attr, const uint8_t *flags_host);
@@ -455,6 +462,24 @@ int safe_hypergeom_tails(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int sign
 int safe_hypergeom_outputs(safe_ctx *ctx, int64_t n, int64_t m, int sign_mode, double enrichment_threshold,
                            const double *pvalues_neg_dev, const double *pvalues_pos_dev, double *nes_dev,
                            double *nes_binary_dev, double *num_enriched_dev);
+
+/* The analytic form of the randomization test for neighborhood_score_type == 'sum' (any attribute values): the null that
+ * run_permutations samples (safepy/safe_extras.py:36-70: the rows with a value are shuffled) has closed-form moments, so no
+ * permutation is drawn, the result has no seed, and p-values run down to the smallest double instead of 1 / num_permutations.
+ * With n_v = n_rows_with_value, mu_j and Q_j the mean and css of safe_attr_column_moments, k_i the members of neighborhood i
+ * that have a value, all outputs f64 [n, col1 - col0] row-major, num_enriched_dev f64 [col1 - col0]:
+ *   ns          x = A . nan_to_num(B)  (safe_score 'sum')
+ *   var         k_i (n_v - k_i) / (n_v (n_v - 1)) * Q_j, rounded in that order
+ *   z           (x - k_i * mu_j) / sqrt(var); written to z_dev when it is not NULL
+ *   pvalues_pos P[Z >= z], pvalues_neg P[Z <= z] for a standard normal Z: the smaller one is erfc(|z| * sqrt(1/2)) / 2 -- one
+ *               erfc per cell -- and the larger one 1 minus that
+ *   degenerate  n_v < 2, k_i = 0, k_i = n_v or a constant column (var not positive): every permuted score equals the observed
+ *               one, so pvalues_pos = pvalues_neg = 1 and z = 0, the permutation test's own limit
+ *   nes, nes_binary, num_enriched: the rules of safe_hypergeom_tails (no 1 / P substitution, p = 0 gives +-inf)
+ * safe_last_kernel_stats names k_moments_emit. */
+int safe_moments_test(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int sign_mode, double enrichment_threshold,
+                      int64_t col0, int64_t col1, double *ns_dev, double *pvalues_neg_dev, double *pvalues_pos_dev,
+                      double *nes_dev, double *nes_binary_dev, double *num_enriched_dev, double *z_dev /* may be NULL */);
 
 /* ---- consumers of nes_binary (SAFE.define_top_attributes / define_domains) ---------------- */
 /* Connected components of the subgraph induced by the enriched nodes of each candidate

@@ -125,6 +125,7 @@ PROTOTYPES = {
     'safe_attr_stats': (C.c_int, [_vp, _pi64, _pi64, _pi64, _pi64]),
     'safe_attr_row_flags': (C.c_int, [_vp, _vp]),
     'safe_attr_column_sums': (C.c_int, [_vp, _vp]),
+    'safe_attr_column_moments': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     'safe_attr_set_row_flags': (C.c_int, [_vp, _vp]),
     'safe_perms_create': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_uint32, _pp]),
     'safe_perms_destroy': (C.c_int, [_vp]),
@@ -141,6 +142,7 @@ PROTOTYPES = {
     'safe_fdr_adjust_rows': (C.c_int, [_vp, _i64, _i64, _vp]),
     'safe_hypergeom_tails': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_hypergeom_outputs': (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'safe_moments_test': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_export_packed_counts': (C.c_int, [_vp, _vp, _i64, _pi64, _pi64, C.POINTER(C.c_int)]),
     'safe_nes_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, _vp, _vp]),
     'safe_outputs_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),

@@ -835,6 +835,15 @@ class Attributes:
         check(lib.safe_attr_column_sums(self.handle, _ptr(out)))
         return out
 
+    def column_moments(self, col0=0, col1=None):
+        """(mean, css) of columns [col0, col1), f64 each: the column's mean over the rows that hold a value (NaN cells inside
+        them count as 0) and its centred sum of squares over the same rows, exactly 0 for a constant column
+        (safe_attr_column_moments).  Two calls return the same bits."""
+        col1 = self.m if col1 is None else col1
+        mean, css = np.empty(max(col1 - col0, 0), dtype=np.float64), np.empty(max(col1 - col0, 0), dtype=np.float64)
+        check(lib.safe_attr_column_moments(self.handle, int(col0), int(col1), _ptr(mean), _ptr(css)))
+        return mean, css
+
     def set_row_flags(self, flags):
         flags = np.ascontiguousarray(flags, dtype=np.uint8)
         assert flags.shape == (self.n,)
@@ -1151,6 +1160,14 @@ def hypergeom_outputs(ctx, n, m, attribute_sign, enrichment_threshold, pvalues_n
     """NES, nes_binary and the enriched counts from two p matrices: out_ptrs = (nes, nes_binary, num_enriched)."""
     check(lib.safe_hypergeom_outputs(ctx.handle, int(n), int(m), _SIGN[attribute_sign], float(enrichment_threshold),
                                      *[C.c_void_p(p) if p else None for p in (pvalues_neg_ptr, pvalues_pos_ptr) + tuple(out_ptrs)]))
+
+
+def moments_test(ctx, nbr, attr, attribute_sign, enrichment_threshold, out_ptrs, col0=0, col1=None, z_ptr=None):
+    """The analytic test of 'sum' scores (exact permutation moments, normal tails; safe_moments_test): out_ptrs = (ns,
+    pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched) device pointers; z_ptr: where the z matrix goes, or None."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_moments_test(ctx.handle, nbr.handle, attr.handle, _SIGN[attribute_sign], float(enrichment_threshold), col0, col1,
+                                *[C.c_void_p(p) if p else None for p in tuple(out_ptrs) + (z_ptr,)]))
 
 
 def fdr_adjust_rows(ctx, n, m, p_ptr):

@@ -126,6 +126,11 @@ enum ScratchSlot {
     SCRATCH_TAILS_TABLE,    // the (p_pos, p_neg) table [sizes][x][counts] | safe_hypergeom_tails | within the call
     SCRATCH_TAILS_TERMS,    // the relative pmf (hi, lo) of the same shape between the passes of k_hyp_tails_table | within the call
     SCRATCH_TAILS_IDS,      // distinct (n, K) values, row / column ids, rows sorted by size id | safe_hypergeom_tails | within the call
+    SCRATCH_MOMENTS_SMALL,  // neighborhood sizes f64 [n] | row factors f64 [n] | column means f64 [mloc] | centred sums of squares f64
+                            //   [mloc] | enriched counters u32 [mloc + 16] | safe_moments_test, safe_attr_column_moments (moments.hip) |
+                            //   within the call
+    SCRATCH_MOMENTS_PARTS,  // per (row chunk, column) partial sum of squares | min | max, f64 [3][chunks][mloc] | k_col_moments ->
+                            //   k_col_moments_fold (moments.hip) | within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,

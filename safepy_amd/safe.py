@@ -759,6 +759,8 @@ class SAFE:
         if 'hypergeom_tails' in kwargs:
             self.hypergeom_tails = kwargs['hypergeom_tails']
         self.validate_config()
+        if self.enrichment_type == 'analytic':
+            self._require_sum_scores_for_moments()             # before any device work
 
         resident = self._resident_attributes()
         if self.background == 'network':
@@ -797,7 +799,9 @@ class SAFE:
                                 "will be ignored for calculating enrichment.\n"
                                 "Consider setting sf.background = 'network'.")
             self._pending_binary = None
-            if (self.enrichment_type == 'hypergeometric') or \
+            if self.enrichment_type == 'analytic':              # additive and opt-in: 'auto' never chooses it
+                self.compute_pvalues_by_moments(_attr=attr, **kwargs)
+            elif (self.enrichment_type == 'hypergeometric') or \
                     ((self.enrichment_type == 'auto') and (stats['n_other'] == 0)):
                 self.compute_pvalues_by_hypergeom(_attr=attr, **kwargs)
             else:
@@ -906,17 +910,58 @@ class SAFE:
             if _attr is None:
                 attr.close()
 
+    def _require_sum_scores_for_moments(self):
+        if self.neighborhood_score_type != 'sum':
+            raise ValueError("how = 'analytic' is defined for neighborhood_score_type = 'sum' only (the permutation null of "
+                             "'%s' is not a sum of draws); use how = 'randomization'" % self.neighborhood_score_type)
+
+    def compute_pvalues_by_moments(self, _attr=None, **kwargs):
+        """how = 'analytic' (additive; no counterpart in the reference): the randomization test of 'sum' scores without
+        permutations.  The null that run_permutations samples (safe_extras.py:36-70) has closed-form mean and variance per
+        cell; pvalues_pos / pvalues_neg are the normal tails of the exact z, so they are deterministic, need no seed and run
+        down to the smallest double instead of 1 / num_permutations (num_permutations and random_seed are ignored).  Sets ns,
+        pvalues_neg, pvalues_pos, nes and nes_binary under the rules of hypergeom_tails = 'attribute_sign'; multiple_testing
+        adjusts every row of both p matrices.  neighborhood_score_type = 'z-score' is refused: its null is not a sum."""
+        if kwargs:
+            if 'verbose' in kwargs:
+                self.verbose = kwargs['verbose']
+            if 'neighborhood_score_type' in kwargs:
+                self.neighborhood_score_type = kwargs['neighborhood_score_type']
+            if self.verbose:
+                logging.warning('Overwriting global settings:')
+                for k in kwargs:
+                    logging.warning('\t%s=%s' % (k, str(kwargs[k])))
+        self.validate_config()
+        self._require_sum_scores_for_moments()                   # before any device work
+        if self.verbose:
+            logging.info('Using the exact permutation moments to calculate enrichment...')
+        ctx = self._ctx()
+        nbr = self._device_neighborhoods()
+        attr = _attr if _attr is not None else self._upload_attributes()
+        try:
+            self._two_sided_results(ctx, attr.n, attr.m, lambda out_ptrs: be.moments_test(
+                ctx, nbr, attr, self.attribute_sign, self.enrichment_threshold, out_ptrs))
+        finally:
+            if _attr is None:
+                attr.close()
+
     def _hypergeom_both_tails(self, ctx, nbr, attr):
         """hypergeom_tails = 'attribute_sign': ns, both p matrices, the signed nes and its binarisation from one device call
-        (backend.hypergeom_tails); multiple_testing adjusts every row of both p matrices (fdrcorrection(row)[1], as safe.py:538-542
-        does for randomization) and recomputes nes, nes_binary and the counts from the adjusted values."""
-        n, m = attr.n, attr.m
+        (backend.hypergeom_tails), finished by _two_sided_results."""
         if attr.stats()['n_other'] != 0:                   # before anything is launched
             raise ValueError("hypergeom_tails = 'attribute_sign' needs 0/1 attribute values (NaN allowed): the matrix holds "
                              "%d other values" % attr.stats()['n_other'])
+        self._two_sided_results(ctx, attr.n, attr.m, lambda out_ptrs: be.hypergeom_tails(
+            ctx, nbr, attr, self.attribute_sign, self.enrichment_threshold, out_ptrs))
+
+    def _two_sided_results(self, ctx, n, m, device_call):
+        """The part the two-sided tests share (hypergeom_tails = 'attribute_sign', how = 'analytic'): device_call(out_ptrs) fills
+        (ns, pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched); multiple_testing adjusts every row of both p matrices
+        (fdrcorrection(row)[1], as safe.py:538-542 does for randomization) and recomputes nes, nes_binary and the counts from the
+        adjusted values; the matrices become the results, on the device until read."""
         bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
         try:
-            be.hypergeom_tails(ctx, nbr, attr, self.attribute_sign, self.enrichment_threshold, [b.ptr for b in bufs])
+            device_call([b.ptr for b in bufs])
             if self.multiple_testing:
                 if self.verbose:
                     logging.info('Running FDR-adjustment of p-values...')

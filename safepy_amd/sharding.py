@@ -706,6 +706,8 @@ def sharded_compute_pvalues(ctx, nbr, local_attr_host, m_total, enrichment_type=
     whose worker processes each decide for their own chunk.  multiple_testing=True adjusts every row
     across ALL attributes as the unsplit call does (the p-value blocks are gathered first).  One upload
     of the block, one exchange of flags / statistics / seed, then the branch."""
+    if enrichment_type == 'analytic':                        # (SAFE.compute_pvalues_by_moments; it would run permutations here)
+        raise ValueError("enrichment_type = 'analytic' has no sharded form: call SAFE.compute_pvalues(how='analytic') on one device")
     from . import backend as be
     attr = be.Attributes.from_host(ctx, local_attr_host)
     try:
