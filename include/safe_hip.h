@@ -504,6 +504,20 @@ int safe_jaccard_condensed(safe_ctx *ctx, int64_t m_top, int64_t n, const double
 int safe_enriched_components_dev(safe_ctx *ctx, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v, const double *values_dev,
                                  int64_t n, int64_t m, const int64_t *cols_host, int64_t n_cols, int32_t *labels_host,
                                  double *kernel_ms);
+/* Enriched-pair counts (SAFE.define_top_attributes, attribute_unimodality_metric = 'radius'): for every chosen column a, with
+ * E_a = {i : value[i, a] > 0} (NaN, 0, -0.0 and negatives are not enriched),
+ *   e_host[a] = |E_a|      q_host[a] = sum over i in E_a, j in E_a of W[i, j]
+ * where W is the membership of `within` -- ANY handle: the raw quadratic form, ordered pairs, the diagonal as W holds it; for a
+ * symmetric W with a full diagonal (q - e) / 2 is the number of unordered pairs of enriched nodes within reach.  Exact integers:
+ * the columns are packed to bits and counted with AND + popcount against the handle's bit matrix.  The host form takes
+ * member_host f64 [n, n_cols] row-major with n = the handle's n; the device form reads the columns cols_host (each in [0, m),
+ * repeats allowed) of values_dev f64 [n, m] in place on the context's stream, n = the handle's n (SAFE_E_INVALID otherwise),
+ * and never copies them densely.  A NULL pointer or a column out of range is SAFE_E_INVALID with nothing written; n_cols == 0
+ * writes nothing.  Both synchronise.  safe_last_kernel_stats names k_profile_pack+k_pair_count. */
+int safe_enriched_pair_counts(safe_ctx *ctx, safe_nbr *within, const double *member_host, int64_t n_cols, int64_t *q_host,
+                              int64_t *e_host);
+int safe_enriched_pair_counts_dev(safe_ctx *ctx, safe_nbr *within, const double *values_dev, int64_t n, int64_t m,
+                                  const int64_t *cols_host, int64_t n_cols, int64_t *q_host, int64_t *e_host, double *kernel_ms);
 /* safe_profile_distances: out_host f64 [m_top (m_top - 1) / 2] = scipy.spatial.distance.pdist(values[:, cols_host].T, metric)
  * (SciPy 1.15, condensed order) for a boolean metric, bit for bit: the columns are packed into bit words (non-zero = set),
  * the four contingency counts of a pair come from popcounts and each metric is one division of exact integers; where a

@@ -186,6 +186,8 @@ PROTOTYPES = {
     'safe_domain_counts': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
     'safe_gather_columns': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
     'safe_enriched_components_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(C.c_double)]),
+    'safe_enriched_pair_counts': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    'safe_enriched_pair_counts_dev': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, C.POINTER(C.c_double)]),
     'safe_profile_distances': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, C.POINTER(C.c_double)]),
     'safe_node_domains': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     'safe_linkage_average': (C.c_int, [_vp, _vp, _i64, _vp, C.POINTER(C.c_double)]),

@@ -386,6 +386,19 @@ class Context:
                                                cols.shape[0], _ptr(out), C.byref(ms)))
         return out, ms.value
 
+    def enriched_pair_counts_dev(self, nbr, values_dev_ptr, n, m, cols):
+        """(q, e, kernel ms) for the columns `cols` of the row-major [n, m] f64 device matrix at values_dev_ptr, read in place
+        (safe_enriched_pair_counts_dev): int64 [len(cols)] each, e[a] = the number of nodes with value > 0 in column cols[a],
+        q[a] = the sum of nbr's membership W[i, j] over the ordered pairs (i, j) of those nodes, the diagonal included -- what
+        enriched_pair_counts gives for the host slice values[:, cols]."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+        q = np.empty(cols.shape[0], dtype=np.int64)
+        e = np.empty(cols.shape[0], dtype=np.int64)
+        ms = C.c_double()
+        check(lib.safe_enriched_pair_counts_dev(self.handle, nbr.handle, C.c_void_p(values_dev_ptr) if values_dev_ptr else None, int(n),
+                                                int(m), _ptr(cols), cols.shape[0], _ptr(q), _ptr(e), C.byref(ms)))
+        return q, e, ms.value
+
     def profile_distances(self, values_dev_ptr, n, m, cols, metric):
         """scipy.spatial.distance.pdist(values[:, cols].T, metric), condensed, for the columns `cols` of the row-major [n, m]
         f64 device matrix at values_dev_ptr and a metric of _lib.METRIC_IDS (name or id), bit for bit (safe_profile_distances).
@@ -1322,6 +1335,19 @@ def enriched_components(ctx, n, edge_u, edge_v, member):
     return out
 
 
+def enriched_pair_counts(ctx, nbr, member):
+    """member: [n, n_cols] (> 0 = enriched), n = nbr.n.  Returns (q, e), int64 [n_cols] each: e[a] = the enriched nodes of column
+    a, q[a] = the sum of nbr's membership W[i, j] over the ordered pairs (i, j) of them, the diagonal included
+    (safe_enriched_pair_counts).  For a symmetric W with a full diagonal (q - e) // 2 pairs i < j are within reach."""
+    member = np.ascontiguousarray(member, dtype=np.float64)
+    if member.ndim != 2 or member.shape[0] != nbr.n:
+        raise ValueError('enriched_pair_counts: member of shape %s for %d nodes' % (member.shape, nbr.n))
+    q = np.empty(member.shape[1], dtype=np.int64)
+    e = np.empty(member.shape[1], dtype=np.int64)
+    check(lib.safe_enriched_pair_counts(ctx.handle, nbr.handle, _ptr(member), member.shape[1], _ptr(q), _ptr(e)))
+    return q, e
+
+
 def jaccard_condensed(ctx, x):
     """scipy pdist(x, 'jaccard') (condensed) for the rows of x [m_top, n]."""
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -1359,6 +1385,11 @@ def gather_columns(ctx, values, cols, n=None, m=None):
 def enriched_components_dev(ctx, values_dev_ptr, n, m, cols, edge_u, edge_v):
     """Context.enriched_components_dev: (labels int32 [len(cols), n], kernel ms)."""
     return ctx.enriched_components_dev(values_dev_ptr, n, m, cols, edge_u, edge_v)
+
+
+def enriched_pair_counts_dev(ctx, nbr, values_dev_ptr, n, m, cols):
+    """Context.enriched_pair_counts_dev: (q, e, kernel ms)."""
+    return ctx.enriched_pair_counts_dev(nbr, values_dev_ptr, n, m, cols)
 
 
 def profile_distances(ctx, values_dev_ptr, n, m, cols, metric):

@@ -5,6 +5,10 @@
 //    one Python call per attribute in the reference).  Here: all attributes at once, min-label
 //    hooking + pointer jumping over the edge list (Shiloach-Vishkin style); the final label of a
 //    node is the smallest node id of its component.
+//  * define_top_attributes with attribute_unimodality_metric = 'radius' (additive; safepy/safe.py:632 reads the setting and
+//    ignores every value but 'connectivity'): for every candidate attribute the number of its enriched nodes and the number of
+//    ordered pairs of them that a membership handle W -- the within-reach relation -- joins: diag(E^T W E) on bit matrices
+//    (k_profile_pack<true> + k_pair_count below).
 //  * define_domains (safepy/safe.py:672-673): the condensed Jaccard distance vector between the
 //    binarised enrichment profiles of the top attributes -- scipy's pdist(m, 'jaccard') inside
 //    linkage(): d = #(x != y and (x != 0 or y != 0)) / #(x != 0 or y != 0), 0 when the denominator
@@ -111,7 +115,10 @@ __global__ __launch_bounds__(256) void k_jaccard_pairs(const unsigned long long 
     out[k] = any == 0 ? 0.0 : static_cast<double>(neq) / static_cast<double>(any);
 }
 
-// bits[w][a] = rows 64 w .. 64 w + 63 of column cols[a] of the row-major [n, m] matrix (non-zero = set; rows >= n: 0)
+// bits[w][a] = rows 64 w .. 64 w + 63 of column cols[a] of the row-major [n, m] matrix (non-zero = set; rows >= n: 0).
+// ENRICHED: the test is > 0 (NaN, 0, -0.0 and negatives are not set: safepy/safe.py:641) and the words of a column lie
+// together, bits[a][w] -- the form k_pair_count walks.
+template <bool ENRICHED>
 __global__ __launch_bounds__(256) void k_profile_pack(const double *__restrict__ values, int64_t n, int64_t m,
                                                       const int64_t *__restrict__ cols, int64_t m_top, int64_t words,
                                                       unsigned long long *__restrict__ bits) {
@@ -123,8 +130,74 @@ __global__ __launch_bounds__(256) void k_profile_pack(const double *__restrict__
     const int cnt = static_cast<int>(n - r0 < 64 ? n - r0 : 64);
     unsigned long long word = 0;
 #pragma unroll 8
-    for (int r = 0; r < cnt; ++r) word |= static_cast<unsigned long long>(p[(r0 + r) * m] != 0.0) << r;
-    bits[w * m_top + a] = word;
+    for (int r = 0; r < cnt; ++r) {
+        const double v = p[(r0 + r) * m];
+        word |= static_cast<unsigned long long>(ENRICHED ? v > 0.0 : v != 0.0) << r;
+    }
+    bits[ENRICHED ? a * words + w : w * m_top + a] = word;
+}
+
+// ---- enriched-pair counts (attribute_unimodality_metric = 'radius') ----
+// q[a] += sum over the rows i set in column a of popcount(W[i][:] & column a), e[a] += the number of those rows.
+//  * A wave owns one (column a, chunk of PC_CHUNK_WORDS x 64 rows, block of 64 KW words).  Its slice of the column -- KW words
+//    per lane, KW = ceil(words / 64) up to PC_MAX_KW, chosen by the host: one block covers the rows of up to 32 768 nodes --
+//    stays in registers; the rows of the chunk are walked through the column's own words (wave-uniform: scalar loads, ctz):
+//    a row that is not enriched costs nothing beyond finding the next set bit, an enriched one costs KW coalesced 512-byte
+//    reads of the row's word block, issued together, and an AND and a popcount per word.  A lane past the last word keeps 0
+//    for its slice and reads the row's last word instead of its own (in bounds, no divergence).  Nothing is decided in
+//    floating point.
+//  * Partial sums are 32-bit per lane (q[a] <= nnz(W) < 2^31: row_ptr is int32), folded with wave shuffles and added to the
+//    64-bit q[a] with one atomic per wave: integer adds commute, so the sums are exact in any order.
+//  * W may be any bit matrix (asymmetric, empty): this is the raw quadratic form diag(E^T W E).
+//  Bound: the stream of W rows, nnz(E) x words x 8 bytes through L2 / the memory-side cache (the bit matrix, 50 MB at 20 000
+//  nodes, does not fit an XCD's L2); the integer work -- two ANDs and two 32-bit popcounts per word -- is ~4 lane-operations
+//  per 8 bytes and stays below it ("Enriched-pair counts").
+constexpr int PC_MAX_KW = 8;                             // most 64-bit words of the column a lane keeps
+constexpr int64_t PC_CHUNK_WORDS = 16;                   // words of the column whose rows a wave walks = 1024 rows
+template <int KW>
+__global__ __launch_bounds__(256) void k_pair_count(const uint64_t *__restrict__ w_bits, int64_t words,
+                                                    const unsigned long long *__restrict__ e_bits, int64_t n_cols,
+                                                    unsigned long long *__restrict__ q, unsigned long long *__restrict__ e) {
+    const int lane = threadIdx.x & 63;
+    const int64_t a = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    if (a >= n_cols) return;                                             // (wave-uniform)
+    const unsigned long long *col = e_bits + a * words;
+    const int64_t wb0 = static_cast<int64_t>(blockIdx.z) * (64 * KW);
+    unsigned long long mine[KW];
+    int64_t at[KW];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const int64_t w = wb0 + k * 64 + lane;
+        at[k] = w < words ? w : words - 1;
+        mine[k] = w < words ? col[w] : 0ull;
+        any |= mine[k] != 0ull;
+    }
+    const bool count_rows = blockIdx.z == 0;                             // e[a] is counted once, by the first word block
+    if (!count_rows && __builtin_amdgcn_ballot_w64(any) == 0ull) return; // no enriched node in this block: nothing to add
+    const int64_t rw0 = static_cast<int64_t>(blockIdx.y) * PC_CHUNK_WORDS;
+    const int64_t rw1 = rw0 + PC_CHUNK_WORDS < words ? rw0 + PC_CHUNK_WORDS : words;
+    unsigned int acc = 0, n_rows = 0;
+    for (int64_t rw = rw0; rw < rw1; ++rw) {
+        unsigned long long rows = col[rw];                               // the same address in every lane
+        n_rows += __popcll(rows);
+        while (rows) {                                                   // bits of rows >= n are never set (k_profile_pack)
+            const int64_t i = rw * 64 + __builtin_ctzll(rows);
+            rows &= rows - 1;
+            const uint64_t *wr = w_bits + i * words;
+            uint64_t v[KW];
+#pragma unroll
+            for (int k = 0; k < KW; ++k) v[k] = wr[at[k]];
+#pragma unroll
+            for (int k = 0; k < KW; ++k) acc += __popcll(v[k] & mine[k]);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) {
+        if (acc) atomicAdd(&q[a], static_cast<unsigned long long>(acc));
+        if (count_rows && n_rows) atomicAdd(&e[a], static_cast<unsigned long long>(n_rows));
+    }
 }
 
 // SciPy 1.15's pdist for 0/1 profiles from the contingency counts (all exact in f64: one rounding, in the division)
@@ -416,7 +489,7 @@ int profile_condensed(const char *fn, safe_ctx *ctx, CallBufs &b, CallTimer &tm,
     hipStream_t s = ctx->stream;
     SAFE_HIP_CHECK(hipMemcpyAsync(d_cols, cols_host, m_top * sizeof(int64_t), hipMemcpyHostToDevice, s));
     SAFE_HIP_CHECK(tm.start(s));
-    hipLaunchKernelGGL(k_profile_pack, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(m_top, 64))), dim3(256),
+    hipLaunchKernelGGL(k_profile_pack<false>, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(m_top, 64))), dim3(256),
                        0, s, values_dev, n, m, d_cols, m_top, words, d_bits);
     SAFE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_profile_pairs, dim3(static_cast<unsigned>(ceil_div(m_top, 256)), static_cast<unsigned>(m_top)), dim3(256), 0, s,
@@ -495,6 +568,56 @@ int linkage_run(const char *fn, safe_ctx *ctx, CallBufs &b, CallTimer &tm, const
         z_host[4 * i + 2] = mg[2];
         z_host[4 * i + 3] = static_cast<double>(count[n + i]);
     }
+    return SAFE_OK;
+}
+
+// Pack + count kernels of checked arguments on the context's stream into q_host / e_host int64 [n_cols].
+// d_values: f64 [n][m] row-major on the device.  Synchronises.
+int pair_counts_run(const char *fn, safe_ctx *ctx, CallBufs &b, const safe_nbr *within, const double *d_values, int64_t m,
+                    const int64_t *cols_host, int64_t n_cols, int64_t *q_host, int64_t *e_host, double *kernel_ms) {
+    const int64_t n = within->n, words = within->words;
+    const int kw = static_cast<int>(std::min<int64_t>(ceil_div(words, 64), PC_MAX_KW));      // words of a column per lane
+    const int64_t chunks = ceil_div(words, PC_CHUNK_WORDS), blocks = ceil_div(words, 64 * kw);
+    SAFE_REQUIRE(ceil_div(n_cols, 4) < (1ll << 31) && ceil_div(n_cols, 64) < 65536 && ceil_div(words, 4) < (1ll << 31) && chunks < 65536 &&
+                     blocks < 65536,
+                 "%s: too many columns or rows for one launch", fn);
+    int64_t *d_cols = nullptr;
+    unsigned long long *d_bits = nullptr, *d_qe = nullptr;
+    CallTimer tm;
+    SAFE_TRY(b.alloc(&d_cols, static_cast<size_t>(n_cols)));
+    SAFE_TRY(b.alloc(&d_bits, static_cast<size_t>(n_cols) * words));
+    SAFE_TRY(b.alloc(&d_qe, static_cast<size_t>(2 * n_cols)));
+    hipStream_t s = ctx->stream;
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_cols, cols_host, n_cols * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    SAFE_HIP_CHECK_AS(fn, hipMemsetAsync(d_qe, 0, 2 * n_cols * sizeof(unsigned long long), s));
+    SAFE_HIP_CHECK_AS(fn, tm.start(s));
+    hipLaunchKernelGGL(k_profile_pack<true>, dim3(static_cast<unsigned>(ceil_div(words, 4)), static_cast<unsigned>(ceil_div(n_cols, 64))),
+                       dim3(256), 0, s, d_values, n, m, d_cols, n_cols, words, d_bits);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    const dim3 grid(static_cast<unsigned>(ceil_div(n_cols, 4)), static_cast<unsigned>(chunks), static_cast<unsigned>(blocks));
+    unsigned long long *d_q = d_qe, *d_e = d_qe + n_cols;
+#define PC_LAUNCH(K) \
+    case K: hipLaunchKernelGGL(k_pair_count<K>, grid, dim3(256), 0, s, within->bits, words, d_bits, n_cols, d_q, d_e); break
+    switch (kw) {
+        PC_LAUNCH(1);
+        PC_LAUNCH(2);
+        PC_LAUNCH(3);
+        PC_LAUNCH(4);
+        PC_LAUNCH(5);
+        PC_LAUNCH(6);
+        PC_LAUNCH(7);
+    default:
+        static_assert(PC_MAX_KW == 8, "one case per KW");
+        hipLaunchKernelGGL(k_pair_count<8>, grid, dim3(256), 0, s, within->bits, words, d_bits, n_cols, d_q, d_e);
+    }
+#undef PC_LAUNCH
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_HIP_CHECK_AS(fn, tm.stop(s));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied out as int64");
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(q_host, d_q, n_cols * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(e_host, d_e, n_cols * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(s));
+    SAFE_HIP_CHECK_AS(fn, tm.finish(ctx, "k_profile_pack+k_pair_count", 2, kernel_ms));
     return SAFE_OK;
 }
 
@@ -648,6 +771,40 @@ int safe_profile_linkage(safe_ctx *ctx, const double *values_dev, int64_t n, int
     double *d_cond = nullptr;
     SAFE_TRY(profile_condensed(fn, ctx, b, tm, values_dev, n, m, cols_host, m_top, metric, &d_cond));
     return linkage_run(fn, ctx, b, tm, d_cond, m_top, "k_profile_pack+k_profile_pairs+k_linkage_expand+k_linkage_nn_chain", 4, z_host, kernel_ms);
+}
+
+int safe_enriched_pair_counts(safe_ctx *ctx, safe_nbr *within, const double *member_host, int64_t n_cols, int64_t *q_host,
+                              int64_t *e_host) {
+    const char *fn = "safe_enriched_pair_counts";
+    SAFE_REQUIRE(ctx && within && n_cols >= 0, "%s: bad argument", fn);
+    if (n_cols == 0) return SAFE_OK;
+    SAFE_REQUIRE(member_host && q_host && e_host, "%s: NULL argument", fn);
+    SAFE_REQUIRE(within->n >= 1 && within->bits, "%s: the membership handle holds no bit matrix", fn);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    const int64_t total = within->n * n_cols;
+    std::vector<int64_t> cols(static_cast<size_t>(n_cols));
+    std::iota(cols.begin(), cols.end(), int64_t(0));
+    CallBufs b;                                                          // (after cols: see CallBufs)
+    double *d_member = nullptr;
+    SAFE_TRY(b.alloc(&d_member, static_cast<size_t>(total)));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_member, member_host, static_cast<size_t>(total) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return pair_counts_run(fn, ctx, b, within, d_member, n_cols, cols.data(), n_cols, q_host, e_host, nullptr);
+}
+
+int safe_enriched_pair_counts_dev(safe_ctx *ctx, safe_nbr *within, const double *values_dev, int64_t n, int64_t m, const int64_t *cols_host,
+                                  int64_t n_cols, int64_t *q_host, int64_t *e_host, double *kernel_ms) {
+    const char *fn = "safe_enriched_pair_counts_dev";
+    SAFE_REQUIRE(ctx && within && n >= 1 && m >= 0 && n_cols >= 0, "%s: bad argument", fn);
+    if (kernel_ms) *kernel_ms = 0;
+    SAFE_REQUIRE(within->n == n && within->bits, "%s: the matrix has %lld rows, the membership handle %lld", fn, (long long)n,
+                 (long long)within->n);
+    if (n_cols == 0) return SAFE_OK;
+    SAFE_REQUIRE(values_dev && cols_host && q_host && e_host, "%s: NULL argument", fn);
+    for (int64_t c = 0; c < n_cols; ++c)
+        SAFE_REQUIRE(cols_host[c] >= 0 && cols_host[c] < m, "%s: column %lld out of [0, %lld)", fn, (long long)cols_host[c], (long long)m);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    CallBufs b;
+    return pair_counts_run(fn, ctx, b, within, values_dev, m, cols_host, n_cols, q_host, e_host, kernel_ms);
 }
 
 }  // extern "C"

@@ -44,6 +44,11 @@ _DEFAULTS = {
 }
 
 
+def _is_real(v):
+    """An int or a float (NumPy's included), not a bool."""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
 def _is_percentage(q):
     return isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool) and 0 <= q <= 100
 
@@ -255,6 +260,10 @@ class SAFE:
 
         self.graph_euclidean = None      # Euclidean pseudo-network of .scatter inputs (safe.py:67, 302-309), if any
         self.attribute_unimodality_metric = 'connectivity'
+        # 'radius' only: enriched nodes within attribute_unimodality_radius_multiple x the neighborhood radius of each other are
+        # "within reach"; an attribute is one region when at least attribute_unimodality_min_fraction of its enriched pairs are
+        self.attribute_unimodality_radius_multiple = 2.0
+        self.attribute_unimodality_min_fraction = 0.65
         self.attribute_distance_metric = 'jaccard'
         self.attribute_distance_threshold = 0.75
         self.domains = None
@@ -349,6 +358,16 @@ class SAFE:
             bad, self.hypergeom_tails = self.hypergeom_tails, 'upper'
             raise ValueError('%s is not a valid setting for hypergeom_tails. '
                              'Valid options are: upper, attribute_sign' % (bad,))
+        multiple = getattr(self, 'attribute_unimodality_radius_multiple', 2.0)
+        if not _is_real(multiple) or not np.isfinite(multiple) or multiple <= 0:
+            self.attribute_unimodality_radius_multiple = 2.0
+            raise ValueError('attribute_unimodality_radius_multiple = %r is not valid: it must be a finite number greater than 0.'
+                             % (multiple,))
+        fraction = getattr(self, 'attribute_unimodality_min_fraction', 0.65)
+        if not _is_real(fraction) or not (0 < fraction <= 1):
+            self.attribute_unimodality_min_fraction = 0.65
+            raise ValueError('attribute_unimodality_min_fraction = %r is not valid: it must be a number in the (0, 1] range.'
+                             % (fraction,))
         if not isinstance(self.num_permutations, int) or (self.num_permutations < 10):
             self.num_permutations = 1000
             raise ValueError('num_permutations must be an integer equal or greater than 10.')
@@ -395,6 +414,8 @@ class SAFE:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('hypergeom_tails', 'upper')     # (objects pickled before the setting existed)
+        self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
+        self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -993,13 +1014,71 @@ class SAFE:
         ev = np.fromiter((v for _, v in g.edges()), dtype=np.int64, count=g.number_of_edges())
         return eu, ev
 
+    def _within_reach(self, ctx):
+        """The within-reach relation of attribute_unimodality_metric = 'radius' as a device membership handle (the caller closes
+        it): what define_neighborhoods would build under the current node_distance_metric with the radius
+        t = attribute_unimodality_radius_multiple x neighborhood_radius_resolved in place of the radius -- the same constructors,
+        so `<` against `<=`, the kept diagonal and unreached pairs are the neighborhood rule.  Returns (handle, t)."""
+        xy, eu, ev, length, weight = arrays = _graph_arrays(self.graph)
+        r = self._resolve_radius(ctx, arrays)
+        t = float(self.attribute_unimodality_radius_multiple) * float(r)
+        if not np.isfinite(t):
+            raise ValueError("attribute_unimodality_metric = 'radius' needs a finite neighborhood radius: it resolved to %r "
+                             '(does every node have x and y coordinates?)' % (r,))
+        if self.node_distance_metric == 'euclidean':
+            if not np.isfinite(xy).all():
+                raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs finite "
+                                 'x and y coordinates for every node')
+            if not t > 0:                                # `distance < t` would drop the diagonal: no node within its own reach
+                raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs a "
+                                 'neighborhood radius greater than 0: it resolved to %r' % (r,))
+            return be.Neighborhoods.euclidean(ctx, xy, t), t
+        w = self._shortpath_weights(xy, eu, ev, length, weight)
+        return be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, t, keep_distances=False), t
+
+    def _enriched_pair_counts(self, cand):
+        """(pairs, within) int64 [len(cand)] of the candidate columns `cand` of nes_binary: the unordered pairs of a column's
+        enriched nodes (nes_binary > 0), and those of them that are within reach of each other.  One device call on the
+        device-resident nes_binary while nobody has read it (it stays there), else on the host slice."""
+        ctx = self._ctx()
+        within_nbr, t = self._within_reach(ctx)
+        try:
+            if self.verbose:
+                logging.info('Within reach: %s distance %s %r (%r x the neighborhood radius %r)'
+                             % (self.node_distance_metric, '<' if self.node_distance_metric == 'euclidean' else '<=', t,
+                                self.attribute_unimodality_radius_multiple, self.neighborhood_radius_resolved))
+            src = self.__dict__.get('_r_nes_binary')
+            if isinstance(src, _DeviceResult) and cand.dtype.kind in 'iu' and cand.min() >= 0 and cand.max() < src.shape[1]:
+                if src.shape[0] != within_nbr.n:
+                    raise ValueError('nes_binary has %d rows, the network %d nodes' % (src.shape[0], within_nbr.n))
+                q, e, _ = ctx.enriched_pair_counts_dev(within_nbr, src.buf.ptr, src.shape[0], src.shape[1], cand)
+            else:
+                q, e = be.enriched_pair_counts(ctx, within_nbr, self.nes_binary[:, cand])
+        finally:
+            within_nbr.close()
+        # W is symmetric with a full diagonal: q counts every unordered pair twice and every enriched node once
+        return e * (e - 1) // 2, (q - e) // 2
+
     def define_top_attributes(self, **kwargs):
-        """safepy/safe.py:610-659.  kwargs: attribute_unimodality_metric, attribute_enrichment_min_size.
-        Adds the columns 'top', 'num_connected_components', 'size_connected_components' (object: sizes in
-        descending order) and 'num_large_connected_components' to self.attributes.  The connected
-        components of all candidate attributes are found in one device call, straight from the
-        device-resident nes_binary while nobody has read it (it stays on the device)."""
-        for option in ('attribute_unimodality_metric', 'attribute_enrichment_min_size'):
+        """safepy/safe.py:610-659.  kwargs: attribute_unimodality_metric, attribute_enrichment_min_size,
+        attribute_unimodality_radius_multiple, attribute_unimodality_min_fraction.
+
+        'connectivity' (the default, the reference's): adds the columns 'top', 'num_connected_components',
+        'size_connected_components' (object: sizes in descending order) and 'num_large_connected_components' to
+        self.attributes.  The connected components of all candidate attributes are found in one device call, straight from the
+        device-resident nes_binary while nobody has read it (it stays on the device).
+
+        'radius' (additive; the reference reads the setting and ignores it): an attribute stays top when at least
+        attribute_unimodality_min_fraction of the pairs of its enriched nodes are within reach of each other -- within
+        attribute_unimodality_radius_multiple x neighborhood_radius_resolved under the current node_distance_metric, by the
+        rule define_neighborhoods applies to its own radius.  Adds 'top', 'num_enriched_pairs', 'num_enriched_pairs_within'
+        (int64) and 'fraction_enriched_pairs_within' (f64); attributes that fail requirement 1 get 0, 0 and NaN.  All candidate
+        attributes are counted in one device call (backend.enriched_pair_counts).  Raises, with self.attributes untouched, when
+        the relation cannot be built (no usable coordinates, a refusal of the constructor).
+
+        Any other value skips requirement 2, as in the reference."""
+        for option in ('attribute_unimodality_metric', 'attribute_enrichment_min_size', 'attribute_unimodality_radius_multiple',
+                       'attribute_unimodality_min_fraction'):
             if option in kwargs:
                 setattr(self, option, kwargs[option])
         self.validate_config()
@@ -1008,6 +1087,28 @@ class SAFE:
             logging.info('Top attributes need >= %d enriched neighborhoods that form one region (%s)'
                          % (min_size, self.attribute_unimodality_metric))
         attrs = self.attributes
+        if self.attribute_unimodality_metric == 'radius':
+            top = np.asarray((attrs['num_neighborhoods_enriched'] >= min_size).values, dtype=bool)   # requirement 1
+            m_all = len(attrs)
+            pairs = np.zeros(m_all, dtype=np.int64)
+            within = np.zeros(m_all, dtype=np.int64)
+            cand = attrs.index.values[top]
+            if len(cand):
+                pairs[top], within[top] = self._enriched_pair_counts(cand)
+            min_fraction = float(self.attribute_unimodality_min_fraction)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                fraction = np.where(top, within.astype(np.float64) / pairs.astype(np.float64), np.nan)
+            fails = top & (within.astype(np.float64) < min_fraction * pairs.astype(np.float64))
+            if self.verbose:
+                logging.info('One region: >= %r of the pairs of enriched neighborhoods within reach (%d of %d candidates fail)'
+                             % (min_fraction, np.count_nonzero(fails), np.count_nonzero(top)))
+            attrs['top'] = top & ~fails
+            attrs['num_enriched_pairs'] = pairs
+            attrs['num_enriched_pairs_within'] = within
+            attrs['fraction_enriched_pairs_within'] = fraction
+            if self.verbose:
+                logging.info('Number of top attributes: %d' % np.sum(attrs['top']))
+            return
         attrs['top'] = (attrs['num_neighborhoods_enriched'] >= min_size).values           # requirement 1 (safe.py:628-629)
 
         if self.attribute_unimodality_metric == 'connectivity':                         # requirement 2 (safe.py:632-656)
