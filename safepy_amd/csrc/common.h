@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "safe_hip.h"
+#include "bits_plan.h"   // BitsQueues, BitsTaskPlan, ceil_div: the host-only planning arithmetic of the bit-sliced launch
 
 #define SAFE_WAVE 64
 #define SAFE_PAD_U16 0xFFFFu
@@ -89,21 +90,21 @@ void draw_worker_shutdown(safe_ctx *ctx);
 // contents must survive.  A slot with several users holds one ROLE: those users never run at the same time, and sharing keeps a
 // single allocation of the largest size.  A new buffer gets a new enumerator in front of N_SCRATCH, not a free-looking old one.
 enum ScratchSlot {
-    SCRATCH_COUNTERS,       // packed u32 counters [mloc][n_pad] | every integer-counter route: launch_bits, launch_lds_f64 (enrich.hip),
+    SCRATCH_COUNTERS,       // packed u32 counters [mloc][n_pad] | every integer-counter route: bits_call_buffers, launch_lds_f64 (enrich.hip),
                             //   mfma_make_plan (mfma.hip) | until the next integer-counter call: ctx->packed_counts points here
     SCRATCH_OPERANDS,       // the attribute operand: bit planes (uint2), f64 tiles, block-sparse i8 planes (d_bs) | launch_bits,
                             //   launch_counts_bits, launch_lds_f64, hypergeom_fused (enrich.hip), counts_setup, mfma_prepare_columns
                             //   (mfma.hip) | within the call
     SCRATCH_F64_MATRIX,     // one f64 [n][mloc] matrix -- observed scores nobody asked for (launch_lds_f64, launch_mfma_run), the hits of
                             //   safe_hypergeom's per-element form -- or hypergeom_fused's (p, -log10 p) table | within the call
-    SCRATCH_TASKS,          // task lists + queue offsets and counters | launch_bits (enrich.hip), counts_setup, mfma_make_plan (mfma.hip) |
+    SCRATCH_TASKS,          // task lists + queue offsets and counters | bits_call_buffers (enrich.hip), counts_setup, mfma_make_plan (mfma.hip) |
                             //   within the call
-    SCRATCH_STREAM_A,       // double buffer, even launches: permuted member ids (launch_bits), permuted source rows (mfma_make_plan);
+    SCRATCH_STREAM_A,       // double buffer, even launches: permuted member ids (bits_call_buffers), permuted source rows (mfma_make_plan);
                             //   or counts_setup's one source-row list | within the call
     SCRATCH_STREAM_B,       // ... odd launches; or the split count form's u16 counts (mfma_counts_split_begin) | within the call
     SCRATCH_COLUMN_META,    // per-column side data: hypergeom_fused's distinct (n, K) values and ids (enrich.hip), mfma_prepare_columns'
                             //   column statistics (mfma.hip) | within the call
-    SCRATCH_BITS_OBSERVED,  // observed sums of every (word group, slice) of the blocked bit-sliced kernel | launch_bits | within the call
+    SCRATCH_BITS_OBSERVED,  // observed sums of every (word group, slice) of the blocked bit-sliced kernel | bits_observe | within the call
     SCRATCH_SPLIT_ROWS,     // row lists + tasks of the split count form's second half | mfma_counts_split_rows | within the call
     SCRATCH_HYP_SMALL,      // neighborhood sizes f64 [n] | enriched counters u32 [mloc + 64] | safe_hypergeom | within the call
     SCRATCH_ENRICHED,       // enriched counters u32 [m + 16] | safe_randomization, safe_outputs_from_counts | within the call
@@ -114,7 +115,7 @@ enum ScratchSlot {
     SCRATCH_MFMA_FILTER,    // source-row ids | per-launch counts of undecided compares | mfma_make_plan | within the call
     SCRATCH_MFMA_Q64,       // filtered 'sum' form: the fixed-point values as i64 [n + 1][mloc] | mfma_prepare_columns | within the call
     SCRATCH_MFMA_Z64,       // filtered z form: value | square + not-NaN flag [n + 1][mloc] | mfma_prepare_columns | within the call
-    SCRATCH_BITS_TAIL_IDS,  // permuted member ids of the column-chunked exchange tail | launch_bits | within the call
+    SCRATCH_BITS_TAIL_IDS,  // permuted member ids of the column-chunked exchange tail | bits_call_buffers | within the call
     SCRATCH_NES_TABLE,      // the NES table f64 [P + 1] | ctx_nes_table alone, for safe_randomization and every safe_outputs_from_* entry
                             //   point | ACROSS calls: the device copy of ctx->nes_tab_host, uploaded again only when the table changes
     SCRATCH_ATTR_STAGED,    // the bytes of a u8 attribute matrix as they came | safe_attr_create_host (attr.hip) | within the call
@@ -211,9 +212,40 @@ int ctx_pinned(safe_ctx *ctx, size_t bytes, void **out);
 // `count` reusable events of the context (timing-enabled, or hipEventDisableTiming); valid until the next request of the same kind
 int ctx_events(safe_ctx *ctx, bool timing, size_t count, hipEvent_t **out);
 void perms_cache_drop(safe_ctx *ctx);   // frees ctx->perm_cache (rng.cpp)
+int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch);   // enrich.hip
+// The frame of a launcher whose spans alternate between ctx->stream and ctx->side_stream (launch_bits, launch_lds_f64,
+// launch_mfma_run).  open: the call's last_kernel record starts at zero under `name`; 2 * n_launch timing events (ev[2 c],
+// ev[2 c + 1] bracket launch c) and n_plain plain ones come from the context's pool; plain[0] says "inputs ready" on ctx->stream
+// and the side stream waits for it.  join, behind the last launch: ctx->stream waits for the side stream (plain[1]).  close,
+// behind the finalize pass: k0 / k1, the call's host wait, kernel_stat_from_events.
+struct SpanFrame {
+    hipEvent_t *ev = nullptr, *plain = nullptr;
+    int64_t n_launch = 0;
+};
+static inline int span_frame_open(safe_ctx *ctx, const char *name, int64_t n_launch, size_t n_plain, SpanFrame *f) {
+    ctx->last_kernel.name = name;
+    ctx->last_kernel.total_ms = ctx->last_kernel.busy_ms = 0.0;
+    ctx->last_kernel.launches = 0;
+    f->n_launch = n_launch;
+    SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &f->ev));
+    SAFE_TRY(ctx_events(ctx, false, n_plain, &f->plain));
+    SAFE_HIP_CHECK(hipEventRecord(f->plain[0], ctx->stream));
+    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, f->plain[0], 0));
+    return SAFE_OK;
+}
+static inline int span_frame_join(safe_ctx *ctx, const SpanFrame &f) {
+    SAFE_HIP_CHECK(hipEventRecord(f.plain[1], ctx->side_stream));
+    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->stream, f.plain[1], 0));
+    return SAFE_OK;
+}
+static inline int span_frame_close(safe_ctx *ctx, const SpanFrame &f) {
+    SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
+    SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    return kernel_stat_from_events(ctx, f.ev, f.n_launch);
+}
 // small per-handle device blocks (row flags, column sums): hipMalloc + hipFree cost tens of microseconds each and a handle
 // is made per compute_pvalues pass, so freed blocks wait in the context for the next handle of the same shape
-int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch);   // enrich.hip
 int ctx_block_alloc(safe_ctx *ctx, size_t bytes, void **out);
 void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes);
 
@@ -326,18 +358,6 @@ struct CallTimer {
     }
 };
 
-struct BitsQueues {
-    int off[9];                                                           // tasks [off[q], off[q+1]) belong to queue q
-};
-// Task lists of the bit-sliced permutation kernel for one launch plan (launch_bits): a function of the membership structure and of
-// `key` only, so the handle keeps the last one (building them took 90 us of every compute_pvalues pass)
-struct BitsTaskPlan {
-    std::vector<int64_t> key;
-    std::vector<int4> tasks;                                              // the lists back to back
-    std::vector<int64_t> list_span, list_first, list_count, launch_list;
-    std::vector<BitsQueues> list_queues;
-};
-
 // Membership structure.  Canonical form: bit matrix; derived: CSR and SELL-64 (sliced
 // ELLPACK with rows sorted by descending count so each 64-row slice is nearly uniform).
 struct safe_nbr {
@@ -360,7 +380,7 @@ struct safe_nbr {
     uint16_t *sell_col2 = nullptr;  // [sell_entries + 1024] 2*column id as u16 (n < 32768 only): LDS byte offsets of a u16 table
     uint16_t *sell_col2b = nullptr; // the same list in blocked order: 8 members of a lane adjacent (one 16-byte load per lane and block)
     std::vector<int32_t> h_slice_width;
-    BitsTaskPlan bits_plan;         // (launch_bits' cache)
+    BitsTaskPlan bits_plan;         // (bits_task_plan's cache, enrich.hip)
     void *bits_plan_pinned = nullptr;              // the plan's task lists in pinned host memory (grow-only): uploaded from there every
     size_t bits_plan_pinned_bytes = 0;             // pass -- an async copy from pageable memory pins the pages first (an ioctl that
                                                    // was seen to take milliseconds once in a few hundred passes)
@@ -558,9 +578,6 @@ struct safe_perms {
     // host-side timing of the stream (safe_perms_timing), ms since the handle was created
     double t_created_s = 0.0, draw_busy_ms = 0.0, drawn_all_ms = 0.0, enqueued_all_ms = 0.0, ring_wait_ms = 0.0;
 };
-
-// launch-geometry helpers
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int safe_attr_prepare(safe_attr *attr);   // row flags + stats (attr.hip)
 int nbr_finalize_from_bits(safe_nbr *nbr);   // bits -> CSR + SELL (nbr.hip)

@@ -480,6 +480,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_permtest_scatter(
 // waves, N up to 20 470) and k_permtest_bits_pre32 (half words, N up to 32 767).
 // --------------------------------------------------------------------------------------
 #define BT_LV 10               // levels of a neighborhood sum: max row count < 1024
+static_assert(BT_LV == BITS_PLAN_LV, "the planning header (bits_plan.h) cuts the forms at the same number of levels");
 
 // 16-byte vector view of the u16 permutation rows: must be may_alias, the rows are read back
 // as unsigned short (without it TBAA lets the compiler move those reads across the refills)
@@ -2332,154 +2333,6 @@ static int launch_scatter(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     return SAFE_OK;
 }
 
-// LDS of a word column plus the permutation rows, the layout of the row-in-LDS kernel of rounds 1-5 (removed): it still sets the
-// number of workgroup slots per CU that the bit-sliced forms' task sizes are cut for (launch_bits)
-static size_t bits_lds_bytes(int64_t n, int64_t stride16) {
-    const size_t t_words = 2 * ((static_cast<size_t>(n) + 2) & ~size_t(1));
-    return (t_words + static_cast<size_t>(stride16) + 4) * sizeof(unsigned int);
-}
-// the word column T of the full-word forms (8 bytes per node) and of the half-word form (4 bytes per node), with the queue slot
-static size_t bits_pre_lds_bytes(int64_t n) { return (2 * ((static_cast<size_t>(n) + 2) & ~size_t(1)) + 4) * sizeof(unsigned int); }
-static size_t bits_half_lds_bytes(int64_t n) { return (((static_cast<size_t>(n) + 4) & ~size_t(3)) + 4) * sizeof(unsigned int); }
-
-// The bit-sliced forms, chosen here and nowhere else:
-//   BITS_BLK    k_permtest_bits_blk: four waves per workgroup, blocked member lists of 8 * id (the LDS byte offsets fit 16 bits:
-//               8 (N + 1) < 65536), neighborhoods below 1024 members;
-//   BITS_PRE16  k_permtest_bits_pre: sixteen waves share one word column (N <= 20 470), lists of 2 * id; also the form of
-//               neighborhoods of 1024 .. 2047 members on the small networks;
-//   BITS_PRE32  k_permtest_bits_pre32: the same over 32-attribute half words (4 bytes per node), lists of ids, up to N = 32 767
-//               (the resident 2 * id lists are u16: sell_col2 exists below N = 32 768 only).
-// levels: of the vertical sums, eleven when a neighborhood has 1024 .. 2047 members (the PRE forms only), else ten.
-enum BitsKind { BITS_NONE = 0, BITS_BLK, BITS_PRE16, BITS_PRE32 };
-struct BitsForm {
-    BitsKind kind;
-    int levels;
-};
-static BitsForm bits_form(int64_t n, int64_t max_count, bool has_col2, size_t lds_limit) {
-    if (!has_col2 || n >= 32768 || max_count >= (2 << BT_LV)) return {BITS_NONE, 0};
-    const int levels = max_count >= (1 << BT_LV) ? BT_LV + 1 : BT_LV;
-    if ((n + 1) * 8 < 65536 && levels == BT_LV) return {BITS_BLK, levels};
-    if (bits_pre_lds_bytes(n) <= lds_limit) return {BITS_PRE16, levels};
-    if (bits_half_lds_bytes(n) <= lds_limit) return {BITS_PRE32, levels};
-    return {BITS_NONE, 0};
-}
-
-// The 8-member blocks of the widest slice of each group of `wv` adjacent slices (at least one): what a permutation costs the wave
-// group of a task
-static std::vector<int64_t> slice_group_blocks(const std::vector<int32_t> &slice_width, int64_t n_slices, int wv) {
-    std::vector<int64_t> blocks(ceil_div(n_slices, wv), 0);
-    for (int64_t s = 0; s < n_slices; ++s) blocks[s / wv] = std::max<int64_t>(blocks[s / wv], slice_width[s] / 8);
-    for (int64_t &b : blocks) b = std::max<int64_t>(b, 1);
-    return blocks;
-}
-
-// Tasks (column unit w in [w_lo, w_hi), slice group g, permutations [p0, p1) of a launch of `span`) cut to about equal cost:
-// tasks_per_unit tasks per column unit, each at least 256 block-permutations and 16 permutations and at most ppt_cap
-// permutations; stably sorted heaviest first for the kernels' dynamic queues.  half_words: a unit is one half (32 columns) of a
-// word group, and a last half without columns has no task.
-static std::vector<int4> cost_sorted_tasks(const std::vector<int64_t> &sg_blocks, int64_t span, int64_t w_lo, int64_t w_hi,
-                                           int64_t tasks_per_unit, int64_t ppt_cap, bool half_words, int64_t mloc) {
-    int64_t blocks_per_perm = 0;
-    for (const int64_t bl : sg_blocks) blocks_per_perm += bl;
-    const int64_t target = std::max<int64_t>(256, blocks_per_perm * span / tasks_per_unit);      // block-permutations per task
-    struct TaskCost { int4 t; int64_t cost; };
-    std::vector<TaskCost> tc;
-    for (size_t g = 0; g < sg_blocks.size(); ++g) {
-        const int64_t bl = sg_blocks[g];
-        int64_t ppt = std::min<int64_t>(std::min<int64_t>(span, ppt_cap), std::max<int64_t>(16, target / bl));
-        const int64_t chunks = ceil_div(span, ppt);
-        ppt = ceil_div(span, chunks);
-        for (int64_t c = 0; c < chunks; ++c) {
-            const int64_t p0 = c * ppt, p1 = std::min<int64_t>(span, p0 + ppt);
-            for (int64_t w = w_lo; w < w_hi; ++w)
-                if (!half_words || (w >> 1) * 64 + (w & 1) * 32 < mloc)
-                    tc.push_back({make_int4(static_cast<int>(w), static_cast<int>(g), static_cast<int>(p0), static_cast<int>(p1)),
-                                  bl * (p1 - p0)});
-        }
-    }
-    std::stable_sort(tc.begin(), tc.end(), [](const TaskCost &a, const TaskCost &b) { return a.cost > b.cost; });
-    std::vector<int4> out(tc.size());
-    for (size_t i = 0; i < tc.size(); ++i) out[i] = tc[i].t;
-    return out;
-}
-
-// The blocked kernel's per-XCD queues: the tasks of one (slice group, permutation range) -- one per word group, adjacent after the
-// stable sort -- go to one queue, (group, range) pairs dealt round-robin in heaviest-first order.  Returns the list queue by queue.
-static std::vector<int4> split_xcd_queues(const std::vector<int4> &list, BitsQueues &bq) {
-    std::vector<std::vector<int4>> q(8);
-    int64_t pair = -1;
-    int last_g = -1, last_p0 = -1;
-    for (const int4 &t : list) {
-        if (t.y != last_g || t.z != last_p0) {
-            ++pair;
-            last_g = t.y;
-            last_p0 = t.z;
-        }
-        q[pair & 7].push_back(t);
-    }
-    std::vector<int4> out;
-    out.reserve(list.size());
-    bq.off[0] = 0;
-    for (int k = 0; k < 8; ++k) {
-        out.insert(out.end(), q[k].begin(), q[k].end());
-        bq.off[k + 1] = static_cast<int>(out.size());
-    }
-    return out;
-}
-
-// The task lists of one launch plan of the bit-sliced forms (all but plan.key): one list per DISTINCT stage-launch size over all
-// n_units column units (word groups, or their halves), then -- the exchange tail -- one per column chunk of xc_wpc word groups
-// over the tail's permutations (starts[n_major] .. the end).  slots: workgroup slots of the chip; one task per slot and unit set.
-// One list per launch size: the stream's stages are 32, 96, 128 ... and short last ones, and a list cut for 128 permutations
-// leaves a 32-permutation launch with half-empty and empty tasks (each still reloads T): a 32-permutation launch took 207 us,
-// 6.5 us per permutation against 3.2 in the long launches.
-static void plan_bits_tasks(BitsTaskPlan &plan, const std::vector<int32_t> &slice_width, int64_t n_slices, int wv, int64_t slots,
-                            const std::vector<int64_t> &starts, int64_t n_units, int64_t mloc, bool half_words, int64_t n_major,
-                            int64_t n_tail, int64_t xc_wpc) {
-    // queue depth per workgroup slot: every task reloads T and flushes its counters (64 wave-atomics + two 32 x 32 bit transposes
-    // per wave: 11 % of the kernel at depth 2, tools/bits_ablate.py dbg=2), so as few tasks as fill the chip once -- depth 1 vs 2:
-    // seeded step 3.52 -> 3.41 ms, 10 000 unseeded permutations 25.8 -> 24.4 ms (tools/exp_ab.sh; round 3 had chosen 2 while the
-    // host stream bound the step)
-    constexpr int64_t tasks_per_slot = 1;
-    // SHORT launches (the ramp at the head of the stream, the stage behind the last draw: nothing else runs beside them) cost
-    // ~150 us + 2 us per permutation alone on the chip (10 / 16 / 32 / 64 / 128 permutations: 160 / 200 / 186 / 266 / 413 us,
-    // tools/r6/short_launch.sh): their heaviest slice group's tasks are the critical path (16 permutations x 40-49 blocks x
-    // 420-700 clocks) and every wave-task carries 13 + 30 + 30-60 kclk of table load, start-up and counter flush.  Cutting
-    // their tasks finer (4 or 8 permutations per task at least) shortened a lone 16-permutation launch to 170 / 145 us but the
-    // seeded step got LONGER (3.16-3.34 -> 3.30-3.38 ms: twice the wave-tasks, each with its fixed part) -- not kept.
-    const std::vector<int64_t> sg_blocks = slice_group_blocks(slice_width, n_slices, wv);
-    // (a column chunk of the tail has fewer word groups: its tasks are cut so that ITS launch fills the slots once too -- with the
-    // stage launches' task size a chunk of the last stage had 288 tasks for 960 slots and lasted as long as a whole stage)
-    auto one_list = [&](int64_t span, int64_t w_lo, int64_t w_hi, int64_t list_span) {
-        BitsQueues bq{};
-        const int64_t tpu = std::max<int64_t>(1, ceil_div(tasks_per_slot * slots, std::max<int64_t>(1, w_hi - w_lo)));
-        // (a task counts at most 255 permutations: eight counter levels)
-        const std::vector<int4> one =
-            w_hi > w_lo ? split_xcd_queues(cost_sorted_tasks(sg_blocks, span, w_lo, w_hi, tpu, 255, half_words, mloc), bq)
-                        : std::vector<int4>();
-        plan.list_queues.push_back(bq);
-        plan.list_span.push_back(list_span);
-        plan.list_first.push_back(static_cast<int64_t>(plan.tasks.size()));
-        plan.list_count.push_back(static_cast<int64_t>(one.size()));
-        plan.tasks.insert(plan.tasks.end(), one.begin(), one.end());
-    };
-    plan = BitsTaskPlan{};
-    plan.launch_list.assign(std::max<int64_t>(n_major + n_tail, 1), 0);
-    for (int64_t k = 0; k < n_tail; ++k) {             // one list per column chunk (possibly empty on a rank with fewer columns)
-        const int64_t w_lo = std::min<int64_t>(k * xc_wpc, n_units);
-        const int64_t w_hi = k + 1 == n_tail ? n_units : std::min<int64_t>((k + 1) * xc_wpc, n_units);
-        plan.launch_list[n_major + k] = static_cast<int64_t>(plan.list_span.size());
-        one_list(starts.back() - starts[n_major], w_lo, w_hi, -1 - k);          // (a list span that never matches a stage's)
-    }
-    for (int64_t c = 0; c < n_major; ++c) {
-        const int64_t span_c = starts[c + 1] - starts[c];
-        size_t k = 0;
-        while (k < plan.list_span.size() && plan.list_span[k] != span_c) ++k;
-        if (k == plan.list_span.size()) one_list(span_c, 0, n_units, span_c);
-        plan.launch_list[c] = static_cast<int64_t>(k);
-    }
-}
-
 // ev[2c], ev[2c+1] bracket launch c (recorded on alternating streams, all complete): sum of the durations, their count, and the
 // union of the intervals -- consecutive launches overlap, so the sum exceeds the time the GPU spent on them
 int kernel_stat_from_events(safe_ctx *ctx, hipEvent_t *ev, int64_t n_launch) {
@@ -2544,21 +2397,267 @@ static void blk_trace_dump(int n_launch) {
                     names[c], cls_work[c], cls_busy[c] / cls_work[c], cls_n[c], ph[c][0] / cls_n[c] / 1e3, ph[c][1] / cls_n[c] / 1e3, ph[c][2] / cls_n[c] / 1e3);
 }
 
+// ---- The bit-sliced launch, step by step (the matrix-core path has the same shape: mfma.hip, launch_mfma_run).  The form and
+//      its geometry, the tail split and the task lists are host arithmetic over plain numbers: bits_plan.h.
+
+// What the environment says to the bit-sliced launch, read on every call and nowhere else.  tail_frac: SAFE_HIP_XCHG_TAIL clamped
+// to [0, 1], read when a chunked exchange is armed -- the share of the permutations that the column-chunked exchange tail takes
+// (bits_tail_lists; 0 = no tail, the default); a positive share also makes a resident table run in the drawn stream's launches
+// (perm_launch_starts), whether or not a tail is cut afterwards.
+// dbg: SAFE_HIP_BITS_DBG, variants of the blocked kernel.  32 / 128 / 256 / 384 / 512 / 640 give correct results (A/B: one-stage carry
+// ripple, ..., 256 = no id stream = no hidden registers, 512 = no half-block gather pipeline); 1 / 2 / 4 / 8 / 16 / 64 skip work
+// (WRONG results) and exist only in a library built with `make DIAG=1`.  Anything else is refused (bits_form_kernel).
+struct BitsSwitches {
+    double tail_frac;
+    int dbg;
+};
+static BitsSwitches bits_switches(const safe_ctx *ctx) {
+    BitsSwitches sw = {0.0, 0};
+    if (ctx->xc_want >= 2)
+        if (const char *e = getenv("SAFE_HIP_XCHG_TAIL")) sw.tail_frac = std::min(1.0, std::max(0.0, atof(e)));
+    if (const char *e = getenv("SAFE_HIP_BITS_DBG")) sw.dbg = atoi(e);
+    if (sw.dbg == 0 && !safe_hidden_regs_checked()) {
+        // the build could not disassemble the stream kernels (no llvm-objdump): nothing vouches for the registers they hide from
+        // the compiler, so the form without them runs (the same counts, ~5 % slower)
+        static bool told = false;
+        if (!told) fprintf(stderr, "safepy_amd: this library was built without the hidden-register check; running k_permtest_bits_blk without the id stream\n");
+        told = true;
+        sw.dbg = 256;
+    }
+    return sw;
+}
+
+// The kernel of a form; dbg picks the variant of the blocked kernel and is checked for every form.  NULL (error set): no such variant.
+static const void *bits_form_kernel(const BitsForm &form, int dbg) {
+    const void *blk_fn = nullptr;
+    switch (dbg) {
+#define BITS_BLK_FN(D) case D: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, D>); break;
+        BITS_BLK_FN(0) BITS_BLK_FN(32) BITS_BLK_FN(128)
+        case 256: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 256>); break;
+        case 384: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 384>); break;
+        BITS_BLK_FN(512) BITS_BLK_FN(640)
+#ifdef SAFE_HIP_DIAG
+        BITS_BLK_FN(1) BITS_BLK_FN(2) BITS_BLK_FN(4) BITS_BLK_FN(7) BITS_BLK_FN(8) BITS_BLK_FN(16) BITS_BLK_FN(64) BITS_BLK_FN(1024) BITS_BLK_FN(2048)
+#endif
+#undef BITS_BLK_FN
+        default:
+            safe_set_error("SAFE_HIP_BITS_DBG=%d is not a variant of this build (correct variants: 0 32 128 256 384 512 640; the "
+                           "work-skipping ones 1 2 4 7 8 16 64 need a library built with make DIAG=1)", dbg);
+            return nullptr;
+    }
+    if (dbg & (95 | 1024 | 2048)) safe_warn_diagnostic("SAFE_HIP_BITS_DBG");
+    const bool lv11 = form.levels > BT_LV;
+    return form.kind == BITS_BLK ? blk_fn
+           : form.half           ? (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV + 1>)
+                                         : reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV>))
+                                 : (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV + 1>)
+                                         : reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV>));
+}
+
+// The call's task lists in nbr->bits_plan (plan_bits_tasks) and their pinned copy.  The lists only depend on the handle and on
+// the numbers of the key: the handle keeps the last plan.
+static int bits_task_plan(safe_ctx *ctx, safe_nbr *nbr, const BitsForm &form, const BitsTail &tail, const std::vector<int64_t> &starts,
+                          int64_t slots, int64_t mloc) {
+    const int64_t n_wg = ceil_div(mloc, 64);
+    std::vector<int64_t> plan_key = {n_wg, slots, tail.n_major + tail.n_chunks, tail.n_major, tail.n_chunks, tail.wpc, form.waves, form.half ? 1 : 0, mloc};
+    plan_key.insert(plan_key.end(), starts.begin(), starts.end());
+    BitsTaskPlan &plan = nbr->bits_plan;
+    if (plan.key == plan_key) return SAFE_OK;
+    // (column units of the tasks: word groups, or their halves)
+    plan_bits_tasks(plan, nbr->h_slice_width, nbr->n_slices, form.waves, slots, starts, form.half ? 2 * n_wg : n_wg, mloc, form.half,
+                    tail.n_major, tail.n_chunks, tail.wpc);
+    // (plan.key is set LAST, below: an allocation or a wait that fails on the way leaves no key, and the next call rebuilds
+    // the plan instead of uploading from a missing or stale pinned copy)
+    const size_t bytes = plan.tasks.size() * sizeof(int4);
+    if (nbr->bits_plan_pinned_bytes < bytes) {
+        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));                 // (an earlier pass may still be reading the old copy)
+        if (nbr->bits_plan_pinned) SAFE_HIP_CHECK(hipHostFree(nbr->bits_plan_pinned));
+        nbr->bits_plan_pinned = nullptr;
+        nbr->bits_plan_pinned_bytes = 0;
+        g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
+        SAFE_HIP_CHECK(hipHostMalloc(&nbr->bits_plan_pinned, bytes + 4096, hipHostMallocDefault));
+        nbr->bits_plan_pinned_bytes = bytes + 4096;
+    } else {
+        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    }
+    memcpy(nbr->bits_plan_pinned, plan.tasks.data(), bytes);
+    plan.key = plan_key;
+    return SAFE_OK;
+}
+
+// consecutive launches run on NS = 2 streams: a launch is as long as its longest task, the next one fills the slots its short
+// tasks leave.  Three or four launches in flight measured WORSE (unseeded 1000-permutation step 3.01 -> 3.19 -> 3.43 ms,
+// round 4): the later launches' workgroups take slots from the long tasks of the first
+constexpr int BITS_NS = 2;
+
+// The device buffers of one call, all from the context's scratch slots
+struct BitsBuffers {
+    uint2 *d_bits = nullptr;                        // the attribute operand: bit planes (taken and filled before the plan: launch_bits)
+    int4 *d_tasks = nullptr;                        // tasks + queue words in one scratch buffer
+    unsigned int *d_queue = nullptr, *d_gl = nullptr;   // eight queue counters per launch; the packed counters [mloc][n_pad]
+    int64_t n_pad = 0, entries_pad = 0;
+    uint16_t *d_ids[BITS_NS] = {nullptr, nullptr};  // permuted member lists of a stage launch, one buffer per stream
+    uint16_t *d_ids_tail = nullptr;                 // the tail's permuted member lists: built once, read by every column chunk's launch
+    uint32_t *d_obs = nullptr;                      // blocked form: observed sums (bits_observe)
+};
+// ... taken here, the task lists uploaded and the queue words and counters cleared on ctx->stream.  span: the longest stage launch
+static int bits_call_buffers(safe_ctx *ctx, const safe_nbr *nbr, const BitsTail &tail, int64_t mloc, int64_t span, int64_t tail_span,
+                             BitsBuffers *b) {
+    const size_t n_task = nbr->bits_plan.tasks.size();
+    const int64_t n_launch = tail.n_major + tail.n_chunks;
+    void *ws = nullptr;
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, n_task * sizeof(int4) + (8 * n_launch + 4) * sizeof(unsigned int), &ws));
+    b->d_tasks = static_cast<int4 *>(ws);
+    b->d_queue = reinterpret_cast<unsigned int *>(b->d_tasks + n_task);
+    b->n_pad = nbr->n_slices * 64;
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(b->n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&b->d_gl)));
+    SAFE_HIP_CHECK(hipMemcpyAsync(b->d_tasks, nbr->bits_plan_pinned, n_task * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK(hipMemsetAsync(b->d_queue, 0, 8 * n_launch * sizeof(unsigned int), ctx->stream));
+    SAFE_HIP_CHECK(hipMemsetAsync(b->d_gl, 0, static_cast<size_t>(b->n_pad) * mloc * sizeof(unsigned int), ctx->stream));
+    safe_trace("launch_bits: buffers ready");
+    b->entries_pad = (nbr->sell_entries + 1024 + 255) / 256 * 256;    // tail: the kernels fetch ids two blocks (2 x 512) ahead
+    for (int s = 0; s < BITS_NS; ++s)
+        SAFE_TRY(ctx_scratch(ctx, scratch_pair(SCRATCH_STREAM_A, s), static_cast<size_t>(span) * b->entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&b->d_ids[s])));
+    if (tail.n_chunks)
+        SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_TAIL_IDS, static_cast<size_t>(tail_span) * b->entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&b->d_ids_tail)));
+    return SAFE_OK;
+}
+
+// Blocked form: the observed sums of every (word group, slice), once: the compare operand of every task, and `ns`
+static int bits_observe(safe_ctx *ctx, const safe_nbr *nbr, const BitsForm &form, int64_t mloc, double *ns_out, BitsBuffers *b) {
+    const int64_t n_wg = ceil_div(mloc, 64);
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_OBSERVED, static_cast<size_t>(n_wg) * nbr->n_slices * 2 * BT_LV * 64 * sizeof(uint32_t),
+                         reinterpret_cast<void **>(&b->d_obs)));
+    const size_t lds_obs = form.lds_bytes + (ns_out ? 4 * 64 * 66 * sizeof(uint16_t) : 0);            // + the waves' transposition tiles
+    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bits_observed), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds_obs)));
+    hipLaunchKernelGGL(k_bits_observed, dim3(n_wg, ceil_div(nbr->n_slices, 4)), dim3(256), lds_obs, ctx->stream, nbr->n, nbr->sell_row,
+                       nbr->slice_off, nbr->slice_width, nbr->sell_col2b, nbr->n_slices, b->d_bits, mloc, b->d_obs, ns_out);
+    SAFE_HIP_CHECK(hipGetLastError());
+    return SAFE_OK;
+}
+
+// Exchange overlap of the sharded step (safe_set_exchange_chunks): the LAST permutations -- the tail -- run as one launch per
+// COLUMN chunk over all of the tail instead of one launch per stage over all columns.  A chunk's counters are then final when
+// its launch ends, and its all-gather overlaps the launches of the later chunks (xc_events; sharding.ChunkedExchange).
+// Tasks keep their size (a chunk has 1/K of the word groups and more permutations), so the kernels' work is the same; the
+// permuted member lists of the tail are built stage by stage beside the earlier launches and shared by the chunks' launches.
+// MEASURED (configs[1] on one MI355X with a one-rank RCCL group, tools/probe/xchg_ab.sh; plain step 3.6 ms, kernels 2.55 ms):
+//   * seeded stream, tail = 0.4 of the permutations: step +0.63 ms.  The stage launches run in step with the host's draws (a
+//     stage every 0.3 ms, kernels 0.5 ms behind), and a tail's launches cannot start before the LAST draw: every stage
+//     moved into the tail waits for the end of the stream.
+//   * seeded, tail = the last stage (waits for nothing new): step +0.7 ms.  A chunk of one stage has 1/K of the tasks: with
+//     the stages' task size 288 tasks for 960 slots (each chunk launch as long as a whole stage), with tasks cut to fill
+//     the slots 4.5 x as many task set-ups (table reload, counter flush): the four chunk launches took 0.72 ms for the
+//     0.31 ms of one launch.
+//   * unseeded (tables generated on the device, nothing to wait for), tail 0.2 / 0.4 / 1.0: kernels +0.2 .. +0.7 ms, step
+//     +1.2 ms: the chunks' copy-out and all-gather kernels crawl on the 16 CUs the persistent workgroups leave free.
+// It hides at most the exchange of K - 1 chunks (~0.9 ms of 1.2 ms at 8 ranks) and never paid for itself at this size, so the
+// tail is OFF by default (SAFE_HIP_XCHG_TAIL=<fraction of the permutations> switches it on; 1e-9 = the last stage); the
+// chunked exchange itself (sharding.ChunkedExchange) then runs its collectives right after the kernels, chunk by chunk
+// beside the derivation of the previous chunk's matrices.  Only the blocked form has a tail (bits_tail_split).
+//
+// In front of the first chunk launch: the tail's permuted member lists, one k_permute_cols per pipeline stage as its tables
+// arrive, on a stream of their own beside the stage launches (in one piece after the last draw they were 0.1 ms of idle GPU).
+// plain[8]: the lists are complete; plain[4 + s]: the stage launches of stream s have ended.
+static int bits_tail_lists(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const std::vector<int64_t> &starts, const BitsTail &tail,
+                           const BitsBuffers &b, hipEvent_t *plain) {
+    hipStream_t tail_ps = ctx->more_streams[1], kstreams[BITS_NS] = {ctx->stream, ctx->side_stream};
+    const int64_t n_stage = static_cast<int64_t>(starts.size()) - 1, entries_pad = b.entries_pad;
+    SAFE_HIP_CHECK(hipStreamWaitEvent(tail_ps, plain[0], 0));
+    for (int64_t t = tail.n_major; t < n_stage; ++t) {
+        SAFE_TRY(perms_wait(perms, starts[t + 1], tail_ps));
+        hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), starts[t + 1] - starts[t]), dim3(256),
+                           static_cast<size_t>(perms->stride16) * sizeof(uint16_t), tail_ps, perms->table16, perms->stride16,
+                           nbr->sell_col2b, nbr->sell_entries, entries_pad, starts[t], starts[t + 1] - starts[t],
+                           static_cast<uint32_t>(8 * nbr->n), b.d_ids_tail + (starts[t] - tail.p_split) * entries_pad, 3);
+        SAFE_HIP_CHECK(hipGetLastError());
+    }
+    SAFE_HIP_CHECK(hipEventRecord(plain[8], tail_ps));
+    // a chunk's counters are final once ITS launch and every stage launch have ended: the chunk launches themselves do not
+    // wait for the stage launches of the other stream (their tails overlap as everywhere else) -- the chunk's event does
+    for (int s = 0; s < BITS_NS; ++s) {
+        SAFE_HIP_CHECK(hipEventRecord(plain[4 + s], kstreams[s]));
+        SAFE_HIP_CHECK(hipStreamWaitEvent(kstreams[s], plain[8], 0));
+    }
+    return SAFE_OK;
+}
+
+// The launches: stage launch c < n_major over permutations [starts[c], starts[c + 1]) of all columns, its member lists permuted in
+// front of it; then the tail's column chunks over [p_split, P).  Launch c runs on stream c % NS so that the tail of one launch
+// (a few long tasks) overlaps the head of the next; ev[2 c], ev[2 c + 1] bracket it.  *xc_rc: recording a chunk's event failed.
+static int bits_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *perms, const BitsForm &form, const void *kfn,
+                             const std::vector<int64_t> &starts, const BitsTail &tail, const BitsBuffers &b, int64_t mloc, double *ns_out,
+                             const SpanFrame &fr, int *xc_rc) {
+    const BitsTaskPlan &plan = nbr->bits_plan;
+    const bool blk = form.kind == BITS_BLK;
+    const int64_t n = nbr->n, P = perms->count, entries_pad = b.entries_pad, n_pad = b.n_pad;
+    hipStream_t kstreams[BITS_NS] = {ctx->stream, ctx->side_stream};
+    // the kernels' workgroups are persistent and fill the register file (4 waves x 128 VGPRs per SIMD): on a CU they hold, the
+    // table kernels of the next pipeline stage (aux stream: scan rounds, row emission) wait for a whole workgroup to finish.  A few
+    // CUs are therefore left out of the grid (16 of 256): the median step shrinks by ~3 % at 1000 permutations, ~6 % at 10 000
+    // (round-3 sweep, CHANGELOG.md; 8 until the kernels got faster than k_permute_cols on 8 CUs: 10 000-permutation step
+    // 27.1 -> 26.3 ms with 16).  Blocked form: four workgroups per CU (the register file holds 16 waves); sixteen-wave forms: one.
+    const int spare = std::min(16, ctx->num_cu / 8);
+    const int64_t grid_max = static_cast<int64_t>(std::max(1, ctx->num_cu - spare)) * form.wgs_per_cu;
+    auto chunk_final = [&](int64_t c, hipStream_t ks) {          // behind chunk launch c on ks: the event that says its counters are final
+        for (int s = 0; s < BITS_NS; ++s)
+            if (kstreams[s] != ks && hipStreamWaitEvent(ks, fr.plain[4 + s], 0) != hipSuccess) *xc_rc = SAFE_E_HIP;
+        if (hipEventRecord(ctx->xc_events[c - tail.n_major], ks) != hipSuccess) *xc_rc = SAFE_E_HIP;
+    };
+    for (int64_t c = 0; c < fr.n_launch; ++c) {
+        const bool in_tail = c >= tail.n_major;                             // a column chunk over the tail's permutations
+        const int64_t p_base = in_tail ? tail.p_split : starts[c], p_limit = in_tail ? P : starts[c + 1];
+        const int64_t list = plan.launch_list[c], n_tasks = plan.list_count[list];     // this launch size's task list
+        const int4 *d_tasks = b.d_tasks + plan.list_first[list];
+        hipStream_t ks = kstreams[c % BITS_NS];
+        if (c == tail.n_major) SAFE_TRY(bits_tail_lists(ctx, nbr, perms, starts, tail, b, fr.plain));
+        if (!in_tail) SAFE_TRY(perms_wait(perms, p_limit, ks));            // host draws + table kernels for this span
+        safe_trace("launch_bits: span tables enqueued");
+        if (!in_tail)
+            hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), p_limit - p_base), dim3(256),
+                               static_cast<size_t>(perms->stride16) * sizeof(uint16_t), ks, perms->table16,
+                               perms->stride16, blk ? nbr->sell_col2b : nbr->sell_col2, nbr->sell_entries, entries_pad, p_base,
+                               p_limit - p_base, static_cast<uint32_t>(static_cast<uint64_t>(n) << form.id_shift), b.d_ids[c % BITS_NS],
+                               form.id_shift);
+        SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c], ks));
+        if (in_tail && n_tasks == 0) {                               // (a rank with fewer columns: nothing in this chunk)
+            SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c + 1], ks));
+            chunk_final(c, ks);
+            continue;
+        }
+        const int64_t grid = std::min<int64_t>(n_tasks, grid_max);
+        unsigned int *queue_c = b.d_queue + 8 * c;
+        const uint16_t *ids_c = in_tail ? b.d_ids_tail : b.d_ids[c % BITS_NS];
+        BitsQueues bq = plan.list_queues[list];
+        void *blk_args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
+                            (void *)&nbr->slice_width, (void *)&b.d_obs, (void *)&nbr->n_slices, (void *)&b.d_bits, (void *)&bq,
+                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&b.d_gl,
+                            (void *)&n_pad};
+        void *pre_args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
+                            (void *)&nbr->slice_width, (void *)&nbr->sell_col2, (void *)&nbr->n_slices, (void *)&b.d_bits, (void *)&n_tasks,
+                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&b.d_gl,
+                            (void *)&n_pad, (void *)&ns_out};
+        SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(grid), dim3(form.block), blk ? blk_args : pre_args, form.lds_bytes, ks));
+        if (in_tail) chunk_final(c, ks);
+        SAFE_HIP_CHECK(hipGetLastError());
+        SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c + 1], ks));
+    }
+    return SAFE_OK;
+}
+
 static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1,
                        const PermOut &out) {
     const int64_t n = nbr->n, mloc = col1 - col0, n_wg = ceil_div(mloc, 64), P = perms->count;
     const BitsForm form = bits_form(n, nbr->max_count, nbr->sell_col2 != nullptr, 160 * 1024);
     SAFE_REQUIRE(form.kind != BITS_NONE, "launch_bits: no bit-sliced form for %lld nodes with neighborhoods of up to %lld members",
                  static_cast<long long>(n), static_cast<long long>(nbr->max_count));
-    const bool blk = form.kind == BITS_BLK, half = form.kind == BITS_PRE32;
-    const int wv = blk ? 4 : 16;                         // waves (= adjacent slices of a task) per workgroup
-    const int id_shift = blk ? 3 : half ? 0 : 1;         // the permuted member lists hold id << id_shift
-    const int64_t n_wgt = half ? 2 * n_wg : n_wg;        // column units of the tasks: word groups, or their halves
     safe_trace("launch_bits: enter");
-    uint2 *d_bits = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&d_bits)));
-    launch_bits_prep(ctx, attr, col0, mloc, n_wg, d_bits);
+    BitsBuffers b;
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, static_cast<size_t>(n_wg) * (n + 1) * sizeof(uint2), reinterpret_cast<void **>(&b.d_bits)));
+    launch_bits_prep(ctx, attr, col0, mloc, n_wg, b.d_bits);
     safe_trace("launch_bits: prep launched");
+    const BitsSwitches sw = bits_switches(ctx);
     // The permutations are consumed in launches of `span` permutations so that the host's draw
     // stream for the next span overlaps this span's kernel.  Inside a launch, tasks = (word
     // group, group of adjacent slices, permutation sub-range), sized to about equal cost
@@ -2568,253 +2667,27 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     // step gets LONGER, 5.2 -> 5.5 / 5.8 ms: a merged launch waits for its last stage's draws)
     int64_t span = 1;
     // (a column-chunked exchange tail, when one is asked for, is cut from the drawn stream's launches whatever the handle's stages)
-    const char *tail_env = ctx->xc_want >= 2 ? getenv("SAFE_HIP_XCHG_TAIL") : nullptr;
-    const std::vector<int64_t> starts = perm_launch_starts(perms, &span, 1, tail_env && atof(tail_env) > 0.0);
-    // Exchange overlap of the sharded step (safe_set_exchange_chunks): the LAST permutations -- the tail -- run as one launch per
-    // COLUMN chunk over all of the tail instead of one launch per stage over all columns.  A chunk's counters are then final when
-    // its launch ends, and its all-gather overlaps the launches of the later chunks (xc_events; sharding.ChunkedExchange).
-    // Tasks keep their size (a chunk has 1/K of the word groups and more permutations), so the kernels' work is the same; the
-    // permuted member lists of the tail are built stage by stage beside the earlier launches and shared by the chunks' launches.
-    // MEASURED (configs[1] on one MI355X with a one-rank RCCL group, tools/probe/xchg_ab.sh; plain step 3.6 ms, kernels 2.55 ms):
-    //   * seeded stream, tail = 0.4 of the permutations: step +0.63 ms.  The stage launches run in step with the host's draws (a
-    //     stage every 0.3 ms, kernels 0.5 ms behind), and a tail's launches cannot start before the LAST draw: every stage
-    //     moved into the tail waits for the end of the stream.
-    //   * seeded, tail = the last stage (waits for nothing new): step +0.7 ms.  A chunk of one stage has 1/K of the tasks: with
-    //     the stages' task size 288 tasks for 960 slots (each chunk launch as long as a whole stage), with tasks cut to fill
-    //     the slots 4.5 x as many task set-ups (table reload, counter flush): the four chunk launches took 0.72 ms for the
-    //     0.31 ms of one launch.
-    //   * unseeded (tables generated on the device, nothing to wait for), tail 0.2 / 0.4 / 1.0: kernels +0.2 .. +0.7 ms, step
-    //     +1.2 ms: the chunks' copy-out and all-gather kernels crawl on the 16 CUs the persistent workgroups leave free.
-    // It hides at most the exchange of K - 1 chunks (~0.9 ms of 1.2 ms at 8 ranks) and never paid for itself at this size, so the
-    // tail is OFF by default (SAFE_HIP_XCHG_TAIL=<fraction of the permutations> switches it on; 1e-9 = the last stage); the
-    // chunked exchange itself (sharding.ChunkedExchange) then runs its collectives right after the kernels, chunk by chunk
-    // beside the derivation of the previous chunk's matrices.  Only the blocked form has a tail.
-    int64_t n_major = static_cast<int64_t>(starts.size()) - 1, p_split = P, xc_wpc = 0;
-    int xc_k = 0;
+    const std::vector<int64_t> starts = perm_launch_starts(perms, &span, 1, sw.tail_frac > 0.0);
     ctx->xc_made = 0;
-    if (ctx->xc_want >= 2 && ctx->xc_cols >= 64 && ctx->xc_cols % 64 == 0 && blk && n_major >= 3 &&
-        static_cast<int64_t>(std::min<int>(ctx->xc_want, safe_ctx::XC_MAX)) * ctx->xc_cols >= mloc) {
-        double frac = 0.0;                              // (off unless asked for: see the measurements above)
-        if (const char *e = getenv("SAFE_HIP_XCHG_TAIL")) frac = std::min(1.0, std::max(0.0, atof(e)));
-        int64_t c_split = 1;
-        while (c_split < n_major - 1 && static_cast<double>(starts[c_split]) < (1.0 - frac) * static_cast<double>(P)) ++c_split;
-        if (frac > 0.0) {
-            n_major = c_split;
-            p_split = starts[c_split];
-            xc_k = std::min<int>(ctx->xc_want, safe_ctx::XC_MAX);
-            xc_wpc = ctx->xc_cols / 64;
-        }
-    }
-    const int64_t n_tail = xc_k, tail_span = P - p_split;
-    const int64_t n_launch = n_major + n_tail;           // stage launches over all columns, then the tail's column chunks
+    const BitsTail tail = bits_tail_split(ctx->xc_want, ctx->xc_cols, safe_ctx::XC_MAX, form.kind == BITS_BLK, starts, P, mloc, sw.tail_frac);
+    const int64_t n_tail = tail.n_chunks, tail_span = P - tail.p_split;
+    const int64_t n_launch = tail.n_major + n_tail;      // stage launches over all columns, then the tail's column chunks
     const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / bits_lds_bytes(n, perms->stride16))));
-    const int64_t slots = static_cast<int64_t>(ctx->num_cu) * per_cu;
-    // the lists only depend on the handle and on these numbers: the handle keeps the last plan
-    std::vector<int64_t> plan_key = {n_wg, slots, n_launch, n_major, n_tail, xc_wpc, wv, half ? 1 : 0, mloc};
-    plan_key.insert(plan_key.end(), starts.begin(), starts.end());
-    BitsTaskPlan &plan = nbr->bits_plan;
-    if (plan.key != plan_key) {
-        plan_bits_tasks(plan, nbr->h_slice_width, nbr->n_slices, wv, slots, starts, n_wgt, mloc, half, n_major, n_tail, xc_wpc);
-        // (plan.key is set LAST, below: an allocation or a wait that fails on the way leaves no key, and the next call rebuilds
-        // the plan instead of uploading from a missing or stale pinned copy)
-        const size_t bytes = plan.tasks.size() * sizeof(int4);
-        if (nbr->bits_plan_pinned_bytes < bytes) {
-            SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));                 // (an earlier pass may still be reading the old copy)
-            if (nbr->bits_plan_pinned) SAFE_HIP_CHECK(hipHostFree(nbr->bits_plan_pinned));
-            nbr->bits_plan_pinned = nullptr;
-            nbr->bits_plan_pinned_bytes = 0;
-            g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-            SAFE_HIP_CHECK(hipHostMalloc(&nbr->bits_plan_pinned, bytes + 4096, hipHostMallocDefault));
-            nbr->bits_plan_pinned_bytes = bytes + 4096;
-        } else {
-            SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-        }
-        memcpy(nbr->bits_plan_pinned, plan.tasks.data(), bytes);
-        plan.key = plan_key;
-    }
-    const std::vector<int4> &tasks = plan.tasks;
-    const std::vector<int64_t> &list_first = plan.list_first, &list_count = plan.list_count, &launch_list = plan.launch_list;
-    const std::vector<BitsQueues> &list_queues = plan.list_queues;
+    SAFE_TRY(bits_task_plan(ctx, nbr, form, tail, starts, static_cast<int64_t>(ctx->num_cu) * per_cu, mloc));
     safe_trace("launch_bits: tasks built");
-    int4 *d_tasks = nullptr;
-    unsigned int *d_queue = nullptr;
-    unsigned int *d_gl = nullptr;
-    {
-        void *ws = nullptr;       // tasks + queue words in one scratch buffer
-        SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, tasks.size() * sizeof(int4) + (8 * n_launch + 4) * sizeof(unsigned int), &ws));
-        d_tasks = static_cast<int4 *>(ws);
-        d_queue = reinterpret_cast<unsigned int *>(d_tasks + tasks.size());
-    }
-    const int64_t n_pad = nbr->n_slices * 64;
-    SAFE_TRY(ctx_scratch(ctx, SCRATCH_COUNTERS, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), reinterpret_cast<void **>(&d_gl)));
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_tasks, nbr->bits_plan_pinned, tasks.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_queue, 0, 8 * n_launch * sizeof(unsigned int), ctx->stream));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_gl, 0, static_cast<size_t>(n_pad) * mloc * sizeof(unsigned int), ctx->stream));
-    safe_trace("launch_bits: buffers ready");
-    int4 *const d_task_lists = d_tasks;
-    const int64_t entries_pad = (nbr->sell_entries + 1024 + 255) / 256 * 256;    // tail: the kernels fetch ids two blocks (2 x 512) ahead
-    // consecutive launches run on NS = 2 streams: a launch is as long as its longest task, the next one fills the slots its short
-    // tasks leave.  Three or four launches in flight measured WORSE (unseeded 1000-permutation step 3.01 -> 3.19 -> 3.43 ms,
-    // round 4): the later launches' workgroups take slots from the long tasks of the first
-    constexpr int NS = 2;
-    uint16_t *d_ids[NS] = {nullptr, nullptr};
-    for (int b = 0; b < NS; ++b)
-        SAFE_TRY(ctx_scratch(ctx, scratch_pair(SCRATCH_STREAM_A, b), static_cast<size_t>(span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids[b])));
-    uint16_t *d_ids_tail = nullptr;                   // the tail's permuted member lists: built once, read by every column chunk's launch
-    if (n_tail)
-        SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_TAIL_IDS, static_cast<size_t>(tail_span) * entries_pad * sizeof(uint16_t), reinterpret_cast<void **>(&d_ids_tail)));
-    hipStream_t kstreams[NS] = {ctx->stream, ctx->side_stream};
-    const size_t lds_T = half ? bits_half_lds_bytes(n) : bits_pre_lds_bytes(n);     // the kernel's word column and queue slot
-    // SAFE_HIP_BITS_DBG: variants of the blocked kernel.  32 / 128 / 256 / 384 / 512 / 640 give correct results (A/B: one-stage carry
-    // ripple, ..., 256 = no id stream = no hidden registers, 512 = no half-block gather pipeline); 1 / 2 / 4 / 8 / 16 / 64 skip work
-    // (WRONG results) and exist only in a library built with `make DIAG=1`.  Anything else is refused.
-    int dbg = 0;
-    if (const char *e = getenv("SAFE_HIP_BITS_DBG")) dbg = atoi(e);
-    if (dbg == 0 && !safe_hidden_regs_checked()) {
-        // the build could not disassemble the stream kernels (no llvm-objdump): nothing vouches for the registers they hide from
-        // the compiler, so the form without them runs (the same counts, ~5 % slower)
-        static bool told = false;
-        if (!told) fprintf(stderr, "safepy_amd: this library was built without the hidden-register check; running k_permtest_bits_blk without the id stream\n");
-        told = true;
-        dbg = 256;
-    }
-    const void *blk_fn = nullptr;
-    switch (dbg) {
-        case 0: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 0>); break;
-        case 32: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 32>); break;
-        case 128: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 128>); break;
-        case 256: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 256>); break;
-        case 384: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk_plain<8, 384>); break;
-        case 512: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 512>); break;
-        case 640: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 640>); break;
-#ifdef SAFE_HIP_DIAG
-        case 1: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 1>); break;
-        case 2: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 2>); break;
-        case 4: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 4>); break;
-        case 7: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 7>); break;
-        case 8: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 8>); break;
-        case 16: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 16>); break;
-        case 64: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 64>); break;
-        case 1024: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 1024>); break;
-        case 2048: blk_fn = reinterpret_cast<const void *>(k_permtest_bits_blk<8, 2048>); break;
-#endif
-        default:
-            SAFE_REQUIRE(false, "SAFE_HIP_BITS_DBG=%d is not a variant of this build (correct variants: 0 32 128 256 384 512 640; the "
-                                "work-skipping ones 1 2 4 7 8 16 64 need a library built with make DIAG=1)", dbg);
-    }
-    if (dbg & (95 | 1024 | 2048)) safe_warn_diagnostic("SAFE_HIP_BITS_DBG");
-    const bool lv11 = form.levels > BT_LV;
-    const void *kfn = blk    ? blk_fn
-                      : half ? (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV + 1>)
-                                     : reinterpret_cast<const void *>(k_permtest_bits_pre32<8, 16, BT_LV>))
-                             : (lv11 ? reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV + 1>)
-                                     : reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV>));
-    SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_T)));
-    uint32_t *d_obs = nullptr;
-    if (blk) {
-        // observed sums of every (word group, slice), once: the compare operand of every task, and `ns`
-        SAFE_TRY(ctx_scratch(ctx, SCRATCH_BITS_OBSERVED, static_cast<size_t>(n_wg) * nbr->n_slices * 2 * BT_LV * 64 * sizeof(uint32_t),
-                             reinterpret_cast<void **>(&d_obs)));
-        const size_t lds_obs = lds_T + (out.ns ? 4 * 64 * 66 * sizeof(uint16_t) : 0);            // + the waves' transposition tiles
-        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bits_observed), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds_obs)));
-        hipLaunchKernelGGL(k_bits_observed, dim3(n_wg, ceil_div(nbr->n_slices, 4)), dim3(256), lds_obs, ctx->stream, n, nbr->sell_row,
-                           nbr->slice_off, nbr->slice_width, nbr->sell_col2b, nbr->n_slices, d_bits, mloc, d_obs, out.ns);
-        SAFE_HIP_CHECK(hipGetLastError());
-    }
-    // the kernels' workgroups are persistent and fill the register file (4 waves x 128 VGPRs per SIMD): on a CU they hold, the
-    // table kernels of the next pipeline stage (aux stream: scan rounds, row emission) wait for a whole workgroup to finish.  A few
-    // CUs are therefore left out of the grid (16 of 256): the median step shrinks by ~3 % at 1000 permutations, ~6 % at 10 000
-    // (round-3 sweep, CHANGELOG.md; 8 until the kernels got faster than k_permute_cols on 8 CUs: 10 000-permutation step
-    // 27.1 -> 26.3 ms with 16).  Blocked form: four workgroups per CU (the register file holds 16 waves); sixteen-wave forms: one.
-    const int spare = std::min(16, ctx->num_cu / 8);
-    const int64_t grid_max = static_cast<int64_t>(std::max(1, ctx->num_cu - spare)) *
-                             (blk ? std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds_T)) : 1);
-    ctx->last_kernel.name = blk ? "k_permtest_bits_blk" : "k_permtest_bits_pre";
-    ctx->last_kernel.total_ms = 0.0;
-    ctx->last_kernel.busy_ms = 0.0;
-    ctx->last_kernel.launches = 0;
-    hipEvent_t *ev = nullptr, *plain = nullptr;                   // pooled on the context
-    SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &ev));
-    SAFE_TRY(ctx_events(ctx, false, 12, &plain));                 // 0: inputs ready, 1..3: end join, 4..7: join before the tail, 8: tail lists
+    SAFE_TRY(bits_call_buffers(ctx, nbr, tail, mloc, span, tail_span, &b));
+    const void *kfn = bits_form_kernel(form, sw.dbg);
+    if (!kfn) return SAFE_E_INVALID;
+    SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(form.lds_bytes)));
+    if (form.kind == BITS_BLK) SAFE_TRY(bits_observe(ctx, nbr, form, mloc, out.ns, &b));
     for (int64_t k = 0; k < n_tail; ++k)
         if (!ctx->xc_events[k]) SAFE_HIP_CHECK(hipEventCreateWithFlags(&ctx->xc_events[k], hipEventDisableTiming));
-    // consecutive spans alternate between two streams so the tail of one launch (a few long
-    // tasks) overlaps the head of the next; both wait for the inputs prepared on ctx->stream
-    hipEvent_t ready = plain[0];
-    SAFE_HIP_CHECK(hipEventRecord(ready, ctx->stream));
-    for (int b = 1; b < NS; ++b) SAFE_HIP_CHECK(hipStreamWaitEvent(kstreams[b], ready, 0));
-    hipStream_t tail_ps = ctx->more_streams[1];
+    SpanFrame fr;                                   // plain 0: inputs ready, 1..3: end join, 4..7: join before the tail, 8: tail lists
+    SAFE_TRY(span_frame_open(ctx, form.kind == BITS_BLK ? "k_permtest_bits_blk" : "k_permtest_bits_pre", n_launch, 12, &fr));
     int xc_rc = SAFE_OK;
-    auto chunk_final = [&](int64_t c, hipStream_t ks) {          // behind chunk launch c on ks: the event that says its counters are final
-        for (int b = 0; b < NS; ++b)
-            if (kstreams[b] != ks && hipStreamWaitEvent(ks, plain[4 + b], 0) != hipSuccess) xc_rc = SAFE_E_HIP;
-        if (hipEventRecord(ctx->xc_events[c - n_major], ks) != hipSuccess) xc_rc = SAFE_E_HIP;
-    };
-    for (int64_t c = 0; c < n_launch; ++c) {
-        const bool tail = c >= n_major;                                     // a column chunk over the tail's permutations
-        const int64_t p_base = tail ? p_split : starts[c], p_limit = tail ? P : starts[c + 1];
-        const int64_t n_tasks = list_count[launch_list[c]];                 // this launch size's task list
-        const int4 *d_tasks = d_task_lists + list_first[launch_list[c]];
-        hipStream_t ks = kstreams[c % NS];
-        if (tail && c == n_major) {
-            // the tail's permuted member lists: one k_permute_cols per pipeline stage as its tables arrive, on a stream of their
-            // own beside the stage launches (in one piece after the last draw they were 0.1 ms of idle GPU)
-            const int64_t n_stage = static_cast<int64_t>(starts.size()) - 1;
-            SAFE_HIP_CHECK(hipStreamWaitEvent(tail_ps, ready, 0));
-            for (int64_t t = n_major; t < n_stage; ++t) {
-                SAFE_TRY(perms_wait(perms, starts[t + 1], tail_ps));
-                hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), starts[t + 1] - starts[t]), dim3(256),
-                                   static_cast<size_t>(perms->stride16) * sizeof(uint16_t), tail_ps, perms->table16, perms->stride16,
-                                   nbr->sell_col2b, nbr->sell_entries, entries_pad, starts[t], starts[t + 1] - starts[t],
-                                   static_cast<uint32_t>(8 * n), d_ids_tail + (starts[t] - p_split) * entries_pad, 3);
-                SAFE_HIP_CHECK(hipGetLastError());
-            }
-            SAFE_HIP_CHECK(hipEventRecord(plain[8], tail_ps));
-            // a chunk's counters are final once ITS launch and every stage launch have ended: the chunk launches themselves do not
-            // wait for the stage launches of the other stream (their tails overlap as everywhere else) -- the chunk's event does
-            for (int b = 0; b < NS; ++b) {
-                SAFE_HIP_CHECK(hipEventRecord(plain[4 + b], kstreams[b]));
-                SAFE_HIP_CHECK(hipStreamWaitEvent(kstreams[b], plain[8], 0));
-            }
-        }
-        if (!tail) SAFE_TRY(perms_wait(perms, p_limit, ks));            // host draws + table kernels for this span
-        safe_trace("launch_bits: span tables enqueued");
-        if (!tail)
-            hipLaunchKernelGGL(k_permute_cols, dim3(ceil_div(entries_pad, 4096), p_limit - p_base), dim3(256),
-                               static_cast<size_t>(perms->stride16) * sizeof(uint16_t), ks, perms->table16,
-                               perms->stride16, blk ? nbr->sell_col2b : nbr->sell_col2, nbr->sell_entries, entries_pad, p_base,
-                               p_limit - p_base, static_cast<uint32_t>(static_cast<uint64_t>(n) << id_shift), d_ids[c % NS], id_shift);
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
-        const int64_t grid = std::min<int64_t>(n_tasks, grid_max);
-        unsigned int *queue_c = d_queue + 8 * c;
-        if (tail && n_tasks == 0) {                                  // (a rank with fewer columns: nothing in this chunk)
-            SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
-            chunk_final(c, ks);
-            continue;
-        }
-        if (blk) {
-            const uint16_t *ids_c = tail ? d_ids_tail : d_ids[c % NS];
-            BitsQueues bq = list_queues[launch_list[c]];
-            void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
-                            (void *)&nbr->slice_width, (void *)&d_obs, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&bq,
-                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
-                            (void *)&n_pad};
-            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(grid), dim3(256), args, lds_T, ks));
-            if (tail) chunk_final(c, ks);
-        } else {
-            const uint16_t *ids_c = d_ids[c % NS];
-            void *args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
-                            (void *)&nbr->slice_width, (void *)&nbr->sell_col2, (void *)&nbr->n_slices, (void *)&d_bits, (void *)&n_tasks,
-                            (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&d_gl,
-                            (void *)&n_pad, (void *)&out.ns};
-            SAFE_HIP_CHECK(hipLaunchKernel(kfn, dim3(grid), dim3(1024), args, lds_T, ks));
-        }
-        SAFE_HIP_CHECK(hipGetLastError());
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
-    }
-    ctx->packed_counts = d_gl;
-    ctx->packed_n_pad = n_pad;
+    SAFE_TRY(bits_launch_spans(ctx, nbr, perms, form, kfn, starts, tail, b, mloc, out.ns, fr, &xc_rc));
+    ctx->packed_counts = b.d_gl;
+    ctx->packed_n_pad = b.n_pad;
     ctx->packed_m = mloc;
     ctx->packed_perms = P;
     ctx->packed_layout = 0;
@@ -2827,19 +2700,13 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
         safe_trace("launch_bits: column chunks enqueued");
         if (ctx->xc_callback) ctx->xc_callback(ctx->xc_user);          // the caller's exchange of the chunks goes out behind these launches
     }
-    for (int b = 1; b < NS; ++b) {
-        SAFE_HIP_CHECK(hipEventRecord(plain[b], kstreams[b]));
-        SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->stream, plain[b], 0));
-    }
-    SAFE_TRY(enrich_finalize_counts(ctx, d_gl, n_pad, nbr->sell_row, mloc, P, out, nullptr));
+    SAFE_TRY(span_frame_join(ctx, fr));
+    SAFE_TRY(enrich_finalize_counts(ctx, b.d_gl, b.n_pad, nbr->sell_row, mloc, P, out, nullptr));
     SAFE_HIP_CHECK(hipGetLastError());
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
     safe_trace("launch_bits: all enqueued");
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));    // tasks (host vector) and temporaries
+    SAFE_TRY(span_frame_close(ctx, fr));            // (the host wait: tasks and temporaries)
     safe_trace("launch_bits: synced");
-    SAFE_TRY(kernel_stat_from_events(ctx, ev, n_launch));
-    if (dbg & 128) blk_trace_dump(static_cast<int>(n_launch));
+    if (sw.dbg & 128) blk_trace_dump(static_cast<int>(n_launch));
     return SAFE_OK;
 }
 
@@ -2909,35 +2776,23 @@ static int launch_lds_f64(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_pe
     const auto kfn = z ? k_permtest_lds<true, NW> : k_permtest_lds<false, NW>;
     SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds_bytes)));
-    ctx->last_kernel.name = "k_permtest_lds";
-    ctx->last_kernel.total_ms = 0.0;
-    ctx->last_kernel.busy_ms = 0.0;
-    ctx->last_kernel.launches = 0;
-    hipEvent_t *ev = nullptr, *plain = nullptr;                   // pooled on the context
-    SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &ev));
-    SAFE_TRY(ctx_events(ctx, false, 2, &plain));
-    hipEvent_t ready = plain[0], side_done = plain[1];
-    SAFE_HIP_CHECK(hipEventRecord(ready, ctx->stream));
-    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ready, 0));
+    SpanFrame fr;
+    SAFE_TRY(span_frame_open(ctx, "k_permtest_lds", n_launch, 2, &fr));
     for (int64_t c = 0; c < n_launch; ++c) {
         const int64_t p_base = starts[c], p_limit = starts[c + 1];
         hipStream_t ks = (c & 1) ? ctx->side_stream : ctx->stream;
         SAFE_TRY(perms_wait(perms, p_limit, ks));
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c], ks));
+        SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c], ks));
         hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * NW), lds_bytes, ks, n, perms->table16, perms->stride16, nbr->sell_row,
                            nbr->slice_off, nbr->slice_width, nbr->sell_col2, nbr->n_slices, d_tiles, n_tasks, d_tasks, p_base,
                            p_limit, d_queue + c, mloc, d_counts, n_pad, d_ns);
         SAFE_HIP_CHECK(hipGetLastError());
-        SAFE_HIP_CHECK(hipEventRecord(ev[2 * c + 1], ks));
+        SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c + 1], ks));
     }
-    SAFE_HIP_CHECK(hipEventRecord(side_done, ctx->side_stream));
-    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->stream, side_done, 0));
+    SAFE_TRY(span_frame_join(ctx, fr));
     SAFE_TRY(enrich_finalize_counts(ctx, d_counts, n_pad, nbr->sell_row, mloc, P, out, d_ns));
     SAFE_HIP_CHECK(hipGetLastError());
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    return kernel_stat_from_events(ctx, ev, n_launch);
+    return span_frame_close(ctx, fr);
 }
 
 // Hypergeometric path for binary attributes with the tail looked up instead of evaluated per

@@ -3110,21 +3110,21 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
     ctx->last_undecided = 0;
     // z-scores: the counters compare against the observed score itself, which may be NaN (k_counts_finalize<true> reads it)
     if (z && !out.ns) SAFE_TRY(ctx_scratch(ctx, SCRATCH_F64_MATRIX, static_cast<size_t>(n) * mloc * sizeof(double), reinterpret_cast<void **>(&out.ns)));
+    // (the frame is opened by hand: the observed-score pass runs between the taking of the events and "inputs ready")
     ctx->last_kernel.name = "k_permtest_mfma";
     ctx->last_kernel.total_ms = 0.0;
     ctx->last_kernel.busy_ms = 0.0;
     ctx->last_kernel.launches = 0;
-    hipEvent_t *ev = nullptr, *plain = nullptr;                   // pooled on the context
-    SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &ev));
-    SAFE_TRY(ctx_events(ctx, false, 2, &plain));
-    hipEvent_t ready = plain[0], side_done = plain[1];
+    SpanFrame fr;
+    fr.n_launch = n_launch;
+    SAFE_TRY(ctx_events(ctx, true, 2 * n_launch, &fr.ev));
+    SAFE_TRY(ctx_events(ctx, false, 2, &fr.plain));
     if (form.filtered()) SAFE_TRY(mfma_observe(ctx, nbr, form, cols, plan, mloc, out.ns));
-    SAFE_HIP_CHECK(hipEventRecord(ready, ctx->stream));
-    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ready, 0));
-    SAFE_TRY(mfma_launch_spans(ctx, nbr, perms, form, cols, plan, mloc, out.ns, mfma_dbg, ev, overflowed));
+    SAFE_HIP_CHECK(hipEventRecord(fr.plain[0], ctx->stream));
+    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, fr.plain[0], 0));
+    SAFE_TRY(mfma_launch_spans(ctx, nbr, perms, form, cols, plan, mloc, out.ns, mfma_dbg, fr.ev, overflowed));
     if (*overflowed) return SAFE_OK;
-    SAFE_HIP_CHECK(hipEventRecord(side_done, ctx->side_stream));
-    SAFE_HIP_CHECK(hipStreamWaitEvent(ctx->stream, side_done, 0));
+    SAFE_TRY(span_frame_join(ctx, fr));
     std::vector<unsigned int> amb_seen(form.filtered() ? n_launch : 0, 0u);
     if (form.filtered())
         SAFE_HIP_CHECK(hipMemcpyAsync(amb_seen.data(), plan.d_amb_cnt, amb_seen.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
@@ -3136,10 +3136,7 @@ static int launch_mfma_run(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_p
         ctx->packed_perms = P;
         ctx->packed_layout = 1;
     }
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k0, ctx->stream));
-    SAFE_HIP_CHECK(hipEventRecord(ctx->k1, ctx->stream));
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    SAFE_TRY(kernel_stat_from_events(ctx, ev, n_launch));
+    SAFE_TRY(span_frame_close(ctx, fr));
 #ifdef SAFE_HIP_DIAG
     if (mfma_dbg == 512 && ctx->diag_prof) {
         unsigned long long prof[64];
