@@ -306,6 +306,26 @@ int safe_attr_column_moments(safe_attr *attr, int64_t col0, int64_t col1, double
 /* Override the row flags (attribute-sharded multi-GPU runs must use the flags of the
  * FULL matrix, not of the local column shard). */
 int safe_attr_set_row_flags(safe_attr *attr, const uint8_t *flags_host);
+/* Additive (attribute_transform = 'rank'): every column of `src` replaced by its midranks.  *out is a new handle that owns a
+ * dense f64 matrix R of the same [n, m] in Fortran order, and no later call can tell it from safe_attr_create_host of R
+ * (statistics, column sums, moments and support lists are built lazily, as for any handle).  For every column j:
+ *   R[i, j] = NaN where src is NaN, else the midrank of the value among the column's non-NaN values: the mean of the 1-based
+ *   positions its tie group takes in ascending order -- scipy.stats.rankdata(col, method='average', nan_policy='omit'), bit for
+ *   bit (a multiple of 0.5).
+ * Equality is IEEE equality of the values widened to f64: -0.0 ties with +0.0, -inf / +inf rank at the ends, subnormals and values
+ * one ulp apart are distinct.
+ * src: any handle -- f32, f64, u8 widened to f32 on upload, either element order, made by _host, _dev, _csc_host or _reindex --
+ * and is not modified.  The new handle inherits src's row flags as they are, flags installed by safe_attr_set_row_flags
+ * included (the set of NaN cells is unchanged; a column shard of a multi-GPU run keeps the full matrix's flags); where src has
+ * none yet, the new handle finds its own on first use, and they are the same.
+ * Any n and m a handle holds; the rows of a column are sorted in chunks of SAFE_RANK_CHUNK and no limit on n comes from the
+ * chunk (n < 2^30).  Runs on the context's stream and synchronises.  Scratch (8 m ceil(n / SAFE_RANK_CHUNK) SAFE_RANK_CHUNK
+ * bytes) belongs to the call and is gone on every return path; R's block is the only allocation that survives.  A NULL argument
+ * is SAFE_E_INVALID and creates nothing (*out = NULL on every failure).  safe_last_kernel_stats names
+ * k_rank_keys+k_rank_sort+k_rank_emit; safe_last_rank_stats gives the three kernels' times (ms) of the context's last call. */
+#define SAFE_RANK_CHUNK 4096
+int safe_attr_rank(safe_attr *src, safe_attr **out);
+int safe_last_rank_stats(safe_ctx *ctx, double *keys_ms, double *sort_ms, double *emit_ms);
 
 /* ------------------------------------------------------------ permutations ---- */
 /* The row-permutation stream of run_permutations (safepy/safe_extras.py:46-58):

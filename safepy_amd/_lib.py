@@ -18,6 +18,7 @@ E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
 SELECT_MAX_NODES = 65536            # SAFE_SELECT_MAX_NODES: nodes safe_pair_distance_select_xy / safe_nbr_distance_select take
 KK_MAX_NODES = 65536                # SAFE_KK_MAX_NODES: nodes safe_kk_create_host / safe_kk_create_nbr take
 LINKAGE_MAX_POINTS = 16384          # SAFE_LINKAGE_MAX_POINTS: points safe_linkage_average / safe_profile_linkage take
+RANK_CHUNK = 4096                   # SAFE_RANK_CHUNK: rows of a column that safe_attr_rank sorts in one workgroup
 # metric ids of safe_profile_distances (SAFE_METRIC_*), by SciPy's metric name
 METRIC_IDS = {'jaccard': 0, 'hamming': 1, 'dice': 2, 'rogerstanimoto': 3, 'russellrao': 4, 'sokalmichener': 5, 'sokalsneath': 6,
               'yule': 7}
@@ -127,6 +128,8 @@ PROTOTYPES = {
     'safe_attr_column_sums': (C.c_int, [_vp, _vp]),
     'safe_attr_column_moments': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     'safe_attr_set_row_flags': (C.c_int, [_vp, _vp]),
+    'safe_attr_rank': (C.c_int, [_vp, _pp]),
+    'safe_last_rank_stats': (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'safe_perms_create': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, C.c_uint32, _pp]),
     'safe_perms_destroy': (C.c_int, [_vp]),
     'safe_perms_read': (C.c_int, [_vp, _i64, _i64, _vp]),

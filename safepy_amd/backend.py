@@ -237,6 +237,12 @@ class Context:
         check(lib.safe_last_kernel_stats(self.handle, name, 128, C.byref(ms), C.byref(cnt)))
         return name.value.decode(), ms.value, cnt.value
 
+    def last_rank_stats(self):
+        """(k_rank_keys, k_rank_sort, k_rank_emit) times in ms of the context's last Attributes.rank()."""
+        ms = [C.c_double() for _ in range(3)]
+        check(lib.safe_last_rank_stats(self.handle, *[C.byref(x) for x in ms]))
+        return tuple(x.value for x in ms)
+
     def last_kernel_busy_ms(self):
         """Time during which at least one launch of the dominant kernel of the last call was running (launches overlap)."""
         ms = C.c_double()
@@ -862,6 +868,16 @@ class Attributes:
         assert flags.shape == (self.n,)
         check(lib.safe_attr_set_row_flags(self.handle, _ptr(flags)))
 
+    def rank(self):
+        """A new handle that owns R, f64 [n, m] in Fortran order (read it with download(np.float64, order='F')): every column
+        of this matrix replaced by its midranks among the column's non-NaN values, NaN where this matrix is NaN --
+        scipy.stats.rankdata(b, method='average', axis=0, nan_policy='omit'), bit for bit, sorted on the device
+        (safe_attr_rank).  This handle is not modified; the new one inherits its row flags, owns its memory (it keeps nothing
+        of this handle alive) and is closed by the caller."""
+        h = C.c_void_p()
+        check(lib.safe_attr_rank(self.handle, C.byref(h)))
+        return type(self)(self.ctx, h, self.n, self.m, dtype=np.float64)
+
     def close(self):
         if self.handle:
             check(lib.safe_attr_destroy(self.handle))
@@ -872,6 +888,9 @@ class Attributes:
             self.close()
         except Exception:
             pass
+
+
+AttributeMatrix = Attributes        # the handle under the name of what it holds
 
 
 class Permutations:

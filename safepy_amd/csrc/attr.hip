@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256) void k_csc_missing_rows(const uint8_t *__restr
     for (int64_t j = blockIdx.y; j < m; j += gridDim.y) out[j * n + i] = static_cast<T>(__builtin_nan(""));
 }
 
-static int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out) {
+int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out) {
     SAFE_REQUIRE(ctx && out, "safe_attr_create: NULL argument");
     SAFE_REQUIRE(dtype == SAFE_DTYPE_F32 || dtype == SAFE_DTYPE_F64, "safe_attr_create: dtype must be f32 or f64 (u8: host form only)");
     SAFE_REQUIRE(n >= 1 && m >= 1, "safe_attr_create: empty matrix (%lld x %lld)", (long long)n, (long long)m);
@@ -515,6 +515,26 @@ static int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, 
     a->row_stride = rs;
     a->col_stride = cs;
     *out = a;
+    return SAFE_OK;
+}
+
+int attr_inherit_flags(safe_attr *dst, const safe_attr *src) {
+    if (!src->flags_ready || !src->row_flags) return SAFE_OK;
+    safe_ctx *ctx = dst->ctx;
+    const size_t flag_bytes = flags_block_bytes(dst->n);
+    uint8_t *flags = nullptr;
+    SAFE_TRY(ctx_block_alloc(ctx, flag_bytes, reinterpret_cast<void **>(&flags)));
+    hipError_t e = hipMemcpyAsync(flags, src->row_flags, flag_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = safe_stream_sync(ctx->stream);
+    if (e != hipSuccess) {
+        ctx_block_free(ctx, flags, flag_bytes);
+        safe_set_error("attr_inherit_flags: %s", hipGetErrorString(e));
+        return SAFE_E_HIP;
+    }
+    dst->row_flags = flags;
+    dst->flags_ready = true;
+    dst->n_rows_with_value = src->n_rows_with_value;
+    dst->h_row_flags = src->h_row_flags;
     return SAFE_OK;
 }
 

@@ -158,6 +158,7 @@ struct safe_ctx {
     void *diag_prof = nullptr;                  // (diagnostic builds) per-phase cycle counters of the matrix-core kernel
     int last_core_slices = 0;                   // slices its matrix-core kernel multiplied (3 of 6 in the filtered form)
     int64_t last_undecided = 0;                 // filtered form: compares decided by k_mfma_resolve (negative: list overflow, six-slice rerun)
+    double rank_ms[3] = {0.0, 0.0, 0.0};        // k_rank_keys, k_rank_sort, k_rank_emit of the last safe_attr_rank (safe_last_rank_stats)
     // grow-only scratch buffers reused across calls (hipMalloc of >100 MB costs milliseconds)
     struct safe_perms *perm_cache = nullptr;    // buffers of the last destroyed permutation handle, reused by the next
     struct PermRing *ring = nullptr;            // node-shared permutation stream (safe_ctx_share_stream), or NULL
@@ -583,6 +584,10 @@ int safe_attr_prepare(safe_attr *attr);   // row flags + stats (attr.hip)
 int nbr_finalize_from_bits(safe_nbr *nbr);   // bits -> CSR + SELL (nbr.hip)
 int nbr_build_transpose(safe_nbr *nbr);      // at_ptr / at_col (nbr.hip)
 int attr_build_support(safe_attr *attr);     // sup_ptr / sup_row of a binary matrix (attr.hip)
+// an attribute handle that owns nothing on the device yet (the checks of safe_attr_create_*; attr.hip)
+int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out);
+// dst (same n, no flags yet) takes a copy of src's row flags if src has any -- computed or installed; else nothing happens (attr.hip)
+int attr_inherit_flags(safe_attr *dst, const safe_attr *src);
 int perms_build_inverse(safe_perms *perms);  // inverse tables (rng.cpp)
 int perms_generate_until(safe_perms *perms, int64_t upto);   // enqueue table rows [generated, upto) on aux_stream (rng.cpp)
 // host/GPU pipeline stages of the permutation stream for `count` permutations: boundaries b[0] = 0 < b[1] < ... < b.back() = count

@@ -246,6 +246,7 @@ class SAFE:
         self.neighborhood_score_type = 'sum'
         self.enrichment_type = 'auto'
         self.hypergeom_tails = 'upper'   # 'attribute_sign': the hypergeometric test follows attribute_sign (both tails, ns, signed nes)
+        self.attribute_transform = 'none'   # 'rank': compute_pvalues tests the per-column midranks of node2attribute (ranked on the device)
         self.enrichment_threshold = 0.05
         self.enrichment_max_log10 = 16
         self.attribute_enrichment_min_size = 10
@@ -358,6 +359,10 @@ class SAFE:
             bad, self.hypergeom_tails = self.hypergeom_tails, 'upper'
             raise ValueError('%s is not a valid setting for hypergeom_tails. '
                              'Valid options are: upper, attribute_sign' % (bad,))
+        if getattr(self, 'attribute_transform', 'none') not in ['none', 'rank']:
+            bad, self.attribute_transform = self.attribute_transform, 'none'
+            raise ValueError('%s is not a valid setting for attribute_transform. '
+                             'Valid options are: none, rank' % (bad,))
         multiple = getattr(self, 'attribute_unimodality_radius_multiple', 2.0)
         if not _is_real(multiple) or not np.isfinite(multiple) or multiple <= 0:
             self.attribute_unimodality_radius_multiple = 2.0
@@ -414,6 +419,7 @@ class SAFE:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('hypergeom_tails', 'upper')     # (objects pickled before the setting existed)
+        self.__dict__.setdefault('attribute_transform', 'none')
         self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
         self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
         if isinstance(self.default_config, dict):
@@ -768,7 +774,15 @@ class SAFE:
 
     # -------------------------------------------------------------- enrichment ----
     def compute_pvalues(self, **kwargs):
-        """safepy/safe.py:432-472."""
+        """safepy/safe.py:432-472.
+
+        attribute_transform = 'rank' (additive; keyword or setting, default 'none'): the test runs on the per-column midranks
+        of node2attribute -- scipy.stats.rankdata(method='average', axis=0, nan_policy='omit'), NaN kept -- computed on the
+        device after background = 'network' has been applied; node2attribute and a resident handle are not touched.  ns then
+        holds rank sums (rank z-scores with neighborhood_score_type = 'z-score'), not sums of attribute values.
+        how = 'analytic' on ranks is the tie-corrected Wilcoxon / Mann-Whitney rank-sum test of every attribute in every
+        neighborhood, how = 'randomization' its permutation form.  'auto' still looks at the raw values; a hypergeometric
+        route (how = 'hypergeometric', or 'auto' on 0/1 data) is refused with a ValueError: ranks are not counts."""
         if 'how' in kwargs:
             self.enrichment_type = kwargs['how']
         if 'neighborhood_score_type' in kwargs:
@@ -779,9 +793,14 @@ class SAFE:
             self.background = kwargs['background']
         if 'hypergeom_tails' in kwargs:
             self.hypergeom_tails = kwargs['hypergeom_tails']
+        if 'attribute_transform' in kwargs:
+            self.attribute_transform = kwargs['attribute_transform']
         self.validate_config()
         if self.enrichment_type == 'analytic':
             self._require_sum_scores_for_moments()             # before any device work
+        ranked = self.attribute_transform == 'rank'
+        if ranked and self.enrichment_type == 'hypergeometric':
+            self._refuse_hypergeom_on_ranks()                  # before any device work
 
         resident = self._resident_attributes()
         if self.background == 'network':
@@ -812,24 +831,32 @@ class SAFE:
                 if resident is not None:
                     self.node2attribute.flags.writeable = False
 
-        attr = resident if resident is not None else self._upload_attributes()
+        raw = resident if resident is not None else self._upload_attributes()
+        attr = raw
         try:
-            stats = attr.stats()
+            stats = raw.stats()
             if stats['max_nan_col'] / self.node2attribute.shape[0] > 0.5:
                 logging.warning("WARNING: more than 50% of nodes in the network are set to NaN and "
                                 "will be ignored for calculating enrichment.\n"
                                 "Consider setting sf.background = 'network'.")
+            hypergeom = (self.enrichment_type == 'hypergeometric') or \
+                ((self.enrichment_type == 'auto') and (stats['n_other'] == 0))      # ('auto' looks at the raw values)
+            if ranked:
+                if hypergeom:
+                    self._refuse_hypergeom_on_ranks()
+                attr = raw.rank()
             self._pending_binary = None
             if self.enrichment_type == 'analytic':              # additive and opt-in: 'auto' never chooses it
                 self.compute_pvalues_by_moments(_attr=attr, **kwargs)
-            elif (self.enrichment_type == 'hypergeometric') or \
-                    ((self.enrichment_type == 'auto') and (stats['n_other'] == 0)):
+            elif hypergeom:
                 self.compute_pvalues_by_hypergeom(_attr=attr, **kwargs)
             else:
                 self.compute_pvalues_by_randomization(_attr=attr, **kwargs)
         finally:
-            if resident is None:
+            if attr is not raw:
                 attr.close()
+            if resident is None:
+                raw.close()
 
         # safe.py:468-472 -- computed by the same kernels, from the same nes
         self.nes_binary, enriched = self._pending_binary
@@ -935,6 +962,11 @@ class SAFE:
         if self.neighborhood_score_type != 'sum':
             raise ValueError("how = 'analytic' is defined for neighborhood_score_type = 'sum' only (the permutation null of "
                              "'%s' is not a sum of draws); use how = 'randomization'" % self.neighborhood_score_type)
+
+    def _refuse_hypergeom_on_ranks(self):
+        raise ValueError("attribute_transform = 'rank' does not go with the hypergeometric test (how = '%s'%s): ranks are not "
+                         "counts; use how = 'analytic' or how = 'randomization', or attribute_transform = 'none'"
+                         % (self.enrichment_type, ' on 0/1 attribute values' if self.enrichment_type == 'auto' else ''))
 
     def compute_pvalues_by_moments(self, _attr=None, **kwargs):
         """how = 'analytic' (additive; no counterpart in the reference): the randomization test of 'sum' scores without
