@@ -74,6 +74,7 @@ typedef struct safe_perms safe_perms;   /* composed row-permutation tables, devi
 typedef struct safe_comm safe_comm;     /* RCCL communicator of the attribute-sharded path */
 typedef struct safe_kk safe_kk;         /* Kamada-Kawai cost function of one distance matrix, device res. */
 typedef struct safe_pairs safe_pairs;   /* one selection of a result matrix, counted and scanned, device res. */
+typedef struct safe_go safe_go;         /* propagated gene-to-term annotations as CSC, device resident */
 typedef struct PermRing safe_ring;      /* node-shared permutation stream (shared memory)    */
 
 /* ------------------------------------------------------------------ context ---- */
@@ -769,6 +770,41 @@ int safe_pairs_create(safe_ctx *ctx, const double *selector_dev, int64_t n, int6
 int safe_pairs_read(safe_pairs *pairs, const double *selector_dev, const double *values_dev, int32_t *indptr_host,
                     int32_t *indices_host, double *data_host, double *kernel_ms);
 int safe_pairs_destroy(safe_pairs *pairs);
+
+/* Additive: the gene-to-term matrix of safepy/utils/make_go.py (make_locus2term, :247-289) built on the device from the
+ * direct annotations and the is_a DAG of one branch: "a matrix of gene-to-term annotations (propagated)" (:18-26).
+ * Cell (row, term) = 1 iff the row (a locus) is annotated to the term or to any descendant of it -- the full ancestor
+ * closure, where the reference's store_predecessors_all (:206-229) keeps one path per term.  Then terms
+ * without a row are dropped (:273-275), then every row without a term that missing_rows does not flag is given to the
+ * root (:277-280), whose column stays in its place among the terms.
+ *
+ * safe_go_create: child_ptr int32 [n_terms + 1] / child_idx int32 [child_ptr[n_terms]]: the children of every term (CSR);
+ * ann_row / ann_term int32 [n_ann]: the direct annotations, duplicates allowed; root: the term that takes the rows
+ * without one; missing_rows u8 [n_rows] or NULL: rows the annotations do not know (they stay empty, are not given to
+ * the root, and are NaN in safe_go_as_attr).  All host memory.  The library levels the terms itself (leaves are level
+ * 0, any other term 1 + the maximum over its children) and runs one launch per level on the context's stream; scratch
+ * comes from the context.  Outputs: *n_kept = terms with at least one row, *nnz = ones of the matrix,
+ * *num_root_assigned = rows given to the root (the number the reference prints, :284); kernel_ms (may be NULL): the
+ * six passes' time.  Synchronises (the totals are host outputs).
+ * SAFE_E_VALUE, before anything is allocated or launched: a cycle among the edges; an index out of range (child, root,
+ * annotation row or term); an annotation on a row of missing_rows; n_rows / n_terms / n_ann that are not below 2^31 (or
+ * n_rows, n_terms below 1).  SAFE_E_UNSUPPORTED: nnz >= 2^31, or more cells than one launch covers.  A refusal writes
+ * to none of the output pointers.
+ *
+ * safe_go_read: indptr_host int64 [n_kept + 1], indices_host int32 [nnz] (the rows of every kept term, ascending),
+ * kept_host int32 [n_kept] (the indices of the kept terms, ascending); *num_root_assigned may be NULL.  The same input
+ * gives the same bytes.  safe_go_as_attr: the CSC expanded, on the device, into the f32 [n_rows, n_kept] safe_attr that
+ * safe_attr_create_csc_host makes of the arrays safe_go_read returns (NaN across missing_rows); the handle may be
+ * destroyed afterwards.  safe_go_pass_ms: ms [SAFE_GO_PASSES] of the create call -- zero + scatter, closure, counts,
+ * root, scans, emit -- and the number of levels (may be NULL).  safe_go_destroy waits for the context's stream; NULL is fine. */
+#define SAFE_GO_PASSES 6
+int safe_go_create(safe_ctx *ctx, int64_t n_rows, int64_t n_terms, const int32_t *child_ptr, const int32_t *child_idx, int64_t n_ann,
+                   const int32_t *ann_row, const int32_t *ann_term, int64_t root, const uint8_t *missing_rows, safe_go **out,
+                   int64_t *n_kept, int64_t *nnz, int64_t *num_root_assigned, double *kernel_ms);
+int safe_go_read(safe_go *go, int64_t *indptr_host, int32_t *indices_host, int32_t *kept_host, int64_t *num_root_assigned);
+int safe_go_as_attr(safe_go *go, safe_attr **out);
+int safe_go_pass_ms(safe_go *go, double *ms, int64_t *n_levels);
+int safe_go_destroy(safe_go *go);
 
 /* Name and average duration (ms) of the dominant kernel of the last enrichment call,
  * measured with HIP events on the context stream (bench.py's roofline object). */

@@ -198,6 +198,11 @@ PROTOTYPES = {
     'safe_pairs_create': (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_double, C.c_int, _pp, _pi64, C.POINTER(C.c_double)]),
     'safe_pairs_read': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     'safe_pairs_destroy': (C.c_int, [_vp]),
+    'safe_go_create': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _pp, _pi64, _pi64, _pi64, C.POINTER(C.c_double)]),
+    'safe_go_read': (C.c_int, [_vp, _vp, _vp, _vp, _pi64]),
+    'safe_go_as_attr': (C.c_int, [_vp, _pp]),
+    'safe_go_pass_ms': (C.c_int, [_vp, C.POINTER(C.c_double), _pi64]),
+    'safe_go_destroy': (C.c_int, [_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

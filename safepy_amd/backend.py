@@ -699,6 +699,77 @@ class Pairs:
             pass
 
 
+class GoClosure:
+    """Direct (locus, term) annotations propagated to every ancestor term of an is_a DAG, on the device (safe_go_create): the
+    CSC of the 0/1 [n_rows, n_kept] matrix stays there; `read` copies it out, `as_attributes` expands it into a device
+    matrix.  child_ptr / child_idx: the children of every term (CSR, int32); ann_row / ann_term: the direct annotations
+    (duplicates allowed); root: the term that takes the loci without one; missing_rows: loci the annotations do not know.
+    Raises SafeHipError E_VALUE for a cycle, an index out of range or an annotation on a missing row."""
+
+    PASSES = ('scatter', 'closure', 'count', 'root', 'scan', 'emit')
+
+    def __init__(self, ctx, n_rows, n_terms, child_ptr, child_idx, ann_row, ann_term, root, missing_rows=None):
+        self.ctx = ctx
+        self.handle = None
+        self.n_rows, self.n_terms = int(n_rows), int(n_terms)
+        child_ptr = np.ascontiguousarray(child_ptr, dtype=np.int32)
+        child_idx = np.ascontiguousarray(child_idx, dtype=np.int32)
+        ann_row = np.ascontiguousarray(ann_row, dtype=np.int32)
+        ann_term = np.ascontiguousarray(ann_term, dtype=np.int32)
+        if child_ptr.shape != (self.n_terms + 1,) or ann_row.shape != ann_term.shape or ann_row.ndim != 1 or child_idx.ndim != 1:
+            raise ValueError('GoClosure: child_ptr must hold n_terms + 1 offsets, ann_row and ann_term the same number of pairs')
+        if child_idx.shape[0] < (int(child_ptr[-1]) if child_ptr.size else 0):
+            raise ValueError('GoClosure: child_idx is shorter than child_ptr[-1]')
+        mis = None
+        if missing_rows is not None:
+            mis = np.ascontiguousarray(np.asarray(missing_rows) != 0, dtype=np.uint8)
+            if mis.shape != (self.n_rows,):
+                raise ValueError('missing_rows: expected %d flags, got shape %s' % (self.n_rows, mis.shape))
+        h = C.c_void_p()
+        n_kept, nnz, assigned = C.c_int64(), C.c_int64(), C.c_int64()
+        ms = C.c_double()
+        check(lib.safe_go_create(ctx.handle, self.n_rows, self.n_terms, _ptr(child_ptr), _ptr(child_idx) if child_idx.size else None,
+                                 ann_row.shape[0], _ptr(ann_row) if ann_row.size else None, _ptr(ann_term) if ann_term.size else None,
+                                 int(root), _ptr(mis), C.byref(h), C.byref(n_kept), C.byref(nnz), C.byref(assigned), C.byref(ms)))
+        self.handle = h
+        self.n_kept, self.nnz, self.num_root_assigned = n_kept.value, nnz.value, assigned.value
+        self.kernel_ms = ms.value
+
+    def read(self):
+        """(indptr int64 [n_kept + 1], indices int32 [nnz], kept int32 [n_kept], num_root_assigned)."""
+        indptr = np.empty(self.n_kept + 1, dtype=np.int64)
+        indices = np.empty(self.nnz, dtype=np.int32)
+        kept = np.empty(self.n_kept, dtype=np.int32)
+        assigned = C.c_int64()
+        check(lib.safe_go_read(self.handle, _ptr(indptr), _ptr(indices) if self.nnz else None, _ptr(kept) if self.n_kept else None,
+                               C.byref(assigned)))
+        return indptr, indices, kept, assigned.value
+
+    def as_attributes(self):
+        """The f32 [n_rows, n_kept] matrix as a device handle (NaN across the missing rows), expanded where the CSC lies."""
+        h = C.c_void_p()
+        check(lib.safe_go_as_attr(self.handle, C.byref(h)))
+        return Attributes(self.ctx, h, self.n_rows, self.n_kept, dtype=np.float32)
+
+    def pass_ms(self):
+        """({pass: ms of the create call}, number of levels)."""
+        ms = (C.c_double * len(self.PASSES))()
+        levels = C.c_int64()
+        check(lib.safe_go_pass_ms(self.handle, ms, C.byref(levels)))
+        return dict(zip(self.PASSES, list(ms))), levels.value
+
+    def close(self):
+        if self.handle:
+            check(lib.safe_go_destroy(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _is_sparse(a):
     """scipy.sparse.issparse without importing SciPy for callers that never touch it."""
     import sys

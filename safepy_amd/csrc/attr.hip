@@ -586,8 +586,13 @@ int safe_attr_create_host(safe_ctx *ctx, const void *b_host, int dtype, int64_t 
     return SAFE_OK;
 }
 
-int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr, const int32_t *indices,
-                              const void *values, int dtype, const uint8_t *missing_rows, safe_attr **out) {
+}  // extern "C"
+
+// The expansion behind safe_attr_create_csc_host.  on_device: indptr, indices, values and missing_rows are device arrays that
+// are complete on the context's stream (safe_go_as_attr: the CSC never left the device); the checks and kernels are the same.
+int attr_create_csc(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr, const int32_t *indices, const void *values,
+                    int dtype, const uint8_t *missing_rows, bool on_device, safe_attr **out) {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     SAFE_REQUIRE(ctx && out && indptr, "safe_attr_create_csc_host: NULL argument");
     SAFE_REQUIRE(nnz >= 0 && (indices || nnz == 0), "safe_attr_create_csc_host: %lld stored entries without indices", (long long)nnz);
     if (nnz >= (1ll << 31)) {
@@ -631,10 +636,10 @@ int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, 
     unsigned int *d_flag = reinterpret_cast<unsigned int *>(sb + off_flag);
     const int32_t *d_rows = static_cast<const int32_t *>(d_idx);
     hipStream_t st = ctx->stream;
-    hipError_t e = hipMemcpyAsync(sb, indptr, static_cast<size_t>(m + 1) * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, indices, idx_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && values && nnz) e = hipMemcpyAsync(sb + off_val, values, static_cast<size_t>(nnz) * esz, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && missing_rows) e = hipMemcpyAsync(sb + off_mis, missing_rows, static_cast<size_t>(n), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(sb, indptr, static_cast<size_t>(m + 1) * 8, kind, st);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_idx, indices, idx_bytes, kind, st);
+    if (e == hipSuccess && values && nnz) e = hipMemcpyAsync(sb + off_val, values, static_cast<size_t>(nnz) * esz, kind, st);
+    if (e == hipSuccess && missing_rows) e = hipMemcpyAsync(sb + off_mis, missing_rows, static_cast<size_t>(n), kind, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 8, st);
     if (e == hipSuccess) {
         const dim3 grid(static_cast<unsigned int>(ceil_div(std::max<int64_t>(nnz, m + 1), 256)));
@@ -707,11 +712,31 @@ int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, 
         a->sup_row_pool_bytes = idx_bytes;
         a->n_ones = nnz;
         a->h_sup_ptr.resize(static_cast<size_t>(m + 1));
-        for (int64_t j = 0; j <= m; ++j) a->h_sup_ptr[static_cast<size_t>(j)] = static_cast<int32_t>(indptr[j]);
+        if (on_device) {                                    // (the int32 offsets k_csc_validate left; the stream is idle)
+            e = hipMemcpy(a->h_sup_ptr.data(), d_ptr, ptr_bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                safe_set_error("safe_attr_create_csc_host: %s", hipGetErrorString(e));
+                a->sup_ptr = a->sup_row = nullptr;
+                a->raw = nullptr;
+                a->owns_raw = false;
+                give_back(true, true);
+                delete a;
+                return SAFE_E_HIP;
+            }
+        } else {
+            for (int64_t j = 0; j <= m; ++j) a->h_sup_ptr[static_cast<size_t>(j)] = static_cast<int32_t>(indptr[j]);
+        }
     }
     give_back(!is_support, false);
     *out = a;
     return SAFE_OK;
+}
+
+extern "C" {
+
+int safe_attr_create_csc_host(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                              const void *values, int dtype, const uint8_t *missing_rows, safe_attr **out) {
+    return attr_create_csc(ctx, n, m, nnz, indptr, indices, values, dtype, missing_rows, false, out);
 }
 
 int safe_attr_create_dev(safe_ctx *ctx, const void *b_dev, int dtype, int64_t n, int64_t m, int64_t row_stride,

@@ -132,6 +132,9 @@ enum ScratchSlot {
                             //   within the call
     SCRATCH_MOMENTS_PARTS,  // per (row chunk, column) partial sum of squares | min | max, f64 [3][chunks][mloc] | k_col_moments ->
                             //   k_col_moments_fold (moments.hip) | within the call
+    SCRATCH_GO_BITS,        // the (term x locus) bit matrix u32 [n_terms][W] | safe_go_create (go.hip) | within the call
+    SCRATCH_GO_WORK,        // annotation pairs | children CSR | level order | per-term counts, flags, offsets | per-word OR |
+                            //   readback words | safe_go_create | within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,
@@ -262,7 +265,7 @@ void ctx_block_free(safe_ctx *ctx, void *p, size_t bytes);
 
 // Device memory of the library: every block comes from dev_alloc and goes back through dev_free.  Who owns a block:
 //   * the context: its scratch slots (ctx_scratch) and pooled small blocks (ctx_block_alloc), until safe_ctx_destroy;
-//   * a handle (safe_nbr, safe_attr, safe_perms, safe_kk, safe_pairs): its members, plain pointers, until the handle's destroy;
+//   * a handle (safe_nbr, safe_attr, safe_perms, safe_kk, safe_pairs, safe_go): its members, plain pointers, until the handle's destroy;
 //   * a call: a CallBufs (below) on the stack of the entry point, until it returns -- on whatever path.
 // calls of hipMalloc / hipHostMalloc made by the library so far (safe_alloc_count): a timed step is expected to make none
 extern std::atomic<long long> g_alloc_calls;
@@ -588,6 +591,11 @@ int attr_build_support(safe_attr *attr);     // sup_ptr / sup_row of a binary ma
 int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out);
 // dst (same n, no flags yet) takes a copy of src's row flags if src has any -- computed or installed; else nothing happens (attr.hip)
 int attr_inherit_flags(safe_attr *dst, const safe_attr *src);
+// the expansion behind safe_attr_create_csc_host; on_device: the four input arrays are device memory, complete on ctx->stream (attr.hip)
+int attr_create_csc(safe_ctx *ctx, int64_t n, int64_t m, int64_t nnz, const int64_t *indptr, const int32_t *indices, const void *values,
+                    int dtype, const uint8_t *missing_rows, bool on_device, safe_attr **out);
+// offs[i] = counts[0] + ... + counts[i - 1], i = 0 .. len, 64-bit, one workgroup on stream s (k_pairs_scan, pairs.hip)
+hipError_t pairs_scan_launch(hipStream_t s, const int32_t *counts, int64_t len, int64_t *offs);
 int perms_build_inverse(safe_perms *perms);  // inverse tables (rng.cpp)
 int perms_generate_until(safe_perms *perms, int64_t upto);   // enqueue table rows [generated, upto) on aux_stream (rng.cpp)
 // host/GPU pipeline stages of the permutation stream for `count` permutations: boundaries b[0] = 0 < b[1] < ... < b.back() = count

@@ -212,6 +212,11 @@ constexpr int64_t PAIRS_INT32_END = int64_t(1) << 31;
 
 }  // namespace
 
+hipError_t pairs_scan_launch(hipStream_t s, const int32_t *counts, int64_t len, int64_t *offs) {
+    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(PAIRS_SCAN_THREADS), 0, s, counts, len, offs);
+    return hipGetLastError();
+}
+
 struct safe_pairs {
     safe_ctx *ctx = nullptr;
     int64_t n = 0, m = 0, nnz = 0;

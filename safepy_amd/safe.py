@@ -498,7 +498,9 @@ class SAFE:
     def load_attributes(self, **kwargs):
         """safepy/safe.py:334-367 over `read_attributes` (safe_io.py:336-430): `attribute_file=` a
         `.txt` / `.gz` path, a pandas DataFrame indexed by node key, or (additive) a ready [N,M]
-        ndarray in node order, or (additive) a scipy.sparse [N,M] matrix in node order, which stays sparse:
+        ndarray in node order, or (additive) a `utils.make_go.GoMatrix` built with `node_label_order=` this network's node
+        keys (its sparse matrix, missing rows and term ids / names are taken as they are; with `keep_on_device=True` the
+        device matrix comes from its `to_attributes`), or (additive) a scipy.sparse [N,M] matrix in node order, which stays sparse:
         `self.node2attribute` is that object, only its stored entries are uploaded and the dense matrix exists on
         the device alone; `missing_rows=` (bool / 0-1 [N], sparse input only) marks the nodes whose whole row is
         missing (NaN), what `fill_value=NaN` gives the nodes a file does not list.  Other kwargs
@@ -508,13 +510,14 @@ class SAFE:
         `self.node2attribute` is made read-only in exchange (assign a new array to replace it)."""
         import pandas as pd
         from . import safe_io
+        from .utils.make_go import GoMatrix
         keep = bool(kwargs.pop('keep_on_device', False))
         missing_rows = kwargs.pop('missing_rows', None)
         self._drop_device_attributes()
         self._missing_rows = None
         if 'attribute_file' in kwargs:
             src = kwargs.pop('attribute_file')
-            if self.path_to_safe_data is None or isinstance(src, (pd.DataFrame, np.ndarray)) or be._is_sparse(src):
+            if self.path_to_safe_data is None or isinstance(src, (pd.DataFrame, np.ndarray, GoMatrix)) or be._is_sparse(src):
                 self.path_to_attribute_file = src
             elif isinstance(src, str):
                 self.path_to_attribute_file = os.path.join(self.path_to_safe_data, src)
@@ -524,6 +527,24 @@ class SAFE:
         if isinstance(src, str):
             assert os.path.exists(src), src
         self.validate_config()
+        if isinstance(src, GoMatrix):
+            if missing_rows is not None:
+                raise TypeError('missing_rows goes with a scipy.sparse attribute_file; a GoMatrix carries its own')
+            keys = self._node_keys() if self.graph is not None else None
+            if src.node_label_order is None or keys is None or list(src.loci) != list(keys):
+                raise ValueError('the rows of this GoMatrix do not follow the nodes of the loaded network: build it with '
+                                 'make_go_matrix(..., node_label_order=<the node keys of the network, in node order>) '
+                                 '(SAFE.nodes[\'key\']) after load_network')
+            a = src.matrix
+            self.node2attribute = a
+            self._missing_rows = np.ascontiguousarray(src.missing_rows, dtype=np.uint8) if np.any(src.missing_rows) else None
+            self._missing_rows_of = a
+            self.attributes = pd.DataFrame({'id': list(src.go_details['id']), 'name': list(src.go_details['name'])})
+            if keep:
+                self._attr_dev = src.to_attributes(self._ctx())
+                self._attr_dev_host = a
+                self._attr_dev_sig = (a.shape, a.nnz)
+            return
         if missing_rows is not None and not be._is_sparse(src):
             raise TypeError('missing_rows goes with a scipy.sparse attribute_file; a dense matrix carries its missing values as NaN')
         if be._is_sparse(src):
