@@ -25,6 +25,11 @@ struct BitsTaskPlan {
     std::vector<int4> tasks;                                              // the lists back to back
     std::vector<int64_t> list_span, list_first, list_count, launch_list;
     std::vector<BitsQueues> list_queues;
+    // the blocked form's per-wave lists (plan_bits_wave_tasks), list k beside list k of the members above: a task is FOUR records,
+    // one per wave, wave_first / wave_count in tasks
+    std::vector<int4> wave_recs;
+    std::vector<int64_t> wave_first, wave_count;
+    std::vector<BitsQueues> wave_queues;
 };
 
 // LDS of a word column plus the permutation rows, the layout of the row-in-LDS kernel of rounds 1-5 (removed): it still sets the
@@ -205,5 +210,92 @@ static inline void plan_bits_tasks(BitsTaskPlan &plan, const std::vector<int32_t
         while (k < plan.list_span.size() && plan.list_span[k] != span_c) ++k;
         if (k == plan.list_span.size()) one_list(span_c, 0, n_units, span_c);
         plan.launch_list[c] = static_cast<int64_t>(k);
+    }
+}
+
+// ---- Per-wave tasks of the blocked form.  A task of plan_bits_tasks gives its four waves four ADJACENT slices over one permutation
+// range, and the waves meet at the barrier at the task's end: the slices are sorted by width, so the wave of the narrowest one
+// waits for the widest (the headline network's first group: 34 / 30 / 26 / 23 blocks per permutation; over all groups 404
+// wave-blocks occupied for 341 used).  Here every wave gets an item of its own -- (slice, permutation range) -- and four items
+// of about equal cost make a task.
+
+// The items of one column unit over a launch of `span`: (slice, p0, p1) and the cost (blocks of the slice + 1) x permutations
+// (the one: what a permutation costs beside its blocks -- compare and count).  Every slice with blocks is cut into ranges of
+// about total cost / (4 tasks_per_unit), at least 16 and at most 255 permutations (eight counter levels), equal to within one
+// permutation; a slice without blocks has no item (its sums and counters are zero either way).  At most max_items items where
+// one range of 255 permutations per slice allows it: the ranges grow until they fit.  Stably sorted heaviest first.
+struct BitsWaveItem {
+    int slice, p0, p1;
+    int64_t cost;
+};
+static inline std::vector<BitsWaveItem> wave_items(const std::vector<int32_t> &slice_width, int64_t n_slices, int64_t span,
+                                                   int64_t tasks_per_unit, int64_t max_items) {
+    constexpr int64_t per_perm = 1;
+    int64_t cost_per_perm = 0;
+    for (int64_t s = 0; s < n_slices; ++s)
+        if (slice_width[s] / 8 > 0) cost_per_perm += slice_width[s] / 8 + per_perm;
+    std::vector<BitsWaveItem> items;
+    if (cost_per_perm == 0 || span <= 0) return items;
+    const int64_t ppt_max = std::min<int64_t>(span, 255);
+    int64_t target = std::max<int64_t>(1, cost_per_perm * span / (4 * tasks_per_unit));
+    for (;;) {
+        items.clear();
+        bool cut = false;                                                   // a slice has more ranges than the 255 permutations force
+        for (int64_t s = 0; s < n_slices; ++s) {
+            const int64_t cps = slice_width[s] / 8 + per_perm;
+            if (cps == per_perm) continue;
+            const int64_t ppt = std::min<int64_t>(ppt_max, std::max<int64_t>(16, target / cps));
+            const int64_t chunks = ceil_div(span, ppt);
+            cut = cut || ppt < ppt_max;
+            for (int64_t c = 0; c < chunks; ++c) {
+                const int64_t p0 = c * span / chunks, p1 = (c + 1) * span / chunks;
+                items.push_back({static_cast<int>(s), static_cast<int>(p0), static_cast<int>(p1), cps * (p1 - p0)});
+            }
+        }
+        if (static_cast<int64_t>(items.size()) <= max_items || !cut) break;
+        target += target / 8 + 1;
+    }
+    std::stable_sort(items.begin(), items.end(), [](const BitsWaveItem &a, const BitsWaveItem &b) { return a.cost > b.cost; });
+    return items;
+}
+
+// The per-wave lists of the blocked form, beside the lists of plan_bits_tasks (which it calls first: the list bookkeeping --
+// list_span, launch_list, one list per distinct launch size and per column chunk of the tail -- is that function's, and so is
+// everything else it writes).  List k: wave_count[k] tasks from task wave_first[k], task t = the records wave_recs[4 t .. 4 t + 3],
+// wave i's {column unit, slice, p0, p1}; slice -1: no item for this wave.  Four consecutive items of wave_items make a QUAD, and
+// a quad's tasks -- one per column unit, all four records naming that unit: the waves share the word column -- go to one queue
+// (the quad's id lists are then fetched into one XCD's L2 only, as with split_xcd_queues), quads dealt round-robin in
+// heaviest-first order.  Items per unit: at most four times the tasks per unit of the list's tasks of plan_bits_tasks.
+static inline void plan_bits_wave_tasks(BitsTaskPlan &plan, const std::vector<int32_t> &slice_width, int64_t n_slices, int64_t slots,
+                                        const std::vector<int64_t> &starts, int64_t n_units, int64_t mloc, int64_t n_major,
+                                        int64_t n_tail, int64_t xc_wpc) {
+    plan_bits_tasks(plan, slice_width, n_slices, 4, slots, starts, n_units, mloc, false, n_major, n_tail, xc_wpc);
+    for (size_t k = 0; k < plan.list_span.size(); ++k) {
+        int64_t span = plan.list_span[k], w_lo = 0, w_hi = n_units;
+        if (span < 0) {                                                     // the list of column chunk -1 - span of the tail
+            const int64_t chunk = -1 - span;
+            span = starts.back() - starts[n_major];
+            w_lo = std::min<int64_t>(chunk * xc_wpc, n_units);
+            w_hi = chunk + 1 == n_tail ? n_units : std::min<int64_t>((chunk + 1) * xc_wpc, n_units);
+        }
+        const int64_t units = std::max<int64_t>(0, w_hi - w_lo);
+        std::vector<std::vector<int4>> q(8);
+        if (units > 0) {
+            const int64_t tpu = std::max<int64_t>(1, ceil_div(slots, units));
+            const std::vector<BitsWaveItem> items = wave_items(slice_width, n_slices, span, tpu, 4 * (plan.list_count[k] / units));
+            for (size_t i = 0; i < items.size(); i += 4)
+                for (int64_t w = w_lo; w < w_hi; ++w)
+                    for (size_t j = i; j < i + 4; ++j)
+                        q[(i / 4) & 7].push_back(j < items.size() ? make_int4(static_cast<int>(w), items[j].slice, items[j].p0, items[j].p1)
+                                                                  : make_int4(static_cast<int>(w), -1, 0, 0));
+        }
+        BitsQueues bq{};
+        plan.wave_first.push_back(static_cast<int64_t>(plan.wave_recs.size() / 4));
+        for (int i = 0; i < 8; ++i) {
+            plan.wave_recs.insert(plan.wave_recs.end(), q[i].begin(), q[i].end());
+            bq.off[i + 1] = static_cast<int>(plan.wave_recs.size() / 4 - plan.wave_first.back());
+        }
+        plan.wave_count.push_back(bq.off[8]);
+        plan.wave_queues.push_back(bq);
     }
 }

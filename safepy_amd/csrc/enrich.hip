@@ -1495,7 +1495,7 @@ __device__ __forceinline__ void bits_blk_body(
     if ((uint32_t)(uintptr_t)((__attribute__((address_space(3))) unsigned int *)lds) != 0u) __builtin_trap();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // One task queue per XCD (workgroups are dealt to the 8 XCDs round-robin: blockIdx & 7).  All word groups of one
-    // (slice group, permutation range) sit in ONE queue, so the member-id lists of that range -- read by every one of its
+    // quad of (slice, permutation range) items sit in ONE queue, so the member-id lists of those ranges -- read by every one of its
     // 69 word-group tasks -- are fetched into one XCD's L2, not into all eight (the id stream was 8 x 41 MB of fabric
     // reads per launch); a workgroup whose queue has run dry takes from the others.
     const int home = blockIdx.x & 7;
@@ -1519,11 +1519,13 @@ __device__ __forceinline__ void bits_blk_body(
         const int slot = *slot_box;
         __syncthreads();
         if (slot < 0) break;
-        const int4 task = tasks[slot];
+        // a task = four items of one word group, one per wave and of about equal cost (plan_bits_wave_tasks): each wave has its
+        // own record {word group, slice, permutation range}, slice -1 = no item -- the waves then reach the barrier at the task's
+        // end together (four ADJACENT slices over one range: the wave of the narrowest waited for the widest)
+        const int4 task = tasks[4 * slot + wave];
         const int wg = task.x;
-        // a task = four adjacent slices (one per wave) of one word group over a permutation range
-        const int64_t s = static_cast<int64_t>(task.y) * 4 + wave;
-        const bool active = s < n_slices;
+        const int64_t s = task.y;
+        const bool active = s >= 0 && s < n_slices;
         const int64_t p_begin = p_base + task.z;
         int64_t p_end = p_base + task.w < p_limit ? p_base + task.w : p_limit;
         if (p_end < p_begin || !active) p_end = p_begin;                  // (nothing to do for this wave; it still joins the barriers)
@@ -2374,6 +2376,32 @@ static void blk_trace_dump(int n_launch) {
     fprintf(stderr, "[blk trace] %u wave-tasks over %d launches; wave-task duration min %.0f median %.0f p90 %.0f max %.0f kclk; "
             "%.3g block-iterations, %.0f clocks per block-iteration per wave (4 waves share a SIMD)\n",
             cnt, n_launch, dur.front() / 1e3, dur[dur.size() / 2] / 1e3, dur[dur.size() * 9 / 10] / 1e3, dur.back() / 1e3, work, busy / std::max(work, 1.0));
+    // what the barrier at a task's end costs: the four waves of a (workgroup, slot) begin together, and each waits from its own end
+    // to the end of the slowest.  A launch's records of one (workgroup, slot) are the four with (nearly) the same begin: sorted
+    // by (workgroup and slot, begin), every four in a row are one task (one CU, one clock); an overflowed trace may leave fewer
+    std::vector<unsigned int> order(cnt);
+    for (unsigned int i = 0; i < cnt; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](unsigned int a, unsigned int b) {
+        const unsigned long long ka = rec[8 * a] >> 2, kb = rec[8 * b] >> 2;
+        return ka != kb ? ka < kb : rec[8 * a + 1] < rec[8 * b + 1];
+    });
+    double wait = 0.0, held = 0.0;
+    for (unsigned int i = 0; i + 3 < cnt;) {
+        const unsigned long long key = rec[8 * order[i]] >> 2;
+        if ((rec[8 * order[i + 3]] >> 2) != key) {
+            ++i;
+            continue;
+        }
+        unsigned long long last = 0;
+        for (int w = 0; w < 4; ++w) last = std::max(last, rec[8 * order[i + w] + 2]);
+        for (int w = 0; w < 4; ++w) {
+            wait += static_cast<double>(last - rec[8 * order[i + w] + 2]);
+            held += static_cast<double>(last - rec[8 * order[i + w] + 1]);
+        }
+        i += 4;
+    }
+    fprintf(stderr, "[blk trace] barrier wait: %.1f %% of wave-task time is a finished wave waiting for the slowest wave of its task\n",
+            100.0 * wait / std::max(held, 1.0));
     double cls_busy[5] = {0, 0, 0, 0, 0}, cls_work[5] = {0, 0, 0, 0, 0};
     for (unsigned int i = 0; i < cnt; ++i) {
         const double nb = static_cast<double>(rec[8 * i + 3] >> 32), np = static_cast<double>(rec[8 * i + 3] & 0xFFFFFFFFu);
@@ -2454,8 +2482,13 @@ static const void *bits_form_kernel(const BitsForm &form, int dbg) {
                                          : reinterpret_cast<const void *>(k_permtest_bits_pre<BT_LV>));
 }
 
-// The call's task lists in nbr->bits_plan (plan_bits_tasks) and their pinned copy.  The lists only depend on the handle and on
-// the numbers of the key: the handle keeps the last plan.
+// The records a form's kernel reads: the blocked form its per-wave lists (four records per task), the sixteen-wave forms the tasks
+static const std::vector<int4> &bits_plan_records(const BitsTaskPlan &plan, const BitsForm &form) {
+    return form.kind == BITS_BLK ? plan.wave_recs : plan.tasks;
+}
+
+// The call's task lists in nbr->bits_plan (plan_bits_tasks, plan_bits_wave_tasks) and their pinned copy.  The lists only depend on
+// the handle and on the numbers of the key: the handle keeps the last plan.
 static int bits_task_plan(safe_ctx *ctx, safe_nbr *nbr, const BitsForm &form, const BitsTail &tail, const std::vector<int64_t> &starts,
                           int64_t slots, int64_t mloc) {
     const int64_t n_wg = ceil_div(mloc, 64);
@@ -2463,12 +2496,16 @@ static int bits_task_plan(safe_ctx *ctx, safe_nbr *nbr, const BitsForm &form, co
     plan_key.insert(plan_key.end(), starts.begin(), starts.end());
     BitsTaskPlan &plan = nbr->bits_plan;
     if (plan.key == plan_key) return SAFE_OK;
-    // (column units of the tasks: word groups, or their halves)
-    plan_bits_tasks(plan, nbr->h_slice_width, nbr->n_slices, form.waves, slots, starts, form.half ? 2 * n_wg : n_wg, mloc, form.half,
-                    tail.n_major, tail.n_chunks, tail.wpc);
+    // (column units of the tasks: word groups, or their halves; the blocked form runs the per-wave lists: four records per task)
+    if (form.kind == BITS_BLK)
+        plan_bits_wave_tasks(plan, nbr->h_slice_width, nbr->n_slices, slots, starts, n_wg, mloc, tail.n_major, tail.n_chunks, tail.wpc);
+    else
+        plan_bits_tasks(plan, nbr->h_slice_width, nbr->n_slices, form.waves, slots, starts, form.half ? 2 * n_wg : n_wg, mloc, form.half,
+                        tail.n_major, tail.n_chunks, tail.wpc);
     // (plan.key is set LAST, below: an allocation or a wait that fails on the way leaves no key, and the next call rebuilds
     // the plan instead of uploading from a missing or stale pinned copy)
-    const size_t bytes = plan.tasks.size() * sizeof(int4);
+    const std::vector<int4> &recs = bits_plan_records(plan, form);
+    const size_t bytes = recs.size() * sizeof(int4);
     if (nbr->bits_plan_pinned_bytes < bytes) {
         SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));                 // (an earlier pass may still be reading the old copy)
         if (nbr->bits_plan_pinned) SAFE_HIP_CHECK(hipHostFree(nbr->bits_plan_pinned));
@@ -2480,7 +2517,7 @@ static int bits_task_plan(safe_ctx *ctx, safe_nbr *nbr, const BitsForm &form, co
     } else {
         SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
     }
-    memcpy(nbr->bits_plan_pinned, plan.tasks.data(), bytes);
+    memcpy(nbr->bits_plan_pinned, recs.data(), bytes);
     plan.key = plan_key;
     return SAFE_OK;
 }
@@ -2501,9 +2538,9 @@ struct BitsBuffers {
     uint32_t *d_obs = nullptr;                      // blocked form: observed sums (bits_observe)
 };
 // ... taken here, the task lists uploaded and the queue words and counters cleared on ctx->stream.  span: the longest stage launch
-static int bits_call_buffers(safe_ctx *ctx, const safe_nbr *nbr, const BitsTail &tail, int64_t mloc, int64_t span, int64_t tail_span,
-                             BitsBuffers *b) {
-    const size_t n_task = nbr->bits_plan.tasks.size();
+static int bits_call_buffers(safe_ctx *ctx, const safe_nbr *nbr, const BitsForm &form, const BitsTail &tail, int64_t mloc, int64_t span,
+                             int64_t tail_span, BitsBuffers *b) {
+    const size_t n_task = bits_plan_records(nbr->bits_plan, form).size();     // (records: what bits_task_plan put into the pinned copy)
     const int64_t n_launch = tail.n_major + tail.n_chunks;
     void *ws = nullptr;
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_TASKS, n_task * sizeof(int4) + (8 * n_launch + 4) * sizeof(unsigned int), &ws));
@@ -2608,8 +2645,9 @@ static int bits_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *per
     for (int64_t c = 0; c < fr.n_launch; ++c) {
         const bool in_tail = c >= tail.n_major;                             // a column chunk over the tail's permutations
         const int64_t p_base = in_tail ? tail.p_split : starts[c], p_limit = in_tail ? P : starts[c + 1];
-        const int64_t list = plan.launch_list[c], n_tasks = plan.list_count[list];     // this launch size's task list
-        const int4 *d_tasks = b.d_tasks + plan.list_first[list];
+        const int64_t list = plan.launch_list[c];                                      // this launch size's task list
+        const int64_t n_tasks = blk ? plan.wave_count[list] : plan.list_count[list];
+        const int4 *d_tasks = b.d_tasks + (blk ? 4 * plan.wave_first[list] : plan.list_first[list]);
         hipStream_t ks = kstreams[c % BITS_NS];
         if (c == tail.n_major) SAFE_TRY(bits_tail_lists(ctx, nbr, perms, starts, tail, b, fr.plain));
         if (!in_tail) SAFE_TRY(perms_wait(perms, p_limit, ks));            // host draws + table kernels for this span
@@ -2621,15 +2659,15 @@ static int bits_launch_spans(safe_ctx *ctx, const safe_nbr *nbr, safe_perms *per
                                p_limit - p_base, static_cast<uint32_t>(static_cast<uint64_t>(n) << form.id_shift), b.d_ids[c % BITS_NS],
                                form.id_shift);
         SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c], ks));
-        if (in_tail && n_tasks == 0) {                               // (a rank with fewer columns: nothing in this chunk)
+        if (n_tasks == 0) {                  // (a rank with fewer columns: nothing in this chunk; per-wave lists: no slice has members)
             SAFE_HIP_CHECK(hipEventRecord(fr.ev[2 * c + 1], ks));
-            chunk_final(c, ks);
+            if (in_tail) chunk_final(c, ks);
             continue;
         }
         const int64_t grid = std::min<int64_t>(n_tasks, grid_max);
         unsigned int *queue_c = b.d_queue + 8 * c;
         const uint16_t *ids_c = in_tail ? b.d_ids_tail : b.d_ids[c % BITS_NS];
-        BitsQueues bq = plan.list_queues[list];
+        BitsQueues bq = blk ? plan.wave_queues[list] : plan.list_queues[list];
         void *blk_args[] = {(void *)&n, (void *)&ids_c, (void *)&entries_pad, (void *)&nbr->sell_row, (void *)&nbr->slice_off,
                             (void *)&nbr->slice_width, (void *)&b.d_obs, (void *)&nbr->n_slices, (void *)&b.d_bits, (void *)&bq,
                             (void *)&d_tasks, (void *)&p_base, (void *)&p_limit, (void *)&queue_c, (void *)&mloc, (void *)&b.d_gl,
@@ -2659,9 +2697,9 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     safe_trace("launch_bits: prep launched");
     const BitsSwitches sw = bits_switches(ctx);
     // The permutations are consumed in launches of `span` permutations so that the host's draw
-    // stream for the next span overlaps this span's kernel.  Inside a launch, tasks = (word
-    // group, group of adjacent slices, permutation sub-range), sized to about equal cost
-    // with several per workgroup slot, heaviest first for the dynamic queue.
+    // stream for the next span overlaps this span's kernel.  Inside a launch, tasks = (word group, group of adjacent
+    // slices, permutation sub-range) -- blocked form: four (slice, sub-range) items, one per wave --, sized to about
+    // equal cost, heaviest first for the dynamic queue.
     // Launches follow the stream's stages, one launch per stage (a launch over m stages after the start-up has fewer tails and
     // less per-task fixed cost -- kernel time per 1000 permutations 4.06 -> 3.94 / 3.89 ms at m = 2 / 3 in round 3 -- but the
     // step gets LONGER, 5.2 -> 5.5 / 5.8 ms: a merged launch waits for its last stage's draws)
@@ -2675,7 +2713,7 @@ static int launch_bits(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms
     const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / bits_lds_bytes(n, perms->stride16))));
     SAFE_TRY(bits_task_plan(ctx, nbr, form, tail, starts, static_cast<int64_t>(ctx->num_cu) * per_cu, mloc));
     safe_trace("launch_bits: tasks built");
-    SAFE_TRY(bits_call_buffers(ctx, nbr, tail, mloc, span, tail_span, &b));
+    SAFE_TRY(bits_call_buffers(ctx, nbr, form, tail, mloc, span, tail_span, &b));
     const void *kfn = bits_form_kernel(form, sw.dbg);
     if (!kfn) return SAFE_E_INVALID;
     SAFE_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(form.lds_bytes)));
