@@ -127,7 +127,13 @@ int safe_nbr_euclidean(safe_ctx *ctx, const double *xy_host, int64_t n, double n
  * from s to t is <= cutoff.  Undirected edges (edge_u[e], edge_v[e]) with weight
  * edge_w[e] ('length' for shortpath_weighted_layout) or unit weight when edge_w is NULL
  * ('shortpath').  keep_distances != 0 also keeps the dense f64 distance matrix
- * (inf where unreached) for safe_nbr_distances (self.node_distances, safe.py:417). */
+ * (inf where unreached) for safe_nbr_distances (self.node_distances, safe.py:417).
+ * Two edges between one pair of nodes are both kept, so the smaller weight wins; nx.Graph
+ * would keep only the weight added last, and de-duplicating is the caller's job.
+ * A negative, NaN or infinite weight is SAFE_E_INVALID: with cutoff = +inf networkx counts a
+ * node behind a path of length +inf as reached, which a matrix whose +inf means "unreached"
+ * cannot say.  Finite weights whose path sum overflows to +inf are accepted, and such a
+ * node is reported unreached. */
 int safe_nbr_shortpath(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t *edge_u,
                        const int32_t *edge_v, const double *edge_w, double cutoff,
                        int keep_distances, safe_nbr **out);

@@ -803,13 +803,17 @@ int safe_nbr_shortpath(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t 
     SAFE_REQUIRE(n_edges == 0 || (edge_u && edge_v), "safe_nbr_shortpath: NULL edge arrays");
     *out = nullptr;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    // undirected CSR adjacency on the host (both directions; self loops once)
+    // undirected CSR adjacency on the host (both directions; self loops once; two edges between one pair are both kept, so the
+    // lighter one counts -- nx.Graph would keep the weight added last: de-duplicating is the caller's job)
     std::vector<int32_t> deg(n + 1, 0);
     for (int64_t e = 0; e < n_edges; ++e) {
         const int32_t u = edge_u[e], v = edge_v[e];
         SAFE_REQUIRE(u >= 0 && u < n && v >= 0 && v < n, "safe_nbr_shortpath: edge %lld has an end point outside [0,%lld)",
                      (long long)e, (long long)n);
-        if (edge_w) SAFE_REQUIRE(edge_w[e] >= 0.0, "safe_nbr_shortpath: edge %lld has a negative or NaN weight", (long long)e);
+        // +inf is refused too: the kernel's +inf means "unreached", networkx's "reached over a path of length +inf"
+        if (edge_w)
+            SAFE_REQUIRE(edge_w[e] >= 0.0 && std::isfinite(edge_w[e]),
+                         "safe_nbr_shortpath: edge %lld has a negative, infinite or NaN weight", (long long)e);
         deg[u + 1]++;
         if (u != v) deg[v + 1]++;
     }
