@@ -456,7 +456,10 @@ int safe_hypergeom(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, double enrichm
  * count / num_permutations (what safe_randomization and safe_outputs_from_* write): both matrices are
  * checked read-only, and if every entry is such a ratio the rows are adjusted from their histogram
  * over the counts, without a sort; otherwise (a caller's own values) they are sorted like the
- * hypergeometric form.  Nothing is modified before the form is chosen. */
+ * hypergeometric form.  Nothing is modified before the form is chosen.  In every form a NaN of either
+ * sign and any payload turns its whole row into 0x7FF8... (np.argsort puts every NaN last, np.minimum
+ * carries it through the row) and -0.0 is the value 0.0, as NumPy sorts it (its adjusted value is +0.0);
+ * negative p-values other than -0.0 are the caller's error and not defined. */
 int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
                     double enrichment_threshold, double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev,
                     double *nes_binary_dev, double *num_enriched_dev);

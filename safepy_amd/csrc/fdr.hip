@@ -37,6 +37,10 @@ __global__ void k_fdr_offsets(int64_t *__restrict__ off, int64_t rows, int64_t m
     if (i <= rows) off[i] = i * m;
 }
 
+// -0.0 -> +0.0, every other value as it is: NumPy sorts and compares the two zeros as one value, and the rows of all three
+// forms come out with the same bits
+__device__ __forceinline__ double plus_zero(double v) { return v == 0.0 ? 0.0 : v; }
+
 // one workgroup per row of the batch; ps / cols: the row sorted ascending with its column ids
 __global__ __launch_bounds__(256) void k_fdr_row(const double *__restrict__ ps, const int32_t *__restrict__ cols, int64_t m,
                                                  double *__restrict__ out) {
@@ -47,8 +51,10 @@ __global__ __launch_bounds__(256) void k_fdr_row(const double *__restrict__ ps, 
     double *o = out + row * m;
     const int t = threadIdx.x;
     const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-    const double last = p[m - 1];
-    if (last != last) {                                             // a NaN anywhere poisons the whole row
+    // The library's float key puts a NaN whose sign bit is set (0xFFF8...: what x86 makes of 0 / 0) BEFORE every number and
+    // the others behind them (it treats -0.0 as +0.0): a row has a NaN iff one of its two ends is one.
+    const double first = p[0], last = p[m - 1];
+    if (first != first || last != last) {                           // a NaN anywhere poisons the whole row
         for (int64_t r = t; r < m; r += 256) o[r] = qnan;
         return;
     }
@@ -56,21 +62,24 @@ __global__ __launch_bounds__(256) void k_fdr_row(const double *__restrict__ ps, 
     const int64_t len = (m + 255) / 256, r0 = static_cast<int64_t>(t) * len, r1 = r0 + len < m ? r0 + len : m;
     const double inf = __longlong_as_double(0x7FF0000000000000ll);
     double mine = inf;
-    for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, p[r] / (static_cast<double>(r + 1) / n_d));
+    for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, plus_zero(p[r]) / (static_cast<double>(r + 1) / n_d));
     part[t] = mine;
     __syncthreads();
     double carry = inf;                                             // minimum over everything right of this thread's chunk
     for (int u = t + 1; u < 256; ++u) carry = fmin(carry, part[u]);
     for (int64_t r = r1 - 1; r >= r0; --r) {
-        carry = fmin(carry, p[r] / (static_cast<double>(r + 1) / n_d));
+        carry = fmin(carry, plus_zero(p[r]) / (static_cast<double>(r + 1) / n_d));
         o[c[r]] = carry > 1.0 ? 1.0 : carry;
     }
 }
 
 // One workgroup = one row: a block-wide radix sort (hipcub::BlockRadixSort: keys and column ids in registers, LDS
 // for the exchanges) leaves thread t with ranks [t IPT, (t + 1) IPT) of the sorted row -- exactly the chunks the
-// Benjamini-Hochberg pass wants.  Keys are the bit patterns of the p-values: non-negative doubles order like their
-// bits and NaN (0x7FF8...) sorts behind every number, as np.argsort puts it; padding keys are all ones.
+// Benjamini-Hochberg pass wants.  Keys are the bit patterns of the p-values after two substitutions: -0.0 becomes +0.0 (key 0;
+// left as 0x8000... it would sort last, and -0.0 / (m / m) would be the running minimum of the whole row) and every NaN, of
+// either sign and any payload, becomes 0x7FF8....  Then positive doubles order like their bits, both zeros sort first as one
+// value and every NaN sorts behind every number, as np.argsort puts them; padding keys are all ones, behind the NaN key, so
+// the ranks below m hold the row and nothing else.  (Negative p-values other than -0.0 are a caller's error: not defined.)
 // (A bitonic network on an LDS copy of the row was tried first: 91 stages x 20 bytes per element = 15 MB of LDS
 // traffic per row, 3.2 ms per 3971 x 4373 matrix.)
 #ifndef FDR_RADIX_BITS
@@ -90,7 +99,12 @@ __global__ __launch_bounds__(256) void k_fdr_row_sort(double *__restrict__ pvals
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
         const int e = t * IPT + i;
-        key[i] = e < m ? static_cast<unsigned long long>(__double_as_longlong(p[e])) : ~0ull;
+        unsigned long long k = ~0ull;
+        if (e < m) {
+            const double v = p[e];
+            k = v != v ? 0x7FF8000000000000ull : static_cast<unsigned long long>(__double_as_longlong(plus_zero(v)));
+        }
+        key[i] = k;
         idx[i] = static_cast<unsigned short>(e);
     }
     __syncthreads();
