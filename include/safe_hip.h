@@ -189,6 +189,29 @@ int safe_pair_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n
 int safe_nbr_distance_select(safe_nbr *nbr, const int64_t *ranks, int64_t n_ranks, double *out_host,
                              int64_t *n_finite_pairs);
 
+/* neighborhood_radius_type 'nearest' (additive; the reference has one radius for the whole network, safepy/safe.py:369-430):
+ * every node's neighborhood reaches to its k-th nearest other node.  With D the node-distance matrix of the metric and
+ * cand_i = { D[i][j] : j != i } (node i is left out by index, a coincident node counts; for a kept matrix only the finite
+ * entries), the radius of row i is r_i = sorted(cand_i)[min(k, |cand_i|) - 1], and 0.0 where cand_i is empty.  Membership is
+ * A[i][j] = (D[i][j] <= r_i): the diagonal always, every tie at the k-th distance, never an unreached node; A need not be
+ * symmetric.  The selection is K3's radix selection per row, one launch.  All four are synchronous on the context's stream.
+ *
+ * safe_row_distance_select_xy (safepy/safe.py:369-430): 'euclidean' -- D = squareform(pdist(xy)), bit for bit; xy_host is
+ *   [n,2] row-major, every coordinate finite (SAFE_E_VALUE otherwise); k < 1 is SAFE_E_INVALID; radii_out_host is f64 [n].
+ * safe_nbr_row_distance_select (safepy/safe.py:369-430): the shortest-path metrics -- D is the matrix a safe_nbr_shortpath
+ *   handle kept (row i = the search from source i), read in place.  SAFE_E_INVALID if the handle kept none, or k < 1.
+ * safe_nbr_euclidean_rows (safepy/safe.py:369-430): the handle of A[i][j] = (D_ij <= radii[i]) for D = squareform(pdist(xy));
+ *   a NaN or negative radius is SAFE_E_VALUE, +inf takes every node.
+ * safe_nbr_from_distances_rows (safepy/safe.py:369-430): a new handle of A[i][j] = (D[i][j] <= radii[i], D[i][j] reached)
+ *   from the matrix src_nbr kept, on src_nbr's context; src_nbr is left as it was.  keep_distances != 0: the new handle
+ *   keeps D[i][j] where A[i][j] = 1 and +inf elsewhere (what a cutoff handle keeps).  SAFE_E_INVALID if src_nbr kept no
+ *   distances, SAFE_E_VALUE on a NaN or negative radius.
+ * A refused call writes nothing. */
+int safe_row_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t k, double *radii_out_host);
+int safe_nbr_row_distance_select(safe_nbr *nbr, int64_t k, double *radii_out_host);
+int safe_nbr_euclidean_rows(safe_ctx *ctx, const double *xy_host, int64_t n, const double *radii_host, safe_nbr **out);
+int safe_nbr_from_distances_rows(safe_nbr *src_nbr, const double *radii_host, int keep_distances, safe_nbr **out);
+
 /* The fused all-pairs kernel on its own (compute_node_distances for 'euclidean', and
  * the K1 roofline bench): xy_dev [n,2]; mask_out_dev int64 [n,n] and/or dist_out_dev
  * f64 [n,n]; either may be NULL.  Same arithmetic as safe_nbr_euclidean

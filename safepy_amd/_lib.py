@@ -107,6 +107,10 @@ PROTOTYPES = {
     'safe_nbr_distances': (C.c_int, [_vp, _vp]),
     'safe_pair_distance_select_xy': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _pi64]),
     'safe_nbr_distance_select': (C.c_int, [_vp, _vp, _i64, _vp, _pi64]),
+    'safe_row_distance_select_xy': (C.c_int, [_vp, _vp, _i64, _i64, _vp]),
+    'safe_nbr_row_distance_select': (C.c_int, [_vp, _i64, _vp]),
+    'safe_nbr_euclidean_rows': (C.c_int, [_vp, _vp, _i64, _vp, _pp]),
+    'safe_nbr_from_distances_rows': (C.c_int, [_vp, _vp, C.c_int, _pp]),
     'safe_euclidean_dense_dev': (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _vp]),
     'safe_edge_lengths': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'safe_layout_spring': (C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, C.c_double, _vp,

@@ -271,6 +271,16 @@ class Context:
                                                _ptr(out) if rk.size else None, C.byref(count)))
         return out, count.value
 
+    def row_distance_select(self, xy, k):
+        """Per node, the distance to its k-th nearest other node under scipy's pdist(xy), bit for bit
+        (safe_row_distance_select_xy): f64 [n]; the farthest node where k exceeds n - 1, 0.0 for a single node."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError('row_distance_select: xy must be [n, 2], got shape %s' % (xy.shape,))
+        out = np.empty(xy.shape[0], dtype=np.float64)
+        check(lib.safe_row_distance_select_xy(self.handle, _ptr(xy), xy.shape[0], int(k), _ptr(out)))
+        return out
+
     def layout_spring(self, row_ptr, col, weight, pos0, k, iterations, threshold, dtype):
         """networkx's Fruchterman-Reingold iterations on the device (safe_layout_spring): CSR adjacency with
         strictly increasing columns per row (weight None = 1), pos0 [n,2] f64, dtype np.float32 (the sparse
@@ -542,6 +552,40 @@ class Neighborhoods:
         h = C.c_void_p()
         check(lib.safe_nbr_from_dense_i64(ctx.handle, _ptr(a), a.shape[0], C.byref(h)))
         return cls(ctx, h)
+
+    @staticmethod
+    def _radii(radii, n, who):
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        if r.shape != (n,):
+            raise ValueError('%s: radii must be one number per node, shape (%d,), got %s' % (who, n, r.shape))
+        return r
+
+    @classmethod
+    def euclidean_rows(cls, ctx, xy, radii):
+        """A[i, j] = (pdist distance of i and j <= radii[i]): one radius per row (safe_nbr_euclidean_rows)."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError('euclidean_rows: xy must be [n, 2], got shape %s' % (xy.shape,))
+        r = cls._radii(radii, xy.shape[0], 'euclidean_rows')
+        h = C.c_void_p()
+        check(lib.safe_nbr_euclidean_rows(ctx.handle, _ptr(xy), xy.shape[0], _ptr(r), C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def from_distances_rows(cls, src, radii, keep_distances=False):
+        """A new handle of A[i, j] = (D[i, j] <= radii[i]) over the reached pairs of the matrix D that `src` kept
+        (safe_nbr_from_distances_rows); `src` is not changed.  keep_distances: the new handle keeps D where A is 1, +inf elsewhere."""
+        r = cls._radii(radii, src.n, 'from_distances_rows')
+        h = C.c_void_p()
+        check(lib.safe_nbr_from_distances_rows(src.handle, _ptr(r), 1 if keep_distances else 0, C.byref(h)))
+        return cls(src.ctx, h)
+
+    def row_distance_select(self, k):
+        """Per node, the k-th smallest finite kept distance to another node (safe_nbr_row_distance_select): f64 [n]; the
+        farthest reached node where k exceeds their number, 0.0 for a node that reaches no other."""
+        out = np.empty(self.n, dtype=np.float64)
+        check(lib.safe_nbr_row_distance_select(self.handle, int(k), _ptr(out)))
+        return out
 
     def set_layout(self, xy):
         """Hint: the 2-D layout the membership came from (node order of the matrix-core kernel only)."""

@@ -474,8 +474,186 @@ __global__ __launch_bounds__(256) void k_select_dist(const double *__restrict__ 
 }
 
 // --------------------------------------------------------------------------------------
+// K3b: the k-th smallest distance of every ROW (neighborhood_radius_type 'nearest': node i's radius is the distance to its
+// k-th nearest other node).  K3's digit plan, one workgroup per row, all six passes inside one launch: a pass sweeps the row's
+// keys once, counts those whose bits above the digit equal the prefix found so far into one 2048-bin u32 histogram in LDS
+// (8 KiB), a workgroup scan finds the bin that holds the wanted rank, and the bin's digit joins the prefix.  The first pass
+// also counts the row's candidates, cnt, and the rank is min(k, cnt) - 1; a row without candidates gives key 0.  Counts are
+// integers, so the result does not depend on the order of the atomics, nor on any order among equal keys.  Once the chosen bin
+// holds a single key, one more sweep fetches it and the row is done (tools/ubench/row_select.hip: 2.32 -> 0.94 ms at 20 000 nodes).
+// That microbenchmark carries a copy of sel_count, row_key and k_row_select with its variants: a change here goes there too, or
+// the figures DESIGN.md quotes stop describing this kernel.
+//
+// XY = true: keys are the squares dx*dx + dy*dy in the operand order of k_euclid_bits, recomputed in every pass (xy is 16 B per
+// node); the caller takes the one root per row.  XY = false: row i of a kept f64 [n][n] distance matrix read in place, +inf is no
+// key.  Node i itself is left out by index in both.
+// --------------------------------------------------------------------------------------
+// key of candidate j of the row (xi, yi) / `row`; `in` = false (j past the end, or the node itself) reads nothing and is no key
+template <bool XY>
+__device__ __forceinline__ unsigned long long row_key(const double *__restrict__ src, const unsigned long long *__restrict__ row,
+                                                      double xi, double yi, int64_t j, bool in) {
+    if (XY) {
+        const double dx = xi - (in ? src[2 * j] : 0.0);
+        const double dy = yi - (in ? src[2 * j + 1] : 0.0);
+        const double s = dx * dx + dy * dy;                                    // no FMA (-ffp-contract=off)
+        return static_cast<unsigned long long>(__double_as_longlong(s));
+    }
+    return in ? row[j] : 0x7FF0000000000000ull;
+}
+
+template <bool XY>
+__global__ __launch_bounds__(256) void k_row_select(const double *__restrict__ src, int64_t n, int64_t k,
+                                                    unsigned long long *__restrict__ keys_out) {
+    __shared__ __align__(16) uint32_t hist[SEL_BINS];
+    __shared__ uint32_t wave_sum[4];
+    __shared__ uint32_t s_digit, s_rem, s_alone;
+    __shared__ unsigned long long s_key;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i = blockIdx.x;
+    const unsigned long long INF_BITS = 0x7FF0000000000000ull;
+    const double xi = XY ? src[2 * i] : 0.0, yi = XY ? src[2 * i + 1] : 0.0;
+    const unsigned long long *row = reinterpret_cast<const unsigned long long *>(src) + (XY ? 0 : i * n);
+    unsigned long long prefix = 0;
+    uint32_t rem = 0;
+    for (int pass = 0; pass < 6; ++pass) {
+        const int nbits = pass < 3 ? 11 : 10;
+        const int shift = pass < 3 ? 52 - 11 * pass : 20 - 10 * (pass - 3);   // 52, 41, 30, 20, 10, 0
+        const int hshift = shift + nbits;                                      // (63 in the first pass: bit 63 of a key is 0)
+        const unsigned int mask = (1u << nbits) - 1;
+        for (int b = tid; b < SEL_BINS; b += 256) hist[b] = 0;
+        __syncthreads();
+        for (int64_t jb = 0; jb < n; jb += 256) {                              // (the same trip count for every lane: sel_count)
+            const int64_t j = jb + tid;
+            const bool in = j < n && j != i;
+            const unsigned long long key = row_key<XY>(src, row, xi, yi, j, in);
+            const bool counts = in && (XY || key < INF_BITS) && (key >> hshift) == prefix;
+            sel_count(hist, counts ? static_cast<int>((key >> shift) & mask) : -1, lane);
+        }
+        __syncthreads();
+        // workgroup scan: a thread owns eight consecutive bins
+        const uint4 lo = reinterpret_cast<const uint4 *>(hist)[2 * tid], hi = reinterpret_cast<const uint4 *>(hist)[2 * tid + 1];
+        const uint32_t c[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t mine = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) mine += c[q];
+        uint32_t incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t v = __shfl_up(incl, d);
+            if (lane >= d) incl += v;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        uint32_t base = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            base += w < wave ? wave_sum[w] : 0u;
+            total += wave_sum[w];
+        }
+        if (pass == 0) {
+            if (total == 0) {                                                  // no candidate (the same for the whole workgroup)
+                if (tid == 0) keys_out[i] = 0ull;
+                return;
+            }
+            rem = static_cast<uint32_t>((k < static_cast<int64_t>(total) ? k : static_cast<int64_t>(total)) - 1);
+        }
+        const uint32_t excl = base + incl - mine;
+        if (rem >= excl && rem - excl < mine) {                                // one thread: the bins before its own hold excl keys
+            uint32_t r = rem - excl;
+            int q = 0;
+            bool found = false;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                if (!found && r < c[t]) {
+                    q = t;
+                    found = true;
+                }
+                if (!found) r -= c[t];
+            }
+            s_digit = static_cast<uint32_t>(8 * tid + q);
+            s_rem = r;
+            s_alone = c[q] == 1;
+        }
+        __syncthreads();
+        prefix = (prefix << nbits) | s_digit;
+        rem = s_rem;
+        if (s_alone && pass < 5) {                                             // (the same for the whole workgroup)
+            // the chosen bin holds ONE key, the wanted one: a last sweep fetches it and the later passes are skipped (untied
+            // distances of a row part after two or three digits; tied ones -- a bin of two or more -- run all six)
+            for (int64_t j = tid; j < n; j += 256) {
+                if (j == i) continue;
+                const unsigned long long key = row_key<XY>(src, row, xi, yi, j, true);
+                if ((XY || key < INF_BITS) && (key >> shift) == prefix) s_key = key;
+            }
+            __syncthreads();
+            if (tid == 0) keys_out[i] = s_key;
+            return;
+        }
+    }
+    if (tid == 0) keys_out[i] = prefix;
+}
+
+// The twin of k_euclid_bits with one threshold per row: bit (i, j) = (s_ij <= c[i]), where c[i] is the largest double whose
+// root is at most the row's radius (squared_threshold_le, on the host), so the rule is sqrt(s) <= r_i without a root per pair.
+__global__ __launch_bounds__(256) void k_euclid_bits_rows(const double *__restrict__ xy, int64_t n, const double *__restrict__ c_row,
+                                                          uint64_t *__restrict__ bits, int64_t words) {
+    __shared__ double sx[64], sy[64];
+    const int64_t w = blockIdx.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.y) * 256 + threadIdx.x;
+    const int64_t j0 = w * 64;
+    if (threadIdx.x < 64) {
+        const int64_t j = j0 + threadIdx.x;
+        sx[threadIdx.x] = j < n ? xy[2 * j] : 0.0;
+        sy[threadIdx.x] = j < n ? xy[2 * j + 1] : 0.0;
+    }
+    __syncthreads();
+    if (i >= n) return;
+    const double xi = xy[2 * i], yi = xy[2 * i + 1], ci = c_row[i];
+    const int jn = static_cast<int>(n - j0 < 64 ? n - j0 : 64);
+    uint64_t word = 0;
+#pragma unroll 8
+    for (int t = 0; t < 64; ++t) {
+        const double dx = xi - sx[t];
+        const double dy = yi - sy[t];
+        const double s = dx * dx + dy * dy;                          // no FMA (-ffp-contract=off)
+        word |= static_cast<uint64_t>((s <= ci) & (t < jn)) << t;
+    }
+    bits[i * words + w] = word;
+}
+
+// Membership from a kept distance matrix and one radius per row: bit (i, j) = (D[i][j] <= r[i]) and D[i][j] reached.  One
+// workgroup per row, a wave per 64-column word (the ballot is the word).  masked_out, when given, receives D[i][j] where the bit
+// is set and +inf elsewhere: the matrix a handle built with a cutoff keeps.
+__global__ __launch_bounds__(256) void k_dist_bits_rows(const double *__restrict__ dist, int64_t n, const double *__restrict__ radii,
+                                                        uint64_t *__restrict__ bits, int64_t words, double *__restrict__ masked_out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = blockIdx.x;
+    const double r = radii[i], inf = __longlong_as_double(0x7FF0000000000000ll);
+    for (int64_t w = wave; w < words; w += 4) {
+        const int64_t j = w * 64 + lane;
+        const double d = j < n ? dist[i * n + j] : inf;
+        const bool member = d <= r && d < inf;
+        const unsigned long long word = __ballot(member);
+        if (lane == 0) bits[i * words + w] = word;
+        if (masked_out && j < n) masked_out[i * n + j] = member ? d : inf;
+    }
+}
+
+// --------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------
+// The `<=` twin of squared_threshold:  sqrt(s) <= r   <=>   s <= C,   C = max{ s : sqrt(s) <= r }  (r >= 0).
+static double squared_threshold_le(double r) {
+    if (std::isinf(r)) return r;
+    double c = r * r;
+    while (c > 0.0 && std::sqrt(c) > r) c = std::nextafter(c, 0.0);
+    for (;;) {
+        const double up = std::nextafter(c, INFINITY);
+        if (std::isinf(up) || std::sqrt(up) > r) return c;
+        c = up;
+    }
+}
+
 // where K3's keys come from: coordinates on the device (xy) or a kept distance matrix (dist)
 struct SelSource {
     const double *xy = nullptr, *dist = nullptr;
@@ -699,6 +877,31 @@ int nbr_build_transpose(safe_nbr *nbr) {
                        nbr->at_ptr, d_cnt, nbr->at_col);
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    return SAFE_OK;
+}
+
+// K3b on the context's stream: keys[i] of every row into a host vector (src is xy [n,2] or a kept matrix [n,n], on the device)
+template <bool XY>
+static int row_select_keys(safe_ctx *ctx, const char *fn, const double *d_src, int64_t n, int64_t k,
+                           std::vector<unsigned long long> *keys) {
+    keys->assign(n, 0);
+    CallBufs b;                                         // (behind *keys: the read-back writes it)
+    unsigned long long *d_keys = nullptr;
+    SAFE_TRY(b.alloc(&d_keys, n));
+    hipLaunchKernelGGL(k_row_select<XY>, dim3(n), dim3(256), 0, ctx->stream, d_src, n, k, d_keys);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(keys->data(), d_keys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
+    return SAFE_OK;
+}
+
+// radii of the per-row builders: none NaN, none negative (+inf is a radius)
+static int check_radii(const char *fn, const double *radii, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(radii[i] >= 0.0)) {
+            safe_set_error("%s: the radius of row %lld is negative or NaN", fn, (long long)i);
+            return SAFE_E_VALUE;
+        }
     return SAFE_OK;
 }
 
@@ -1026,6 +1229,95 @@ int safe_nbr_distance_select(safe_nbr *nbr, const int64_t *ranks, int64_t n_rank
     if (n_finite_pairs) *n_finite_pairs = count;                      // (known even where a rank is refused)
     SAFE_TRY(rc);
     for (int64_t t = 0; t < n_ranks; ++t) std::memcpy(&out_host[t], &keys[t], sizeof(double));
+    return SAFE_OK;
+}
+
+int safe_row_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t k, double *radii_out_host) {
+    const char *fn = "safe_row_distance_select_xy";
+    SAFE_REQUIRE(ctx && xy_host && radii_out_host, "%s: NULL argument", fn);
+    SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 64, "%s: n=%lld out of range", fn, (long long)n);
+    SAFE_REQUIRE(k >= 1, "%s: k=%lld, the number of nearest nodes must be at least 1", fn, (long long)k);
+    for (int64_t i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy_host[i])) {
+            safe_set_error("%s: node %lld has a coordinate that is not finite", fn, (long long)(i / 2));
+            return SAFE_E_VALUE;
+        }
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    CallBufs b;
+    double *d_xy = nullptr;
+    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_TRY(row_select_keys<true>(ctx, fn, d_xy, n, k, &keys));
+    for (int64_t i = 0; i < n; ++i) {
+        double s;
+        std::memcpy(&s, &keys[i], sizeof s);
+        radii_out_host[i] = std::sqrt(s);                                 // the one root per row (k_row_select)
+    }
+    return SAFE_OK;
+}
+
+int safe_nbr_row_distance_select(safe_nbr *nbr, int64_t k, double *radii_out_host) {
+    const char *fn = "safe_nbr_row_distance_select";
+    SAFE_REQUIRE(nbr && radii_out_host, "%s: NULL argument", fn);
+    SAFE_REQUIRE(nbr->dist != nullptr, "%s: handle was built without keep_distances", fn);
+    SAFE_REQUIRE(k >= 1, "%s: k=%lld, the number of nearest nodes must be at least 1", fn, (long long)k);
+    safe_ctx *ctx = nbr->ctx;
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    SAFE_TRY(row_select_keys<false>(ctx, fn, nbr->dist, nbr->n, k, &keys));
+    std::memcpy(radii_out_host, keys.data(), nbr->n * sizeof(double));
+    return SAFE_OK;
+}
+
+int safe_nbr_euclidean_rows(safe_ctx *ctx, const double *xy_host, int64_t n, const double *radii_host, safe_nbr **out) {
+    const char *fn = "safe_nbr_euclidean_rows";
+    SAFE_REQUIRE(ctx && xy_host && radii_host && out, "%s: NULL argument", fn);
+    *out = nullptr;
+    SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 64, "%s: n=%lld out of range", fn, (long long)n);
+    SAFE_TRY(check_radii(fn, radii_host, n));
+    std::vector<double> c(n);
+    for (int64_t i = 0; i < n; ++i) c[i] = squared_threshold_le(radii_host[i]);
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    NbrPtr nbr(nullptr, nbr_free);
+    SAFE_TRY(nbr_new(ctx, n, &nbr));
+    CallBufs b;                                         // (behind c: the upload reads it)
+    double *d_xy = nullptr, *d_c = nullptr;
+    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_TRY(b.alloc(&d_c, n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_c, c.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_euclid_bits_rows, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n, d_c, nbr->bits,
+                       nbr->words);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_TRY(nbr_finalize_from_bits(nbr.get()));        // (waits for the stream: the uploads have read xy_host and c)
+    nbr->h_xy.assign(xy_host, xy_host + 2 * n);         // node order of the block-sparse form (mfma.hip)
+    *out = nbr.release();
+    return SAFE_OK;
+}
+
+int safe_nbr_from_distances_rows(safe_nbr *src_nbr, const double *radii_host, int keep_distances, safe_nbr **out) {
+    const char *fn = "safe_nbr_from_distances_rows";
+    SAFE_REQUIRE(src_nbr && radii_host && out, "%s: NULL argument", fn);
+    *out = nullptr;
+    SAFE_REQUIRE(src_nbr->dist != nullptr, "%s: the source handle was built without keep_distances", fn);
+    const int64_t n = src_nbr->n;
+    SAFE_TRY(check_radii(fn, radii_host, n));
+    safe_ctx *ctx = src_nbr->ctx;
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    NbrPtr nbr(nullptr, nbr_free);
+    SAFE_TRY(nbr_new(ctx, n, &nbr));
+    if (keep_distances) SAFE_TRY(dev_alloc(&nbr->dist, n * n));
+    CallBufs b;
+    double *d_r = nullptr;
+    SAFE_TRY(b.alloc(&d_r, n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_r, radii_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_dist_bits_rows, dim3(n), dim3(256), 0, ctx->stream, src_nbr->dist, n, d_r, nbr->bits, nbr->words,
+                       nbr->dist);
+    SAFE_HIP_CHECK_AS(fn, hipGetLastError());
+    SAFE_TRY(nbr_finalize_from_bits(nbr.get()));        // (waits for the stream: the upload has read radii_host)
+    nbr->h_xy = src_nbr->h_xy;
+    *out = nbr.release();
     return SAFE_OK;
 }
 

@@ -5,7 +5,7 @@ error behaviour as `safepy.safe.SAFE` (safepy/safe.py:37-608) for
 `define_neighborhoods()` / `compute_pvalues()` (+ the additive `compute_node_distances()` and
 `node_distance_percentile()`); the arithmetic runs in libsafe_hip.so on an MI355X.  One departure:
 `neighborhood_radius_type`, which the reference reads and ignores, acts here ('absolute' and 'percentile'
-radii; 'diameter' is the reference's rule).  `print_output_files()` writes the reference's
+radii, and 'nearest': every node's own radius, out to its k-th nearest node; 'diameter' is the reference's rule).  `print_output_files()` writes the reference's
 three tables, the node-by-attribute text made on the device; `save()` pickles the object.  The plot methods
 (`plot_network`, `plot_sample_attributes`, `plot_composite_network`, `plot_composite_network_contours`) draw with
 matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  Additive:
@@ -51,6 +51,11 @@ def _is_real(v):
 
 def _is_percentage(q):
     return isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool) and 0 <= q <= 100
+
+
+def _is_neighbor_count(k):
+    """A real number with an integral value of at least 1 (50, 50.0): the k of neighborhood_radius_type = 'nearest'."""
+    return _is_real(k) and np.isfinite(k) and k >= 1 and float(k) == int(k)
 
 
 def _percentile_ranks(count, q):
@@ -239,6 +244,7 @@ class SAFE:
         self.neighborhood_radius_type = None
         self.neighborhood_radius = None
         self.neighborhood_radius_resolved = None     # the radius the last define_neighborhoods / compute_node_distances used (float)
+        self.neighborhood_radii = None               # 'nearest' only: every node's own radius, f64 [N] (resolved = their median)
 
         self.background = 'attribute_file'
         self.num_permutations = 1000
@@ -342,10 +348,15 @@ class SAFE:
             bad, self.node_distance_metric = self.node_distance_metric, self.default_config.get('nodeDistanceType')
             raise ValueError('%s is not a valid setting for node_distance_metric. '
                              'Valid options are: euclidean, shortpath, shortpath_weighted_layout' % bad)
-        if self.neighborhood_radius_type not in [None, 'diameter', 'absolute', 'percentile']:
+        if self.neighborhood_radius_type not in [None, 'diameter', 'absolute', 'percentile', 'nearest']:
             bad, self.neighborhood_radius_type = self.neighborhood_radius_type, self.default_config.get('neighborhoodRadiusType')
             raise ValueError('%s is not a valid setting for neighborhood_radius_type. '
-                             'Valid options are: diameter, absolute, percentile' % bad)
+                             'Valid options are: diameter, absolute, percentile, nearest' % bad)
+        if self.neighborhood_radius_type == 'nearest' and not _is_neighbor_count(self.neighborhood_radius):
+            bad, self.neighborhood_radius = self.neighborhood_radius, float(self.default_config.get('neighborhoodRadius'))
+            self.neighborhood_radius_type = self.default_config.get('neighborhoodRadiusType')
+            raise ValueError('neighborhood_radius = %r is not a number of nodes: with neighborhood_radius_type = nearest '
+                             'it must be a whole number of at least 1.' % (bad,))
         if self.neighborhood_radius_type == 'percentile' and not _is_percentage(self.neighborhood_radius):
             bad, self.neighborhood_radius = self.neighborhood_radius, float(self.default_config.get('neighborhoodRadius'))
             self.neighborhood_radius_type = self.default_config.get('neighborhoodRadiusType')
@@ -422,6 +433,7 @@ class SAFE:
         self.__dict__.setdefault('attribute_transform', 'none')
         self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
         self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
+        self.__dict__.setdefault('neighborhood_radii', None)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -715,10 +727,52 @@ class SAFE:
         finally:
             nbr.close()
 
+    def _nearest_radii(self, ctx, arrays):
+        """neighborhood_radius_type = 'nearest': (the unbounded shortest-path handle with its kept matrix, or None for
+        'euclidean'; every node's distance to its k-th nearest other node, f64 [N]), k = int(neighborhood_radius).  The
+        caller closes the handle."""
+        xy, eu, ev, length, weight = arrays
+        k = min(int(self.neighborhood_radius), 2 ** 62)
+        if self.node_distance_metric == 'euclidean':
+            return None, ctx.row_distance_select(xy, k)
+        w = self._shortpath_weights(xy, eu, ev, length, weight)
+        src = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, np.inf, keep_distances=True)
+        try:
+            return src, src.row_distance_select(k)
+        except Exception:
+            src.close()
+            raise
+
+    def _set_nearest_radii(self, radii):
+        self.neighborhood_radii = radii
+        self.neighborhood_radius_resolved = float(np.median(radii))
+        return self.neighborhood_radius_resolved
+
+    def _nearest_neighborhoods(self, ctx, arrays):
+        """The membership handle of neighborhood_radius_type = 'nearest', A[i, j] = (D[i, j] <= r_i); sets neighborhood_radii
+        and neighborhood_radius_resolved.  A shortest-path handle keeps the masked distances (D where A is 1)."""
+        src, radii = self._nearest_radii(ctx, arrays)
+        try:
+            if src is None:
+                nbr = be.Neighborhoods.euclidean_rows(ctx, arrays[0], radii)
+            else:
+                nbr = be.Neighborhoods.from_distances_rows(src, radii, keep_distances=True)
+        finally:
+            if src is not None:
+                src.close()
+        self._set_nearest_radii(radii)
+        return nbr
+
     def _resolve_radius(self, ctx, arrays):
         """The radius in distance units (the hop cutoff for 'shortpath') that neighborhood_radius stands for under
         neighborhood_radius_type; kept as self.neighborhood_radius_resolved."""
         kind = self.neighborhood_radius_type
+        if kind == 'nearest':                           # one radius per node: the typical one stands for them
+            src, radii = self._nearest_radii(ctx, arrays)
+            if src is not None:
+                src.close()
+            return self._set_nearest_radii(radii)
+        self.neighborhood_radii = None
         if kind == 'percentile':
             r = self._distance_percentiles(ctx, arrays, [self.neighborhood_radius])[0]
         elif kind == 'absolute' or self.node_distance_metric == 'shortpath':
@@ -743,17 +797,32 @@ class SAFE:
     def define_neighborhoods(self, **kwargs):
         """safepy/safe.py:369-430.  kwargs: node_distance_metric, neighborhood_radius_type,
         neighborhood_radius (persisted on self).  Sets self.neighborhoods (and, for the
-        shortest-path metrics, self.node_distances); returns None."""
+        shortest-path metrics, self.node_distances); returns None.
+
+        neighborhood_radius_type = 'nearest' (additive): k = int(neighborhood_radius); node i's radius r_i is the distance to its
+        k-th nearest other node (the farthest reached one where fewer exist, 0.0 where none does; node i is left out by index, so a
+        coincident node counts), and j is a member of row i iff D[i, j] <= r_i -- the diagonal always, every tie at the k-th
+        distance, never an unreached node.  The membership is in general not symmetric.  Sets neighborhood_radii (f64 [N]) and
+        neighborhood_radius_resolved (their median); node_distances holds the distances inside every node's own radius."""
         self._override_neighborhood_settings(kwargs)
         xy, eu, ev, length, weight = _graph_arrays(self.graph)
         ctx = self._ctx()
         if self.node_distance_metric != 'euclidean':
             self._node_distances = None          # replaced below (a copy still on the device is not fetched first)
         self._invalidate_neighborhoods()
-        radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
-        if self.node_distance_metric == 'euclidean':
+        self.neighborhood_radii = None               # (a call that fails below leaves no radii of an earlier one behind)
+        nearest = self.neighborhood_radius_type == 'nearest'
+        if nearest:
+            self.neighborhood_radius_resolved = None
+            self._nbr = self._nearest_neighborhoods(ctx, (xy, eu, ev, length, weight))
+            if self.node_distance_metric != 'euclidean':
+                self._nbr.set_layout(xy)
+                self._node_distances = ('device-shortpath', self._nbr)
+        elif self.node_distance_metric == 'euclidean':
+            radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
             self._nbr = be.Neighborhoods.euclidean(ctx, xy, radius)
         else:
+            radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
             w = self._shortpath_weights(xy, eu, ev, length, weight)
             self._nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, radius, keep_distances=True)
             self._nbr.set_layout(xy)
@@ -761,8 +830,14 @@ class SAFE:
         if self.verbose:
             num_neighbors = self._nbr.row_counts()
             logging.info('Node distance metric: %s' % self.node_distance_metric)
-            logging.info('Neighborhood definition: %.2f x %s' % (self.neighborhood_radius, self.neighborhood_radius_type))
-            if self.neighborhood_radius_type not in (None, 'diameter'):
+            if nearest:
+                logging.info('Neighborhood definition: %d nearest nodes' % int(self.neighborhood_radius))
+                logging.info('Neighborhood radii in distance units (min / median / max): %r / %r / %r'
+                             % (float(np.min(self.neighborhood_radii)), self.neighborhood_radius_resolved,
+                                float(np.max(self.neighborhood_radii))))
+            else:
+                logging.info('Neighborhood definition: %.2f x %s' % (self.neighborhood_radius, self.neighborhood_radius_type))
+            if self.neighborhood_radius_type not in (None, 'diameter', 'nearest'):
                 logging.info('Neighborhood radius in distance units: %r' % self.neighborhood_radius_resolved)
             logging.info('Number of nodes per neighborhood (mean +/- std): %.2f +/- %.2f'
                          % (np.mean(num_neighbors), np.std(num_neighbors)))
@@ -776,6 +851,13 @@ class SAFE:
         xy, eu, ev, length, weight = _graph_arrays(self.graph)
         ctx = self._ctx()
         n = xy.shape[0]
+        if self.neighborhood_radius_type == 'nearest' and self.node_distance_metric != 'euclidean':
+            nbr = self._nearest_neighborhoods(ctx, (xy, eu, ev, length, weight))      # the distances inside every node's own radius
+            try:
+                self._node_distances = ('dense-shortpath', nbr.distances())
+            finally:
+                nbr.close()
+            return
         radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
         if self.node_distance_metric == 'euclidean':
             d_xy = ctx.alloc(xy.nbytes)
