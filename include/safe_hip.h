@@ -27,6 +27,7 @@
  *     a flag or a timing event back or keep host memory alive for their kernels:
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
  *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_fdr_adjust, safe_fdr_adjust_rows,
+ *     safe_fdr_adjust_scope, safe_fdr_adjust_matrix,
  *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
  *     (tests/test_gpu_stream_order.py measures both lists).
@@ -66,6 +67,10 @@ extern "C" {
 #define SAFE_SIGN_HIGHEST 0   /* attribute_sign == 'highest' */
 #define SAFE_SIGN_LOWEST 1    /* attribute_sign == 'lowest'  */
 #define SAFE_SIGN_BOTH 2      /* attribute_sign == 'both'    */
+
+#define SAFE_FDR_SCOPE_ROWS 0 /* multiple_testing_scope == 'attributes': every node's row (the reference)  */
+#define SAFE_FDR_SCOPE_COLS 1 /* multiple_testing_scope == 'neighborhoods': every attribute's column       */
+#define SAFE_FDR_SCOPE_ALL 2  /* multiple_testing_scope == 'all': the whole matrix as one family           */
 
 typedef struct safe_ctx safe_ctx;
 typedef struct safe_nbr safe_nbr;       /* neighborhood membership, device resident     */
@@ -490,6 +495,29 @@ int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutation
 /* Benjamini-Hochberg adjustment of every row of ONE matrix (f64 [n,m] row-major), in place: what safe_fdr_adjust with
  * num_permutations = 0 does to pvalues_pos_dev, without the NES epilogue (the rows are sorted; no histogram form). */
 int safe_fdr_adjust_rows(safe_ctx *ctx, int64_t n, int64_t m, double *p_dev);
+
+/* safe_fdr_adjust with the family named by `scope` (additive; the reference adjusts rows only, safepy/safe.py:536-542, 599-605):
+ *   SAFE_FDR_SCOPE_ROWS  np.apply_along_axis(lambda r: fdrcorrection(r)[1], 1, p): safe_fdr_adjust itself, the same bytes
+ *   SAFE_FDR_SCOPE_COLS  the same along axis 0: one attribute's column across the n neighborhoods
+ *   SAFE_FDR_SCOPE_ALL   fdrcorrection(p.ravel())[1].reshape(p.shape): the n m tests as one family
+ * in place on pvalues_neg_dev / pvalues_pos_dev, then NES, nes_binary and the per-attribute counts by the epilogue of
+ * safe_fdr_adjust (safe.py:546-554 / 608, 468-472).  The NaN rule of safe_fdr_adjust holds for the family: a NaN of either sign
+ * and any payload turns its whole column -- with SAFE_FDR_SCOPE_ALL the whole matrix -- into 0x7FF8...; -0.0 is the value 0.0.
+ * With num_permutations > 0 both matrices are checked read-only first; if every entry is a count ratio the families are
+ * adjusted from histograms over the counts (columns: num_permutations <= 4095; whole matrix: <= 16383), otherwise they are
+ * sorted, and the result is the same.  The whole-matrix sort takes n m < 2^31 entries: beyond that SAFE_E_UNSUPPORTED, before
+ * anything is written.  Bad arguments (NULL, n or m < 1, scope outside 0 ... 2, enrichment_threshold outside (0, 1)) are
+ * SAFE_E_VALUE, before anything is written. */
+int safe_fdr_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
+                          double enrichment_threshold, int scope, double *pvalues_neg_dev, double *pvalues_pos_dev,
+                          double *nes_dev, double *nes_binary_dev, double *num_enriched_dev);
+
+/* Benjamini-Hochberg adjustment of ONE matrix (f64 [n,m] row-major) in place along `scope`, without the NES epilogue: the scoped
+ * counterpart of safe_fdr_adjust_rows (the two-sided tests call it on both matrices, then safe_hypergeom_outputs).
+ * count_denominator = 0: the families are sorted.  count_denominator = P > 0: the caller says the entries are counts / P; the
+ * matrix is checked read-only, and anything that is not such a ratio, or a P beyond the count form's limit, goes through the
+ * sort with the same result.  Errors as safe_fdr_adjust_scope. */
+int safe_fdr_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int64_t count_denominator, double *p_dev);
 
 /* The hypergeometric test with BOTH tails, for 0/1 attributes (NaN allowed): what compute_pvalues_by_hypergeom would set if it
  * followed attribute_sign the way the randomization route does (safepy/safe.py:546-554; the reference computes the upper tail

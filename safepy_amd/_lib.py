@@ -14,6 +14,7 @@ ABI_VERSION = 9
 DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
+FDR_SCOPE_ROWS, FDR_SCOPE_COLS, FDR_SCOPE_ALL = 0, 1, 2      # SAFE_FDR_SCOPE_*
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
 SELECT_MAX_NODES = 65536            # SAFE_SELECT_MAX_NODES: nodes safe_pair_distance_select_xy / safe_nbr_distance_select take
 KK_MAX_NODES = 65536                # SAFE_KK_MAX_NODES: nodes safe_kk_create_host / safe_kk_create_nbr take
@@ -147,6 +148,8 @@ PROTOTYPES = {
     'safe_jaccard_condensed': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     'safe_fdr_adjust': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'safe_fdr_adjust_rows': (C.c_int, [_vp, _i64, _i64, _vp]),
+    'safe_fdr_adjust_scope': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'safe_fdr_adjust_matrix': (C.c_int, [_vp, _i64, _i64, C.c_int, _i64, _vp]),
     'safe_hypergeom_tails': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_hypergeom_outputs': (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'safe_moments_test': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1322,6 +1322,29 @@ def fdr_adjust_rows(ctx, n, m, p_ptr):
     check(lib.safe_fdr_adjust_rows(ctx.handle, int(n), int(m), C.c_void_p(p_ptr) if p_ptr else None))
 
 
+# multiple_testing_scope -> SAFE_FDR_SCOPE_*: the family one Benjamini-Hochberg run adjusts
+FDR_SCOPES = {'attributes': _lib.FDR_SCOPE_ROWS, 'neighborhoods': _lib.FDR_SCOPE_COLS, 'all': _lib.FDR_SCOPE_ALL}
+
+
+def _fdr_scope(scope):
+    return FDR_SCOPES[scope] if isinstance(scope, str) else int(scope)
+
+
+def fdr_adjust_matrix(ctx, n, m, scope, p_ptr, count_denominator=0):
+    """Benjamini-Hochberg on one f64 [n, m] device matrix, in place, along `scope` ('attributes': rows, 'neighborhoods': columns,
+    'all': the whole matrix; or a SAFE_FDR_SCOPE_* number).  count_denominator = P > 0: the entries are counts / P (checked; the
+    histogram forms); 0: the families are sorted."""
+    check(lib.safe_fdr_adjust_matrix(ctx.handle, int(n), int(m), _fdr_scope(scope), int(count_denominator),
+                                     C.c_void_p(p_ptr) if p_ptr else None))
+
+
+def fdr_adjust_scope(ctx, n, m, num_permutations, attribute_sign, enrichment_threshold, scope, out_ptrs):
+    """fdr_adjust with the family named by `scope` (see fdr_adjust_matrix): out_ptrs = (pvalues_neg or None, pvalues_pos, nes,
+    nes_binary, num_enriched); num_permutations = 0 selects the hypergeometric form."""
+    check(lib.safe_fdr_adjust_scope(ctx.handle, int(n), int(m), int(num_permutations), _SIGN[attribute_sign], float(enrichment_threshold),
+                                    _fdr_scope(scope), *[C.c_void_p(p) if p else None for p in out_ptrs]))
+
+
 def packed_counts_info(ctx):
     """(n_pad, m, layout) of the integer counters the last randomization call left on the device;
     layout -1 = none (f64 kernels)."""

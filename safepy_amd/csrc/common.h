@@ -135,6 +135,9 @@ enum ScratchSlot {
     SCRATCH_GO_BITS,        // the (term x locus) bit matrix u32 [n_terms][W] | safe_go_create (go.hip) | within the call
     SCRATCH_GO_WORK,        // annotation pairs | children CSR | level order | per-term counts, flags, offsets | per-word OR |
                             //   readback words | safe_go_create | within the call
+    SCRATCH_FDR_SCOPE,      // 64-bit histogram [P + 1] | adjusted values f64 [P + 1] | u32 flags of the whole-matrix count form, or the
+                            //   one u32 flag of the column count form | safe_fdr_adjust_scope, safe_fdr_adjust_matrix (fdr_scope.hip) |
+                            //   within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "fdr_shared.h"
 
 namespace {
 
@@ -270,7 +271,9 @@ __global__ void k_fdr_u32_to_f64(const unsigned int *__restrict__ in, double *__
     if (i < count) out[i] = static_cast<double>(in[i]);
 }
 
-int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_perm = 0) {
+}  // namespace
+
+int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
     const char *sort_env = getenv("SAFE_HIP_FDR_SORT");                   // "cub": library sort for every row length (tests); "sort": never the histogram form
     // randomization form: p-values are counts / n_perm -- no sort needed (k_fdr_row_counts); table + histogram must fit LDS
     if (n_perm > 0 && (n_perm + 1) * 12 <= 60 * 1024 && !sort_env) {
@@ -343,7 +346,37 @@ int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_per
     return SAFE_OK;
 }
 
-}  // namespace
+int fdr_all_count_ratios(safe_ctx *ctx, const double *const *mats, int n_mats, int64_t total, int64_t n_perm, bool *all) {
+    unsigned int *d_flag = nullptr;
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
+    SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
+    for (int k = 0; k < n_mats; ++k)
+        hipLaunchKernelGGL(k_fdr_check_ratio, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, mats[k], total,
+                           static_cast<double>(n_perm), d_flag);
+    SAFE_HIP_CHECK(hipGetLastError());
+    void *pinned = nullptr;
+    SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), &pinned));
+    SAFE_HIP_CHECK(hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
+    *all = *static_cast<unsigned int *>(pinned) == 0u;
+    return SAFE_OK;
+}
+
+int fdr_nes_epilogue(safe_ctx *ctx, const char *who, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
+                     double enrichment_threshold, const double *pvalues_neg_dev, const double *pvalues_pos_dev, double *nes_dev,
+                     double *nes_binary_dev, double *num_enriched_dev) {
+    CallBufs b;
+    unsigned int *d_enr = nullptr;
+    SAFE_TRY(b.alloc(&d_enr, m));
+    SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, m * sizeof(unsigned int), ctx->stream));
+    hipLaunchKernelGGL(k_nes_from_pvalues, dim3(ceil_div(m, 64), ceil_div(n, 64)), dim3(256), 0, ctx->stream, pvalues_neg_dev,
+                       pvalues_pos_dev, n, m, num_permutations > 0 ? 1.0 / static_cast<double>(num_permutations) : 0.0, sign_mode,
+                       -std::log10(enrichment_threshold), nes_p_cut(enrichment_threshold), nes_dev, nes_binary_dev, d_enr);
+    hipLaunchKernelGGL(k_fdr_u32_to_f64, dim3(ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, m);
+    SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    SAFE_HIP_CHECK_AS(who, safe_stream_sync(ctx->stream));
+    return SAFE_OK;
+}
 
 extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
                                double enrichment_threshold, double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev,
@@ -359,33 +392,15 @@ extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_
     // checked READ-ONLY first, and anything that is not a count ratio goes through the sort like the hypergeometric form.
     int64_t hist_perm = 0;
     if (num_permutations > 0 && (num_permutations + 1) * 12 <= 60 * 1024 && !getenv("SAFE_HIP_FDR_SORT")) {
-        unsigned int *d_flag = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
-        SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
-        const int64_t total = n * m;
-        for (const double *mat : {static_cast<const double *>(pvalues_neg_dev), static_cast<const double *>(pvalues_pos_dev)})
-            hipLaunchKernelGGL(k_fdr_check_ratio, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, mat, total,
-                               static_cast<double>(num_permutations), d_flag);
-        SAFE_HIP_CHECK(hipGetLastError());
-        void *pinned = nullptr;
-        SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), &pinned));
-        SAFE_HIP_CHECK(hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-        if (*static_cast<unsigned int *>(pinned) == 0u) hist_perm = num_permutations;
+        const double *mats[2] = {pvalues_neg_dev, pvalues_pos_dev};
+        bool all = false;
+        SAFE_TRY(fdr_all_count_ratios(ctx, mats, 2, n * m, num_permutations, &all));
+        if (all) hist_perm = num_permutations;
     }
     if (num_permutations > 0) SAFE_TRY(fdr_matrix(ctx, pvalues_neg_dev, n, m, hist_perm));
     SAFE_TRY(fdr_matrix(ctx, pvalues_pos_dev, n, m, hist_perm));
-    CallBufs b;
-    unsigned int *d_enr = nullptr;
-    SAFE_TRY(b.alloc(&d_enr, m));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, m * sizeof(unsigned int), ctx->stream));
-    hipLaunchKernelGGL(k_nes_from_pvalues, dim3(ceil_div(m, 64), ceil_div(n, 64)), dim3(256), 0, ctx->stream, pvalues_neg_dev,
-                       pvalues_pos_dev, n, m, num_permutations > 0 ? 1.0 / static_cast<double>(num_permutations) : 0.0, sign_mode,
-                       -std::log10(enrichment_threshold), nes_p_cut(enrichment_threshold), nes_dev, nes_binary_dev, d_enr);
-    hipLaunchKernelGGL(k_fdr_u32_to_f64, dim3(ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, m);
-    SAFE_HIP_CHECK_AS("safe_fdr_adjust", hipGetLastError());
-    SAFE_HIP_CHECK_AS("safe_fdr_adjust", safe_stream_sync(ctx->stream));
-    return SAFE_OK;
+    return fdr_nes_epilogue(ctx, "safe_fdr_adjust", n, m, num_permutations, sign_mode, enrichment_threshold, pvalues_neg_dev, pvalues_pos_dev,
+                            nes_dev, nes_binary_dev, num_enriched_dev);
 }
 
 // Benjamini-Hochberg on every row of one matrix, in place: fdr_matrix's sort form (what safe_fdr_adjust with

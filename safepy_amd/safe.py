@@ -249,6 +249,9 @@ class SAFE:
         self.background = 'attribute_file'
         self.num_permutations = 1000
         self.multiple_testing = False
+        # read only when multiple_testing is on: the family one Benjamini-Hochberg run adjusts -- 'attributes' (every node's row, the
+        # reference), 'neighborhoods' (every attribute's column), 'all' (the whole matrix); compute_pvalues
+        self.multiple_testing_scope = 'attributes'
         self.neighborhood_score_type = 'sum'
         self.enrichment_type = 'auto'
         self.hypergeom_tails = 'upper'   # 'attribute_sign': the hypergeometric test follows attribute_sign (both tails, ns, signed nes)
@@ -370,6 +373,11 @@ class SAFE:
             bad, self.hypergeom_tails = self.hypergeom_tails, 'upper'
             raise ValueError('%s is not a valid setting for hypergeom_tails. '
                              'Valid options are: upper, attribute_sign' % (bad,))
+        scope = getattr(self, 'multiple_testing_scope', 'attributes')
+        if not isinstance(scope, str) or scope not in ['attributes', 'neighborhoods', 'all']:
+            self.multiple_testing_scope = 'attributes'
+            raise ValueError('%s is not a valid setting for multiple_testing_scope. '
+                             'Valid options are: attributes, neighborhoods, all' % (scope,))
         if getattr(self, 'attribute_transform', 'none') not in ['none', 'rank']:
             bad, self.attribute_transform = self.attribute_transform, 'none'
             raise ValueError('%s is not a valid setting for attribute_transform. '
@@ -431,6 +439,7 @@ class SAFE:
         self.__dict__.update(state)
         self.__dict__.setdefault('hypergeom_tails', 'upper')     # (objects pickled before the setting existed)
         self.__dict__.setdefault('attribute_transform', 'none')
+        self.__dict__.setdefault('multiple_testing_scope', 'attributes')
         self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
         self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
         self.__dict__.setdefault('neighborhood_radii', None)
@@ -885,7 +894,22 @@ class SAFE:
         holds rank sums (rank z-scores with neighborhood_score_type = 'z-score'), not sums of attribute values.
         how = 'analytic' on ranks is the tie-corrected Wilcoxon / Mann-Whitney rank-sum test of every attribute in every
         neighborhood, how = 'randomization' its permutation form.  'auto' still looks at the raw values; a hypergeometric
-        route (how = 'hypergeometric', or 'auto' on 0/1 data) is refused with a ValueError: ranks are not counts."""
+        route (how = 'hypergeometric', or 'auto' on 0/1 data) is refused with a ValueError: ranks are not counts.
+
+        multiple_testing_scope (additive; keyword or setting, default 'attributes'; read only when multiple_testing is on): the
+        family that one Benjamini-Hochberg run adjusts, on every route that honours multiple_testing.
+          'attributes'     each node's row across the attributes -- np.apply_along_axis(lambda r: fdrcorrection(r)[1], 1, p), the
+                           reference (safe.py:536-542, 599-605) and the bytes of a call without the keyword;
+          'neighborhoods'  each attribute's column across the nodes (the same along axis 0): "in which neighborhoods is this
+                           attribute enriched?", what num_neighborhoods_enriched and define_top_attributes read;
+          'all'            the whole matrix as one family of N M tests -- fdrcorrection(p.ravel())[1].reshape(p.shape): "which
+                           (node, attribute) calls can I trust?", what nes_binary and enriched_pairs are.
+        nes, nes_binary and num_neighborhoods_enriched are recomputed from the adjusted values as for 'attributes', and the
+        results stay on the device under lazy_outputs.  The NaN rule is the row rule applied to the family: one NaN p-value (a
+        node without a score) turns its whole family NaN -- its column under 'neighborhoods', the WHOLE matrix under 'all'.
+        The attribute-sharded drivers (safepy_amd.sharding, run_batch.py) keep the row scope and do not take the keyword."""
+        if 'multiple_testing_scope' in kwargs:
+            self.multiple_testing_scope = kwargs['multiple_testing_scope']
         if 'how' in kwargs:
             self.enrichment_type = kwargs['how']
         if 'neighborhood_score_type' in kwargs:
@@ -973,6 +997,16 @@ class SAFE:
         (lazy_outputs, the default) or copied to the host right away."""
         return _DeviceResult(buf, shape) if self.lazy_outputs else buf.download(shape)
 
+    def _fdr_adjust(self, ctx, n, m, num_permutations, out_ptrs):
+        """multiple_testing on the randomization and the upper-tail hypergeometric route: Benjamini-Hochberg along
+        multiple_testing_scope, then nes, nes_binary and the counts from the adjusted values.  'attributes' is the call the
+        reference's behaviour has always gone through (backend.fdr_adjust)."""
+        if self.multiple_testing_scope == 'attributes':
+            be.fdr_adjust(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold, out_ptrs)
+        else:
+            be.fdr_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
+                                self.multiple_testing_scope, out_ptrs)
+
     def compute_pvalues_by_randomization(self, _attr=None, **kwargs):
         """safepy/safe.py:474-554 (no 1 s sleep, no multiprocessing split: `processes` is
         accepted and ignored -- the reference's own split is broken at this commit)."""
@@ -1000,8 +1034,7 @@ class SAFE:
                              [b.ptr for b in bufs])
             if self.multiple_testing:                  # safe.py:536-542, then 546-554 and 468-472 on the adjusted values
                 logging.info('Running FDR-adjustment of p-values...')
-                be.fdr_adjust(ctx, n, m, self.num_permutations, self.attribute_sign, self.enrichment_threshold,
-                              [b.ptr for b in bufs[1:]])
+                self._fdr_adjust(ctx, n, m, self.num_permutations, [b.ptr for b in bufs[1:]])
             enriched = bufs[5].download((m,))
             res = [self._result(b, (n, m)) for b in bufs[:5]]
             bufs = bufs[5:] if self.lazy_outputs else bufs       # handed over: the results own their buffers now
@@ -1048,8 +1081,7 @@ class SAFE:
             if self.multiple_testing:                  # safe.py:599-605, then 608 and 468-472 on the adjusted values
                 if self.verbose:
                     logging.info('Running FDR-adjustment of p-values...')
-                be.fdr_adjust(ctx, n, m, 0, self.attribute_sign, self.enrichment_threshold,
-                              [None] + [b.ptr for b in bufs])
+                self._fdr_adjust(ctx, n, m, 0, [None] + [b.ptr for b in bufs])
             enriched = bufs[3].download((m,))
             res = [self._result(b, (n, m)) for b in bufs[:3]]
             bufs = bufs[3:] if self.lazy_outputs else bufs       # handed over: the results own their buffers now
@@ -1112,8 +1144,8 @@ class SAFE:
 
     def _two_sided_results(self, ctx, n, m, device_call):
         """The part the two-sided tests share (hypergeom_tails = 'attribute_sign', how = 'analytic'): device_call(out_ptrs) fills
-        (ns, pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched); multiple_testing adjusts every row of both p matrices
-        (fdrcorrection(row)[1], as safe.py:538-542 does for randomization) and recomputes nes, nes_binary and the counts from the
+        (ns, pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched); multiple_testing adjusts both p matrices along
+        multiple_testing_scope (by default every row: fdrcorrection(row)[1], as safe.py:538-542 does for randomization) and recomputes nes, nes_binary and the counts from the
         adjusted values; the matrices become the results, on the device until read."""
         bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
         try:
@@ -1121,8 +1153,11 @@ class SAFE:
             if self.multiple_testing:
                 if self.verbose:
                     logging.info('Running FDR-adjustment of p-values...')
-                be.fdr_adjust_rows(ctx, n, m, bufs[1].ptr)
-                be.fdr_adjust_rows(ctx, n, m, bufs[2].ptr)
+                for b in bufs[1:3]:
+                    if self.multiple_testing_scope == 'attributes':
+                        be.fdr_adjust_rows(ctx, n, m, b.ptr)
+                    else:
+                        be.fdr_adjust_matrix(ctx, n, m, self.multiple_testing_scope, b.ptr)
                 be.hypergeom_outputs(ctx, n, m, self.attribute_sign, self.enrichment_threshold, bufs[1].ptr, bufs[2].ptr,
                                      [b.ptr for b in bufs[3:]])
             enriched = bufs[5].download((m,))
