@@ -121,7 +121,7 @@ enum ScratchSlot {
     SCRATCH_ATTR_STAGED,    // the bytes of a u8 attribute matrix as they came | safe_attr_create_host (attr.hip) | within the call
     SCRATCH_HYP_DUMMY,      // 64 write-only f64 for the padding rows / columns of branch-free epilogues (HypLookup::dummy) |
                             //   hypergeom_fused | within the call
-    SCRATCH_FDR_FLAG,       // one u32 flag | safe_fdr_adjust's count-ratio check and fdr_matrix's histogram form (fdr.hip) | within the call
+    SCRATCH_FDR_FLAG,       // one u32 flag | the count-ratio check and the count forms of the safe_fdr_adjust* entry points (with_flag, fdr.hip) | within the call
     SCRATCH_TAILS_SMALL,    // neighborhood sizes f64 [n] | enriched counters u32 [mloc] | largest count u32 | safe_hypergeom_tails,
                             //   safe_hypergeom_outputs (hyptails.hip) | within the call
     SCRATCH_TAILS_TABLE,    // the (p_pos, p_neg) table [sizes][x][counts] | safe_hypergeom_tails | within the call
@@ -135,9 +135,8 @@ enum ScratchSlot {
     SCRATCH_GO_BITS,        // the (term x locus) bit matrix u32 [n_terms][W] | safe_go_create (go.hip) | within the call
     SCRATCH_GO_WORK,        // annotation pairs | children CSR | level order | per-term counts, flags, offsets | per-word OR |
                             //   readback words | safe_go_create | within the call
-    SCRATCH_FDR_SCOPE,      // 64-bit histogram [P + 1] | adjusted values f64 [P + 1] | u32 flags of the whole-matrix count form, or the
-                            //   one u32 flag of the column count form | safe_fdr_adjust_scope, safe_fdr_adjust_matrix (fdr_scope.hip) |
-                            //   within the call
+    SCRATCH_FDR_SCOPE,      // 64-bit histogram [P + 1] | adjusted values f64 [P + 1] | u32 flags of the whole-matrix count form |
+                            //   safe_fdr_adjust_scope, safe_fdr_adjust_matrix (fdr.hip) | within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,

@@ -1,96 +1,163 @@
-// multiple_testing=True: Benjamini-Hochberg adjustment of every ROW of the p-value matrices
-// (across attributes), i.e. np.apply_along_axis(fdrcorrection, 1, pvalues)[:, 1, :] of
-// safepy/safe.py:536-542 (randomization) and 599-605 (hypergeometric), followed by the NES /
-// binarisation steps that depend on the adjusted values (safe.py:546-554, 608, 468-472).
+// multiple_testing=True: Benjamini-Hochberg adjustment of the p-value matrices along multiple_testing_scope, followed by the NES /
+// binarisation steps that depend on the adjusted values (safe.py:546-554, 608, 468-472).  The family of one adjustment is every
+// ROW (one node's neighborhood across its m attributes), i.e. np.apply_along_axis(fdrcorrection, 1, pvalues)[:, 1, :] of
+// safepy/safe.py:536-542 (randomization) and 599-605 (hypergeometric); or every COLUMN (one attribute across the n neighborhoods:
+// np.apply_along_axis(lambda c: fdrcorrection(c)[1], 0, p)); or the WHOLE matrix (fdrcorrection(p.ravel())[1].reshape(p.shape)).
 //
 // statsmodels' fdrcorrection(pvals) (method 'indep'), operation by operation:
 //     order = argsort(pvals); ps = pvals[order]
 //     raw = ps / (arange(1, n+1) / float(n))
 //     corrected = minimum.accumulate(raw[::-1])[::-1];  corrected[corrected > 1] = 1
 //     out[order] = corrected
-// Ties need no care: tied entries end up with the same value whatever their order (the running
-// minimum from the right passes through the group's last member).  NaN p-values sort last and
-// np.minimum propagates them through the whole row, so a row with any NaN becomes all NaN.
+// Ties need no care: tied entries end up with the same value whatever their order (the running minimum from the right passes
+// through the group's last member).  NaN p-values sort last and np.minimum propagates them through the whole family, so a family
+// with any NaN, of either sign and any payload, becomes all 0x7FF8... -- for the whole-matrix scope that is the whole matrix --
+// and -0.0 is the value 0.0.  Every form does the same two divisions on the same doubles (fdr_raw; the count is n for a column, n m
+// for the whole matrix, exact in f64); all counting is in integers and fmin of numbers does not depend on the order, so identical
+// calls give identical bytes.
 //
-// Randomization form (p = counts / num_permutations): no sort, the row's histogram over the counts (k_fdr_row_counts).
-// Rows of up to 8192 attributes are adjusted by ONE kernel, one workgroup per row: block-wide radix sort of the
-// row's p-values with their column ids, then the Benjamini-Hochberg pass on the registers that hold the
-// sorted row (k_fdr_row_sort, instead of the library's segmented radix sort of the whole matrix + its temporaries).  Longer rows: hipCUB segmented radix sort,
-// rows batched so a call stays below 2^31 keys, then the same BH pass (k_fdr_row).
+// The form of a call is chosen in fdr_plan.h (fdr_form) and nowhere else:
+//   rows, count form      p = counts / num_permutations: no sort, the row's histogram over the counts (k_fdr_row_counts).
+//   rows, block sort      rows of up to 8192 attributes are adjusted by ONE kernel, one workgroup per row: block-wide radix sort of
+//                         the row's p-values with their column ids, then the Benjamini-Hochberg pass on the registers that hold the
+//                         sorted row (k_fdr_row_sort, instead of the library's segmented radix sort of the whole matrix + its
+//                         temporaries).
+//   rows, library sort    longer rows: hipCUB segmented radix sort, rows batched so a call stays below 2^31 keys, then the same BH
+//                         pass (k_fdr_row).
+//   columns, count form   k_fdr_col_counts: p = c / P with P <= FDR_COL_HIST_MAX_P.  A workgroup owns a tile of adjacent columns
+//                         (its row reads are contiguous), one LDS histogram of P + 1 bins per column; a wave turns a column's
+//                         histogram into the table of adjusted values (the same bin rule, fdr_ratio_bin); one table look-up per
+//                         entry.
+//   columns, sort form    tiled LDS transpose into per-call memory, the row sort forms on the [m, n] transpose, transpose back.
+//   matrix, count form    P <= FDR_ALL_HIST_MAX_P: k_fdr_all_hist (per-workgroup LDS histograms flushed with integer atomics
+//                         into 64-bit counters), k_fdr_all_table (one workgroup: the P + 1 adjusted values), k_fdr_all_map.
+//                         Two reads and one write of the matrix.
+//   matrix, sort form     one device-wide radix sort of the n m keys (fdr_key) with the cell index as payload; the running minimum
+//                         from the right as per-block minima (k_fdr_all_blockmin), a carry pass (k_fdr_all_carry) and the apply
+//                         pass, which scatters back (k_fdr_all_apply).  The keys-only sort with a binary search per cell was not
+//                         built.  n m >= 2^31 is beyond the library sort: SAFE_E_UNSUPPORTED.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
+#include <cstdlib>
 
 #include "common.h"
-#include "fdr_shared.h"
+#include "fdr_plan.h"
+
+static_assert(FDR_SCOPE_ROWS == SAFE_FDR_SCOPE_ROWS && FDR_SCOPE_COLS == SAFE_FDR_SCOPE_COLS && FDR_SCOPE_ALL == SAFE_FDR_SCOPE_ALL,
+              "fdr_plan.h numbers the scopes as safe_hip.h does");
 
 namespace {
 
+__device__ __forceinline__ double fdr_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
+__device__ __forceinline__ double fdr_key_value(unsigned long long k) { return __longlong_as_double(static_cast<long long>(k)); }
+__device__ __forceinline__ double fdr_qnan() { return fdr_key_value(FDR_KEY_NAN); }
+
+// one entry into an LDS histogram over the counts; what keeps it out goes to `bad`: 1 = a NaN, 2 = not a count ratio
+__device__ __forceinline__ void hist_add(unsigned int *hist, double v, double P, unsigned int &bad) {
+    const int bin = fdr_ratio_bin(v, P);
+    if (bin >= 0) atomicAdd(&hist[bin], 1u);
+    else bad |= bin == FDR_BIN_NAN ? 1u : 2u;
+}
+
+// part[u]: the minimum of thread u's share of the sorted family; `carry` joined with the shares right of thread t's
+__device__ __forceinline__ double suffix_min(const double *part, int t, double carry) {
+    for (int u = t + 1; u < FDR_THREADS; ++u) carry = fmin(carry, part[u]);
+    return carry;
+}
+
+// A family's histogram over the counts -> table[c] = the adjusted value of every entry with count c, by one workgroup.  All
+// members of a tie end up with the value of the tie's LAST sorted position (header above), so cum[c] = #entries with count <= c
+// is that position, raw[c] = (c / P) / (cum[c] / count) the value statsmodels computes there, and table[c] = min over the occupied
+// c' >= c: block scan (thread t owns the bins fdr_span gives it), reverse running minimum.  H: the counters (u32 in LDS, u64 in
+// memory); unoccupied bins count as +inf.
+template <typename H>
+__device__ __forceinline__ void hist_to_table(const H *__restrict__ hist, int bins, double P, double count_d, double *__restrict__ table) {
+    __shared__ H part_u[FDR_THREADS];
+    __shared__ double part_d[FDR_THREADS];
+    const int t = threadIdx.x;
+    int b0, b1;
+    fdr_span(bins, FDR_THREADS, t, b0, b1);
+    H local = 0;
+    for (int c = b0; c < b1; ++c) local += hist[c];
+    part_u[t] = local;
+    __syncthreads();
+    H cum = 0;
+    for (int u = 0; u < t; ++u) cum += part_u[u];
+    double mn = fdr_inf();
+    for (int c = b0; c < b1; ++c) {
+        const H h = hist[c];
+        cum += h;
+        const double raw = h ? fdr_raw(static_cast<double>(c) / P, static_cast<double>(cum), count_d) : fdr_inf();
+        table[c] = raw;
+        mn = fmin(mn, raw);
+    }
+    part_d[t] = mn;
+    __syncthreads();
+    double carry = suffix_min(part_d, t, fdr_inf());
+    for (int c = b1 - 1; c >= b0; --c) {
+        carry = fmin(carry, table[c]);
+        table[c] = fdr_clamp(carry);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------- rows, sort forms ----
+
 __global__ void k_fdr_cols(int32_t *__restrict__ idx, int64_t count, int64_t m) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x;
     if (i < count) idx[i] = static_cast<int32_t>(i % m);
 }
 
 __global__ void k_fdr_offsets(int64_t *__restrict__ off, int64_t rows, int64_t m) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x;
     if (i <= rows) off[i] = i * m;
 }
 
-// -0.0 -> +0.0, every other value as it is: NumPy sorts and compares the two zeros as one value, and the rows of all three
-// forms come out with the same bits
-__device__ __forceinline__ double plus_zero(double v) { return v == 0.0 ? 0.0 : v; }
-
 // one workgroup per row of the batch; ps / cols: the row sorted ascending with its column ids
-__global__ __launch_bounds__(256) void k_fdr_row(const double *__restrict__ ps, const int32_t *__restrict__ cols, int64_t m,
-                                                 double *__restrict__ out) {
-    __shared__ double part[256];
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row(const double *__restrict__ ps, const int32_t *__restrict__ cols, int64_t m,
+                                                         double *__restrict__ out) {
+    __shared__ double part[FDR_THREADS];
     const int64_t row = blockIdx.x;
     const double *p = ps + row * m;
     const int32_t *c = cols + row * m;
     double *o = out + row * m;
     const int t = threadIdx.x;
-    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
     // The library's float key puts a NaN whose sign bit is set (0xFFF8...: what x86 makes of 0 / 0) BEFORE every number and
     // the others behind them (it treats -0.0 as +0.0): a row has a NaN iff one of its two ends is one.
     const double first = p[0], last = p[m - 1];
     if (first != first || last != last) {                           // a NaN anywhere poisons the whole row
-        for (int64_t r = t; r < m; r += 256) o[r] = qnan;
+        for (int64_t r = t; r < m; r += FDR_THREADS) o[r] = fdr_qnan();
         return;
     }
     const double n_d = static_cast<double>(m);
-    const int64_t len = (m + 255) / 256, r0 = static_cast<int64_t>(t) * len, r1 = r0 + len < m ? r0 + len : m;
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    double mine = inf;
-    for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, plus_zero(p[r]) / (static_cast<double>(r + 1) / n_d));
+    int64_t r0, r1;
+    fdr_span<int64_t>(m, FDR_THREADS, t, r0, r1);
+    double mine = fdr_inf();
+    for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, fdr_raw(fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d));
     part[t] = mine;
     __syncthreads();
-    double carry = inf;                                             // minimum over everything right of this thread's chunk
-    for (int u = t + 1; u < 256; ++u) carry = fmin(carry, part[u]);
+    double carry = suffix_min(part, t, fdr_inf());                  // minimum over everything right of this thread's chunk
     for (int64_t r = r1 - 1; r >= r0; --r) {
-        carry = fmin(carry, plus_zero(p[r]) / (static_cast<double>(r + 1) / n_d));
-        o[c[r]] = carry > 1.0 ? 1.0 : carry;
+        carry = fmin(carry, fdr_raw(fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d));
+        o[c[r]] = fdr_clamp(carry);
     }
 }
 
 // One workgroup = one row: a block-wide radix sort (hipcub::BlockRadixSort: keys and column ids in registers, LDS
 // for the exchanges) leaves thread t with ranks [t IPT, (t + 1) IPT) of the sorted row -- exactly the chunks the
-// Benjamini-Hochberg pass wants.  Keys are the bit patterns of the p-values after two substitutions: -0.0 becomes +0.0 (key 0;
-// left as 0x8000... it would sort last, and -0.0 / (m / m) would be the running minimum of the whole row) and every NaN, of
-// either sign and any payload, becomes 0x7FF8....  Then positive doubles order like their bits, both zeros sort first as one
-// value and every NaN sorts behind every number, as np.argsort puts them; padding keys are all ones, behind the NaN key, so
-// the ranks below m hold the row and nothing else.  (Negative p-values other than -0.0 are a caller's error: not defined.)
+// Benjamini-Hochberg pass wants.  Keys: fdr_key of the p-values; padding keys are all ones, behind the NaN key, so
+// the ranks below m hold the row and nothing else.
 // (A bitonic network on an LDS copy of the row was tried first: 91 stages x 20 bytes per element = 15 MB of LDS
 // traffic per row, 3.2 ms per 3971 x 4373 matrix.)
 #ifndef FDR_RADIX_BITS
 #define FDR_RADIX_BITS 8
 #endif
 template <int IPT>
-__global__ __launch_bounds__(256) void k_fdr_row_sort(double *__restrict__ pvals, int64_t m) {
-    using BlockSort = hipcub::BlockRadixSort<unsigned long long, 256, IPT, unsigned short, FDR_RADIX_BITS>;
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_sort(double *__restrict__ pvals, int64_t m) {
+    using BlockSort = hipcub::BlockRadixSort<unsigned long long, FDR_THREADS, IPT, unsigned short, FDR_RADIX_BITS>;
     __shared__ typename BlockSort::TempStorage temp;
-    __shared__ double part[256];
+    __shared__ double part[FDR_THREADS];
     __shared__ int has_nan;
     const int t = threadIdx.x;
     double *p = pvals + static_cast<int64_t>(blockIdx.x) * m;
@@ -100,82 +167,59 @@ __global__ __launch_bounds__(256) void k_fdr_row_sort(double *__restrict__ pvals
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
         const int e = t * IPT + i;
-        unsigned long long k = ~0ull;
-        if (e < m) {
-            const double v = p[e];
-            k = v != v ? 0x7FF8000000000000ull : static_cast<unsigned long long>(__double_as_longlong(plus_zero(v)));
-        }
-        key[i] = k;
+        key[i] = e < m ? fdr_key(p[e]) : ~0ull;
         idx[i] = static_cast<unsigned short>(e);
     }
     __syncthreads();
     BlockSort(temp).Sort(key, idx, 0, 64);
-    // the same arithmetic, in the same order, as k_fdr_row; rank of key[i] = t * IPT + i
+    // the same arithmetic, in the same order, as k_fdr_row, on the registers that hold the sorted row; rank of key[i] = t * IPT + i
     const double n_d = static_cast<double>(m);
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
     const int r0 = t * IPT;
-    double mine = inf;
+    double mine = fdr_inf();
     bool nan_here = false;
 #pragma unroll
     for (int i = IPT - 1; i >= 0; --i) {
         if (r0 + i >= m) continue;
-        const double v = __longlong_as_double(static_cast<long long>(key[i]));
+        const double v = fdr_key_value(key[i]);
         nan_here |= v != v;
-        mine = fmin(mine, v / (static_cast<double>(r0 + i + 1) / n_d));
+        mine = fmin(mine, fdr_raw(v, static_cast<double>(r0 + i + 1), n_d));
     }
     part[t] = mine;
     if (nan_here) has_nan = 1;
     __syncthreads();
-    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
     if (has_nan) {                                                  // a NaN anywhere poisons the whole row
-        for (int64_t r = t; r < m; r += 256) p[r] = qnan;
+        for (int64_t r = t; r < m; r += FDR_THREADS) p[r] = fdr_qnan();
         return;
     }
-    double carry = inf;                                             // minimum over everything right of this thread's chunk
-    for (int u = t + 1; u < 256; ++u) carry = fmin(carry, part[u]);
+    double carry = suffix_min(part, t, fdr_inf());                  // minimum over everything right of this thread's chunk
 #pragma unroll
     for (int i = IPT - 1; i >= 0; --i) {
         if (r0 + i >= m) continue;
-        const double v = __longlong_as_double(static_cast<long long>(key[i]));
-        carry = fmin(carry, v / (static_cast<double>(r0 + i + 1) / n_d));
-        p[idx[i]] = carry > 1.0 ? 1.0 : carry;
+        carry = fmin(carry, fdr_raw(fdr_key_value(key[i]), static_cast<double>(r0 + i + 1), n_d));
+        p[idx[i]] = fdr_clamp(carry);
     }
 }
 
+// ------------------------------------------------------------------------------------------------------ the count forms ----
+
 // The same adjustment WITHOUT a sort, for p-values that are counts / num_permutations (the randomization form: every entry is one of
-// P + 1 values).  All members of a tie end up with the value of the tie's LAST sorted position (header above), so a row needs only
-// its histogram over the counts: cum[c] = #entries with count <= c is that last position, raw[c] = (c / P) / (cum[c] / n) the
-// value statsmodels computes there -- the same two divisions on the same doubles -- and adj[c] = min over the occupied c' >= c.
-// One workgroup per row: LDS histogram, block scan, reverse running minimum, one table look-up per entry.  0.9 ms -> HBM speed
-// per matrix at 3971 x 4373.  An entry that is not exactly c / P raises `flag` (the caller then sorts instead).
-__global__ __launch_bounds__(256) void k_fdr_row_counts(double *__restrict__ pvals, int64_t m, int64_t n_perm, unsigned int *__restrict__ flag) {
+// P + 1 values): a row needs only its histogram over the counts (hist_to_table).  One workgroup per row: LDS histogram, the table,
+// one table look-up per entry.  0.9 ms -> HBM speed per matrix at 3971 x 4373.  An entry that is not exactly c / P raises `flag`
+// (the caller then sorts instead).
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_counts(double *__restrict__ pvals, int64_t m, int64_t n_perm, unsigned int *__restrict__ flag) {
     extern __shared__ unsigned char fdr_lds[];
     const int bins = static_cast<int>(n_perm) + 1;
     double *adj = reinterpret_cast<double *>(fdr_lds);                    // [bins]
     unsigned int *hist = reinterpret_cast<unsigned int *>(adj + bins);   // [bins]
-    __shared__ unsigned int part_u[256];
-    __shared__ double part_d[256];
-    __shared__ int bad;
+    __shared__ unsigned int bad;
     const int t = threadIdx.x;
     double *p = pvals + static_cast<int64_t>(blockIdx.x) * m;
-    const double P = static_cast<double>(n_perm), n_d = static_cast<double>(m);
-    for (int c = t; c < bins; c += 256) hist[c] = 0u;
+    const double P = static_cast<double>(n_perm);
+    for (int c = t; c < bins; c += FDR_THREADS) hist[c] = 0u;
     if (t == 0) bad = 0;
     __syncthreads();
-    int mine_bad = 0;                                                     // 1: a NaN (poisons the row), 2: not a count ratio
-    for (int64_t e = t; e < m; e += 256) {
-        const double v = p[e];
-        if (v != v) {
-            mine_bad |= 1;
-            continue;
-        }
-        const double cf = rint(v * P);
-        if (!(cf >= 0.0 && cf <= P) || cf / P != v) {
-            mine_bad |= 2;
-            continue;
-        }
-        atomicAdd(&hist[static_cast<int>(cf)], 1u);
-    }
+    unsigned int mine_bad = 0;                                            // 1: a NaN (poisons the row), 2: not a count ratio
+    for (int64_t e = t; e < m; e += FDR_THREADS) hist_add(hist, p[e], P, mine_bad);
     if (mine_bad) atomicOr(&bad, mine_bad);
     __syncthreads();
     if (bad & 2) {
@@ -183,55 +227,220 @@ __global__ __launch_bounds__(256) void k_fdr_row_counts(double *__restrict__ pva
         return;
     }
     if (bad & 1) {                                                        // np.minimum propagates the NaN through the whole row
-        const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-        for (int64_t e = t; e < m; e += 256) p[e] = qnan;
+        for (int64_t e = t; e < m; e += FDR_THREADS) p[e] = fdr_qnan();
         return;
     }
-    // cum over ascending counts: thread t owns the bins [b0, b1)
-    const int per = (bins + 255) / 256, b0 = t * per < bins ? t * per : bins, b1 = b0 + per < bins ? b0 + per : bins;
-    unsigned int local = 0;
-    for (int c = b0; c < b1; ++c) local += hist[c];
-    part_u[t] = local;
+    hist_to_table(hist, bins, P, static_cast<double>(m), adj);
     __syncthreads();
-    unsigned int before = 0;
-    for (int u = 0; u < t; ++u) before += part_u[u];
-    // raw values of the occupied bins (unoccupied: +inf), then the running minimum from the right
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    double mn = inf;
-    {
-        unsigned int cum = before;
-        for (int c = b0; c < b1; ++c) {
-            const unsigned int h = hist[c];
-            cum += h;
-            adj[c] = h ? (static_cast<double>(c) / P) / (static_cast<double>(cum) / n_d) : inf;
-        }
-        for (int c = b1 - 1; c >= b0; --c) mn = fmin(mn, adj[c]);
-    }
-    part_d[t] = mn;
-    __syncthreads();
-    double carry = inf;
-    for (int u = t + 1; u < 256; ++u) carry = fmin(carry, part_d[u]);
-    for (int c = b1 - 1; c >= b0; --c) {
-        carry = fmin(carry, adj[c]);
-        adj[c] = carry > 1.0 ? 1.0 : carry;
-    }
-    __syncthreads();
-    for (int64_t e = t; e < m; e += 256) p[e] = adj[static_cast<int>(rint(p[e] * P))];
+    for (int64_t e = t; e < m; e += FDR_THREADS) p[e] = adj[static_cast<int>(fdr_count_of(p[e], P))];
 }
 
-// read-only: is every non-NaN entry a count ratio c / P, c in [0, P]?  (what the histogram form needs; anything else is sorted)
-__global__ __launch_bounds__(256) void k_fdr_check_ratio(const double *__restrict__ p, int64_t total, double P, unsigned int *__restrict__ flag) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    bool bad = false;
-    if (i < total) {
-        const double v = p[i];
-        if (v == v) {
-            const double cf = rint(v * P);
-            bad = !(cf >= 0.0 && cf <= P) || cf / P != v;
-        }
-    }
+// read-only: is every non-NaN entry a count ratio c / P, c in [0, P]?  (what the count forms need; anything else is sorted)
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_check_ratio(const double *__restrict__ p, int64_t total, double P, unsigned int *__restrict__ flag) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x;
+    const bool bad = i < total && fdr_ratio_bin(p[i], P) == FDR_BIN_NOT_RATIO;
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
+
+// slot[col][bin]: first the histogram (low word), then -- written by the lane that owns the bin -- the adjusted value
+__global__ __launch_bounds__(FDR_COL_THREADS) void k_fdr_col_counts(double *__restrict__ pvals, int64_t n, int64_t m, int64_t n_perm, int tile,
+                                                        unsigned int *__restrict__ flag) {
+    extern __shared__ unsigned long long col_slot[];
+    __shared__ int col_nan[FDR_COL_TILE_MAX];
+    const int bins = static_cast<int>(n_perm) + 1;
+    const int t = threadIdx.x;
+    const int64_t c0 = static_cast<int64_t>(blockIdx.x) * tile;
+    const int w = static_cast<int>(m - c0 < tile ? m - c0 : tile);
+    // thread t walks column t % w, from row t / w on in steps of FDR_COL_THREADS / w rows: a wave reads whole row segments of the tile
+    const int col = t % w, step = FDR_COL_THREADS / w;
+    const int64_t row0 = t / w < step ? t / w : n;
+    const double P = static_cast<double>(n_perm), n_d = static_cast<double>(n);
+    for (int i = t; i < w * bins; i += FDR_COL_THREADS) col_slot[i] = 0ull;
+    if (t < FDR_COL_TILE_MAX) col_nan[t] = 0;
+    __syncthreads();
+    for (int64_t row = row0; row < n; row += step) {
+        const int bin = fdr_ratio_bin(pvals[row * m + c0 + col], P);
+        if (bin >= 0) atomicAdd(reinterpret_cast<unsigned int *>(&col_slot[col * bins + bin]), 1u);
+        else if (bin == FDR_BIN_NAN) atomicOr(&col_nan[col], 1);
+        else atomicOr(flag, 1u);                                        // (cannot happen: the caller checked the matrix)
+    }
+    __syncthreads();
+    // one wave per column: lane l owns the bins [b0, b1); hist_to_table's scan with wave shuffles in place of the LDS partials
+    const int lane = t & 63;
+    int b0, b1;
+    fdr_span(bins, 64, lane, b0, b1);
+    for (int wc = t >> 6; wc < w; wc += FDR_COL_THREADS / 64) {
+        if (col_nan[wc]) continue;
+        unsigned long long *slot = col_slot + wc * bins;
+        unsigned int local = 0;
+        for (int c = b0; c < b1; ++c) local += static_cast<unsigned int>(slot[c]);
+        unsigned int upto = local;                                      // inclusive sum over the lanes
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int o = __shfl_up(upto, d);
+            if (lane >= d) upto += o;
+        }
+        double mn = fdr_inf();
+        unsigned int cum = upto - local;
+        for (int c = b0; c < b1; ++c) {
+            const unsigned int h = static_cast<unsigned int>(slot[c]);
+            cum += h;
+            const double raw = h ? fdr_raw(static_cast<double>(c) / P, static_cast<double>(cum), n_d) : fdr_inf();
+            slot[c] = static_cast<unsigned long long>(__double_as_longlong(raw));
+            mn = fmin(mn, raw);
+        }
+        double right = mn;                                              // inclusive minimum over the lanes from the right
+        for (int d = 1; d < 64; d <<= 1) {
+            const double o = __shfl_down(right, d);
+            if (lane + d < 64) right = fmin(right, o);
+        }
+        double carry = __shfl_down(right, 1);
+        if (lane == 63) carry = fdr_inf();
+        for (int c = b1 - 1; c >= b0; --c) {
+            carry = fmin(carry, fdr_key_value(slot[c]));
+            slot[c] = static_cast<unsigned long long>(__double_as_longlong(fdr_clamp(carry)));
+        }
+    }
+    __syncthreads();
+    for (int64_t row = row0; row < n; row += step) {
+        double *cell = pvals + row * m + c0 + col;
+        if (col_nan[col]) {                                             // np.minimum carries the NaN through the whole column
+            *cell = fdr_qnan();
+            continue;
+        }
+        const double cf = fdr_count_of(*cell, P);
+        if (!(cf >= 0.0 && cf <= P)) continue;
+        *cell = fdr_key_value(col_slot[col * bins + static_cast<int>(cf)]);
+    }
+}
+
+// flags: 1 = a NaN, 2 = an entry that is no count ratio
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_hist(const double *__restrict__ p, int64_t total, int64_t n_perm,
+                                                              unsigned long long *__restrict__ hist, unsigned int *__restrict__ flags) {
+    extern __shared__ unsigned int all_hist[];
+    const int bins = static_cast<int>(n_perm) + 1;
+    const int t = threadIdx.x;
+    const double P = static_cast<double>(n_perm);
+    for (int c = t; c < bins; c += FDR_THREADS) all_hist[c] = 0u;
+    __syncthreads();
+    unsigned int bad = 0;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + t; i < total; i += static_cast<int64_t>(gridDim.x) * FDR_THREADS)
+        hist_add(all_hist, p[i], P, bad);
+    if (bad) atomicOr(flags, bad);
+    __syncthreads();
+    for (int c = t; c < bins; c += FDR_THREADS)
+        if (all_hist[c]) atomicAdd(&hist[c], static_cast<unsigned long long>(all_hist[c]));
+}
+
+// one workgroup: table[c] = the adjusted value of every entry with count c, from the one histogram in memory
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_table(const unsigned long long *__restrict__ hist, int64_t n_perm, double total_d,
+                                                               double *__restrict__ table) {
+    hist_to_table(hist, static_cast<int>(n_perm) + 1, static_cast<double>(n_perm), total_d, table);
+}
+
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_map(double *__restrict__ p, int64_t total, int64_t n_perm, const double *__restrict__ table,
+                                                             const unsigned int *__restrict__ flags) {
+    const unsigned int f = *flags;
+    if (f & 2u) return;                                                 // (cannot happen: the caller checked the matrix)
+    const double P = static_cast<double>(n_perm);
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * FDR_THREADS)
+        p[i] = (f & 1u) ? fdr_qnan() : table[static_cast<int>(fdr_count_of(p[i], P))];
+}
+
+// -------------------------------------------------------------------------------------------------- columns, sort form ----
+
+// out[c][r] = in[r][c]; one 32 x 32 tile per workgroup, tiles numbered along the columns of `in` first
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_transpose(const double *__restrict__ in, int64_t rows, int64_t cols, double *__restrict__ out) {
+    __shared__ double tile[FDR_TR_TILE][FDR_TR_TILE + 1];
+    const int64_t tiles_c = (cols + FDR_TR_TILE - 1) / FDR_TR_TILE;
+    const int64_t tr = static_cast<int64_t>(blockIdx.x) / tiles_c, tc = static_cast<int64_t>(blockIdx.x) - tr * tiles_c;
+    const int x = threadIdx.x & 31, y = threadIdx.x >> 5;
+    for (int k = y; k < FDR_TR_TILE; k += 8) {
+        const int64_t r = tr * FDR_TR_TILE + k, c = tc * FDR_TR_TILE + x;
+        if (r < rows && c < cols) tile[k][x] = in[r * cols + c];
+    }
+    __syncthreads();
+    for (int k = y; k < FDR_TR_TILE; k += 8) {
+        const int64_t c = tc * FDR_TR_TILE + k, r = tr * FDR_TR_TILE + x;
+        if (r < rows && c < cols) out[c * rows + r] = tile[x][k];
+    }
+}
+
+// --------------------------------------------------------------------------------------------------- matrix, sort form ----
+
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_keys(const double *__restrict__ p, int64_t total, unsigned long long *__restrict__ keys,
+                                                              unsigned int *__restrict__ cells) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x;
+    if (i >= total) return;
+    keys[i] = fdr_key(p[i]);
+    cells[i] = static_cast<unsigned int>(i);
+}
+
+__device__ __forceinline__ double all_raw(const unsigned long long *__restrict__ keys, int64_t r, double total_d) {
+    return fdr_raw(fdr_key_value(keys[r]), static_cast<double>(r + 1), total_d);
+}
+
+// workgroup b: the minimum of the raw values of the sorted ranks [b FDR_ALL_BLOCK, (b + 1) FDR_ALL_BLOCK)
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_blockmin(const unsigned long long *__restrict__ keys, int64_t total, double *__restrict__ blockmin) {
+    __shared__ double part[FDR_THREADS];
+    const int t = threadIdx.x;
+    const double total_d = static_cast<double>(total);
+    const int64_t r0 = static_cast<int64_t>(blockIdx.x) * FDR_ALL_BLOCK + t * FDR_ALL_IPT;
+    double mine = fdr_inf();
+    for (int i = 0; i < FDR_ALL_IPT; ++i)
+        if (r0 + i < total) mine = fmin(mine, all_raw(keys, r0 + i, total_d));
+    part[t] = mine;
+    __syncthreads();
+    for (int s = FDR_THREADS / 2; s > 0; s >>= 1) {
+        if (t < s) part[t] = fmin(part[t], part[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) blockmin[blockIdx.x] = part[0];
+}
+
+// one workgroup: carry[b] = the minimum over every workgroup right of b
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_carry(const double *__restrict__ blockmin, int64_t blocks, double *__restrict__ carry) {
+    __shared__ double part[FDR_THREADS];
+    const int t = threadIdx.x;
+    int64_t b0, b1;
+    fdr_span<int64_t>(blocks, FDR_THREADS, t, b0, b1);
+    double mine = fdr_inf();
+    for (int64_t b = b0; b < b1; ++b) mine = fmin(mine, blockmin[b]);
+    part[t] = mine;
+    __syncthreads();
+    double run = suffix_min(part, t, fdr_inf());
+    for (int64_t b = b1 - 1; b >= b0; --b) {
+        carry[b] = run;
+        run = fmin(run, blockmin[b]);
+    }
+}
+
+// the running minimum from the right inside the workgroup's ranks, joined with carry[b], written to the cells the ranks came from
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_apply(const unsigned long long *__restrict__ keys, const unsigned int *__restrict__ cells,
+                                                               int64_t total, const double *__restrict__ carry, double *__restrict__ out) {
+    __shared__ double part[FDR_THREADS];
+    const int t = threadIdx.x;
+    const double total_d = static_cast<double>(total);
+    const int64_t r0 = static_cast<int64_t>(blockIdx.x) * FDR_ALL_BLOCK + t * FDR_ALL_IPT;
+    // every NaN carries the largest key: the matrix has one iff the last sorted key is one, and then all of it becomes NaN
+    if (keys[total - 1] == FDR_KEY_NAN) {
+        for (int i = 0; i < FDR_ALL_IPT; ++i)
+            if (r0 + i < total) out[cells[r0 + i]] = fdr_qnan();
+        return;
+    }
+    double mine = fdr_inf();
+    for (int i = 0; i < FDR_ALL_IPT; ++i)
+        if (r0 + i < total) mine = fmin(mine, all_raw(keys, r0 + i, total_d));
+    part[t] = mine;
+    __syncthreads();
+    double run = suffix_min(part, t, carry[blockIdx.x]);
+    for (int i = FDR_ALL_IPT - 1; i >= 0; --i) {
+        if (r0 + i >= total) continue;
+        run = fmin(run, all_raw(keys, r0 + i, total_d));
+        out[cells[r0 + i]] = fdr_clamp(run);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- the epilogue ----
 
 // NES / binarisation from (adjusted) p-values; n_perm == 0: hypergeometric form nes = -log10(p_pos)
 __global__ __launch_bounds__(256) void k_nes_from_pvalues(const double *__restrict__ p_neg, const double *__restrict__ p_pos,
@@ -267,147 +476,265 @@ __global__ __launch_bounds__(256) void k_nes_from_pvalues(const double *__restri
 }
 
 __global__ void k_fdr_u32_to_f64(const unsigned int *__restrict__ in, double *__restrict__ out, int64_t count) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x;
     if (i < count) out[i] = static_cast<double>(in[i]);
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------------------- host ----
 
-int fdr_matrix(safe_ctx *ctx, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
-    const char *sort_env = getenv("SAFE_HIP_FDR_SORT");                   // "cub": library sort for every row length (tests); "sort": never the histogram form
-    // randomization form: p-values are counts / n_perm -- no sort needed (k_fdr_row_counts); table + histogram must fit LDS
-    if (n_perm > 0 && (n_perm + 1) * 12 <= 60 * 1024 && !sort_env) {
-        unsigned int *d_flag = nullptr;
-        SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
-        SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
-        const size_t lds = static_cast<size_t>(n_perm + 1) * 12;
-        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_row_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds)));
-        hipLaunchKernelGGL(k_fdr_row_counts, dim3(n), dim3(256), lds, ctx->stream, p_dev, m, n_perm, d_flag);
-        SAFE_HIP_CHECK(hipGetLastError());
-        void *pinned = nullptr;
-        SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), &pinned));
-        SAFE_HIP_CHECK(hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-        if (*static_cast<unsigned int *>(pinned) == 0u) return SAFE_OK;
-        // (cannot happen: safe_fdr_adjust validated the matrix before it chose this form)
-        safe_set_error("safe_fdr_adjust: num_permutations = %lld but a p-value is not a multiple of 1 / num_permutations",
-                       (long long)n_perm);
-        return SAFE_E_VALUE;
-    }
-    if (m <= 8192 && !(sort_env && !strcmp(sort_env, "cub"))) {
-        const int64_t ipt = ceil_div(m, 256);                                // items per thread: the sort pads the row to 256 * IPT
-#define FDR_SORT(I) hipLaunchKernelGGL(k_fdr_row_sort<I>, dim3(n), dim3(256), 0, ctx->stream, p_dev, m)
-        if (ipt <= 4) FDR_SORT(4);
-        else if (ipt <= 8) FDR_SORT(8);
-        else if (ipt <= 12) FDR_SORT(12);
-        else if (ipt <= 16) FDR_SORT(16);
-        else if (ipt <= 20) FDR_SORT(20);
-        else if (ipt <= 24) FDR_SORT(24);
-        else if (ipt <= 28) FDR_SORT(28);
-        else FDR_SORT(32);
-#undef FDR_SORT
-        SAFE_HIP_CHECK(hipGetLastError());
-        SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-        return SAFE_OK;
-    }
-    // rows per batch: at most 2^27 keys per library call (temporaries ~ 3 GB)
-    const int64_t batch_rows = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(1) << 27) / std::max<int64_t>(m, 1)));
-    const int64_t batch_items = batch_rows * m;
-    SAFE_REQUIRE(m < (int64_t(1) << 31) - 1 && batch_items < (int64_t(1) << 31), "safe_fdr_adjust: %lld attributes per row are too many",
-                 (long long)m);
-    double *keys_out = nullptr;
-    int32_t *vals_in = nullptr, *vals_out = nullptr;
-    int64_t *offsets = nullptr;
-    uint8_t *temp = nullptr;
-    size_t temp_bytes = 0;
-    const char *fn = "safe_fdr_adjust";
-    CallBufs b;
-    SAFE_TRY(b.alloc(&keys_out, batch_items));
-    SAFE_TRY(b.alloc(&vals_in, batch_items));
-    SAFE_TRY(b.alloc(&vals_out, batch_items));
-    SAFE_TRY(b.alloc(&offsets, batch_rows + 1));
-    hipLaunchKernelGGL(k_fdr_cols, dim3(ceil_div(batch_items, 256)), dim3(256), 0, ctx->stream, vals_in, batch_items, m);
-    hipLaunchKernelGGL(k_fdr_offsets, dim3(ceil_div(batch_rows + 1, 256)), dim3(256), 0, ctx->stream, offsets, batch_rows, m);
-    SAFE_HIP_CHECK_AS(fn, hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, p_dev, keys_out, vals_in, vals_out,
-                                                                      static_cast<int>(batch_items), static_cast<int>(batch_rows),
-                                                                      offsets, offsets + 1, 0, 64, ctx->stream));
-    SAFE_TRY(b.alloc(&temp, std::max<size_t>(temp_bytes, 16)));
-    for (int64_t r0 = 0; r0 < n; r0 += batch_rows) {
-        const int64_t rows = std::min<int64_t>(batch_rows, n - r0);
-        double *block = p_dev + r0 * m;
-        SAFE_HIP_CHECK_AS(fn, hipcub::DeviceSegmentedRadixSort::SortPairs(temp, temp_bytes, block, keys_out, vals_in, vals_out,
-                                                                          static_cast<int>(rows * m), static_cast<int>(rows), offsets,
-                                                                          offsets + 1, 0, 64, ctx->stream));
-        hipLaunchKernelGGL(k_fdr_row, dim3(rows), dim3(256), 0, ctx->stream, keys_out, vals_out, m, block);
-        SAFE_HIP_CHECK_AS(fn, hipGetLastError());
-    }
-    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
-    return SAFE_OK;
-}
-
-int fdr_all_count_ratios(safe_ctx *ctx, const double *const *mats, int n_mats, int64_t total, int64_t n_perm, bool *all) {
-    unsigned int *d_flag = nullptr;
-    SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
-    for (int k = 0; k < n_mats; ++k)
-        hipLaunchKernelGGL(k_fdr_check_ratio, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, mats[k], total,
-                           static_cast<double>(n_perm), d_flag);
-    SAFE_HIP_CHECK(hipGetLastError());
-    void *pinned = nullptr;
-    SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), &pinned));
-    SAFE_HIP_CHECK(hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    SAFE_HIP_CHECK(safe_stream_sync(ctx->stream));
-    *all = *static_cast<unsigned int *>(pinned) == 0u;
-    return SAFE_OK;
-}
-
-int fdr_nes_epilogue(safe_ctx *ctx, const char *who, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
-                     double enrichment_threshold, const double *pvalues_neg_dev, const double *pvalues_pos_dev, double *nes_dev,
-                     double *nes_binary_dev, double *num_enriched_dev) {
-    CallBufs b;
-    unsigned int *d_enr = nullptr;
-    SAFE_TRY(b.alloc(&d_enr, m));
-    SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, m * sizeof(unsigned int), ctx->stream));
-    hipLaunchKernelGGL(k_nes_from_pvalues, dim3(ceil_div(m, 64), ceil_div(n, 64)), dim3(256), 0, ctx->stream, pvalues_neg_dev,
-                       pvalues_pos_dev, n, m, num_permutations > 0 ? 1.0 / static_cast<double>(num_permutations) : 0.0, sign_mode,
-                       -std::log10(enrichment_threshold), nes_p_cut(enrichment_threshold), nes_dev, nes_binary_dev, d_enr);
-    hipLaunchKernelGGL(k_fdr_u32_to_f64, dim3(ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_enr, num_enriched_dev, m);
+// the end of every form: its launches are checked and the stream has drained
+int drained(safe_ctx *ctx, const char *who) {
     SAFE_HIP_CHECK_AS(who, hipGetLastError());
     SAFE_HIP_CHECK_AS(who, safe_stream_sync(ctx->stream));
     return SAFE_OK;
 }
 
+// the u32 at d_flag, read once the launches before it are checked and the stream has drained
+int read_flag(safe_ctx *ctx, const char *who, const unsigned int *d_flag, unsigned int *value) {
+    void *pinned = nullptr;
+    SAFE_TRY(ctx_pinned(ctx, sizeof(unsigned int), &pinned));
+    SAFE_HIP_CHECK(hipMemcpyAsync(pinned, d_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    SAFE_TRY(drained(ctx, who));
+    *value = *static_cast<unsigned int *>(pinned);
+    return SAFE_OK;
+}
+
+// ... of the context's flag, zeroed for the kernels `launch(flag)` starts
+template <typename Launch>
+int with_flag(safe_ctx *ctx, const char *who, Launch launch, unsigned int *value) {
+    unsigned int *d_flag = nullptr;
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_FLAG, sizeof(unsigned int), reinterpret_cast<void **>(&d_flag)));
+    SAFE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), ctx->stream));
+    launch(d_flag);
+    return read_flag(ctx, who, d_flag, value);
+}
+
+// the end of a count form: `bad` is what its kernels left in the flag (cannot happen: the entry point validated the matrix before
+// it chose the form)
+int count_form_done(const char *who, unsigned int bad, int64_t n_perm) {
+    if (!bad) return SAFE_OK;
+    safe_set_error("%s: a p-value is not a multiple of 1 / %lld", who, (long long)n_perm);
+    return SAFE_E_VALUE;
+}
+
+template <int K = 0>
+void launch_row_sort(int ipt, hipStream_t stream, double *p_dev, int64_t n, int64_t m) {
+    if constexpr (K < FDR_IPT_RUNGS) {
+        if (ipt == FDR_IPT_LADDER[K]) hipLaunchKernelGGL(k_fdr_row_sort<FDR_IPT_LADDER[K]>, dim3(n), dim3(FDR_THREADS), 0, stream, p_dev, m);
+        else launch_row_sort<K + 1>(ipt, stream, p_dev, n, m);
+    }
+}
+
+// Benjamini-Hochberg on every row of p_dev (f64 [n, m] row-major) in place, in the row form `kind` of f.  n_perm: the count
+// denominator of the histogram form.  The stream has drained when it returns.
+int adjust_rows(safe_ctx *ctx, const char *who, FdrKind kind, const FdrForm &f, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
+    if (kind == FDR_ROW_HIST) {
+        unsigned int bad = 0;
+        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_row_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(f.lds_bytes)));
+        SAFE_TRY(with_flag(ctx, who, [&](unsigned int *flag) {
+            hipLaunchKernelGGL(k_fdr_row_counts, dim3(n), dim3(FDR_THREADS), f.lds_bytes, ctx->stream, p_dev, m, n_perm, flag);
+        }, &bad));
+        return count_form_done(who, bad, n_perm);
+    }
+    if (kind == FDR_ROW_BLOCK_SORT) {
+        launch_row_sort(f.ipt, ctx->stream, p_dev, n, m);
+        return drained(ctx, who);
+    }
+    SAFE_REQUIRE(kind == FDR_ROW_LIBRARY_SORT, "%s: %lld attributes per row are too many", who, (long long)m);
+    const int64_t batch_rows = f.batch_rows, batch_items = batch_rows * m;
+    double *keys_out = nullptr;
+    int32_t *vals_in = nullptr, *vals_out = nullptr;
+    int64_t *offsets = nullptr;
+    uint8_t *temp = nullptr;
+    size_t temp_bytes = 0;
+    CallBufs b;
+    SAFE_TRY(b.alloc(&keys_out, batch_items));
+    SAFE_TRY(b.alloc(&vals_in, batch_items));
+    SAFE_TRY(b.alloc(&vals_out, batch_items));
+    SAFE_TRY(b.alloc(&offsets, batch_rows + 1));
+    hipLaunchKernelGGL(k_fdr_cols, dim3(ceil_div(batch_items, FDR_THREADS)), dim3(FDR_THREADS), 0, ctx->stream, vals_in, batch_items, m);
+    hipLaunchKernelGGL(k_fdr_offsets, dim3(ceil_div(batch_rows + 1, FDR_THREADS)), dim3(FDR_THREADS), 0, ctx->stream, offsets, batch_rows, m);
+    SAFE_HIP_CHECK_AS(who, hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, temp_bytes, p_dev, keys_out, vals_in, vals_out,
+                                                                       static_cast<int>(batch_items), static_cast<int>(batch_rows),
+                                                                       offsets, offsets + 1, 0, 64, ctx->stream));
+    SAFE_TRY(b.alloc(&temp, std::max<size_t>(temp_bytes, 16)));
+    for (int64_t r0 = 0; r0 < n; r0 += batch_rows) {
+        const int64_t rows = std::min<int64_t>(batch_rows, n - r0);
+        double *block = p_dev + r0 * m;
+        SAFE_HIP_CHECK_AS(who, hipcub::DeviceSegmentedRadixSort::SortPairs(temp, temp_bytes, block, keys_out, vals_in, vals_out,
+                                                                           static_cast<int>(rows * m), static_cast<int>(rows), offsets,
+                                                                           offsets + 1, 0, 64, ctx->stream));
+        hipLaunchKernelGGL(k_fdr_row, dim3(rows), dim3(FDR_THREADS), 0, ctx->stream, keys_out, vals_out, m, block);
+        SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    }
+    return drained(ctx, who);
+}
+
+int adjust_cols_counts(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
+    unsigned int bad = 0;
+    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_col_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(f.lds_bytes)));
+    SAFE_TRY(with_flag(ctx, who, [&](unsigned int *flag) {
+        hipLaunchKernelGGL(k_fdr_col_counts, dim3(ceil_div(m, f.tile)), dim3(FDR_COL_THREADS), f.lds_bytes, ctx->stream, p_dev, n, m, n_perm,
+                           f.tile, flag);
+    }, &bad));
+    return count_form_done(who, bad, n_perm);
+}
+
+int adjust_cols_sort(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t n, int64_t m) {
+    CallBufs b;
+    double *t_dev = nullptr;
+    SAFE_TRY(b.alloc(&t_dev, n * m));
+    const int64_t tiles = ceil_div(n, FDR_TR_TILE) * ceil_div(m, FDR_TR_TILE);
+    hipLaunchKernelGGL(k_fdr_transpose, dim3(tiles), dim3(FDR_THREADS), 0, ctx->stream, p_dev, n, m, t_dev);
+    SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    SAFE_TRY(adjust_rows(ctx, who, f.row_kind, f, t_dev, m, n, 0));
+    hipLaunchKernelGGL(k_fdr_transpose, dim3(tiles), dim3(FDR_THREADS), 0, ctx->stream, t_dev, m, n, p_dev);
+    return drained(ctx, who);
+}
+
+int adjust_all_counts(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t total, int64_t n_perm) {
+    const int64_t bins = n_perm + 1;
+    unsigned long long *hist = nullptr;                              // [bins], then the table f64 [bins], then the u32 flags
+    SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_SCOPE, static_cast<size_t>(bins) * 16 + 16, reinterpret_cast<void **>(&hist)));
+    double *table = reinterpret_cast<double *>(hist + bins);
+    unsigned int *flags = reinterpret_cast<unsigned int *>(table + bins), bad = 0;
+    SAFE_HIP_CHECK(hipMemsetAsync(hist, 0, static_cast<size_t>(bins) * 16 + 16, ctx->stream));       // (one fill for all three)
+    const int64_t grid = std::min<int64_t>(ceil_div(total, FDR_THREADS), 2048);
+    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_all_hist), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(f.lds_bytes)));
+    hipLaunchKernelGGL(k_fdr_all_hist, dim3(grid), dim3(FDR_THREADS), f.lds_bytes, ctx->stream, p_dev, total, n_perm, hist, flags);
+    hipLaunchKernelGGL(k_fdr_all_table, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, hist, n_perm, static_cast<double>(total), table);
+    hipLaunchKernelGGL(k_fdr_all_map, dim3(grid), dim3(FDR_THREADS), 0, ctx->stream, p_dev, total, n_perm, table, flags);
+    SAFE_TRY(read_flag(ctx, who, flags, &bad));
+    return count_form_done(who, bad & 2u, n_perm);
+}
+
+int adjust_all_sort(safe_ctx *ctx, const char *who, double *p_dev, int64_t total) {
+    CallBufs b;
+    unsigned long long *keys_in = nullptr, *keys_out = nullptr;
+    unsigned int *cells_in = nullptr, *cells_out = nullptr;
+    double *blockmin = nullptr, *carry = nullptr;
+    uint8_t *temp = nullptr;
+    size_t temp_bytes = 0;
+    const int64_t blocks = ceil_div(total, FDR_ALL_BLOCK);
+    SAFE_TRY(b.alloc(&keys_in, total));
+    SAFE_TRY(b.alloc(&keys_out, total));
+    SAFE_TRY(b.alloc(&cells_in, total));
+    SAFE_TRY(b.alloc(&cells_out, total));
+    SAFE_TRY(b.alloc(&blockmin, blocks));
+    SAFE_TRY(b.alloc(&carry, blocks));
+    SAFE_HIP_CHECK_AS(who, hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys_in, keys_out, cells_in, cells_out,
+                                                              static_cast<int>(total), 0, 64, ctx->stream));
+    SAFE_TRY(b.alloc(&temp, std::max<size_t>(temp_bytes, 16)));
+    hipLaunchKernelGGL(k_fdr_all_keys, dim3(ceil_div(total, FDR_THREADS)), dim3(FDR_THREADS), 0, ctx->stream, p_dev, total, keys_in, cells_in);
+    SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    SAFE_HIP_CHECK_AS(who, hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, cells_in, cells_out,
+                                                              static_cast<int>(total), 0, 64, ctx->stream));
+    hipLaunchKernelGGL(k_fdr_all_blockmin, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, total, blockmin);
+    hipLaunchKernelGGL(k_fdr_all_carry, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, blockmin, blocks, carry);
+    hipLaunchKernelGGL(k_fdr_all_apply, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, cells_out, total, carry, p_dev);
+    return drained(ctx, who);
+}
+
+// One matrix along `scope`, in place: the form from fdr_plan.h, then its launches.  hist_perm > 0: every entry is a count ratio
+// c / hist_perm (checked).  The stream has drained when it returns.
+int adjust_matrix(safe_ctx *ctx, const char *who, FdrSwitch sw, int scope, double *p_dev, int64_t n, int64_t m, int64_t hist_perm) {
+    const FdrForm f = fdr_form(scope, n, m, hist_perm, sw);
+    switch (f.kind) {
+    case FDR_UNSUPPORTED:
+        safe_set_error("%s: %lld x %lld p-values as one family are beyond the library sort (2^31 items)", who, (long long)n, (long long)m);
+        return SAFE_E_UNSUPPORTED;
+    case FDR_COL_COUNTS: return adjust_cols_counts(ctx, who, f, p_dev, n, m, hist_perm);
+    case FDR_COL_SORT: return adjust_cols_sort(ctx, who, f, p_dev, n, m);
+    case FDR_ALL_COUNTS: return adjust_all_counts(ctx, who, f, p_dev, n * m, hist_perm);
+    case FDR_ALL_SORT: return adjust_all_sort(ctx, who, p_dev, n * m);
+    default: return adjust_rows(ctx, who, f.kind, f, p_dev, n, m, hist_perm);
+    }
+}
+
+// What an entry point asks for: the matrices pos (and neg, in the randomization form of the entry points with an epilogue) of
+// f64 [n, m] adjusted in place along `scope`; nes != NULL: then nes, nes_binary and the per-attribute counts from the adjusted values.
+struct FdrCall {
+    const char *who;               // the entry point, for error texts
+    int bad_arguments;             // its code for them: SAFE_E_INVALID (safe_fdr_adjust, _rows) or SAFE_E_VALUE (_scope, _matrix)
+    bool epilogue;
+    int64_t n, m, n_perm;
+    int scope, sign_mode;
+    double enrichment_threshold;
+    double *neg, *pos, *nes, *nes_binary, *num_enriched;
+};
+
+// (SAFE_REQUIRE: SAFE_E_INVALID, which run turns into the entry point's own code)
+int validate(const safe_ctx *ctx, const FdrCall &c) {
+    SAFE_REQUIRE(ctx && c.pos && (!c.epilogue || (c.nes && c.nes_binary && c.num_enriched)), "%s: NULL argument", c.who);
+    SAFE_REQUIRE(c.n >= 1 && c.m >= 1 && c.n_perm >= 0, "%s: bad sizes", c.who);
+    if (c.epilogue) {
+        SAFE_REQUIRE(c.n_perm == 0 || c.neg, "%s: the randomization form needs pvalues_neg", c.who);
+        SAFE_REQUIRE(c.sign_mode >= SAFE_SIGN_HIGHEST && c.sign_mode <= SAFE_SIGN_BOTH, "%s: bad sign_mode %d", c.who, c.sign_mode);
+        SAFE_REQUIRE(c.enrichment_threshold > 0.0 && c.enrichment_threshold < 1.0, "%s: enrichment_threshold must be in (0,1)", c.who);
+    }
+    SAFE_REQUIRE(c.scope >= SAFE_FDR_SCOPE_ROWS && c.scope <= SAFE_FDR_SCOPE_ALL, "%s: bad scope %d", c.who, c.scope);
+    return SAFE_OK;
+}
+
+// The body of the four entry points.  The library's own empirical p-values are count ratios c / num_permutations and need no
+// sort.  A caller may hand over other values with num_permutations > 0 (only the 0 -> 1 / P rule of the NES depends on it): where
+// a count form exists the matrices are checked READ-ONLY first (k_fdr_check_ratio), and one entry of either that is not a count
+// ratio sends both through the sort, like the hypergeometric form.  A refusal writes nothing.
+int run(safe_ctx *ctx, const FdrCall &c) {
+    if (validate(ctx, c) != SAFE_OK) return c.bad_arguments;
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    const FdrSwitch sw = fdr_switch(getenv("SAFE_HIP_FDR_SORT"));
+    const int n_mats = c.epilogue && c.n_perm > 0 ? 2 : 1;             // the randomization form: pvalues_neg, then pvalues_pos
+    double *mats[2] = {n_mats == 2 ? c.neg : c.pos, c.pos};
+    int64_t hist_perm = 0;
+    if (fdr_count_form_exists(c.scope, c.n_perm, sw)) {
+        unsigned int bad = 0;
+        SAFE_TRY(with_flag(ctx, c.who, [&](unsigned int *flag) {
+            for (int k = 0; k < n_mats; ++k)
+                hipLaunchKernelGGL(k_fdr_check_ratio, dim3(ceil_div(c.n * c.m, FDR_THREADS)), dim3(FDR_THREADS), 0, ctx->stream, mats[k],
+                                   c.n * c.m, static_cast<double>(c.n_perm), flag);
+        }, &bad));
+        if (!bad) hist_perm = c.n_perm;
+    }
+    for (int k = 0; k < n_mats; ++k) SAFE_TRY(adjust_matrix(ctx, c.who, sw, c.scope, mats[k], c.n, c.m, hist_perm));
+    if (!c.epilogue) return SAFE_OK;
+    CallBufs b;
+    unsigned int *d_enr = nullptr;
+    SAFE_TRY(b.alloc(&d_enr, c.m));
+    SAFE_HIP_CHECK(hipMemsetAsync(d_enr, 0, c.m * sizeof(unsigned int), ctx->stream));
+    hipLaunchKernelGGL(k_nes_from_pvalues, dim3(ceil_div(c.m, 64), ceil_div(c.n, 64)), dim3(256), 0, ctx->stream, c.neg, c.pos, c.n, c.m,
+                       c.n_perm > 0 ? 1.0 / static_cast<double>(c.n_perm) : 0.0, c.sign_mode, -std::log10(c.enrichment_threshold),
+                       nes_p_cut(c.enrichment_threshold), c.nes, c.nes_binary, d_enr);
+    hipLaunchKernelGGL(k_fdr_u32_to_f64, dim3(ceil_div(c.m, FDR_THREADS)), dim3(FDR_THREADS), 0, ctx->stream, d_enr, c.num_enriched, c.m);
+    return drained(ctx, c.who);
+}
+
+}  // namespace
+
 extern "C" int safe_fdr_adjust(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
                                double enrichment_threshold, double *pvalues_neg_dev, double *pvalues_pos_dev, double *nes_dev,
                                double *nes_binary_dev, double *num_enriched_dev) {
-    SAFE_REQUIRE(ctx && pvalues_pos_dev && nes_dev && nes_binary_dev && num_enriched_dev, "safe_fdr_adjust: NULL argument");
-    SAFE_REQUIRE(n >= 1 && m >= 1 && num_permutations >= 0, "safe_fdr_adjust: bad sizes");
-    SAFE_REQUIRE(num_permutations == 0 || pvalues_neg_dev, "safe_fdr_adjust: the randomization form needs pvalues_neg");
-    SAFE_REQUIRE(sign_mode >= SAFE_SIGN_HIGHEST && sign_mode <= SAFE_SIGN_BOTH, "safe_fdr_adjust: bad sign_mode %d", sign_mode);
-    SAFE_REQUIRE(enrichment_threshold > 0.0 && enrichment_threshold < 1.0, "safe_fdr_adjust: enrichment_threshold must be in (0,1)");
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    // The library's own empirical p-values are count ratios c / num_permutations and need no sort (k_fdr_row_counts).  A caller may
-    // hand over other values with num_permutations > 0 (only the 0 -> 1 / P rule of the NES depends on it): both matrices are
-    // checked READ-ONLY first, and anything that is not a count ratio goes through the sort like the hypergeometric form.
-    int64_t hist_perm = 0;
-    if (num_permutations > 0 && (num_permutations + 1) * 12 <= 60 * 1024 && !getenv("SAFE_HIP_FDR_SORT")) {
-        const double *mats[2] = {pvalues_neg_dev, pvalues_pos_dev};
-        bool all = false;
-        SAFE_TRY(fdr_all_count_ratios(ctx, mats, 2, n * m, num_permutations, &all));
-        if (all) hist_perm = num_permutations;
-    }
-    if (num_permutations > 0) SAFE_TRY(fdr_matrix(ctx, pvalues_neg_dev, n, m, hist_perm));
-    SAFE_TRY(fdr_matrix(ctx, pvalues_pos_dev, n, m, hist_perm));
-    return fdr_nes_epilogue(ctx, "safe_fdr_adjust", n, m, num_permutations, sign_mode, enrichment_threshold, pvalues_neg_dev, pvalues_pos_dev,
-                            nes_dev, nes_binary_dev, num_enriched_dev);
+    return run(ctx, {"safe_fdr_adjust", SAFE_E_INVALID, true, n, m, num_permutations, SAFE_FDR_SCOPE_ROWS, sign_mode, enrichment_threshold,
+                     pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, num_enriched_dev});
 }
 
-// Benjamini-Hochberg on every row of one matrix, in place: fdr_matrix's sort form (what safe_fdr_adjust with
-// num_permutations = 0 does to pvalues_pos), without the NES epilogue
+// Benjamini-Hochberg on every row of one matrix, in place: the sort form (what safe_fdr_adjust with num_permutations = 0 does to
+// pvalues_pos), without the NES epilogue
 extern "C" int safe_fdr_adjust_rows(safe_ctx *ctx, int64_t n, int64_t m, double *p_dev) {
-    SAFE_REQUIRE(ctx && p_dev, "safe_fdr_adjust_rows: NULL argument");
-    SAFE_REQUIRE(n >= 1 && m >= 1, "safe_fdr_adjust_rows: bad sizes");
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    return fdr_matrix(ctx, p_dev, n, m);
+    return run(ctx, {"safe_fdr_adjust_rows", SAFE_E_INVALID, false, n, m, 0, SAFE_FDR_SCOPE_ROWS, 0, 0.0, nullptr, p_dev, nullptr, nullptr, nullptr});
+}
+
+extern "C" int safe_fdr_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
+                                     double enrichment_threshold, int scope, double *pvalues_neg_dev, double *pvalues_pos_dev,
+                                     double *nes_dev, double *nes_binary_dev, double *num_enriched_dev) {
+    return run(ctx, {"safe_fdr_adjust_scope", SAFE_E_VALUE, true, n, m, num_permutations, scope, sign_mode, enrichment_threshold,
+                     pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, num_enriched_dev});
+}
+
+extern "C" int safe_fdr_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int64_t count_denominator, double *p_dev) {
+    return run(ctx, {"safe_fdr_adjust_matrix", SAFE_E_VALUE, false, n, m, count_denominator, scope, 0, 0.0, nullptr, p_dev, nullptr, nullptr,
+                     nullptr});
 }

@@ -999,13 +999,10 @@ class SAFE:
 
     def _fdr_adjust(self, ctx, n, m, num_permutations, out_ptrs):
         """multiple_testing on the randomization and the upper-tail hypergeometric route: Benjamini-Hochberg along
-        multiple_testing_scope, then nes, nes_binary and the counts from the adjusted values.  'attributes' is the call the
-        reference's behaviour has always gone through (backend.fdr_adjust)."""
-        if self.multiple_testing_scope == 'attributes':
-            be.fdr_adjust(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold, out_ptrs)
-        else:
-            be.fdr_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
-                                self.multiple_testing_scope, out_ptrs)
+        multiple_testing_scope, then nes, nes_binary and the counts from the adjusted values.  The library chooses the form of
+        every scope; 'attributes' gives the bytes of backend.fdr_adjust, the reference's behaviour."""
+        be.fdr_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
+                            self.multiple_testing_scope, out_ptrs)
 
     def compute_pvalues_by_randomization(self, _attr=None, **kwargs):
         """safepy/safe.py:474-554 (no 1 s sleep, no multiprocessing split: `processes` is
@@ -1154,10 +1151,7 @@ class SAFE:
                 if self.verbose:
                     logging.info('Running FDR-adjustment of p-values...')
                 for b in bufs[1:3]:
-                    if self.multiple_testing_scope == 'attributes':
-                        be.fdr_adjust_rows(ctx, n, m, b.ptr)
-                    else:
-                        be.fdr_adjust_matrix(ctx, n, m, self.multiple_testing_scope, b.ptr)
+                    be.fdr_adjust_matrix(ctx, n, m, self.multiple_testing_scope, b.ptr)
                 be.hypergeom_outputs(ctx, n, m, self.attribute_sign, self.enrichment_threshold, bufs[1].ptr, bufs[2].ptr,
                                      [b.ptr for b in bufs[3:]])
             enriched = bufs[5].download((m,))

@@ -1,6 +1,7 @@
-"""Designed p-value rows, count matrices and the dispatch constants of safepy_amd/csrc/fdr.hip, shared by
-tests/test_fdr_cases_cpu.py and tests/test_gpu_fdr.py.  Host only.  The reference of everything built here is
-oracle.safe_oracle.fdrcorrection / fdr_rows (pinned to statsmodels on the bits by tests/test_oracle_golden.py).
+"""Designed p-value rows, count matrices and the dispatch constants of safepy_amd/csrc/fdr.hip (chosen in fdr_plan.h; pinned to
+what that header answers by tests/test_fdr_cases_cpu.py), shared by tests/test_fdr_cases_cpu.py and tests/test_gpu_fdr.py.
+Host only.  The reference of everything built here is oracle.safe_oracle.fdrcorrection / fdr_rows (pinned to statsmodels on
+the bits by tests/test_oracle_golden.py).
 
 fdr.hip adjusts a row in one of three forms:
   block sort    k_fdr_row_sort<IPT>: 256 threads, thread t holds the sorted ranks [t IPT, (t + 1) IPT); rows of up to
@@ -19,11 +20,11 @@ import numpy as np
 
 from oracle import safe_oracle as orc
 
-THREADS = 256                               # fdr.hip: __launch_bounds__(256), part[256], `t * IPT + i`, `(m + 255) / 256`
-IPT_LADDER = (4, 8, 12, 16, 20, 24, 28, 32)  # fdr.hip, fdr_matrix: `if (ipt <= 4) FDR_SORT(4); ... else FDR_SORT(32);`
-BLOCK_SORT_MAX = 8192                       # fdr.hip, fdr_matrix: `if (m <= 8192 && ...` = 256 * IPT_LADDER[-1]
-HIST_BYTES_PER_BIN = 12                     # fdr.hip, fdr_matrix: `(n_perm + 1) * 12 <= 60 * 1024` (f64 table + u32 histogram)
-HIST_LDS_BYTES = 60 * 1024                  # the same line
+THREADS = 256                               # fdr_plan.h: FDR_THREADS (part[], `t * IPT + i`, the parts of fdr_span)
+IPT_LADDER = (4, 8, 12, 16, 20, 24, 28, 32)  # fdr_plan.h: FDR_IPT_LADDER, the rung chosen by fdr_row_form
+BLOCK_SORT_MAX = 8192                       # fdr_plan.h: FDR_BLOCK_SORT_MAX = 256 * IPT_LADDER[-1]
+HIST_BYTES_PER_BIN = 12                     # fdr_plan.h: FDR_ROW_HIST_BIN_BYTES (f64 table + u32 histogram)
+HIST_LDS_BYTES = 60 * 1024                  # fdr_plan.h: FDR_ROW_HIST_LDS_BYTES
 HIST_MAX_P = HIST_LDS_BYTES // HIST_BYTES_PER_BIN - 1      # 5119
 
 CHAIN_THREADS = (0, 1, 127, 254, 255)       # the threads whose chunk gets the row's single minimum
@@ -41,7 +42,7 @@ def ipt_for(m):
 
 
 def chunk(m, form):
-    """Sorted ranks per thread: IPT (form 'block') or ceil(m / 256) (form 'library')."""
+    """Sorted ranks per thread: IPT (form 'block') or ceil(m / 256) (form 'library': fdr_plan.h, fdr_span over m)."""
     if form == 'block':
         assert ipt_for(m) is not None, m
         return ipt_for(m)
@@ -78,7 +79,7 @@ def hist_id(P):
 
 
 def hist_bins(P, t):
-    """The bins [b0, b1) of thread t in k_fdr_row_counts (fdr.hip: `per = (bins + 255) / 256`)."""
+    """The bins [b0, b1) of thread t in k_fdr_row_counts (fdr_plan.h: fdr_span over P + 1 bins and 256 parts)."""
     bins = P + 1
     per = -(-bins // THREADS)
     return min(t * per, bins), min(t * per + per, bins)

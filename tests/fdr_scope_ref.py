@@ -1,11 +1,12 @@
-"""multiple_testing_scope on the host: the constants safepy_amd/csrc/fdr_scope.hip dispatches on, NumPy restatements of its two
-count forms, and the designed matrices shared by tests/test_fdr_scope_cpu.py, tests/test_gpu_fdr_scope.py and
-tests/test_gpu_fdr_scope_api.py.  The reference of everything is oracle.safe_oracle.fdrcorrection (pinned to statsmodels on the
-bits by tests/test_oracle_golden.py): along axis 0 for the column scope, on the ravelled matrix for the whole-matrix scope.
+"""multiple_testing_scope on the host: the constants safepy_amd/csrc/fdr_plan.h chooses the column and whole-matrix forms of
+fdr.hip by (pinned to what the header answers by tests/test_fdr_scope_cpu.py), NumPy restatements of the two count forms, and
+the designed matrices shared by tests/test_fdr_scope_cpu.py, tests/test_gpu_fdr_scope.py and tests/test_gpu_fdr_scope_api.py.
+The reference of everything is oracle.safe_oracle.fdrcorrection (pinned to statsmodels on the bits by
+tests/test_oracle_golden.py): along axis 0 for the column scope, on the ravelled matrix for the whole-matrix scope.
 
-fdr_scope.hip adjusts
+fdr.hip adjusts
   a column   from its histogram over the counts (k_fdr_col_counts: a workgroup owns col_tile(P) adjacent columns, P <= COL_HIST_MAX_P),
-             or as a row of the transposed matrix (k_fdr_transpose in TR_TILE x TR_TILE tiles, then fdr.hip's row forms);
+             or as a row of the transposed matrix (k_fdr_transpose in TR_TILE x TR_TILE tiles, then the row forms);
   the matrix from one histogram (k_fdr_all_hist / _table / _map, P <= ALL_HIST_MAX_P), or from one sort: workgroup b of the
              suffix-minimum kernels owns the sorted ranks [b ALL_BLOCK, (b + 1) ALL_BLOCK), its thread t the ALL_IPT ranks from
              b ALL_BLOCK + t ALL_IPT on; k_fdr_all_carry joins the workgroups.
@@ -19,7 +20,7 @@ from oracle import safe_oracle as orc
 
 SCOPES = {'attributes': 0, 'neighborhoods': 1, 'all': 2}     # SAFE_FDR_SCOPE_ROWS / _COLS / _ALL
 
-COL_LDS_BYTES = 128 * 1024                  # fdr_scope.hip: FDR_COL_LDS_BYTES
+COL_LDS_BYTES = 128 * 1024                  # fdr_plan.h: FDR_COL_LDS_BYTES
 COL_TILE_MAX = 16                           # FDR_COL_TILE_MAX
 COL_TILE_MIN = 4                            # FDR_COL_TILE_MIN
 COL_HIST_MAX_P = COL_LDS_BYTES // (8 * COL_TILE_MIN) - 1     # 4095
@@ -30,7 +31,7 @@ ALL_BLOCK = 256 * ALL_IPT                   # FDR_ALL_BLOCK
 
 
 def col_tile(P):
-    """Columns per workgroup of k_fdr_col_counts (scope_cols_counts: `min(FDR_COL_TILE_MAX, FDR_COL_LDS_BYTES / (8 * bins))`)."""
+    """Columns per workgroup of k_fdr_col_counts (fdr_plan.h: fdr_col_tile)."""
     return min(COL_TILE_MAX, COL_LDS_BYTES // (8 * (P + 1)))
 
 

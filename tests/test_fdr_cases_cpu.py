@@ -1,51 +1,111 @@
-"""tests/fdr_cases.py on the host: the constants it mirrors are still the ones safepy_amd/csrc/fdr.hip dispatches on (a change
-of the dispatch fails here until the shapes are revisited), every designed length reaches the kernel it is meant for, and the
-designed rows have the properties they claim when pushed through oracle.safe_oracle.fdrcorrection.  No GPU."""
-import os
-import re
-
+"""tests/fdr_cases.py on the host: the constants it mirrors are still the ones safepy_amd/csrc/fdr_plan.h dispatches on -- asked of
+the header itself, built for the host and run as a program (tests/fdr_plan_driver.py); a change of the dispatch fails here until
+the shapes are revisited -- every designed length reaches the kernel it is meant for, and the designed rows have the properties
+they claim when pushed through oracle.safe_oracle.fdrcorrection.  No GPU."""
 import numpy as np
 import pytest
 
 import fdr_cases as fc
+import fdr_plan_driver as fp
 from oracle import safe_oracle as orc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
-def source():
-    with open(os.path.join(ROOT, 'safepy_amd', 'csrc', 'fdr.hip')) as f:
-        return f.read()
+def plan(tmp_path_factory):
+    return fp.build(tmp_path_factory.mktemp('fdr_plan'))
 
 
 # ----------------------------------------------------------------------------------------------- the constants ----
 
-def test_the_ipt_ladder_is_the_one_in_the_source(source):
-    ladder = re.findall(r'if \(ipt <= (\d+)\) FDR_SORT\((\d+)\);', source)
-    last = re.findall(r'else FDR_SORT\((\d+)\);', source)
-    assert [int(a) for a, b in ladder] == [int(b) for a, b in ladder] == list(fc.IPT_LADDER[:-1])
-    assert [int(v) for v in last] == [fc.IPT_LADDER[-1]]
-    assert sorted(int(v) for v in re.findall(r'FDR_SORT\((\d+)\)', source)) == list(fc.IPT_LADDER)
-    assert 'k_fdr_row_sort<I>, dim3(n), dim3(%d)' % fc.THREADS in source
-    assert 'const int64_t ipt = ceil_div(m, %d);' % fc.THREADS in source
-
-
-def test_the_hand_over_to_the_library_sort_is_the_one_in_the_source(source):
-    assert source.count('m <= %d' % fc.BLOCK_SORT_MAX) == 1 and len(re.findall(r'm <= \d+', source)) == 1
+def test_the_constants_are_the_ones_of_the_header(plan):
+    c, ladder = fp.constants(plan)
+    assert ladder == fc.IPT_LADDER and c['THREADS'] == fc.THREADS and c['BLOCK_SORT_MAX'] == fc.BLOCK_SORT_MAX
     assert fc.BLOCK_SORT_MAX == fc.THREADS * fc.IPT_LADDER[-1]
     assert fc.BLOCK_SORT_MAX <= 1 << 16                          # column ids travel as unsigned short
-    assert 'const int64_t len = (m + %d) / %d' % (fc.THREADS - 1, fc.THREADS) in source
-
-
-def test_the_lds_rule_of_the_histogram_form_is_the_one_in_the_source(source):
-    rule = '(%%s + 1) * %d <= 60 * 1024' % fc.HIST_BYTES_PER_BIN
-    assert source.count(rule % 'n_perm') == 1 and source.count(rule % 'num_permutations') == 1
-    assert source.count('60 * 1024') == 2
+    assert (c['ROW_HIST_BIN_BYTES'], c['ROW_HIST_LDS_BYTES'], c['ROW_HIST_MAX_P']) == (fc.HIST_BYTES_PER_BIN, fc.HIST_LDS_BYTES, fc.HIST_MAX_P)
     assert fc.HIST_LDS_BYTES == 60 * 1024 and fc.HIST_MAX_P == 5119
     assert (fc.HIST_MAX_P + 1) * fc.HIST_BYTES_PER_BIN <= fc.HIST_LDS_BYTES < (fc.HIST_MAX_P + 2) * fc.HIST_BYTES_PER_BIN
-    assert 'const int per = (bins + %d) / %d' % (fc.THREADS - 1, fc.THREADS) in source
     assert fc.HIST_MAX_P in fc.HIST_P and fc.HIST_MAX_P + 1 in fc.HIST_P
+    assert (c['SEG_BATCH_KEYS'], c['SORT_MAX_ITEMS']) == (1 << 27, 1 << 31)
+
+
+def test_the_ipt_ladder_is_the_one_in_the_source(plan):
+    """Rows, default switch: every length up to 8193 goes to the rung fdr_cases.ipt_for names; 8192 is the last row of the block
+    sort, 8193 the first of the library sort."""
+    lengths = sorted(set(fc.sort_lengths()) | set(range(1, fc.BLOCK_SORT_MAX + 2)))
+    got = fp.forms(plan, [(fp.ROWS, 10, m, 0, None) for m in lengths])
+    for m, f in zip(lengths, got):
+        want = fc.ipt_for(m)
+        assert f['kind'] == f['row_kind'] == (fp.ROW_LIBRARY_SORT if want is None else fp.ROW_BLOCK_SORT), m
+        assert f['ipt'] == (want or 0), m
+    assert tuple(sorted({f['ipt'] for f in got} - {0})) == fc.IPT_LADDER
+    by_m = dict(zip(lengths, got))
+    assert by_m[fc.BLOCK_SORT_MAX]['kind'] == fp.ROW_BLOCK_SORT and by_m[fc.BLOCK_SORT_MAX + 1]['kind'] == fp.ROW_LIBRARY_SORT
+    assert by_m[fc.BLOCK_SORT_MAX + 1]['batch_rows'] == 10       # all ten rows in one call of the library sort
+
+
+def test_the_hand_over_to_the_library_sort_is_the_one_in_the_source(plan):
+    """SAFE_HIP_FDR_SORT: under 'cub' every row length goes to the library sort, under any other value the hand-over stays at
+    8192 / 8193; no count form exists under either."""
+    for f in fp.forms(plan, [(fp.ROWS, 3, m, P, 'cub') for m in fc.library_lengths() for P in (0, 100)]):
+        assert f['kind'] == fp.ROW_LIBRARY_SORT and f['batch_rows'] == 3
+    block = fp.forms(plan, [(fp.ROWS, 3, m, P, 'block') for m in (fc.BLOCK_SORT_MAX, fc.BLOCK_SORT_MAX + 1) for P in (0, 100)])
+    assert [f['kind'] for f in block] == [fp.ROW_BLOCK_SORT] * 2 + [fp.ROW_LIBRARY_SORT] * 2 and block[0]['ipt'] == fc.IPT_LADDER[-1]
+    assert not any(fp.exists(plan, [(scope, P, sw) for scope in (fp.ROWS, fp.COLS, fp.ALL) for P in (1, 100, 4095) for sw in ('cub', 'block', 'sort')]))
+    assert all(fp.exists(plan, [(scope, P, None) for scope in (fp.ROWS, fp.COLS, fp.ALL) for P in (1, 100, 4095)]))
+
+
+def test_the_lds_rule_of_the_histogram_form_is_the_one_in_the_source(plan):
+    """The row count form serves exactly P <= HIST_MAX_P, with (P + 1) * 12 bytes of LDS."""
+    span = list(range(0, fc.HIST_MAX_P + 300))
+    assert fp.exists(plan, [(fp.ROWS, P, None) for P in span]) == [1 <= P <= fc.HIST_MAX_P for P in span]
+    for P, f in zip(fc.HIST_P, fp.forms(plan, [(fp.ROWS, 9, 300, P, None) for P in fc.HIST_P])):
+        if P <= fc.HIST_MAX_P:
+            assert f['kind'] == fp.ROW_HIST and f['lds'] == (P + 1) * fc.HIST_BYTES_PER_BIN <= fc.HIST_LDS_BYTES, P
+        else:
+            assert f['kind'] == fp.ROW_BLOCK_SORT and f['ipt'] == fc.ipt_for(300), P
+
+
+def test_the_span_helper_is_the_one_the_cases_mirror(plan):
+    """fdr_span equals fdr_cases.hist_bins for every thread of every designed P, and gives the library sort's chunk."""
+    cases = [(P, t) for P in fc.HIST_P for t in range(fc.THREADS)]
+    got = plan('span %d %d %d' % (P + 1, fc.THREADS, t) for P, t in cases)
+    assert [tuple(int(x) for x in r) for r in got] == [fc.hist_bins(P, t) for P, t in cases]
+    for m in fc.library_lengths():
+        got = plan('span %d %d %d' % (m, fc.THREADS, t) for t in range(fc.THREADS))
+        c = fc.chunk(m, 'library')
+        assert [tuple(int(x) for x in r) for r in got] == [(min(t * c, m), min(t * c + c, m)) for t in range(fc.THREADS)], m
+
+
+def test_the_key_transform_orders_like_argsort(plan):
+    """On the bit patterns of the designed rows -- NaN of both signs and all ones, -0.0, the subnormals -- sorting by fdr_key is
+    np.argsort; every NaN has the one key behind every number and below the padding key, both zeros the key 0."""
+    for name, row in fc.rows(1024):
+        k = fp.keys(plan, row)
+        assert np.array_equal(np.argsort(k, kind='stable'), np.argsort(row, kind='stable')), name
+        nan = np.isnan(row)
+        assert (k[nan] == 0x7FF8000000000000).all() and (k[~nan] < 0x7FF8000000000000).all(), name
+        assert np.array_equal(k[~nan], fc.bits(row[~nan] + 0.0)) and (k < fc.ALL_ONES_BITS).all(), name
+    zeros = fp.keys(plan, np.array([0.0, -0.0]))
+    assert zeros.tolist() == [0, 0]
+
+
+def test_the_ratio_rule_is_numpys(plan):
+    """fdr_ratio_bin on a designed count matrix, and on it with one entry that is no count ratio: a bin exactly where
+    np.rint(p P) / P == p, the bin np.rint(p P); NaN of either sign is told apart from an entry that is no ratio."""
+    P = 257
+    p = fc.count_matrix(P, 300)[1]
+    q = p.copy()
+    q[3, 7] = 0.123456
+    for mat, n_bad in ((p, 0), (q, 1)):
+        got = fp.ratio_bins(plan, mat, P).reshape(mat.shape)
+        nan = np.isnan(mat)
+        with np.errstate(invalid='ignore'):
+            ratio = ~nan & (np.rint(mat * P) / P == mat)
+        assert nan.sum() == 2 and (got[nan] == fp.BIN_NAN).all()
+        assert np.array_equal(got >= 0, ratio) and (got[~nan & ~ratio] == fp.BIN_NOT_RATIO).all() and (~nan & ~ratio).sum() == n_bad
+        assert np.array_equal(got[ratio], np.rint(mat[ratio] * P).astype(np.int64))
+    assert fp.ratio_bins(plan, np.array([-1.0 / P, (P + 1.0) / P, 1.0, 0.0, -0.0]), P).tolist() == [fp.BIN_NOT_RATIO, fp.BIN_NOT_RATIO, P, 0, 0]
 
 
 # ------------------------------------------------------------------------------------------------- the lengths ----

@@ -1,6 +1,7 @@
-"""multiple_testing_scope without a GPU: the NumPy restatements of the two count forms of safepy_amd/csrc/fdr_scope.hip against
+"""multiple_testing_scope without a GPU: the NumPy restatements of the column and whole-matrix count forms of safepy_amd/csrc/fdr.hip against
 oracle.safe_oracle.fdrcorrection (along axis 0, and on the ravelled matrix) on the GPU tests' own case lists, a hand-worked 3 x 4
-example with three different answers, the setting's validation and pickling, and the new symbols in header, binding and library."""
+example with three different answers, the forms safepy_amd/csrc/fdr_plan.h chooses (built for the host and run as a program:
+tests/fdr_plan_driver.py), the setting's validation and pickling, and the new symbols in header, binding and library."""
 import ctypes
 import os
 import pickle
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import fdr_cases as fc
+import fdr_plan_driver as fp
 import fdr_scope_ref as fs
 from oracle import safe_oracle as orc
 
@@ -18,18 +20,55 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ------------------------------------------------------------------------------------------------- the constants ----
 
-def test_the_constants_are_the_ones_in_the_source():
-    with open(os.path.join(ROOT, 'safepy_amd', 'csrc', 'fdr_scope.hip')) as f:
-        source = f.read()
-    for line in ('FDR_COL_LDS_BYTES = 128 * 1024;', 'FDR_COL_TILE_MAX = %d;' % fs.COL_TILE_MAX, 'FDR_COL_TILE_MIN = %d;' % fs.COL_TILE_MIN,
-                 'FDR_COL_HIST_MAX_P = FDR_COL_LDS_BYTES / (8 * FDR_COL_TILE_MIN) - 1;', 'FDR_ALL_HIST_MAX_P = 64 * 1024 / 4 - 1;',
-                 'FDR_TR_TILE = %d;' % fs.TR_TILE, 'FDR_ALL_IPT = %d;' % fs.ALL_IPT, 'FDR_ALL_BLOCK = 256 * FDR_ALL_IPT;',
-                 'std::min<int64_t>(FDR_COL_TILE_MAX, FDR_COL_LDS_BYTES / (8 * bins))'):
-        assert line in source, line
-    assert (fs.COL_HIST_MAX_P, fs.ALL_HIST_MAX_P, fs.ALL_BLOCK) == (4095, 16383, 2048)
+@pytest.fixture(scope='module')
+def plan(tmp_path_factory):
+    return fp.build(tmp_path_factory.mktemp('fdr_plan'))
+
+
+def test_the_constants_are_the_ones_in_the_source(plan):
+    c, _ = fp.constants(plan)
+    assert (c['COL_LDS_BYTES'], c['COL_TILE_MAX'], c['COL_TILE_MIN']) == (fs.COL_LDS_BYTES, fs.COL_TILE_MAX, fs.COL_TILE_MIN) == (128 * 1024, 16, 4)
+    assert (c['COL_HIST_MAX_P'], c['ALL_HIST_MAX_P'], c['ALL_BLOCK']) == (fs.COL_HIST_MAX_P, fs.ALL_HIST_MAX_P, fs.ALL_BLOCK) == (4095, 16383, 2048)
+    assert (c['TR_TILE'], c['ALL_IPT'], c['COL_BIN_BYTES']) == (fs.TR_TILE, fs.ALL_IPT, 8) and c['ALL_BLOCK'] == c['THREADS'] * c['ALL_IPT']
     assert fs.col_tile(1000) == 16 and fs.col_tile(fs.COL_HIST_MAX_P) == fs.COL_TILE_MIN
     assert fs.col_tile(fs.COL_HIST_MAX_P) * 8 * (fs.COL_HIST_MAX_P + 1) <= fs.COL_LDS_BYTES
     assert 4 * (fs.ALL_HIST_MAX_P + 1) <= 64 * 1024 < 4 * (fs.ALL_HIST_MAX_P + 2)
+
+
+def test_the_column_forms_are_the_ones_the_header_chooses(plan):
+    """The column count form serves exactly P <= COL_HIST_MAX_P, with the tile of fdr_scope_ref.col_tile and its tables inside
+    128 KiB; the sort form is the row form of the [m, n] transpose."""
+    span = list(range(0, fs.COL_HIST_MAX_P + 300))
+    assert fp.exists(plan, [(fp.COLS, P, None) for P in span]) == [1 <= P <= fs.COL_HIST_MAX_P for P in span]
+    for P, f in zip(fs.COLS_COUNT_P, fp.forms(plan, [(fp.COLS, 257, 70, P, None) for P in fs.COLS_COUNT_P])):
+        if P <= fs.COL_HIST_MAX_P:
+            assert f['kind'] == fp.COL_COUNTS and f['tile'] == fs.col_tile(P) >= fs.COL_TILE_MIN, P
+            assert f['lds'] == f['tile'] * 8 * (P + 1) <= fs.COL_LDS_BYTES, P
+        else:
+            assert f['kind'] == fp.COL_SORT and (f['row_kind'], f['ipt']) == (fp.ROW_BLOCK_SORT, fc.ipt_for(257)), P
+    m = 70
+    cols = fp.forms(plan, [(fp.COLS, n, m, 0, None) for n in fs.COLS_SORT_N])
+    rows = fp.forms(plan, [(fp.ROWS, m, n, 0, None) for n in fs.COLS_SORT_N])
+    for n, c, r in zip(fs.COLS_SORT_N, cols, rows):
+        assert c['kind'] == fp.COL_SORT and (c['row_kind'], c['ipt'], c['batch_rows']) == (r['kind'], r['ipt'], r['batch_rows']), n
+        assert c['ipt'] == (fc.ipt_for(n) or 0) and c['row_kind'] == (fp.ROW_BLOCK_SORT if n <= fc.BLOCK_SORT_MAX else fp.ROW_LIBRARY_SORT), n
+
+
+def test_the_matrix_forms_are_the_ones_the_header_chooses(plan):
+    """The whole-matrix count form serves exactly P <= ALL_HIST_MAX_P; the sort form ends below 2^31 items -- refused at
+    n m = 2^31 and at n = 2^31 with m = 1 unless the count form serves, allowed at 2^31 - 1."""
+    span = [0, 1, 2, 4096, fs.ALL_HIST_MAX_P - 1, fs.ALL_HIST_MAX_P, fs.ALL_HIST_MAX_P + 1, fs.ALL_HIST_MAX_P + 2, 1 << 20]
+    assert fp.exists(plan, [(fp.ALL, P, None) for P in span]) == [1 <= P <= fs.ALL_HIST_MAX_P for P in span]
+    big = 1 << 31
+    cases = [(fp.ALL, 1 << 16, 1 << 15, 0, None), (fp.ALL, big, 1, 0, None), (fp.ALL, 1, big, 0, None), (fp.ALL, 1 << 40, 1 << 40, 0, None),
+             (fp.ALL, 1 << 16, 1 << 15, fs.ALL_HIST_MAX_P + 1, None), (fp.ALL, 1 << 16, 1 << 15, 100, 'sort'),
+             (fp.ALL, big - 1, 1, 0, None), (fp.ALL, 1, big - 1, 0, None), (fp.ALL, 46341, 46340, 0, None),
+             (fp.ALL, 1 << 16, 1 << 15, 100, None), (fp.ALL, big, 1, fs.ALL_HIST_MAX_P, None)]
+    kinds = [f['kind'] for f in fp.forms(plan, cases)]
+    assert kinds == [fp.UNSUPPORTED] * 6 + [fp.ALL_SORT] * 3 + [fp.ALL_COUNTS] * 2
+    assert 46341 * 46340 < big
+    f = fp.forms(plan, [(fp.ALL, 255, 257, P, None) for P in fs.ALL_COUNT_P])
+    assert [x['kind'] for x in f] == [fp.ALL_COUNTS] * 4 + [fp.ALL_SORT] and [x['lds'] for x in f[:4]] == [4 * (P + 1) for P in fs.ALL_COUNT_P[:4]]
 
 
 def test_chain_positions_reach_every_kind_of_chunk():

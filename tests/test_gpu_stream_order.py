@@ -64,7 +64,7 @@ SYNCHRONISES = {
     'safe_permtest_counts': 'enrich.hip:3210 finish_kernel_timing; the launchers also wait for their host task lists (enrich.hip:2436, 2946, 3045)',
     'safe_randomization': 'enrich.hip:3523 temporaries of the call; its callers rely on the call having finished when it returns',
     'safe_hypergeom': 'enrich.hip:3614 host id vectors and temporaries of the call (and enrich.hip:3174, 3607)',
-    'safe_fdr_adjust': 'fdr.hip:371 reads back the count-ratio flag; fdr.hip:384 frees the enriched counters',
+    'safe_fdr_adjust': 'fdr.hip: read_flag reads back the count-ratio flag; run frees the enriched counters when it returns',
     'safe_outputs_from_counts': 'enrich.hip:3649 reads back the out-of-range flag (SAFE_E_VALUE)',
     'safe_outputs_from_packed_counts': 'enrich.hip:3684 the slab epilogue followed by a wait: the call has finished when it returns',
     'safe_nes_from_packed_counts': 'enrich.hip:3684 (it is safe_outputs_from_packed_counts with one output)',
