@@ -263,9 +263,13 @@ __global__ __launch_bounds__(256) void k_mfma_slice(const void *__restrict__ raw
 // z-scores: the scale of the SQUARES of a column (always the rounding regime: b*b is itself a rounded f64 product,
 // as in the reference's np.power(B0, 2)): max^2 sits just below 2^46.  scale2[j] = 2^-shift2[j].
 // inexact[j] = 1 unless both the values and their squares are held exactly (values on one binary grid spanning <= 22 bits).
+// var_floor[j]: where the squares are held rounded a neighborhood of IDENTICAL values has EXX - mean^2 = the rounding of its squares,
+// of either sign, up to half a grid step -- not zero (std == 0 -> NaN, safe_extras.py:29).  A variance of that size can also be a
+// real one, so below |var_floor| = one grid step of the squares (scale2) the score evaluation asks mf_identical_values; the sign
+// carries the input type (negative: f32, the squares were formed in f32).  0 where the squares are exact.
 __global__ void k_mfma_colfinish_sq(const unsigned long long *__restrict__ maxbits, const unsigned int *__restrict__ neg_lowbit,
-                                    int64_t mloc, int *__restrict__ shift2, double *__restrict__ scale2,
-                                    unsigned int *__restrict__ inexact, int *__restrict__ bad) {
+                                    int64_t mloc, int *__restrict__ shift2, double *__restrict__ scale2, double *__restrict__ var_floor,
+                                    int f32, unsigned int *__restrict__ inexact, int *__restrict__ bad) {
     const int64_t j = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (j >= mloc) return;
     const double mx = __longlong_as_double(static_cast<long long>(maxbits[j]));
@@ -283,7 +287,21 @@ __global__ void k_mfma_colfinish_sq(const unsigned long long *__restrict__ maxbi
     }
     shift2[j] = sh;
     scale2[j] = ldexp(1.0, -sh);
+    var_floor[j] = rounded ? (f32 ? -ldexp(1.0, -sh) : ldexp(1.0, -sh)) : 0.0;
     inexact[j] = rounded;
+}
+
+// Do the exact sums s1 (values), s2 (squares' image) of c present values say "c times the same value x"?  s1 = c x and
+// s2 = c q2(x), q2 as k_mfma_slice_z forms it (the square in the input's own type, on the grid of scale2).  Sums of different
+// values that pass are, to the image, the same neighborhood.  (Columns whose VALUES are rounded too: x is not the input, no match.)
+__device__ __forceinline__ bool mf_identical_values(long long s1, long long s2, int c, double sc1, double sc2, bool f32) {
+    if (c <= 0) return false;
+    const long long x = s1 / c;
+    if (x * c != s1) return false;
+    const double v = static_cast<double>(x) * sc1;
+    const float vf = static_cast<float>(v);
+    const double sq = f32 ? static_cast<double>(vf * vf) : v * v;
+    return static_cast<double>(s2) == rint(sq / sc2) * static_cast<double>(c);
 }
 
 // z-score slices: bs[16-column tile][row][7 slices][32 bytes]; bytes 0-15 of slice t = digit t of q1 = fixed-point B0 of
@@ -541,10 +559,11 @@ __global__ __launch_bounds__(512) void k_permtest_mfma(
 
             // z-scores: this lane's attribute column and the power-of-two scales of its sum / sum of squares
             const int64_t colz = static_cast<int64_t>(ct) * 16 + (col_in_tile & 15);
-            double sc1 = 1.0, sc2 = 1.0;
+            double sc1 = 1.0, sc2 = 1.0, var_floor = 0.0;
             if (Z && colz < mloc) {
                 sc1 = col_scale[colz];
                 sc2 = col_scale[mloc + colz];
+                var_floor = col_scale[2 * mloc + colz];
             }
 
             v16i acc[NS];
@@ -802,9 +821,12 @@ __global__ __launch_bounds__(512) void k_permtest_mfma(
                             const double members = static_cast<double>(acc[NS - 1][r]);
                             const double mean = (static_cast<double>(v) * sc1) / members;          // safe_extras.py:21-23
                             const double exx = (static_cast<double>(w) * sc2) / members;           // safe_extras.py:25-26
-                            const double sd = sqrt(exx - mean * mean);                            // safe_extras.py:27
+                            const double var = exx - mean * mean;
+                            const double sd = sqrt(var);                                          // safe_extras.py:27
                             double zs = mean / sd;                                                // safe_extras.py:28
-                            if (sd == 0.0) zs = __longlong_as_double(0x7FF8000000000000ll);       // safe_extras.py:29
+                            // safe_extras.py:29 (std == 0); rounded squares: identical values leave their rounding (k_mfma_colfinish_sq)
+                            if (sd == 0.0 || (fabs(var) <= fabs(var_floor) && mf_identical_values(v, w, acc[NS - 1][r], sc1, sc2, var_floor < 0.0)))
+                                zs = __longlong_as_double(0x7FF8000000000000ll);
                             if (members < 3.0) zs = __longlong_as_double(0x7FF8000000000000ll);   // safe_extras.py:30
                             if (q == 0) {
                                 obs[r * 512] = __double_as_longlong(zs);
@@ -2585,9 +2607,13 @@ __global__ __launch_bounds__(256) void k_mfma_resolve_z(const ulonglong2 *__rest
             const double members = static_cast<double>(present);
             const double mean = (static_cast<double>(s1) * sc1) / members;          // safe_extras.py:21-23
             const double exx = (static_cast<double>(s2) * sc2) / members;           // safe_extras.py:25-26
-            const double sd = sqrt(exx - mean * mean);                              // safe_extras.py:27
+            const double var = exx - mean * mean;
+            const double sd = sqrt(var);                                            // safe_extras.py:27
             double zs = mean / sd;                                                  // safe_extras.py:28
-            if (sd == 0.0) zs = __longlong_as_double(0x7FF8000000000000ll);         // safe_extras.py:29
+            // safe_extras.py:29 (std == 0); rounded squares: identical values leave their rounding (k_mfma_colfinish_sq)
+            const double var_floor = col_scale[2 * mloc + col];
+            if (sd == 0.0 || (fabs(var) <= fabs(var_floor) && mf_identical_values(s1, s2, present, sc1, sc2, var_floor < 0.0)))
+                zs = __longlong_as_double(0x7FF8000000000000ll);
             if (members < 3.0) zs = __longlong_as_double(0x7FF8000000000000ll);     // safe_extras.py:30
             const unsigned int add = (static_cast<unsigned int>(zs >= o) << 16) | static_cast<unsigned int>(zs <= o);
             if (add) atomicAdd(&gl_counts[col * n_padr + u], add);
@@ -2777,7 +2803,7 @@ const void *mfma_form_kernel(const MfmaForm &f, int dbg) {
 struct MfmaColumns {
     MfmaLayout lay;
     unsigned char *d_bs = nullptr;      // the slice scratch (lay)
-    double *d_scale = nullptr;          // [mloc] power-of-two scales (z-scores: + [mloc] of the squares)
+    double *d_scale = nullptr;          // [mloc] power-of-two scales (z-scores: + [mloc] of the squares + [mloc] var_floor, k_mfma_colfinish_sq)
     long long *d_q64 = nullptr;         // (filtered 'sum' form) the fixed-point values as 64-bit words, [n + 1][mloc]: the resolve kernel's operand
     longlong2 *d_z64 = nullptr;         // (filtered z form) value | square + not-NaN flag, [n + 1][mloc]
     int n_slices = MF_NS;               // i8 slices of this call: 2 / 4 / 6 by the bits its columns need (k_mfma_colfinish); z-scores: seven
@@ -2791,13 +2817,13 @@ int mfma_prepare_columns(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *at
     if (lay.split_off) SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_Q64, static_cast<size_t>(n + 1) * mloc * sizeof(long long), reinterpret_cast<void **>(&cols->d_q64)));
     if (lay.zf_hi_off) SAFE_TRY(ctx_scratch(ctx, SCRATCH_MFMA_Z64, static_cast<size_t>(n + 1) * mloc * sizeof(longlong2), reinterpret_cast<void **>(&cols->d_z64)));
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_OPERANDS, lay.bytes, reinterpret_cast<void **>(&cols->d_bs)));
-    void *d_colbuf = nullptr;                    // maxbits u64 | sumsq f64 | scale, scale2 f64 | cnt, small, rounded, neg_lowbit u32 | shift, shift2 i32 | bad, need i32
-    const size_t colbuf_bytes = static_cast<size_t>(mloc) * (8 + 8 + 16 + 4 + 4 + 4 + 4 + 4 + 4 + 8) + 64;   // (+ zeros, inexact u32)
+    void *d_colbuf = nullptr;                    // maxbits u64 | sumsq f64 | scale, scale2, var_floor f64 | cnt, small, rounded, neg_lowbit u32 | shift, shift2 i32 | bad, need i32
+    const size_t colbuf_bytes = static_cast<size_t>(mloc) * (8 + 8 + 24 + 4 + 4 + 4 + 4 + 4 + 4 + 8) + 64;   // (+ zeros, inexact u32)
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_COLUMN_META, colbuf_bytes, &d_colbuf));
     unsigned long long *d_max = static_cast<unsigned long long *>(d_colbuf);
     double *d_sumsq = reinterpret_cast<double *>(d_max + mloc);
     double *d_scale = cols->d_scale = d_sumsq + mloc;
-    unsigned int *d_cnt = reinterpret_cast<unsigned int *>(d_scale + 2 * mloc);
+    unsigned int *d_cnt = reinterpret_cast<unsigned int *>(d_scale + 3 * mloc);
     unsigned int *d_small = d_cnt + mloc, *d_rounded = d_small + mloc, *d_lowbit = d_rounded + mloc;
     unsigned int *d_zero = d_lowbit + mloc, *d_inexact = d_zero + mloc;
     int *d_shift = reinterpret_cast<int *>(d_inexact + mloc);
@@ -2816,7 +2842,7 @@ int mfma_prepare_columns(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *at
     const dim3 sgrid(n_ct, ceil_div(n + 1, 32));
     if (z) {
         hipLaunchKernelGGL(k_mfma_colfinish_sq, dim3(ceil_div(mloc, 256)), dim3(256), 0, ctx->stream, d_max, d_lowbit, mloc, d_shift + mloc,
-                           d_scale + mloc, d_inexact, d_bad);
+                           d_scale + mloc, d_scale + 2 * mloc, f32 ? 1 : 0, d_inexact, d_bad);
         if (f32)
             hipLaunchKernelGGL(k_mfma_slice_z<float>, sgrid, dim3(256), 0, ctx->stream, attr->raw, n, attr->row_stride, attr->col_stride,
                                col0, mloc, n_ct, d_shift, d_shift + mloc, d_max, cols->d_bs, d_small, d_rounded, d_zero, lay.zf_hi_off, lay.zf_lo_off,
