@@ -400,6 +400,24 @@ int safe_perms_slice(safe_perms *perms, int64_t p0, int64_t p1, safe_perms **out
  * num_permutations index) only -- restated in oracle/safe_oracle.py for the tests. */
 int safe_perms_create_device(safe_ctx *ctx, int64_t n, const uint8_t *movable_host, int64_t num_permutations,
                              uint64_t key, safe_perms **out);
+/* RESTRICTED permutations: the device stream of safe_perms_create_device with the rows shuffled only inside strata of
+ * comparable nodes (the strata= / blocks= argument of permutation-test packages).  stratum_host is int32 [n]: the label of
+ * every row, >= 0, read only where the row is movable.  The movable rows are listed stratum by stratum -- strata in ascending
+ * label order, rows ascending inside a stratum -- and row q of the table shuffles every stratum on its own with the device
+ * stream's algorithm applied to that stratum's element list: each element draws one of 64 buckets, buckets keep ascending
+ * element order, Fisher-Yates runs from the top inside each bucket, Lemire draws with the same fallback counters; the element
+ * index e and the step i are local to the stratum, and the stratum's rank s (0-based position among the distinct labels of
+ * the movable rows) goes into word 2 of every Philox counter: (s << 16) | tag for the tags 0xB0C7, 0x5AFE, 0xFA11.  So a
+ * partition with ONE stratum gives the tables of safe_perms_create_device with the same key bit for bit, and the tables
+ * depend on (key, movable rows, partition, permutation index) only.  Rows that are not movable and the padding entry n map to
+ * themselves; a stratum of one row stays put.  Rows of the table are i.i.d. (no composition step).  The handle is the one
+ * safe_perms_create_device returns (32-bit and, for n < 65535, 16-bit table, every stage complete behind the launch, role 3
+ * in safe_perms_timing); it never enters or consults the resident-table reuse of seeded handles.
+ * Refusals (nothing written, *out = NULL): more than 65535 movable rows SAFE_E_UNSUPPORTED; a negative label on a movable
+ * row SAFE_E_VALUE; NULL arguments, n out of range, a negative count SAFE_E_INVALID.  num_permutations = 0 and no movable row
+ * at all are valid, as for safe_perms_create_device. */
+int safe_perms_create_device_strata(safe_ctx *ctx, int64_t n, const uint8_t *movable_host, const int32_t *stratum_host,
+                                    int64_t num_permutations, uint64_t key, safe_perms **out);
 /* One permutation stream per NODE (multi-GPU runs; the reference's workers each repeat the whole stream,
  * safepy/safe.py:489-519, 1339-1353).  The stream of safe_extras.py:46-58 is sequential, so a rank cannot draw "its part":
  * safe_ctx_share_stream attaches the context to a shared-memory ring named `name` (the same string on every rank of the

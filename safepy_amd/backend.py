@@ -1073,6 +1073,27 @@ class Permutations:
         self.handle = h
         return self
 
+    @classmethod
+    def stratified(cls, ctx, n, movable, strata, num_permutations, key):
+        """Restricted permutations generated on the device (safe_perms_create_device_strata): the movable rows are shuffled only
+        inside their strata.  strata: int32 [n] labels >= 0, read where `movable` is set; key: 64 bits, None = OS entropy.  The
+        tables are a function of (key, movable rows, partition, permutation index); one stratum gives the tables of
+        Permutations(seed=None, device_key=key).  More than 65535 movable rows are refused."""
+        movable = np.ascontiguousarray(movable, dtype=np.uint8)
+        strata = np.ascontiguousarray(strata, dtype=np.int32)
+        if movable.shape != (n,) or strata.shape != (n,):
+            raise ValueError('movable and strata must have one entry per row (%d)' % n)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.n, self.count = int(n), int(num_permutations)
+        self.handle = None
+        self.device_key = int.from_bytes(os.urandom(8), 'little') if key is None else int(key) & 0xFFFFFFFFFFFFFFFF
+        h = C.c_void_p()
+        check(lib.safe_perms_create_device_strata(ctx.handle, self.n, _ptr(movable), _ptr(strata), self.count,
+                                                  C.c_uint64(self.device_key), C.byref(h)))
+        self.handle = h
+        return self
+
     def slice(self, p0, p1):
         """Permutations [p0, p1) as a handle of their own (safe_perms_slice): one rank's range of a permutation-axis split."""
         other = Permutations.__new__(Permutations)

@@ -572,6 +572,10 @@ struct safe_perms {
     // the other ranks fetch them instead of drawing (no draw thread, no swap workers on those ranks)
     bool device_gen = false;        // tables generated on the device (safe_perms_create_device): no host stream at all
     int32_t *d_movpos = nullptr;    // [n] movable rows (first k used) | [n] position of a row in that list (-1: fixed)
+    // restricted permutations (safe_perms_create_device_strata) only, allocated on first use and kept with the handle:
+    // [S + 1] starts of the strata in the stratum-ordered list of movable rows | [n_big] strata the whole wave shuffles
+    int32_t *d_strata = nullptr;
+    int32_t *h_strata = nullptr;    // pinned staging of d_strata (2n + 8 entries each)
     struct PermRing *ring = nullptr;               // the context's ring while this handle takes part in a shared call, else NULL
     bool ring_consumer = false;
     // Identity of the composed table while the handle is parked in ctx->perm_cache (rng.cpp, perms_create_impl): the stream is a

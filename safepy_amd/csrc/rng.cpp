@@ -145,12 +145,13 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
 }
 
-// bucket of element e of permutation q: six bits of a byte of the Philox words of counter (q, e >> 4, 0xB0C7, 0)
-__device__ __forceinline__ uint32_t device_bucket_word(uint32_t q, uint32_t e, uint32_t key0, uint32_t key1, uint32_t &cached_block,
-                                                       uint32_t (&w)[4]) {
+// bucket of element e of permutation q: six bits of a byte of the Philox words of counter (q, e >> 4, s << 16 | 0xB0C7, 0).
+// s is the stratum's rank (k_perms_device_strata below: e is then local to the stratum); the unstratified stream is s = 0.
+__device__ __forceinline__ uint32_t device_bucket_word(uint32_t q, uint32_t s, uint32_t e, uint32_t key0, uint32_t key1,
+                                                       uint32_t &cached_block, uint32_t (&w)[4]) {
     if ((e >> 4) != cached_block) {
         cached_block = e >> 4;
-        philox4x32_10(q, cached_block, 0xB0C7u, 0u, key0, key1, w);
+        philox4x32_10(q, cached_block, (s << 16) | 0xB0C7u, 0u, key0, key1, w);
     }
     const uint32_t word = (e >> 2) & 3u;
     const uint32_t v = word == 0 ? w[0] : word == 1 ? w[1] : word == 2 ? w[2] : w[3];
@@ -158,17 +159,18 @@ __device__ __forceinline__ uint32_t device_bucket_word(uint32_t q, uint32_t e, u
 }
 
 // the draw of step i of bucket b of permutation q: uniform on [0, i] by Lemire's multiply-shift; the word is word (i & 3) of
-// counter (q, b << 16 | i >> 2, 0x5AFE, 0); the few low products that would bias the draw (probability (i + 1) / 2^32) are
-// rejected and the draw falls back to the words of counters (q, b << 16 | i, 0xFA11, r), r = 0, 1, ..., in order
-__device__ __forceinline__ uint32_t device_draw(uint32_t q, uint32_t b, uint32_t i, uint32_t key0, uint32_t key1) {
+// counter (q, b << 16 | i >> 2, s << 16 | 0x5AFE, 0); the few low products that would bias the draw (probability (i + 1) / 2^32)
+// are rejected and the draw falls back to the words of counters (q, b << 16 | i, s << 16 | 0xFA11, r), r = 0, 1, ..., in order
+// (s: the stratum's rank, 0 for the unstratified stream; i is local to the stratum)
+__device__ __forceinline__ uint32_t device_draw(uint32_t q, uint32_t s, uint32_t b, uint32_t i, uint32_t key0, uint32_t key1) {
     const uint32_t range = i + 1u, thresh = (0u - range) % range;
     uint32_t w[4];
-    philox4x32_10(q, (b << 16) | (i >> 2), 0x5AFEu, 0u, key0, key1, w);
+    philox4x32_10(q, (b << 16) | (i >> 2), (s << 16) | 0x5AFEu, 0u, key0, key1, w);
     const uint32_t first = (i & 3u) == 0 ? w[0] : (i & 3u) == 1 ? w[1] : (i & 3u) == 2 ? w[2] : w[3];
     uint64_t m = static_cast<uint64_t>(first) * range;
     if (static_cast<uint32_t>(m) >= thresh) return static_cast<uint32_t>(m >> 32);
     for (uint32_t r = 0;; ++r) {
-        philox4x32_10(q, (b << 16) | i, 0xFA11u, r, key0, key1, w);
+        philox4x32_10(q, (b << 16) | i, (s << 16) | 0xFA11u, r, key0, key1, w);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             m = static_cast<uint64_t>(w[t]) * range;
@@ -183,20 +185,17 @@ __device__ __forceinline__ uint32_t device_draw(uint32_t q, uint32_t b, uint32_t
 // LDS steps instead of k.  Buckets laid end to end are a uniform permutation: for a target order, the elements' buckets are
 // determined by the bucket sizes (probability 64^-k) and every bucket must come out in the target's order (1 / size! each),
 // whatever the target.
-__global__ __launch_bounds__(64) void k_perms_device(int64_t n, int64_t k, int64_t count, uint32_t key0, uint32_t key1,
-                                                     const int32_t *__restrict__ mov, const int32_t *__restrict__ pos_of,
-                                                     int32_t *__restrict__ table, uint16_t *__restrict__ table16, int64_t stride16) {
-    extern __shared__ uint32_t lds32[];                               // hist [64 lanes][64 buckets] u32 | x [kpad] u16
-    const int lane = threadIdx.x;
-    const uint32_t q = blockIdx.x;
-    uint32_t *hist = lds32;
-    uint16_t *x = reinterpret_cast<uint16_t *>(lds32 + 64 * 64);
-    const uint32_t ku = static_cast<uint32_t>(k), ce = (ku + 63u) / 64u;
-    const uint32_t e0 = min(ku, lane * ce), e1 = min(ku, e0 + ce);
+// (the shuffle as a function of the element list it runs on: elements [0, m) of stratum s sit at x[base .. base + m) and are
+// named base + e there; the unstratified stream is the one list s = 0, base = 0, m = k.  Every lane of the wave calls it; the
+// caller places a barrier between the last call and its first read of x.)
+__device__ __forceinline__ void wave_shuffle(uint32_t q, uint32_t s, uint32_t base, uint32_t m, uint32_t key0, uint32_t key1,
+                                             uint32_t *hist, uint16_t *x, int lane) {
+    const uint32_t ce = (m + 63u) / 64u;
+    const uint32_t e0 = min(m, lane * ce), e1 = min(m, e0 + ce);
     uint32_t *my_hist = hist + lane * 64;
     for (int b = 0; b < 64; ++b) my_hist[b] = 0;
     uint32_t cached = 0xFFFFFFFFu, w[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t e = e0; e < e1; ++e) my_hist[device_bucket_word(q, e, key0, key1, cached, w)] += 1u;
+    for (uint32_t e = e0; e < e1; ++e) my_hist[device_bucket_word(q, s, e, key0, key1, cached, w)] += 1u;
     __syncthreads();
     // lane b: size of bucket b, its start (exclusive scan over the buckets), and every lane's first slot inside it
     uint32_t total = 0;
@@ -217,22 +216,27 @@ __global__ __launch_bounds__(64) void k_perms_device(int64_t n, int64_t k, int64
     __syncthreads();
     cached = 0xFFFFFFFFu;
     for (uint32_t e = e0; e < e1; ++e) {
-        const uint32_t b = device_bucket_word(q, e, key0, key1, cached, w);
+        const uint32_t b = device_bucket_word(q, s, e, key0, key1, cached, w);
         const uint32_t at = my_hist[b];
         my_hist[b] = at + 1u;
-        x[at] = static_cast<uint16_t>(e);
+        x[base + at] = static_cast<uint16_t>(base + e);
     }
     __syncthreads();
     if (total >= 2u) {                                                // Fisher-Yates from the top inside bucket `lane`
-        uint16_t *xb = x + start;
+        uint16_t *xb = x + base + start;
         for (uint32_t i = total - 1u; i >= 1u; --i) {
-            const uint32_t j = device_draw(q, static_cast<uint32_t>(lane), i, key0, key1);
+            const uint32_t j = device_draw(q, s, static_cast<uint32_t>(lane), i, key0, key1);
             const uint16_t xi = xb[i], xj = xb[j];
             xb[i] = xj;
             xb[j] = xi;
         }
     }
-    __syncthreads();
+}
+
+// row q of the table (and of its 16-bit copy) from the shuffled positions x: list entry t now holds old list entry x[t]
+__device__ __forceinline__ void write_table_row(uint32_t q, int64_t n, const int32_t *__restrict__ mov, const int32_t *__restrict__ pos_of,
+                                                const uint16_t *x, int32_t *__restrict__ table, uint16_t *__restrict__ table16,
+                                                int64_t stride16, int lane) {
     const int64_t stride = n + 1;
     int32_t *row = table + static_cast<int64_t>(q) * stride;
     uint16_t *row16 = table16 ? table16 + static_cast<int64_t>(q) * stride16 : nullptr;
@@ -245,7 +249,99 @@ __global__ __launch_bounds__(64) void k_perms_device(int64_t n, int64_t k, int64
         if (r < stride) row[r] = v;
         if (row16) row16[r] = static_cast<uint16_t>(v);
     }
+}
+
+__global__ __launch_bounds__(64) void k_perms_device(int64_t n, int64_t k, int64_t count, uint32_t key0, uint32_t key1,
+                                                     const int32_t *__restrict__ mov, const int32_t *__restrict__ pos_of,
+                                                     int32_t *__restrict__ table, uint16_t *__restrict__ table16, int64_t stride16) {
+    extern __shared__ uint32_t lds32[];                               // hist [64 lanes][64 buckets] u32 | x [kpad] u16
+    const int lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    uint32_t *hist = lds32;
+    uint16_t *x = reinterpret_cast<uint16_t *>(lds32 + 64 * 64);
+    wave_shuffle(q, 0u, 0u, static_cast<uint32_t>(k), key0, key1, hist, x, lane);
+    __syncthreads();
+    write_table_row(q, n, mov, pos_of, x, table, table16, stride16, lane);
     (void)count;
+}
+
+// --------------------------------------------------------------------------------------
+// Restricted permutations (safe_perms_create_device_strata): the movable rows are listed stratum by stratum (strata in
+// ascending label order, rows ascending inside a stratum) and every stratum's element list is shuffled on its own with the
+// algorithm above -- element index e and step i local to the stratum, the stratum's rank s in word 2 of every Philox counter
+// (s << 16 | tag), so one stratum (s = 0) is the unstratified stream bit for bit.  One wave per permutation as before; x holds
+// the whole list, a stratum shuffles its sub-range x[offs[s] .. offs[s + 1]).  Two forms of the same algorithm, same bytes:
+//   * a stratum of fewer than `wave_min` elements is shuffled by ONE LANE (lanes take strata l, l + 64, ...): the lane runs
+//     the three steps in sequence on its own 64-entry histogram row, visiting only the buckets that hold an element (a bit
+//     mask), so a pair costs a handful of LDS steps and no barrier -- thousands of pairs do not cost thousands of barriers;
+//   * the others are shuffled by the whole wave, one after another (big[0 .. n_big), ascending), with wave_shuffle.
+// A lane touches only its own histogram row and its own strata's part of x, so the lane pass needs no barrier; wave_shuffle
+// clears and rebuilds the rows behind its own barriers.  offs and big are read from global memory (at k = 65535 they do not
+// fit beside x).  wave_min is a performance constant only (kStrataWaveMin below).
+// --------------------------------------------------------------------------------------
+__device__ __forceinline__ void lane_shuffle(uint32_t q, uint32_t s, uint32_t base, uint32_t m, uint32_t key0, uint32_t key1,
+                                             uint32_t *my_hist, uint16_t *x) {
+    if (m == 1u) {                                                    // a stratum of one row stays put
+        x[base] = static_cast<uint16_t>(base);
+        return;
+    }
+    uint64_t occupied = 0;                                            // buckets that hold an element: only they are valid in my_hist
+    uint32_t cached = 0xFFFFFFFFu, w[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t e = 0; e < m; ++e) {
+        const uint32_t b = device_bucket_word(q, s, e, key0, key1, cached, w);
+        const uint64_t bit = 1ull << b;
+        my_hist[b] = (occupied & bit) ? my_hist[b] + 1u : 1u;
+        occupied |= bit;
+    }
+    uint32_t run = 0;                                                 // exclusive scan over the occupied buckets, ascending
+    for (uint64_t o = occupied; o; o &= o - 1ull) {
+        const int b = __ffsll(static_cast<unsigned long long>(o)) - 1;
+        const uint32_t c = my_hist[b];
+        my_hist[b] = run;
+        run += c;
+    }
+    for (uint32_t e = 0; e < m; ++e) {                                // stable: ascending element index inside a bucket
+        const uint32_t b = device_bucket_word(q, s, e, key0, key1, cached, w);
+        const uint32_t at = my_hist[b];
+        my_hist[b] = at + 1u;
+        x[base + at] = static_cast<uint16_t>(base + e);
+    }
+    uint32_t lo = 0;                                                  // my_hist[b] is now the END of bucket b
+    for (uint64_t o = occupied; o; o &= o - 1ull) {
+        const int b = __ffsll(static_cast<unsigned long long>(o)) - 1;
+        const uint32_t hi = my_hist[b];
+        uint16_t *xb = x + base + lo;
+        for (uint32_t i = hi - lo - 1u; i >= 1u; --i) {               // (a bucket of one: no step)
+            const uint32_t j = device_draw(q, s, static_cast<uint32_t>(b), i, key0, key1);
+            const uint16_t xi = xb[i], xj = xb[j];
+            xb[i] = xj;
+            xb[j] = xi;
+        }
+        lo = hi;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_perms_device_strata(int64_t n, int64_t n_strata, int64_t n_big, uint32_t wave_min, uint32_t key0,
+                                                            uint32_t key1, const int32_t *__restrict__ mov,
+                                                            const int32_t *__restrict__ pos_of, const int32_t *__restrict__ offs,
+                                                            const int32_t *__restrict__ big, int32_t *__restrict__ table,
+                                                            uint16_t *__restrict__ table16, int64_t stride16) {
+    extern __shared__ uint32_t lds32[];                               // hist [64 lanes][64 buckets] u32 | x [kpad] u16
+    const int lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    uint32_t *hist = lds32;
+    uint16_t *x = reinterpret_cast<uint16_t *>(lds32 + 64 * 64);
+    for (int64_t s = lane; s < n_strata; s += 64) {
+        const uint32_t base = static_cast<uint32_t>(offs[s]), m = static_cast<uint32_t>(offs[s + 1]) - base;
+        if (m < wave_min) lane_shuffle(q, static_cast<uint32_t>(s), base, m, key0, key1, hist + lane * 64, x);
+    }
+    for (int64_t t = 0; t < n_big; ++t) {
+        const uint32_t s = static_cast<uint32_t>(big[t]);
+        const uint32_t base = static_cast<uint32_t>(offs[s]), m = static_cast<uint32_t>(offs[s + 1]) - base;
+        wave_shuffle(q, s, base, m, key0, key1, hist, x, lane);
+    }
+    __syncthreads();
+    write_table_row(q, n, mov, pos_of, x, table, table16, stride16, lane);
 }
 
 // --------------------------------------------------------------------------------------
@@ -862,10 +958,12 @@ static void perms_free(safe_perms *p) {
     }
     if (p->movpos_ready) (void)hipEventDestroy(p->movpos_ready);
     if (p->h_movpos) (void)hipHostFree(p->h_movpos);
+    if (p->h_strata) (void)hipHostFree(p->h_strata);
     for (hipEvent_t e : p->chunk_done)
         if (e) (void)hipEventDestroy(e);
     for (const void *q : {(const void *)p->d_targets_odd, (const void *)p->d_targets, (const void *)p->d_big, (const void *)p->d_cur,
-                          (const void *)p->d_movpos, (const void *)p->table, (const void *)p->table16, (const void *)p->inverse_t})
+                          (const void *)p->d_movpos, (const void *)p->d_strata, (const void *)p->table, (const void *)p->table16,
+                          (const void *)p->inverse_t})
         (void)dev_free(q);
     if (p->stream) draw_stream_free(p->stream);
     if (p->stream2) draw_stream_free(p->stream2);
@@ -897,15 +995,24 @@ int safe_rng_permutations_host(uint32_t seed, const int64_t *values, int64_t n_i
     return SAFE_OK;
 }
 
+// A partition of the movable rows for safe_perms_create_device_strata: `order` lists them stratum by stratum (strata in
+// ascending label order, rows ascending inside one), offs[s] .. offs[s + 1] is stratum s's part of that list, `big` the strata
+// that the whole wave shuffles (k_perms_device_strata), ascending.
+struct StrataPlan {
+    std::vector<int32_t> order, offs, big;
+    uint32_t wave_min = 0;
+};
+
 // the movable rows and their positions in that list, on the device (both the replay of a seeded stream and the device stream
-// write the row maps through them)
-static int upload_movpos(safe_perms *p) {
+// write the row maps through them); `order`: the list in another order than ascending (a stratified handle)
+static int upload_movpos(safe_perms *p, const int32_t *order = nullptr) {
     const int64_t n = p->n, k = p->k, n_pad = (n + 3) & ~int64_t(3);      // two halves of n_pad entries, padded with -1
     int32_t *h = p->h_movpos;                                  // (the previous handle's upload has completed: destroy synchronises)
+    if (!order) order = p->h_movable.data();
     for (int64_t i = 0; i < 2 * n_pad; ++i) h[i] = -1;
     for (int64_t t = 0; t < k; ++t) {
-        h[t] = p->h_movable[t];
-        h[n_pad + p->h_movable[t]] = static_cast<int32_t>(t);
+        h[t] = order[t];
+        h[n_pad + order[t]] = static_cast<int32_t>(t);
     }
     SAFE_HIP_CHECK(hipMemcpyAsync(p->d_movpos, h, static_cast<size_t>(2 * n_pad) * sizeof(int32_t), hipMemcpyHostToDevice, p->ctx->aux_stream));
     if (p->movpos_ready) SAFE_HIP_CHECK(hipEventRecord(p->movpos_ready, p->ctx->aux_stream));
@@ -924,7 +1031,7 @@ static int record_all_stages(safe_perms *p) {
 }
 
 // whole table on the device (k_perms_device); every pipeline stage is complete once the kernel has run
-static int perms_generate_on_device(safe_perms *p, uint64_t key) {
+static int perms_generate_on_device(safe_perms *p, uint64_t key, const StrataPlan *strata) {
     safe_ctx *ctx = p->ctx;
     const int64_t n = p->n, k = p->k, count = p->count;
     SAFE_REQUIRE(k <= 65535, "device permutation stream: %lld movable rows (16-bit positions hold 65535)", (long long)k);
@@ -936,10 +1043,24 @@ static int perms_generate_on_device(safe_perms *p, uint64_t key) {
     SAFE_HIP_CHECK(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
     SAFE_REQUIRE(lds <= static_cast<size_t>(lds_limit), "device permutation stream: %lld movable rows need %zu bytes of LDS, a workgroup of this "
                  "device gets %d (gfx950: 160 KiB); use the NumPy-compatible stream (SAFE_HIP_DEVICE_STREAM=0)", (long long)k, lds, lds_limit);
-    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_perms_device), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds)));
-    hipLaunchKernelGGL(k_perms_device, dim3(count), dim3(64), lds, gs, n, k, count, static_cast<uint32_t>(key),
-                       static_cast<uint32_t>(key >> 32), d_mov, d_pos, p->table, p->table16, p->stride16);
+    if (strata) {
+        // the starts of the strata and the list of wave-shuffled ones go up behind the row lists, on the same stream
+        const int64_t n_strata = static_cast<int64_t>(strata->offs.size()) - 1, n_big = static_cast<int64_t>(strata->big.size());
+        memcpy(p->h_strata, strata->offs.data(), static_cast<size_t>(n_strata + 1) * sizeof(int32_t));
+        if (n_big) memcpy(p->h_strata + n_strata + 1, strata->big.data(), static_cast<size_t>(n_big) * sizeof(int32_t));
+        SAFE_HIP_CHECK(hipMemcpyAsync(p->d_strata, p->h_strata, static_cast<size_t>(n_strata + 1 + n_big) * sizeof(int32_t),
+                                      hipMemcpyHostToDevice, gs));
+        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_perms_device_strata), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(lds)));
+        hipLaunchKernelGGL(k_perms_device_strata, dim3(count), dim3(64), lds, gs, n, n_strata, n_big, strata->wave_min,
+                           static_cast<uint32_t>(key), static_cast<uint32_t>(key >> 32), d_mov, d_pos, p->d_strata,
+                           p->d_strata + n_strata + 1, p->table, p->table16, p->stride16);
+    } else {
+        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_perms_device), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(lds)));
+        hipLaunchKernelGGL(k_perms_device, dim3(count), dim3(64), lds, gs, n, k, count, static_cast<uint32_t>(key),
+                           static_cast<uint32_t>(key >> 32), d_mov, d_pos, p->table, p->table16, p->stride16);
+    }
     SAFE_HIP_CHECK(hipGetLastError());
     SAFE_TRY(record_all_stages(p));
     SAFE_HIP_CHECK(hipMemcpyAsync(p->d_cur, p->table + (count - 1) * (n + 1), (n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, gs));
@@ -957,7 +1078,7 @@ static uint64_t movable_fingerprint(const uint8_t *movable_host, int64_t n) {
 
 static int perms_create_impl(safe_ctx *ctx, int64_t n, const uint8_t *movable_host, int64_t num_permutations, int has_seed,
                              uint32_t seed, bool shared, const char *who, safe_perms **out, bool device_gen = false,
-                             uint64_t device_key = 0) {
+                             uint64_t device_key = 0, const StrataPlan *strata = nullptr) {
     SAFE_REQUIRE(ctx && movable_host && out, "%s: NULL argument", who);
     SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "%s: n out of range", who);
     SAFE_REQUIRE(num_permutations >= 0, "%s: negative permutation count", who);
@@ -1083,6 +1204,13 @@ static int perms_create_impl(safe_ctx *ctx, int64_t n, const uint8_t *movable_ho
             if (e == hipSuccess && !p->staged[b]) e = hipEventCreateWithFlags(&p->staged[b], safe_event_flags(hipEventDisableTiming));
         }
         if (!p->ring_consumer && !device_gen) p->h_local.resize(std::max<int64_t>(k, 1) + 64);
+        if (strata && e == hipSuccess) {                     // S + 1 starts and at most S wave-shuffled strata, S <= k <= n
+            if (!p->d_strata && (rc = dev_alloc(&p->d_strata, static_cast<size_t>(2 * n + 8))) != SAFE_OK) break;
+            if (!p->h_strata) {
+                g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
+                e = hipHostMalloc(reinterpret_cast<void **>(&p->h_strata), static_cast<size_t>(2 * n + 8) * sizeof(int32_t), hipHostMallocDefault);
+            }
+        }
         if (p->twin) {
             p->h_local2.resize(std::max<int64_t>(k, 1) + 64);
             p->chunk_src.assign(p->stages.size() + 1, 0);
@@ -1114,8 +1242,8 @@ static int perms_create_impl(safe_ctx *ctx, int64_t n, const uint8_t *movable_ho
             if (rc != SAFE_OK) p->ring = nullptr;            // (no call is open on the ring: nothing to end)
         }
     } while (0);
-    if (rc == SAFE_OK) rc = upload_movpos(p);
-    if (rc == SAFE_OK && device_gen && num_permutations > 0) rc = perms_generate_on_device(p, device_key);
+    if (rc == SAFE_OK) rc = upload_movpos(p, strata ? strata->order.data() : nullptr);
+    if (rc == SAFE_OK && device_gen && num_permutations > 0) rc = perms_generate_on_device(p, device_key, strata);
     if (rc != SAFE_OK) {
         perms_free(p);
         return rc;
@@ -1139,6 +1267,44 @@ int safe_perms_create_shared(safe_ctx *ctx, int64_t n, const uint8_t *movable_ho
 int safe_perms_create_device(safe_ctx *ctx, int64_t n, const uint8_t *movable_host, int64_t num_permutations, uint64_t key,
                              safe_perms **out) {
     return perms_create_impl(ctx, n, movable_host, num_permutations, 0, 0u, false, "safe_perms_create_device", out, true, key);
+}
+
+// strata of at least this many movable rows are shuffled by the whole wave, smaller ones by one lane each (k_perms_device_strata).
+// A performance constant only: the tables do not depend on it.  SAFE_HIP_STRATA_WAVE_MIN=<m> overrides it (read per call) for the
+// measurements of tools/strata_time.py and for the tests that run one partition through both forms.
+static constexpr uint32_t kStrataWaveMin = 256;
+
+int safe_perms_create_device_strata(safe_ctx *ctx, int64_t n, const uint8_t *movable_host, const int32_t *stratum_host,
+                                    int64_t num_permutations, uint64_t key, safe_perms **out) {
+    if (out) *out = nullptr;
+    SAFE_REQUIRE(ctx && movable_host && stratum_host && out, "safe_perms_create_device_strata: NULL argument");
+    SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 1, "safe_perms_create_device_strata: n out of range");
+    SAFE_REQUIRE(num_permutations >= 0, "safe_perms_create_device_strata: negative permutation count");
+    StrataPlan plan;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!movable_host[i]) continue;                                   // (labels of rows that do not move are never read)
+        if (stratum_host[i] < 0) {
+            safe_set_error("safe_perms_create_device_strata: row %lld has the negative stratum label %d", (long long)i, stratum_host[i]);
+            return SAFE_E_VALUE;
+        }
+        plan.order.push_back(static_cast<int32_t>(i));
+    }
+    const int64_t k = static_cast<int64_t>(plan.order.size());
+    if (k > 65535) {
+        safe_set_error("safe_perms_create_device_strata: %lld movable rows (16-bit positions hold 65535)", (long long)k);
+        return SAFE_E_UNSUPPORTED;
+    }
+    // strata in ascending label order, rows ascending inside one
+    std::stable_sort(plan.order.begin(), plan.order.end(), [&](int32_t a, int32_t b) { return stratum_host[a] < stratum_host[b]; });
+    plan.wave_min = kStrataWaveMin;
+    if (const char *e = getenv("SAFE_HIP_STRATA_WAVE_MIN")) plan.wave_min = static_cast<uint32_t>(std::max<long long>(2, atoll(e)));
+    for (int64_t t = 0; t < k; ++t)
+        if (t == 0 || stratum_host[plan.order[t]] != stratum_host[plan.order[t - 1]]) plan.offs.push_back(static_cast<int32_t>(t));
+    plan.offs.push_back(static_cast<int32_t>(k));
+    for (size_t s = 0; s + 1 < plan.offs.size(); ++s)
+        if (static_cast<uint32_t>(plan.offs[s + 1] - plan.offs[s]) >= plan.wave_min) plan.big.push_back(static_cast<int32_t>(s));
+    return perms_create_impl(ctx, n, movable_host, num_permutations, 0, 0u, false, "safe_perms_create_device_strata", out, true, key,
+                             &plan);
 }
 
 int safe_ctx_share_stream(safe_ctx *ctx, const char *name, int local_rank, int local_world, int64_t capacity_bytes) {

@@ -41,7 +41,40 @@ _DEFAULTS = {
     'unimodalityType': 'connectivity',
     'groupDistanceType': 'jaccard',
     'groupDistanceThreshold': '0.75',
+    # additive (no counterpart in the reference's file): restricted permutations, see SAFE.compute_pvalues
+    'permutationStrata': '',
+    'permutationStrataBins': '10',
 }
+
+
+def _neighborhood_size_strata(counts, bins):
+    """permutation_strata = 'neighborhood_size': int32 [N], the stratum of every node -- the nodes in ascending (neighborhood
+    size, node index) order (a stable argsort), cut into `bins` groups by np.array_split.  Exact: no quantile arithmetic."""
+    order = np.argsort(np.asarray(counts), kind='stable')
+    strata = np.empty(len(order), dtype=np.int32)
+    for b, part in enumerate(np.array_split(order, bins)):
+        strata[part] = b
+    return strata
+
+
+def _factorise_strata(labels, n):
+    """Array-like stratum labels in node order -> int32 [N] ranks among the distinct labels (np.unique).  ValueError for a wrong
+    length and for missing labels (None, NaN)."""
+    arr = np.asarray(labels)
+    if arr.ndim != 1 or arr.shape[0] != n:
+        raise ValueError('permutation_strata needs one label per node in node order: expected length %d, got shape %s'
+                         % (n, arr.shape))
+    if arr.dtype == object:
+        missing = any(v is None or (isinstance(v, (float, np.floating)) and v != v) for v in arr)
+    else:
+        missing = bool(np.issubdtype(arr.dtype, np.floating) and np.isnan(arr).any())
+    if missing:
+        raise ValueError('permutation_strata holds missing labels (None / NaN): every node needs a stratum')
+    try:
+        ranks = np.unique(arr, return_inverse=True)[1]
+    except TypeError as exc:
+        raise ValueError('permutation_strata labels cannot be ordered against each other (%s)' % exc)
+    return np.ascontiguousarray(ranks.reshape(-1), dtype=np.int32)
 
 
 def _is_real(v):
@@ -252,6 +285,12 @@ class SAFE:
         # read only when multiple_testing is on: the family one Benjamini-Hochberg run adjusts -- 'attributes' (every node's row, the
         # reference), 'neighborhoods' (every attribute's column), 'all' (the whole matrix); compute_pvalues
         self.multiple_testing_scope = 'attributes'
+        # restricted permutations of how='randomization' (compute_pvalues): None, one label per node, or 'neighborhood_size'
+        # (nodes binned into permutation_strata_bins groups by the size of their neighborhood)
+        self.permutation_strata = None
+        self.permutation_strata_bins = 10
+        self.permutation_strata_resolved = None      # int32 [N]: every node's stratum in the last stratified call
+        self.permutation_strata_sizes = None         # int64 [S]: movable rows per stratum in that call
         self.neighborhood_score_type = 'sum'
         self.enrichment_type = 'auto'
         self.hypergeom_tails = 'upper'   # 'attribute_sign': the hypergeometric test follows attribute_sign (both tails, ns, signed nes)
@@ -335,6 +374,12 @@ class SAFE:
         self.attribute_unimodality_metric = option('Analysis parameters', 'unimodalityType')
         self.attribute_distance_metric = option('Analysis parameters', 'groupDistanceType')
         self.attribute_distance_threshold = float(option('Analysis parameters', 'groupDistanceThreshold'))
+        self.permutation_strata = option('Analysis parameters', 'permutationStrata') or None      # empty = free shuffle
+        bins = option('Analysis parameters', 'permutationStrataBins')
+        try:
+            self.permutation_strata_bins = int(bins)
+        except (ValueError, TypeError):                    # validate_config names the bad value
+            self.permutation_strata_bins = bins
 
         # the reference falls back on its package folder (safe.py:186-188); here: this package's
         self.output_dir = os.path.dirname(path_to_ini_file) if path_to_ini_file else ''
@@ -378,6 +423,19 @@ class SAFE:
             self.multiple_testing_scope = 'attributes'
             raise ValueError('%s is not a valid setting for multiple_testing_scope. '
                              'Valid options are: attributes, neighborhoods, all' % (scope,))
+        strata = getattr(self, 'permutation_strata', None)
+        if isinstance(strata, str) and strata != 'neighborhood_size':
+            self.permutation_strata = None
+            raise ValueError('%s is not a valid setting for permutation_strata. Valid options are: None, '
+                             'neighborhood_size, or one label per node.' % (strata,))
+        if strata is not None and not isinstance(strata, str) and np.ndim(strata) != 1:
+            self.permutation_strata = None
+            raise ValueError('permutation_strata must be None, neighborhood_size or a one-dimensional array-like with one '
+                             'label per node, not %r' % (strata,))
+        bins = getattr(self, 'permutation_strata_bins', 10)
+        if not isinstance(bins, (int, np.integer)) or isinstance(bins, (bool, np.bool_)) or bins < 1:
+            self.permutation_strata_bins = 10
+            raise ValueError('permutation_strata_bins = %r is not valid: it must be an integer equal or greater than 1.' % (bins,))
         if getattr(self, 'attribute_transform', 'none') not in ['none', 'rank']:
             bad, self.attribute_transform = self.attribute_transform, 'none'
             raise ValueError('%s is not a valid setting for attribute_transform. '
@@ -443,6 +501,10 @@ class SAFE:
         self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
         self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
         self.__dict__.setdefault('neighborhood_radii', None)
+        self.__dict__.setdefault('permutation_strata', None)
+        self.__dict__.setdefault('permutation_strata_bins', 10)
+        self.__dict__.setdefault('permutation_strata_resolved', None)
+        self.__dict__.setdefault('permutation_strata_sizes', None)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -907,7 +969,31 @@ class SAFE:
         nes, nes_binary and num_neighborhoods_enriched are recomputed from the adjusted values as for 'attributes', and the
         results stay on the device under lazy_outputs.  The NaN rule is the row rule applied to the family: one NaN p-value (a
         node without a score) turns its whole family NaN -- its column under 'neighborhoods', the WHOLE matrix under 'all'.
-        The attribute-sharded drivers (safepy_amd.sharding, run_batch.py) keep the row scope and do not take the keyword."""
+        The attribute-sharded drivers (safepy_amd.sharding, run_batch.py) keep the row scope and do not take the keyword.
+
+        permutation_strata (additive; keyword or setting, default None = the free shuffle and its bytes; with
+        permutation_strata_bins): a RESTRICTED permutation null for how = 'randomization' -- the attribute rows are shuffled only
+        among nodes of one stratum, so an attribute that merely tracks a node property that also shapes the neighborhoods
+        (degree, neighborhood size, batch, gene family) is not called enriched for that property's geography.
+          array-like       one label per node in node order; any labels np.unique can order (ints, strings); None / NaN labels
+                           and a wrong length raise ValueError;
+          'neighborhood_size'  the nodes in ascending (size of their current neighborhood, node index) order, cut into
+                           permutation_strata_bins (an int >= 1, default 10) groups by np.array_split; needs
+                           define_neighborhoods first.
+        The tables are generated on the device (backend.Permutations.stratified), every stratum shuffled on its own by the
+        unseeded route's generator; everything behind the tables -- counting kernels, multiple_testing and its scope,
+        attribute_transform = 'rank', background = 'network', both score types, the three signs, lazy_outputs -- is unchanged.
+        Key: random_seed = None uses device_stream_key or OS entropy like the unseeded route; an integer random_seed IS the
+        key (zero-extended to 64 bits) -- there is no NumPy stream to reproduce under strata, so a seeded stratified call is
+        simply repeatable, and SAFE_HIP_DEVICE_STREAM=0 does not apply.  After the call permutation_strata_resolved (int32 [N]:
+        every node's stratum, its rank among the distinct labels) and permutation_strata_sizes (int64 [S]: the rows that hold a
+        value, per stratum) are set.  Refused with a ValueError that leaves every result as it was: how = 'analytic' (the
+        stratified moments are not implemented), a hypergeometric route ('auto' on 0/1 data included: pass
+        how = 'randomization'), more than 65535 rows that hold a value.  The attribute-sharded drivers do not take the
+        keyword."""
+        for name in ('permutation_strata', 'permutation_strata_bins'):
+            if name in kwargs:
+                setattr(self, name, kwargs[name])
         if 'multiple_testing_scope' in kwargs:
             self.multiple_testing_scope = kwargs['multiple_testing_scope']
         if 'how' in kwargs:
@@ -928,6 +1014,14 @@ class SAFE:
         ranked = self.attribute_transform == 'rank'
         if ranked and self.enrichment_type == 'hypergeometric':
             self._refuse_hypergeom_on_ranks()                  # before any device work
+        stratified = self.permutation_strata is not None
+        if stratified:                                         # before any device work, too
+            if self.enrichment_type == 'analytic':
+                raise ValueError("permutation_strata does not go with how = 'analytic': the stratified permutation moments are "
+                                 "not implemented; use how = 'randomization'")
+            if self.enrichment_type == 'hypergeometric':
+                self._refuse_hypergeom_on_strata()
+            self._resolve_permutation_strata(self.node2attribute.shape[0], check_only=True)     # (bad labels are refused here)
 
         resident = self._resident_attributes()
         if self.background == 'network':
@@ -968,6 +1062,8 @@ class SAFE:
                                 "Consider setting sf.background = 'network'.")
             hypergeom = (self.enrichment_type == 'hypergeometric') or \
                 ((self.enrichment_type == 'auto') and (stats['n_other'] == 0))      # ('auto' looks at the raw values)
+            if stratified and hypergeom:
+                self._refuse_hypergeom_on_strata()
             if ranked:
                 if hypergeom:
                     self._refuse_hypergeom_on_ranks()
@@ -1014,17 +1110,25 @@ class SAFE:
         logging.info('Using randomization to calculate enrichment...')
         if 'num_permutations' in kwargs:
             self.num_permutations = kwargs['num_permutations']
+        for name in ('permutation_strata', 'permutation_strata_bins'):
+            if name in kwargs:
+                setattr(self, name, kwargs[name])
         self.validate_config()
         score_type = 'z-score' if self.neighborhood_score_type == 'z-score' else 'sum'
 
+        strata = None
+        if self.permutation_strata is not None:            # (refusals come before any device work)
+            strata = self._resolve_permutation_strata(_attr.n if _attr is not None else self.node2attribute.shape[0])
         ctx = self._ctx()
         nbr = self._device_neighborhoods()
         attr = _attr if _attr is not None else self._upload_attributes()
         n, m = attr.n, attr.m
-        # random_seed=None (the default, like the reference's): the tables are generated on the device (backend.Permutations);
-        # `device_stream_key` (None = OS entropy) makes such a run repeatable for tests and debugging
-        perms = be.Permutations(ctx, n, attr.row_flags(), self.num_permutations, self.random_seed,
-                                device_key=getattr(self, 'device_stream_key', None))
+        try:
+            perms = self._permutations(ctx, attr, strata)
+        except Exception:
+            if _attr is None:
+                attr.close()
+            raise
         bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
         try:
             be.randomization(ctx, nbr, attr, perms, score_type, self.attribute_sign, self.enrichment_threshold,
@@ -1089,6 +1193,50 @@ class SAFE:
                 b.free()
             if _attr is None:
                 attr.close()
+
+    def _permutations(self, ctx, attr, strata):
+        """The permutation tables of a randomization call over the rows of `attr` that hold a value.  strata = None: the free
+        shuffle -- the NumPy-compatible stream of an integer random_seed, or (random_seed = None, the default, like the
+        reference's) tables generated on the device; `device_stream_key` (None = OS entropy) makes such a run repeatable for
+        tests and debugging.  strata = int32 [N] ranks: restricted permutations generated on the device, keyed by the integer
+        random_seed or, without one, like the unseeded route; sets permutation_strata_resolved / permutation_strata_sizes."""
+        flags = attr.row_flags()
+        if strata is None:
+            return be.Permutations(ctx, attr.n, flags, self.num_permutations, self.random_seed,
+                                   device_key=getattr(self, 'device_stream_key', None))
+        movable = int(np.count_nonzero(flags))
+        if movable > 65535:
+            raise ValueError('permutation_strata: %d rows hold a value, the restricted permutations are generated for at most '
+                             '65535' % movable)
+        key = getattr(self, 'device_stream_key', None)
+        if self.random_seed is not None:
+            key = int(self.random_seed)
+            if key < 0 or key > 0xFFFFFFFF:
+                raise ValueError('Seed must be between 0 and 2**32 - 1')
+        perms = be.Permutations.stratified(ctx, attr.n, flags, strata, self.num_permutations, key)
+        self.permutation_strata_resolved = strata
+        self.permutation_strata_sizes = np.bincount(strata[flags != 0], minlength=int(strata.max()) + 1).astype(np.int64)
+        return perms
+
+    def _resolve_permutation_strata(self, n, check_only=False):
+        """int32 [N]: every node's stratum under the current permutation_strata setting (not None).  ValueError for labels that
+        do not fit the nodes and for 'neighborhood_size' without neighborhoods.  check_only: the refusals alone, nothing read
+        from the device."""
+        if isinstance(self.permutation_strata, str):       # 'neighborhood_size' (validate_config)
+            if self._nbr is None and self._neighborhoods_host is None:
+                raise ValueError("permutation_strata = 'neighborhood_size' needs neighborhoods: call define_neighborhoods() first")
+            if check_only:
+                return None
+            counts = self._device_neighborhoods().row_counts()
+            if len(counts) != n:
+                raise ValueError('permutation_strata: the neighborhoods cover %d nodes, the attributes %d' % (len(counts), n))
+            return _neighborhood_size_strata(counts, int(self.permutation_strata_bins))
+        return _factorise_strata(self.permutation_strata, n)
+
+    def _refuse_hypergeom_on_strata(self):
+        raise ValueError("permutation_strata restricts the permutations of the randomization test; this call takes the "
+                         "hypergeometric test (how = '%s'%s), which has none: pass how = 'randomization'"
+                         % (self.enrichment_type, ' on 0/1 attribute values' if self.enrichment_type == 'auto' else ''))
 
     def _require_sum_scores_for_moments(self):
         if self.neighborhood_score_type != 'sum':
