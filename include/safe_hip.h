@@ -26,7 +26,8 @@
  *     context's stream like them but return only once it has drained, because they read
  *     a flag or a timing event back or keep host memory alive for their kernels:
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
- *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_fdr_adjust, safe_fdr_adjust_rows,
+ *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_score_weighted, safe_moments_test_weighted,
+ *     safe_permtest_counts_weighted, safe_fdr_adjust, safe_fdr_adjust_rows,
  *     safe_fdr_adjust_scope, safe_fdr_adjust_matrix,
  *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
@@ -579,6 +580,62 @@ int safe_hypergeom_outputs(safe_ctx *ctx, int64_t n, int64_t m, int sign_mode, d
 int safe_moments_test(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int sign_mode, double enrichment_threshold,
                       int64_t col0, int64_t col1, double *ns_dev, double *pvalues_neg_dev, double *pvalues_pos_dev,
                       double *nes_dev, double *nes_binary_dev, double *num_enriched_dev, double *z_dev /* may be NULL */);
+
+/* ---- distance-weighted neighborhoods (weights.hip) ---------------------------------------------------------------------
+ * A membership handle may carry one weight w_ik >= 0 per member k of row i.  Weights change nothing any entry point above
+ * computes on the handle; only the three *_weighted entry points below read them.  All arithmetic is f64, every operation
+ * rounded, in the order written (the library is built with -ffp-contract=off).
+ *   members     of row i = its CSR entries (safe_nbr_csr), in ascending column order
+ *   D[i,k]      the node distance: sqrt(dx*dx + dy*dy) of the coordinates (the bits of scipy's pdist), or the matrix a
+ *               shortest-path handle kept
+ *   u           D[i,k] / r_i, and u = 0 when r_i == 0 (0 / 0 is never evaluated); r_i = radii_host[i]; h = bandwidth
+ *   kind        SAFE_WEIGHT_UNIFORM       1.0
+ *               SAFE_WEIGHT_TRIANGULAR    max(0, 1 - u)
+ *               SAFE_WEIGHT_EPANECHNIKOV  max(0, 1 - u*u)
+ *               SAFE_WEIGHT_GAUSSIAN      exp(-0.5 * (t*t)), t = u / h (the argument is exact to the contract; the device's exp
+ *                                         is faithfully rounded, not NumPy's bits)
+ * A member whose weight is 0 stays a member: the stored pattern is the membership's, with explicit zeros.
+ * safe_nbr_weights_from_xy: xy_host f64 [n,2] row-major.  safe_nbr_weights_from_distances: from the kept matrix.  Both take
+ * radii_host f64 [n] and build the weights on the device.  Refusals: a non-finite coordinate, a NaN or negative radius, a
+ * bandwidth that is not finite and > 0 (read for every kind) SAFE_E_VALUE; no kept distances, an unknown kind, a NULL argument
+ * SAFE_E_INVALID.  safe_nbr_set_weights installs the caller's weights, f64 [nnz] in CSR order; a NaN, infinite or negative one
+ * is SAFE_E_VALUE.  safe_nbr_weights reads them back in CSR order (SAFE_E_INVALID without weights); safe_nbr_clear_weights
+ * removes them.  A refused call leaves the handle's previous weights, or lack of them, as they were.  Synchronous. */
+#define SAFE_WEIGHT_UNIFORM 0
+#define SAFE_WEIGHT_TRIANGULAR 1
+#define SAFE_WEIGHT_EPANECHNIKOV 2
+#define SAFE_WEIGHT_GAUSSIAN 3
+int safe_nbr_weights_from_xy(safe_nbr *nbr, const double *xy_host, int kind, const double *radii_host, double bandwidth);
+int safe_nbr_weights_from_distances(safe_nbr *nbr, int kind, const double *radii_host, double bandwidth);
+int safe_nbr_set_weights(safe_nbr *nbr, const double *w_host);
+int safe_nbr_weights(safe_nbr *nbr, double *out_host);
+int safe_nbr_clear_weights(safe_nbr *nbr);
+
+/* The weighted 'sum' score of columns [col0, col1): ns_dev f64 [n, col1 - col0] row-major,
+ *   x_ij = (((0.0 + w_i,k1 * v_k1,j) + w_i,k2 * v_k2,j) + ...)   over the members in ascending k,
+ * v = the attribute value widened to f64, NaN -> 0; one accumulator per cell, every product and every sum rounded: this order
+ * is the contract.  SAFE_E_INVALID when the handle has no weights.  safe_last_kernel_stats names k_score_weighted (lanes along
+ * contiguous columns), or k_permtest_weighted for row-contiguous (Fortran-order) storage: the same sums in the same order. */
+int safe_score_weighted(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int64_t col0, int64_t col1, double *ns_dev);
+
+/* safe_moments_test for the weighted score.  Per row, over the members with row_flags = 1 in ascending k: W1_i = sum w,
+ * W2_i = sum w*w, c_i their number, and the smallest and the largest w.  With n_v, mu_j, Q_j of safe_attr_column_moments:
+ *   g_i = (n_v*W2_i - W1_i*W1_i) / (n_v*(n_v - 1));  var = g_i * Q_j;  z = (x_ij - W1_i*mu_j) / sqrt(var)
+ *   g_i := 0 when n_v < 2, or c_i = 0, or c_i = n_v and the smallest flagged weight equals the largest (the whole population
+ *   at one weight: decided on min / max, because equal non-dyadic weights leave dust), or the computed value is not positive
+ * A cell with var not positive gets pvalues_pos = pvalues_neg = 1 and z = 0.  Tails, nes, nes_binary and the counts are
+ * safe_moments_test's.  With all weights 1.0 g_i has the bits of its f_i.  safe_last_kernel_stats names k_weights_emit. */
+int safe_moments_test_weighted(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, int sign_mode, double enrichment_threshold,
+                               int64_t col0, int64_t col1, double *ns_dev, double *pvalues_neg_dev, double *pvalues_pos_dev,
+                               double *nes_dev, double *nes_binary_dev, double *num_enriched_dev, double *z_dev /* may be NULL */);
+
+/* safe_permtest_counts for the weighted score ('sum' only): with T_p = row p of the permutation table as safe_perms_read
+ * delivers it, S_p[i,j] = the weighted score with v taken at row T_p[k] instead of k, same order;
+ * counts_pos = #{p : S_p >= x}, counts_neg = #{p : S_p <= x} as f64 [n, col1 - col0]; ns_dev may be NULL.  Any safe_perms
+ * handle.  safe_outputs_from_counts turns the counts into p-values, nes and nes_binary.  safe_last_kernel_stats names
+ * k_permtest_weighted. */
+int safe_permtest_counts_weighted(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1,
+                                  double *ns_dev, double *counts_neg_dev, double *counts_pos_dev);
 
 /* ---- consumers of nes_binary (SAFE.define_top_attributes / define_domains) ---------------- */
 /* Connected components of the subgraph induced by the enriched nodes of each candidate

@@ -524,6 +524,7 @@ class Neighborhoods:
         n, nnz, mx = C.c_int64(), C.c_int64(), C.c_int64()
         check(lib.safe_nbr_info(handle, C.byref(n), C.byref(nnz), C.byref(mx)))
         self.n, self.nnz, self.max_row_count = n.value, nnz.value, mx.value
+        self.has_weights = False         # set_weights* / clear_weights
 
     @classmethod
     def euclidean(cls, ctx, xy, nr):
@@ -626,6 +627,47 @@ class Neighborhoods:
         check(lib.safe_nbr_distance_select(self.handle, _ptr(rk) if rk.size else None, rk.shape[0],
                                            _ptr(out) if rk.size else None, C.byref(count)))
         return out, count.value
+
+    # ---- distance weights: one f64 per member, in the order of csr() (weights.hip) ----
+    @staticmethod
+    def _weight_kind(kind):
+        if kind not in _lib.WEIGHT_KINDS:
+            raise ValueError('%r is not a weight kind. Valid options are: %s' % (kind, ', '.join(_lib.WEIGHT_KINDS)))
+        return _lib.WEIGHT_KINDS[kind]
+
+    def set_weights_from_xy(self, xy, kind, radii, bandwidth=0.5):
+        """Weights of every member from the pdist distance of the coordinates and the row's radius
+        (safe_nbr_weights_from_xy); kind: 'uniform', 'triangular', 'epanechnikov', 'gaussian'; radii: a number or one per node."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.shape != (self.n, 2):
+            raise ValueError('set_weights_from_xy: xy must be [%d, 2], got shape %s' % (self.n, xy.shape))
+        r = self._radii(np.broadcast_to(np.asarray(radii, dtype=np.float64), (self.n,)), self.n, 'set_weights_from_xy')
+        check(lib.safe_nbr_weights_from_xy(self.handle, _ptr(xy), self._weight_kind(kind), _ptr(r), float(bandwidth)))
+        self.has_weights = True
+
+    def set_weights_from_distances(self, kind, radii, bandwidth=0.5):
+        """The same from the distance matrix the handle kept (safe_nbr_weights_from_distances)."""
+        r = self._radii(np.broadcast_to(np.asarray(radii, dtype=np.float64), (self.n,)), self.n, 'set_weights_from_distances')
+        check(lib.safe_nbr_weights_from_distances(self.handle, self._weight_kind(kind), _ptr(r), float(bandwidth)))
+        self.has_weights = True
+
+    def set_weights(self, w):
+        """The caller's weights, f64 [nnz] in the order of csr(), finite and >= 0 (safe_nbr_set_weights)."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.nnz,):
+            raise ValueError('set_weights: one weight per member, shape (%d,), got %s' % (self.nnz, w.shape))
+        check(lib.safe_nbr_set_weights(self.handle, _ptr(w)))
+        self.has_weights = True
+
+    def weights(self):
+        """f64 [nnz] in the order of csr() (safe_nbr_weights); SafeHipError when the handle has none."""
+        out = np.empty(max(self.nnz, 1), dtype=np.float64)
+        check(lib.safe_nbr_weights(self.handle, _ptr(out)))
+        return out[:self.nnz]
+
+    def clear_weights(self):
+        check(lib.safe_nbr_clear_weights(self.handle))
+        self.has_weights = False
 
     def close(self):
         if self.handle:
@@ -1336,6 +1378,26 @@ def moments_test(ctx, nbr, attr, attribute_sign, enrichment_threshold, out_ptrs,
     col1 = attr.m if col1 is None else col1
     check(lib.safe_moments_test(ctx.handle, nbr.handle, attr.handle, _SIGN[attribute_sign], float(enrichment_threshold), col0, col1,
                                 *[C.c_void_p(p) if p else None for p in tuple(out_ptrs) + (z_ptr,)]))
+
+
+def score_weighted(ctx, nbr, attr, out_ptr, col0=0, col1=None):
+    """The weighted 'sum' score of a handle that carries weights (safe_score_weighted): f64 [n, col1 - col0] at out_ptr."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_score_weighted(ctx.handle, nbr.handle, attr.handle, col0, col1, C.c_void_p(out_ptr)))
+
+
+def moments_test_weighted(ctx, nbr, attr, attribute_sign, enrichment_threshold, out_ptrs, col0=0, col1=None, z_ptr=None):
+    """moments_test for the weighted score (safe_moments_test_weighted): the same out_ptrs and z_ptr."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_moments_test_weighted(ctx.handle, nbr.handle, attr.handle, _SIGN[attribute_sign], float(enrichment_threshold), col0,
+                                         col1, *[C.c_void_p(p) if p else None for p in tuple(out_ptrs) + (z_ptr,)]))
+
+
+def permtest_counts_weighted(ctx, nbr, attr, perms, ns_ptr, neg_ptr, pos_ptr, col0=0, col1=None):
+    """permtest_counts for the weighted 'sum' score (safe_permtest_counts_weighted); ns_ptr may be None."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_permtest_counts_weighted(ctx.handle, nbr.handle, attr.handle, perms.handle, col0, col1,
+                                            C.c_void_p(ns_ptr) if ns_ptr else None, C.c_void_p(neg_ptr), C.c_void_p(pos_ptr)))
 
 
 def fdr_adjust_rows(ctx, n, m, p_ptr):

@@ -137,6 +137,13 @@ enum ScratchSlot {
                             //   readback words | safe_go_create | within the call
     SCRATCH_FDR_SCOPE,      // 64-bit histogram [P + 1] | adjusted values f64 [P + 1] | u32 flags of the whole-matrix count form |
                             //   safe_fdr_adjust_scope, safe_fdr_adjust_matrix (fdr.hip) | within the call
+    SCRATCH_WEIGHT_INPUTS,  // radii f64 [n] | layout f64 [n][2] | safe_nbr_weights_from_xy, safe_nbr_weights_from_distances (weights.hip) |
+                            //   within the call
+    SCRATCH_WEIGHT_ROWS,    // weight sums W1 f64 [n] | row factors g f64 [n] | column means f64 [mloc] | centred sums of squares f64
+                            //   [mloc] | enriched counters u32 [mloc + 16] | safe_moments_test_weighted (weights.hip) | within the call
+    SCRATCH_WEIGHT_TILES,   // the attribute operand of the weighted permutation kernel: f64 tiles [tile][n + 1][16] |
+                            //   safe_permtest_counts_weighted, and the weighted score of row-contiguous storage (weights.hip) |
+                            //   within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,
@@ -393,6 +400,9 @@ struct safe_nbr {
     std::vector<int64_t> h_slice_off;
     std::vector<int32_t> h_row_count;   // host copy of per-row counts
     double *dist = nullptr;         // optional [n][n]
+    // distance weights (weights.hip), or NULL: one f64 per member.  No entry point outside weights.hip reads them.
+    double *w_csr = nullptr;        // [nnz] in CSR order
+    double *w_sell = nullptr;       // [sell_entries] beside sell_col, padding entries 0.0
     // CSR of the transpose (column k -> rows i with A[i,k] = 1), built on first use
     int32_t *at_ptr = nullptr;      // [n+1]
     int32_t *at_col = nullptr;      // [nnz], unordered inside a column
@@ -590,6 +600,8 @@ struct safe_perms {
 };
 
 int safe_attr_prepare(safe_attr *attr);   // row flags + stats (attr.hip)
+// mu_j and Q_j of columns [col0, col1) into d_mean / d_css [col1 - col0], enqueued on the context's stream (moments.hip)
+int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col1, const char *who, double *d_mean, double *d_css);
 int nbr_finalize_from_bits(safe_nbr *nbr);   // bits -> CSR + SELL (nbr.hip)
 int nbr_build_transpose(safe_nbr *nbr);      // at_ptr / at_col (nbr.hip)
 int attr_build_support(safe_attr *attr);     // sup_ptr / sup_row of a binary matrix (attr.hip)

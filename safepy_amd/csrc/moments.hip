@@ -181,7 +181,9 @@ __global__ __launch_bounds__(256) void k_moments_emit(const MomentsEmit e) {
     }
 }
 
-// mu_j and Q_j of columns [col0, col1) into d_mean / d_css [col1 - col0], enqueued on the context's stream
+}  // namespace
+
+// mu_j and Q_j of columns [col0, col1) into d_mean / d_css [col1 - col0], enqueued on the context's stream (also weights.hip)
 int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col1, const char *who, double *d_mean, double *d_css) {
     const int64_t n = attr->n, mloc = col1 - col0, chunks = ceil_div(n, MOM_ROW_CHUNK);
     const double nv = static_cast<double>(attr->n_rows_with_value);
@@ -205,8 +207,6 @@ int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col
     SAFE_HIP_CHECK_AS(who, hipGetLastError());
     return SAFE_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -746,7 +746,8 @@ static void nbr_free(safe_nbr *nbr) {
     for (const void *q : {(const void *)nbr->bits, (const void *)nbr->row_ptr, (const void *)nbr->col, (const void *)nbr->sell_row,
                           (const void *)nbr->sell_pos, (const void *)nbr->slice_off, (const void *)nbr->slice_width,
                           (const void *)nbr->sell_col, (const void *)nbr->sell_col2, (const void *)nbr->sell_col2b,
-                          (const void *)nbr->dist, (const void *)nbr->at_ptr, (const void *)nbr->at_col})
+                          (const void *)nbr->dist, (const void *)nbr->at_ptr, (const void *)nbr->at_col, (const void *)nbr->w_csr,
+                          (const void *)nbr->w_sell})
         (void)dev_free(q);
     nbr_free_blocks(nbr);
     if (nbr->bits_plan_pinned) (void)hipHostFree(nbr->bits_plan_pinned);

@@ -10,7 +10,9 @@ three tables, the node-by-attribute text made on the device; `save()` pickles th
 (`plot_network`, `plot_sample_attributes`, `plot_composite_network`, `plot_composite_network_contours`) draw with
 matplotlib, imported when they run; their data-parallel parts run on the device (plot.hip).  Additive:
 `enriched_pairs()` / `enriched_table()` return the enriched (node, attribute) pairs as a scipy.sparse array / a long
-DataFrame, compacted on the device while the result matrices are still there (pairs.hip).  The MATLAB / Cytoscape
+DataFrame, compacted on the device while the result matrices are still there (pairs.hip).  Additive:
+`neighborhood_weighting` gives every member of a neighborhood a distance-decay weight (`neighborhood_weights`,
+`set_neighborhood_weights`; weights.hip) and `compute_pvalues` tests the weighted sum.  The MATLAB / Cytoscape
 loaders are out of scope.
 """
 import configparser
@@ -45,6 +47,39 @@ _DEFAULTS = {
     'permutationStrata': '',
     'permutationStrataBins': '10',
 }
+
+
+_WEIGHTINGS = ('none', 'uniform', 'triangular', 'epanechnikov', 'gaussian', 'custom')     # neighborhood_weighting
+
+
+def _member_weights(w, indptr, indices):
+    """set_neighborhood_weights: the weights of W -- scipy.sparse or dense [N, N] -- on the members of a CSR membership, f64
+    [nnz] in its order, 0 where W stores nothing.  ValueError for a wrong shape, a negative, NaN or infinite value, and a
+    non-zero entry outside the membership."""
+    n = len(indptr) - 1
+    if np.ndim(w) != 2 or tuple(np.shape(w)) != (n, n):
+        raise ValueError('neighborhood weights must be a [%d, %d] matrix, got shape %s' % (n, n, tuple(np.shape(w))))
+    rows = np.repeat(np.arange(n), np.diff(indptr))
+    if be._is_sparse(w):
+        from scipy import sparse
+        w = sparse.csr_array(w, dtype=np.float64)
+        w.sum_duplicates()
+        stored = w.data
+        data = np.asarray(w[rows, indices], dtype=np.float64).reshape(-1) if len(rows) else np.zeros(0)
+        outside = np.count_nonzero(stored) != np.count_nonzero(data)      # every member entry is a stored one or 0
+    else:
+        w = np.asarray(w, dtype=np.float64)
+        stored = w
+        data = w[rows, indices]
+        mask = np.ones(w.shape, dtype=bool)
+        mask[rows, indices] = False
+        outside = bool(np.any(w[mask] != 0))
+    if not np.all(np.isfinite(stored)) or np.any(stored < 0):
+        raise ValueError('neighborhood weights must be finite and >= 0')
+    if outside:
+        raise ValueError('neighborhood weights hold a non-zero entry outside the membership: a node that is not a member of a '
+                         'neighborhood cannot carry weight in it')
+    return np.ascontiguousarray(data, dtype=np.float64)
 
 
 def _neighborhood_size_strata(counts, bins):
@@ -278,6 +313,10 @@ class SAFE:
         self.neighborhood_radius = None
         self.neighborhood_radius_resolved = None     # the radius the last define_neighborhoods / compute_node_distances used (float)
         self.neighborhood_radii = None               # 'nearest' only: every node's own radius, f64 [N] (resolved = their median)
+        # distance-weighted neighborhood scores (define_neighborhoods, set_neighborhood_weights): 'none' (flat, the reference),
+        # 'uniform', 'triangular', 'epanechnikov', 'gaussian' (with neighborhood_weight_bandwidth), 'custom'
+        self.neighborhood_weighting = 'none'
+        self.neighborhood_weight_bandwidth = 0.5
 
         self.background = 'attribute_file'
         self.num_permutations = 1000
@@ -325,6 +364,7 @@ class SAFE:
         self.lazy_outputs = True         # result matrices stay on the device until first read (_LazyArray)
         self._nbr = None                 # backend.Neighborhoods matching _neighborhoods_host / lazily downloaded
         self._neighborhoods_host = None
+        self._weights_host = None        # (indptr, indices, data) of neighborhood_weights once fetched or given; pickled
         self._node_distances = None
         self._pending_binary = None
         self._attr_dev = None            # resident node2attribute (load_attributes(keep_on_device=True))
@@ -436,6 +476,16 @@ class SAFE:
         if not isinstance(bins, (int, np.integer)) or isinstance(bins, (bool, np.bool_)) or bins < 1:
             self.permutation_strata_bins = 10
             raise ValueError('permutation_strata_bins = %r is not valid: it must be an integer equal or greater than 1.' % (bins,))
+        weighting = getattr(self, 'neighborhood_weighting', 'none')
+        if not isinstance(weighting, str) or weighting not in _WEIGHTINGS:
+            self.neighborhood_weighting = 'none'
+            raise ValueError('%s is not a valid setting for neighborhood_weighting. '
+                             'Valid options are: %s' % (weighting, ', '.join(_WEIGHTINGS)))
+        bandwidth = getattr(self, 'neighborhood_weight_bandwidth', 0.5)
+        if not _is_real(bandwidth) or not np.isfinite(bandwidth) or bandwidth <= 0:
+            self.neighborhood_weight_bandwidth = 0.5
+            raise ValueError('neighborhood_weight_bandwidth = %r is not valid: it must be a finite number greater than 0.'
+                             % (bandwidth,))
         if getattr(self, 'attribute_transform', 'none') not in ['none', 'rank']:
             bad, self.attribute_transform = self.attribute_transform, 'none'
             raise ValueError('%s is not a valid setting for attribute_transform. '
@@ -472,6 +522,7 @@ class SAFE:
     def __getstate__(self):
         for name in ('ns', 'pvalues_neg', 'pvalues_pos', 'nes', 'nes_binary'):
             getattr(self, name)              # results still on the device come to the host first
+        self.neighborhood_weights            # (weights still on the device become _weights_host: host arrays)
         nd = self._node_distances
         if isinstance(nd, tuple) and nd[0] == 'device-shortpath':
             self._node_distances = ('dense-shortpath', nd[1].distances())
@@ -505,6 +556,9 @@ class SAFE:
         self.__dict__.setdefault('permutation_strata_bins', 10)
         self.__dict__.setdefault('permutation_strata_resolved', None)
         self.__dict__.setdefault('permutation_strata_sizes', None)
+        self.__dict__.setdefault('neighborhood_weighting', 'none')
+        self.__dict__.setdefault('neighborhood_weight_bandwidth', 0.5)
+        self.__dict__.setdefault('_weights_host', None)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -714,8 +768,50 @@ class SAFE:
     def neighborhoods(self, value):
         self._invalidate_neighborhoods()
         self._neighborhoods_host = value
+        if getattr(self, 'neighborhood_weighting', 'none') == 'custom':      # the weights went with the membership they were for
+            self.neighborhood_weighting = 'none'
+
+    @property
+    def neighborhood_weights(self):
+        """Additive, read-only: the weights of the members of every neighborhood as a scipy.sparse.csr_array, f64 [N, N], with
+        the pattern of the membership -- a member at weight 0 is a stored zero -- or None under neighborhood_weighting = 'none'
+        (and for a membership that carries no weights).  Fetched from the device on first read."""
+        if getattr(self, 'neighborhood_weighting', 'none') == 'none':
+            return None
+        if self._weights_host is None:
+            if self._nbr is None or not self._nbr.has_weights:
+                return None
+            indptr, indices = self._nbr.csr()
+            self._weights_host = (indptr, indices, self._nbr.weights())
+        from scipy import sparse
+        indptr, indices, data = self._weights_host
+        n = len(indptr) - 1
+        return sparse.csr_array((data.copy(), indices.copy(), indptr.copy()), shape=(n, n))
+
+    def set_neighborhood_weights(self, W):
+        """Additive: custom weights for the members of the current neighborhoods (after define_neighborhoods, or an assigned
+        `neighborhoods`).  W: scipy.sparse or dense [N, N], finite and >= 0; members W does not store get 0 and stay members.
+        A wrong shape, a negative, NaN or infinite value, or a non-zero entry outside the membership is a ValueError that
+        changes nothing.  Sets neighborhood_weighting = 'custom'."""
+        nbr = self._device_neighborhoods()
+        indptr, indices = nbr.csr()
+        data = _member_weights(W, indptr, indices)
+        nbr.set_weights(data)
+        self._weights_host = (indptr, indices, data)
+        self.neighborhood_weighting = 'custom'
+
+    def _weighted(self):
+        """True when compute_pvalues scores the neighborhoods with weights; ValueError when the setting asks for weights that
+        the current membership does not carry."""
+        if getattr(self, 'neighborhood_weighting', 'none') == 'none':
+            return False
+        if self._weights_host is None and (self._nbr is None or not self._nbr.has_weights):
+            raise ValueError("neighborhood_weighting = '%s' but the neighborhoods carry no weights: call define_neighborhoods() "
+                             "or set_neighborhood_weights()" % self.neighborhood_weighting)
+        return True
 
     def _invalidate_neighborhoods(self):
+        self._weights_host = None
         nd = self._node_distances
         if isinstance(nd, tuple) and nd[0] == 'device-shortpath':     # still on the device, owned by the handle that goes away
             self._node_distances = ('dense-shortpath', nd[1].distances()) if nd[1] is self._nbr and nd[1].handle else None
@@ -732,7 +828,9 @@ class SAFE:
             if self._neighborhoods_host is None:
                 raise RuntimeError('neighborhoods are not defined: call define_neighborhoods() first')
             self._nbr = be.Neighborhoods.from_dense(self._ctx(), self._neighborhoods_host)
-            try:                          # a layout, when the graph has one, only orders the nodes on the device
+            if self._weights_host is not None:        # (an unpickled object: the weights travel as host arrays)
+                self._nbr.set_weights(self._weights_host[2])
+            try:                         # a layout, when the graph has one, only orders the nodes on the device
                 xy = _graph_arrays(self.graph)[0]
                 if xy.shape == (self._nbr.n, 2) and np.isfinite(xy).all():
                     self._nbr.set_layout(xy)
@@ -771,6 +869,9 @@ class SAFE:
             self.neighborhood_radius_type = kwargs['neighborhood_radius_type']
         if 'neighborhood_radius' in kwargs:
             self.neighborhood_radius = kwargs['neighborhood_radius']
+        for name in ('neighborhood_weighting', 'neighborhood_weight_bandwidth'):
+            if name in kwargs:
+                setattr(self, name, kwargs[name])
         self.validate_config()
 
     def _shortpath_weights(self, xy, eu, ev, length, weight):
@@ -874,8 +975,21 @@ class SAFE:
         k-th nearest other node (the farthest reached one where fewer exist, 0.0 where none does; node i is left out by index, so a
         coincident node counts), and j is a member of row i iff D[i, j] <= r_i -- the diagonal always, every tie at the k-th
         distance, never an unreached node.  The membership is in general not symmetric.  Sets neighborhood_radii (f64 [N]) and
-        neighborhood_radius_resolved (their median); node_distances holds the distances inside every node's own radius."""
+        neighborhood_radius_resolved (their median); node_distances holds the distances inside every node's own radius.
+
+        neighborhood_weighting (additive; keyword or setting, default 'none' = flat neighborhoods and today's bytes), with
+        neighborhood_weight_bandwidth (default 0.5, finite and > 0, read by 'gaussian' only): a distance-decay weight for every
+        member k of every neighborhood i, from u = D[i, k] / r_i (u = 0 where r_i = 0), D the node distance of the metric and
+        r_i = neighborhood_radius_resolved, or neighborhood_radii[i] under 'nearest':
+          'uniform' 1 | 'triangular' max(0, 1 - u) | 'epanechnikov' max(0, 1 - u u) | 'gaussian' exp(-0.5 (u / h)^2)
+        built on the device beside the membership and read back as neighborhood_weights.  A member at weight 0 stays a member.
+        compute_pvalues then tests the weighted 'sum' score.  'custom' here is a ValueError: build the neighborhoods first, then
+        call set_neighborhood_weights(W).  The shortest-path metrics build the weights from the N x N matrix the handle keeps."""
         self._override_neighborhood_settings(kwargs)
+        weighting = self.neighborhood_weighting
+        if weighting == 'custom':                    # before any device work; nothing changes
+            raise ValueError("neighborhood_weighting = 'custom' is not something define_neighborhoods can build: define the "
+                             "neighborhoods under another setting (or 'none'), then give the weights to set_neighborhood_weights()")
         xy, eu, ev, length, weight = _graph_arrays(self.graph)
         ctx = self._ctx()
         if self.node_distance_metric != 'euclidean':
@@ -898,6 +1012,12 @@ class SAFE:
             self._nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, radius, keep_distances=True)
             self._nbr.set_layout(xy)
             self._node_distances = ('device-shortpath', self._nbr)
+        if weighting != 'none':
+            radii = self.neighborhood_radii if nearest else self.neighborhood_radius_resolved
+            if self.node_distance_metric == 'euclidean':
+                self._nbr.set_weights_from_xy(xy, weighting, radii, self.neighborhood_weight_bandwidth)
+            else:
+                self._nbr.set_weights_from_distances(weighting, radii, self.neighborhood_weight_bandwidth)
         if self.verbose:
             num_neighbors = self._nbr.row_counts()
             logging.info('Node distance metric: %s' % self.node_distance_metric)
@@ -990,7 +1110,17 @@ class SAFE:
         value, per stratum) are set.  Refused with a ValueError that leaves every result as it was: how = 'analytic' (the
         stratified moments are not implemented), a hypergeometric route ('auto' on 0/1 data included: pass
         how = 'randomization'), more than 65535 rows that hold a value.  The attribute-sharded drivers do not take the
-        keyword."""
+        keyword.
+
+        neighborhood_weighting other than 'none' (additive; a setting of define_neighborhoods / set_neighborhood_weights): the
+        neighborhoods carry weights and ns holds the weighted sums x_ij = sum_k w_ik v_kj, added over the members in ascending
+        node order.  how = 'analytic' evaluates the exact permutation moments of that weighted sum (mean W1_i mu_j, variance
+        (n_v W2_i - W1_i^2) / (n_v (n_v - 1)) Q_j) and normal tails; how = 'randomization', and 'auto' on values other than
+        0/1, count the permuted weighted scores.  multiple_testing and its scope, permutation_strata, attribute_transform =
+        'rank', background = 'network', the three signs and lazy_outputs work as without weights.  Refused with a ValueError
+        before any result changes: a hypergeometric route ('auto' on 0/1 data included: pass how = 'analytic' or
+        how = 'randomization') and neighborhood_score_type = 'z-score'.  safe_extras, safepy_amd.sharding and run_batch.py do
+        not take the setting: they score flat neighborhoods."""
         for name in ('permutation_strata', 'permutation_strata_bins'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
@@ -1022,6 +1152,11 @@ class SAFE:
             if self.enrichment_type == 'hypergeometric':
                 self._refuse_hypergeom_on_strata()
             self._resolve_permutation_strata(self.node2attribute.shape[0], check_only=True)     # (bad labels are refused here)
+        weighted = self._weighted()                            # before any device work, too
+        if weighted:
+            self._require_sum_scores_for_weights()
+            if self.enrichment_type == 'hypergeometric':
+                self._refuse_hypergeom_on_weights()
 
         resident = self._resident_attributes()
         if self.background == 'network':
@@ -1064,6 +1199,8 @@ class SAFE:
                 ((self.enrichment_type == 'auto') and (stats['n_other'] == 0))      # ('auto' looks at the raw values)
             if stratified and hypergeom:
                 self._refuse_hypergeom_on_strata()
+            if weighted and hypergeom:
+                self._refuse_hypergeom_on_weights()
             if ranked:
                 if hypergeom:
                     self._refuse_hypergeom_on_ranks()
@@ -1115,6 +1252,9 @@ class SAFE:
                 setattr(self, name, kwargs[name])
         self.validate_config()
         score_type = 'z-score' if self.neighborhood_score_type == 'z-score' else 'sum'
+        weighted = self._weighted()                        # (refusals come before any device work)
+        if weighted:
+            self._require_sum_scores_for_weights()
 
         strata = None
         if self.permutation_strata is not None:            # (refusals come before any device work)
@@ -1131,9 +1271,19 @@ class SAFE:
             raise
         bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
         try:
-            be.randomization(ctx, nbr, attr, perms, score_type, self.attribute_sign, self.enrichment_threshold,
-                             [b.ptr for b in bufs])
-            if self.multiple_testing:                  # safe.py:536-542, then 546-554 and 468-472 on the adjusted values
+            if weighted:                               # the weighted counts, then the epilogue every count route shares
+                counts = [ctx.alloc_f64(n, m) for _ in range(2)]
+                try:
+                    be.permtest_counts_weighted(ctx, nbr, attr, perms, bufs[0].ptr, counts[0].ptr, counts[1].ptr)
+                    be.outputs_from_counts(ctx, n, m, self.num_permutations, self.attribute_sign, self.enrichment_threshold,
+                                           counts[0].ptr, counts[1].ptr, bufs[0].ptr, [b.ptr for b in bufs[1:]])
+                finally:
+                    for b in counts:
+                        b.free()
+            else:
+                be.randomization(ctx, nbr, attr, perms, score_type, self.attribute_sign, self.enrichment_threshold,
+                                 [b.ptr for b in bufs])
+            if self.multiple_testing:                 # safe.py:536-542, then 546-554 and 468-472 on the adjusted values
                 logging.info('Running FDR-adjustment of p-values...')
                 self._fdr_adjust(ctx, n, m, self.num_permutations, [b.ptr for b in bufs[1:]])
             enriched = bufs[5].download((m,))
@@ -1163,6 +1313,8 @@ class SAFE:
                 for k in kwargs:
                     logging.warning('\t%s=%s' % (k, str(kwargs[k])))
         self.validate_config()
+        if self._weighted():                               # before any device work
+            self._refuse_hypergeom_on_weights()
         if self.verbose:
             logging.info('Using the hypergeometric test to calculate enrichment...')
         ctx = self._ctx()
@@ -1238,6 +1390,17 @@ class SAFE:
                          "hypergeometric test (how = '%s'%s), which has none: pass how = 'randomization'"
                          % (self.enrichment_type, ' on 0/1 attribute values' if self.enrichment_type == 'auto' else ''))
 
+    def _refuse_hypergeom_on_weights(self):
+        raise ValueError("neighborhood_weighting = '%s' scores neighborhoods with real weights; this call takes the "
+                         "hypergeometric test (how = '%s'%s), which counts members: pass how = 'analytic' or how = 'randomization'"
+                         % (self.neighborhood_weighting, self.enrichment_type,
+                            ' on 0/1 attribute values' if self.enrichment_type == 'auto' else ''))
+
+    def _require_sum_scores_for_weights(self):
+        if self.neighborhood_score_type == 'z-score':
+            raise ValueError("neighborhood_weighting = '%s' is defined for neighborhood_score_type = 'sum' only; use "
+                             "neighborhood_weighting = 'none' with 'z-score'" % self.neighborhood_weighting)
+
     def _require_sum_scores_for_moments(self):
         if self.neighborhood_score_type != 'sum':
             raise ValueError("how = 'analytic' is defined for neighborhood_score_type = 'sum' only (the permutation null of "
@@ -1266,13 +1429,14 @@ class SAFE:
                     logging.warning('\t%s=%s' % (k, str(kwargs[k])))
         self.validate_config()
         self._require_sum_scores_for_moments()                   # before any device work
+        test = be.moments_test_weighted if self._weighted() else be.moments_test
         if self.verbose:
             logging.info('Using the exact permutation moments to calculate enrichment...')
         ctx = self._ctx()
         nbr = self._device_neighborhoods()
         attr = _attr if _attr is not None else self._upload_attributes()
         try:
-            self._two_sided_results(ctx, attr.n, attr.m, lambda out_ptrs: be.moments_test(
+            self._two_sided_results(ctx, attr.n, attr.m, lambda out_ptrs: test(
                 ctx, nbr, attr, self.attribute_sign, self.enrichment_threshold, out_ptrs))
         finally:
             if _attr is None:
