@@ -144,6 +144,35 @@ int safe_nbr_shortpath(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t 
                        const int32_t *edge_v, const double *edge_w, double cutoff,
                        int keep_distances, safe_nbr **out);
 
+/* node_distance_metric 'diffusion' (additive; the reference's metrics, safepy/safe.py:389-417, count hops or measure a 2-D
+ * layout): the truncated random-walk-with-restart kernel of the network and the cosine-normalised distance derived from it.
+ * Every operation is f64, rounded, in the order written (no fused multiply-add, no floating-point atomics: identical calls
+ * give identical bytes).
+ *   Edges: undirected (edge_u[e], edge_v[e]) with weight edge_w[e], or 1 when edge_w is NULL.  Each edge is one CSR entry in
+ *     each direction, a self-loop one entry; a row's entries are ordered by (neighbor id, input order); duplicate edges are
+ *     all kept and add.
+ *   Normalised adjacency: d_i = the row's entry weights added in entry order; r_i = 1.0 / sqrt(d_i), 0 where d_i == 0;
+ *     s_ik = (w_ik * r_i) * r_k.
+ *   Iteration: X_0 = I; for t = 0 .. steps-1: acc = 0.0, then over row i's entries in order acc = acc + s_ik * X_t[k][j];
+ *     X_{t+1}[i][j] = beta * acc for j != i and alpha + beta * acc for j == i, alpha = restart, beta = 1.0 - alpha.
+ *     K = X_steps  (in exact arithmetic alpha * sum_{t < steps} (beta S)^t + (beta S)^steps: the walks of at most `steps`
+ *     steps, the restart-weighted series with its last term at full weight; it tends to alpha * inv(I - beta S)).
+ *   Distance: for i != j, a = min(i, j), b = max(i, j): D[i][j] = +inf (unreached) if K[a][b] == 0, else
+ *     1.0 - K[a][b] / sqrt(K[a][a] * K[b][b]) with negative results set to 0.0; D[i][i] = 0.0.  D is exactly symmetric.
+ * A[i][j] = (D[i][j] <= cutoff and reached), the diagonal always.  The handle keeps the distances exactly as a
+ * safe_nbr_shortpath handle with keep_distances does (D where A is 1, +inf elsewhere; cutoff = +inf keeps every reached
+ * pair), so safe_nbr_distances, safe_nbr_distance_select, safe_nbr_row_distance_select, safe_nbr_from_distances_rows and
+ * safe_nbr_weights_from_distances serve it unchanged.  kernel_out_host: f64 [n,n] row-major or NULL; receives K.
+ * SAFE_E_INVALID: restart outside (0, 1), steps < 1, a NaN cutoff, an edge id outside [0, n), a negative, NaN or infinite
+ * weight (zero is allowed).  SAFE_E_UNSUPPORTED: n > SAFE_SELECT_MAX_NODES.  A refused call writes nothing and leaves *out
+ * untouched.  Device memory at peak: three n x n f64 matrices (two scratch iterates, released on every return path, and the
+ * kept matrix).  Synchronous on the context's stream.  safe_last_diffusion_stats: the time (ms) of all step launches, their
+ * number, and the time of the distance transform in the context's last call. */
+int safe_nbr_diffusion(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v,
+                       const double *edge_w, double restart, int steps, double cutoff, double *kernel_out_host,
+                       safe_nbr **out);
+int safe_last_diffusion_stats(safe_ctx *ctx, double *steps_ms, int *steps, double *transform_ms);
+
 /* Membership supplied by the caller as the reference's own layout: self.neighborhoods,
  * int64 [n,n] row-major with entries in {0,1} (safe.py:387,430).  Any other value is
  * SAFE_E_VALUE. */

@@ -96,6 +96,8 @@ PROTOTYPES = {
     'safe_timer_stop_ms': (C.c_int, [_vp, C.POINTER(C.c_double)]),
     'safe_nbr_euclidean': (C.c_int, [_vp, _vp, _i64, C.c_double, _pp]),
     'safe_nbr_shortpath': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_double, C.c_int, _pp]),
+    'safe_nbr_diffusion': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, C.c_double, C.c_int, C.c_double, _vp, _pp]),
+    'safe_last_diffusion_stats': (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     'safe_nbr_from_dense_i64': (C.c_int, [_vp, _vp, _i64, _pp]),
     'safe_nbr_set_layout': (C.c_int, [_vp, _vp]),
     'safe_nbr_block_count': (C.c_int, [_vp, _pi64]),

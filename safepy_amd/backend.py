@@ -243,6 +243,12 @@ class Context:
         check(lib.safe_last_rank_stats(self.handle, *[C.byref(x) for x in ms]))
         return tuple(x.value for x in ms)
 
+    def last_diffusion_stats(self):
+        """(ms of all k_diffusion_step launches, their number, ms of k_diffusion_transform) of the context's last Neighborhoods.diffusion()."""
+        steps_ms, steps, transform_ms = C.c_double(), C.c_int(), C.c_double()
+        check(lib.safe_last_diffusion_stats(self.handle, C.byref(steps_ms), C.byref(steps), C.byref(transform_ms)))
+        return steps_ms.value, steps.value, transform_ms.value
+
     def last_kernel_busy_ms(self):
         """Time during which at least one launch of the dominant kernel of the last call was running (launches overlap)."""
         ms = C.c_double()
@@ -543,6 +549,22 @@ class Neighborhoods:
         check(lib.safe_nbr_shortpath(ctx.handle, int(n), eu.shape[0], _ptr(eu), _ptr(ev), _ptr(ew), float(cutoff),
                                      1 if keep_distances else 0, C.byref(h)))
         return cls(ctx, h)
+
+    @classmethod
+    def diffusion(cls, ctx, n, edge_u, edge_v, edge_w, restart, steps, cutoff, want_kernel=False):
+        """The random-walk-with-restart handle (safe_nbr_diffusion): A[i, j] = (D[i, j] <= cutoff and reached), the distances
+        kept as a shortest-path handle keeps them.  edge_w: None = unit weights.  want_kernel: returns (handle, K f64 [n, n])."""
+        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
+        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
+        ew = None if edge_w is None else np.ascontiguousarray(edge_w, dtype=np.float64)
+        if eu.shape != ev.shape or eu.ndim != 1 or (ew is not None and ew.shape != eu.shape):
+            raise ValueError('diffusion: edge_u, edge_v (and edge_w) must be one-dimensional arrays of one length')
+        kernel = np.empty((int(n), int(n)), dtype=np.float64) if want_kernel else None
+        h = C.c_void_p()
+        check(lib.safe_nbr_diffusion(ctx.handle, int(n), eu.shape[0], _ptr(eu), _ptr(ev), _ptr(ew), float(restart), int(steps),
+                                     float(cutoff), _ptr(kernel), C.byref(h)))
+        nbr = cls(ctx, h)
+        return (nbr, kernel) if want_kernel else nbr
 
     @classmethod
     def from_dense(cls, ctx, a):

@@ -144,6 +144,9 @@ enum ScratchSlot {
     SCRATCH_WEIGHT_TILES,   // the attribute operand of the weighted permutation kernel: f64 tiles [tile][n + 1][16] |
                             //   safe_permtest_counts_weighted, and the weighted score of row-contiguous storage (weights.hip) |
                             //   within the call
+    SCRATCH_DIFFUSION_GRAPH,// CSR of the network: row starts i32 [n + 1] | neighbor ids i32 [entries] | entry weights, then the scaled entries
+                            //   s_ik, f64 [entries] | row scales r f64 [n] | rows by descending entry count i32 [n] | safe_nbr_diffusion
+                            //   (diffusion.hip) | within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,
@@ -170,6 +173,8 @@ struct safe_ctx {
     void *diag_prof = nullptr;                  // (diagnostic builds) per-phase cycle counters of the matrix-core kernel
     int last_core_slices = 0;                   // slices its matrix-core kernel multiplied (3 of 6 in the filtered form)
     int64_t last_undecided = 0;                 // filtered form: compares decided by k_mfma_resolve (negative: list overflow, six-slice rerun)
+    double diffusion_ms[2] = {0.0, 0.0};        // all k_diffusion_step launches, k_diffusion_transform of the last safe_nbr_diffusion
+    int diffusion_steps = 0;                    //   and the number of step launches (safe_last_diffusion_stats)
     double rank_ms[3] = {0.0, 0.0, 0.0};        // k_rank_keys, k_rank_sort, k_rank_emit of the last safe_attr_rank (safe_last_rank_stats)
     // grow-only scratch buffers reused across calls (hipMalloc of >100 MB costs milliseconds)
     struct safe_perms *perm_cache = nullptr;    // buffers of the last destroyed permutation handle, reused by the next
@@ -603,6 +608,11 @@ int safe_attr_prepare(safe_attr *attr);   // row flags + stats (attr.hip)
 // mu_j and Q_j of columns [col0, col1) into d_mean / d_css [col1 - col0], enqueued on the context's stream (moments.hip)
 int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col1, const char *who, double *d_mean, double *d_css);
 int nbr_finalize_from_bits(safe_nbr *nbr);   // bits -> CSR + SELL (nbr.hip)
+// a handle under construction (nbr.hip; diffusion.hip builds one too): nbr_new allocates the bit matrix, and the handle is freed
+// on every return path until it is released into the caller's *out
+void nbr_free(safe_nbr *nbr);
+using NbrPtr = std::unique_ptr<safe_nbr, void (*)(safe_nbr *)>;
+int nbr_new(safe_ctx *ctx, int64_t n, NbrPtr *out);
 int nbr_build_transpose(safe_nbr *nbr);      // at_ptr / at_col (nbr.hip)
 int attr_build_support(safe_attr *attr);     // sup_ptr / sup_row of a binary matrix (attr.hip)
 // an attribute handle that owns nothing on the device yet (the checks of safe_attr_create_*; attr.hip)

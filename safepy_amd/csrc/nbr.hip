@@ -741,7 +741,7 @@ static int sel_keys(safe_ctx *ctx, const SelSource &src, const char *who, const 
     return SAFE_OK;
 }
 
-static void nbr_free(safe_nbr *nbr) {
+void nbr_free(safe_nbr *nbr) {
     if (!nbr) return;
     for (const void *q : {(const void *)nbr->bits, (const void *)nbr->row_ptr, (const void *)nbr->col, (const void *)nbr->sell_row,
                           (const void *)nbr->sell_pos, (const void *)nbr->slice_off, (const void *)nbr->slice_width,
@@ -754,10 +754,7 @@ static void nbr_free(safe_nbr *nbr) {
     delete nbr;
 }
 
-// a handle under construction: freed on every return path until it is released into the caller's *out
-using NbrPtr = std::unique_ptr<safe_nbr, void (*)(safe_nbr *)>;
-
-static int nbr_new(safe_ctx *ctx, int64_t n, NbrPtr *out) {
+int nbr_new(safe_ctx *ctx, int64_t n, NbrPtr *out) {
     SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 64, "neighborhood size n=%lld out of range", (long long)n);
     NbrPtr nbr(new safe_nbr(), nbr_free);
     nbr->ctx = ctx;

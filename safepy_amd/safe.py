@@ -46,6 +46,9 @@ _DEFAULTS = {
     # additive (no counterpart in the reference's file): restricted permutations, see SAFE.compute_pvalues
     'permutationStrata': '',
     'permutationStrataBins': '10',
+    # additive: the random-walk-with-restart kernel of node_distance_metric = 'diffusion', see SAFE.define_neighborhoods
+    'diffusionRestart': '0.5',
+    'diffusionSteps': '32',
 }
 
 
@@ -317,6 +320,10 @@ class SAFE:
         # 'uniform', 'triangular', 'epanechnikov', 'gaussian' (with neighborhood_weight_bandwidth), 'custom'
         self.neighborhood_weighting = 'none'
         self.neighborhood_weight_bandwidth = 0.5
+        # node_distance_metric = 'diffusion' only: the restart probability alpha in (0, 1) and the number of steps T >= 1 of the
+        # truncated random-walk-with-restart kernel X_{t+1} = alpha I + (1 - alpha) S X_t, X_0 = I, K = X_T (define_neighborhoods)
+        self.diffusion_restart = 0.5
+        self.diffusion_steps = 32
 
         self.background = 'attribute_file'
         self.num_permutations = 1000
@@ -420,6 +427,15 @@ class SAFE:
             self.permutation_strata_bins = int(bins)
         except (ValueError, TypeError):                    # validate_config names the bad value
             self.permutation_strata_bins = bins
+        restart, steps = option('Analysis parameters', 'diffusionRestart'), option('Analysis parameters', 'diffusionSteps')
+        try:
+            self.diffusion_restart = float(restart)
+        except (ValueError, TypeError):                    # validate_config names the bad value
+            self.diffusion_restart = restart
+        try:
+            self.diffusion_steps = int(steps)
+        except (ValueError, TypeError):
+            self.diffusion_steps = steps
 
         # the reference falls back on its package folder (safe.py:186-188); here: this package's
         self.output_dir = os.path.dirname(path_to_ini_file) if path_to_ini_file else ''
@@ -432,10 +448,18 @@ class SAFE:
             bad, self.background = self.background, self.default_config.get('background')
             raise ValueError('%s is not a valid setting for background. '
                              'Valid options are: attribute_file, network.' % bad)
-        if self.node_distance_metric not in ['euclidean', 'shortpath', 'shortpath_weighted_layout']:
+        if self.node_distance_metric not in ['euclidean', 'shortpath', 'shortpath_weighted_layout', 'diffusion']:
             bad, self.node_distance_metric = self.node_distance_metric, self.default_config.get('nodeDistanceType')
             raise ValueError('%s is not a valid setting for node_distance_metric. '
-                             'Valid options are: euclidean, shortpath, shortpath_weighted_layout' % bad)
+                             'Valid options are: euclidean, shortpath, shortpath_weighted_layout, diffusion' % bad)
+        restart = getattr(self, 'diffusion_restart', 0.5)
+        if not _is_real(restart) or not (0 < restart < 1):
+            self.diffusion_restart = 0.5
+            raise ValueError('diffusion_restart = %r is not valid: it must be a number in the (0, 1) range.' % (restart,))
+        steps = getattr(self, 'diffusion_steps', 32)
+        if not isinstance(steps, (int, np.integer)) or isinstance(steps, (bool, np.bool_)) or steps < 1:
+            self.diffusion_steps = 32
+            raise ValueError('diffusion_steps = %r is not valid: it must be an integer equal or greater than 1.' % (steps,))
         if self.neighborhood_radius_type not in [None, 'diameter', 'absolute', 'percentile', 'nearest']:
             bad, self.neighborhood_radius_type = self.neighborhood_radius_type, self.default_config.get('neighborhoodRadiusType')
             raise ValueError('%s is not a valid setting for neighborhood_radius_type. '
@@ -559,6 +583,8 @@ class SAFE:
         self.__dict__.setdefault('neighborhood_weighting', 'none')
         self.__dict__.setdefault('neighborhood_weight_bandwidth', 0.5)
         self.__dict__.setdefault('_weights_host', None)
+        self.__dict__.setdefault('diffusion_restart', 0.5)
+        self.__dict__.setdefault('diffusion_steps', 32)
         if isinstance(self.default_config, dict):
             cp = configparser.ConfigParser()
             cp.read_dict({'DEFAULT': self.default_config})
@@ -869,7 +895,7 @@ class SAFE:
             self.neighborhood_radius_type = kwargs['neighborhood_radius_type']
         if 'neighborhood_radius' in kwargs:
             self.neighborhood_radius = kwargs['neighborhood_radius']
-        for name in ('neighborhood_weighting', 'neighborhood_weight_bandwidth'):
+        for name in ('neighborhood_weighting', 'neighborhood_weight_bandwidth', 'diffusion_restart', 'diffusion_steps'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
         self.validate_config()
@@ -882,6 +908,16 @@ class SAFE:
             return length                               # weight='length', missing -> 1 (networkx)
         return weight                                   # default weight attr 'weight', missing -> 1
 
+    def _graph_distances(self, ctx, arrays, cutoff):
+        """The membership handle of the network metrics with its kept distance matrix: all-pairs shortest paths bounded by
+        `cutoff` ('shortpath', 'shortpath_weighted_layout'), or the random-walk-with-restart distance of 'diffusion' (the
+        graph's 'weight' edge attribute, 1 where missing; 'length' is never used) with members D <= cutoff."""
+        xy, eu, ev, length, weight = arrays
+        w = self._shortpath_weights(xy, eu, ev, length, weight)
+        if self.node_distance_metric == 'diffusion':
+            return be.Neighborhoods.diffusion(ctx, xy.shape[0], eu, ev, w, self.diffusion_restart, self.diffusion_steps, cutoff)
+        return be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, cutoff, keep_distances=True)
+
     def _distance_percentiles(self, ctx, arrays, qs):
         """np.percentile(v, q), bit for bit, for every q of `qs`.  v is the multiset of node distances of the pairs i < j
         under the current metric: pdist(xy), or the finite D[i, j] of the all-pairs shortest paths (row i = the search
@@ -891,8 +927,7 @@ class SAFE:
         if self.node_distance_metric == 'euclidean':
             plan = _percentile_plan(ctx.pair_distance_select(xy, [])[1], qs)
             return _percentile_values(plan, ctx.pair_distance_select(xy, plan[0])[0])
-        w = self._shortpath_weights(xy, eu, ev, length, weight)
-        nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, np.inf, keep_distances=True)
+        nbr = self._graph_distances(ctx, arrays, np.inf)
         try:
             plan = _percentile_plan(nbr.distance_select([])[1], qs)
             return _percentile_values(plan, nbr.distance_select(plan[0])[0])
@@ -907,13 +942,23 @@ class SAFE:
         k = min(int(self.neighborhood_radius), 2 ** 62)
         if self.node_distance_metric == 'euclidean':
             return None, ctx.row_distance_select(xy, k)
-        w = self._shortpath_weights(xy, eu, ev, length, weight)
-        src = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, np.inf, keep_distances=True)
+        src = self._graph_distances(ctx, arrays, np.inf)
         try:
             return src, src.row_distance_select(k)
         except Exception:
             src.close()
             raise
+
+    def _refuse_diffusion_diameter(self):
+        """'diffusion' distances are 1 - a similarity, in [0, 1]: a fraction of the layout's extent ('diameter') means nothing."""
+        if self.node_distance_metric == 'diffusion' and self.neighborhood_radius_type in (None, 'diameter'):
+            raise ValueError("neighborhood_radius_type = 'diameter' is not defined for node_distance_metric = 'diffusion' (the "
+                             "distance does not come from a layout): use 'percentile', 'nearest' or 'absolute'")
+
+    def _set_layout_hint(self, xy):
+        """The layout only orders the nodes on the device.  'diffusion' needs none: an edge list without finite coordinates gets no hint."""
+        if self.node_distance_metric != 'diffusion' or np.isfinite(xy).all():
+            self._nbr.set_layout(xy)
 
     def _set_nearest_radii(self, radii):
         self.neighborhood_radii = radii
@@ -939,6 +984,7 @@ class SAFE:
         """The radius in distance units (the hop cutoff for 'shortpath') that neighborhood_radius stands for under
         neighborhood_radius_type; kept as self.neighborhood_radius_resolved."""
         kind = self.neighborhood_radius_type
+        self._refuse_diffusion_diameter()
         if kind == 'nearest':                           # one radius per node: the typical one stands for them
             src, radii = self._nearest_radii(ctx, arrays)
             if src is not None:
@@ -977,6 +1023,16 @@ class SAFE:
         distance, never an unreached node.  The membership is in general not symmetric.  Sets neighborhood_radii (f64 [N]) and
         neighborhood_radius_resolved (their median); node_distances holds the distances inside every node's own radius.
 
+        node_distance_metric = 'diffusion' (additive), with the settings / keywords diffusion_restart (alpha, default 0.5, in (0, 1))
+        and diffusion_steps (T, default 32, an integer >= 1; INI keys diffusionRestart / diffusionSteps): a layout-free, continuous
+        distance from the truncated random-walk-with-restart kernel K = X_T of X_{t+1} = alpha I + (1 - alpha) S X_t, X_0 = I, S the
+        symmetrically normalised adjacency (the 'weight' edge attribute, 1 where missing): D[i, j] = 1 - K[i, j] / sqrt(K[i, i] K[j, j]), +inf
+        where no walk of at most T steps joins i and j, computed on the device in f64 with a fixed order of operations
+        (include/safe_hip.h, safe_nbr_diffusion).  It orders nodes at equal hop distance by the number of paths that join them.
+        Radius types 'percentile' (over the finite D[i, j], i < j), 'nearest' and 'absolute' (a radius in [0, 1) is a
+        "1 - similarity") apply as for the shortest-path metrics, members are D <= radius, and node_distances holds the kept
+        distances; 'diameter' is a ValueError before any device work.  Holds three N x N f64 matrices on the device at peak.
+
         neighborhood_weighting (additive; keyword or setting, default 'none' = flat neighborhoods and today's bytes), with
         neighborhood_weight_bandwidth (default 0.5, finite and > 0, read by 'gaussian' only): a distance-decay weight for every
         member k of every neighborhood i, from u = D[i, k] / r_i (u = 0 where r_i = 0), D the node distance of the metric and
@@ -986,6 +1042,7 @@ class SAFE:
         compute_pvalues then tests the weighted 'sum' score.  'custom' here is a ValueError: build the neighborhoods first, then
         call set_neighborhood_weights(W).  The shortest-path metrics build the weights from the N x N matrix the handle keeps."""
         self._override_neighborhood_settings(kwargs)
+        self._refuse_diffusion_diameter()                # before any device work; nothing changes
         weighting = self.neighborhood_weighting
         if weighting == 'custom':                    # before any device work; nothing changes
             raise ValueError("neighborhood_weighting = 'custom' is not something define_neighborhoods can build: define the "
@@ -1001,16 +1058,15 @@ class SAFE:
             self.neighborhood_radius_resolved = None
             self._nbr = self._nearest_neighborhoods(ctx, (xy, eu, ev, length, weight))
             if self.node_distance_metric != 'euclidean':
-                self._nbr.set_layout(xy)
+                self._set_layout_hint(xy)
                 self._node_distances = ('device-shortpath', self._nbr)
         elif self.node_distance_metric == 'euclidean':
             radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
             self._nbr = be.Neighborhoods.euclidean(ctx, xy, radius)
         else:
             radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
-            w = self._shortpath_weights(xy, eu, ev, length, weight)
-            self._nbr = be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, radius, keep_distances=True)
-            self._nbr.set_layout(xy)
+            self._nbr = self._graph_distances(ctx, (xy, eu, ev, length, weight), radius)
+            self._set_layout_hint(xy)
             self._node_distances = ('device-shortpath', self._nbr)
         if weighting != 'none':
             radii = self.neighborhood_radii if nearest else self.neighborhood_radius_resolved
@@ -1039,6 +1095,7 @@ class SAFE:
         f64 [N,N] == squareform(pdist(xy)) (safe.py:397).  Shortest-path metrics: the same
         dict-of-dicts define_neighborhoods stores (safe.py:417)."""
         self._override_neighborhood_settings(kwargs)
+        self._refuse_diffusion_diameter()
         xy, eu, ev, length, weight = _graph_arrays(self.graph)
         ctx = self._ctx()
         n = xy.shape[0]
@@ -1061,8 +1118,7 @@ class SAFE:
                 d_xy.free()
                 d_out.free()
         else:
-            w = self._shortpath_weights(xy, eu, ev, length, weight)
-            nbr = be.Neighborhoods.shortpath(ctx, n, eu, ev, w, radius, keep_distances=True)
+            nbr = self._graph_distances(ctx, (xy, eu, ev, length, weight), radius)
             self._node_distances = ('dense-shortpath', nbr.distances())
             nbr.close()
 
@@ -1509,6 +1565,8 @@ class SAFE:
                 raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs a "
                                  'neighborhood radius greater than 0: it resolved to %r' % (r,))
             return be.Neighborhoods.euclidean(ctx, xy, t), t
+        if self.node_distance_metric == 'diffusion':
+            return self._graph_distances(ctx, arrays, t), t
         w = self._shortpath_weights(xy, eu, ev, length, weight)
         return be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, t, keep_distances=False), t
 
