@@ -21,6 +21,24 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _xy(xy, who, n=None):
+    """Layout coordinates as the library reads them: C-contiguous f64 [n, 2] (any n when none is given)."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or (n is not None and xy.shape[0] != n):
+        raise ValueError('%s: xy must be [%s, 2], got shape %s' % (who, 'n' if n is None else n, xy.shape))
+    return xy
+
+
+def _edges(edge_u, edge_v, edge_w, who):
+    """An edge list as the library reads it: int32 end points and f64 weights (None = unit weights), one-dimensional, one length."""
+    eu = np.ascontiguousarray(edge_u, dtype=np.int32)
+    ev = np.ascontiguousarray(edge_v, dtype=np.int32)
+    ew = None if edge_w is None else np.ascontiguousarray(edge_w, dtype=np.float64)
+    if eu.shape != ev.shape or eu.ndim != 1 or (ew is not None and ew.shape != eu.shape):
+        raise ValueError('%s: edge_u, edge_v (and edge_w) must be one-dimensional arrays of one length' % who)
+    return eu, ev, ew
+
+
 def _split_off_cores(cpus, n_cores, slot=0):
     """(CPUs of `n_cores` whole physical cores, the rest) of the CPU set `cpus`, or None when the topology cannot be read or
     fewer than n_cores + 2 cores would be left."""
@@ -256,9 +274,8 @@ class Context:
         return ms.value
 
     def edge_lengths(self, xy, edge_u, edge_v):
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
-        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
+        xy = _xy(xy, 'edge_lengths')
+        eu, ev, _ = _edges(edge_u, edge_v, None, 'edge_lengths')
         out = np.empty(eu.shape[0], dtype=np.float64)
         check(lib.safe_edge_lengths(self.handle, _ptr(xy), xy.shape[0], eu.shape[0], _ptr(eu), _ptr(ev), _ptr(out)))
         return out
@@ -267,9 +284,7 @@ class Context:
         """Order statistics of scipy's pdist(xy) without the N (N - 1) / 2 distances (safe_pair_distance_select_xy): the
         elements of the 0-based `ranks` of the ascending multiset, bit for bit.  Returns (values f64 [len(ranks)], number
         of pairs); no ranks = the count alone."""
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[1] != 2:
-            raise ValueError('pair_distance_select: xy must be [n, 2], got shape %s' % (xy.shape,))
+        xy = _xy(xy, 'pair_distance_select')
         rk = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64)
         out = np.empty(rk.shape[0], dtype=np.float64)
         count = C.c_int64(0)
@@ -280,9 +295,7 @@ class Context:
     def row_distance_select(self, xy, k):
         """Per node, the distance to its k-th nearest other node under scipy's pdist(xy), bit for bit
         (safe_row_distance_select_xy): f64 [n]; the farthest node where k exceeds n - 1, 0.0 for a single node."""
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[1] != 2:
-            raise ValueError('row_distance_select: xy must be [n, 2], got shape %s' % (xy.shape,))
+        xy = _xy(xy, 'row_distance_select')
         out = np.empty(xy.shape[0], dtype=np.float64)
         check(lib.safe_row_distance_select_xy(self.handle, _ptr(xy), xy.shape[0], int(k), _ptr(out)))
         return out
@@ -397,10 +410,7 @@ class Context:
         of the row-major [n, m] f64 device matrix at values_dev_ptr, read in place (safe_enriched_components_dev): what
         enriched_components gives for the host slice values[:, cols].  Returns (labels, kernel ms)."""
         cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
-        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
-        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
-        if eu.shape != ev.shape or eu.ndim != 1:
-            raise ValueError('enriched_components_dev: edge lists of shapes %s and %s' % (eu.shape, ev.shape))
+        eu, ev, _ = _edges(edge_u, edge_v, None, 'enriched_components_dev')
         out = np.empty((cols.shape[0], int(n)), dtype=np.int32)
         ms = C.c_double()
         check(lib.safe_enriched_components_dev(self.handle, eu.shape[0], _ptr(eu) if eu.size else None, _ptr(ev) if ev.size else None,
@@ -534,17 +544,14 @@ class Neighborhoods:
 
     @classmethod
     def euclidean(cls, ctx, xy, nr):
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        assert xy.ndim == 2 and xy.shape[1] == 2
+        xy = _xy(xy, 'euclidean')
         h = C.c_void_p()
         check(lib.safe_nbr_euclidean(ctx.handle, _ptr(xy), xy.shape[0], float(nr), C.byref(h)))
         return cls(ctx, h)
 
     @classmethod
     def shortpath(cls, ctx, n, edge_u, edge_v, edge_w, cutoff, keep_distances=False):
-        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
-        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
-        ew = None if edge_w is None else np.ascontiguousarray(edge_w, dtype=np.float64)
+        eu, ev, ew = _edges(edge_u, edge_v, edge_w, 'shortpath')
         h = C.c_void_p()
         check(lib.safe_nbr_shortpath(ctx.handle, int(n), eu.shape[0], _ptr(eu), _ptr(ev), _ptr(ew), float(cutoff),
                                      1 if keep_distances else 0, C.byref(h)))
@@ -554,11 +561,7 @@ class Neighborhoods:
     def diffusion(cls, ctx, n, edge_u, edge_v, edge_w, restart, steps, cutoff, want_kernel=False):
         """The random-walk-with-restart handle (safe_nbr_diffusion): A[i, j] = (D[i, j] <= cutoff and reached), the distances
         kept as a shortest-path handle keeps them.  edge_w: None = unit weights.  want_kernel: returns (handle, K f64 [n, n])."""
-        eu = np.ascontiguousarray(edge_u, dtype=np.int32)
-        ev = np.ascontiguousarray(edge_v, dtype=np.int32)
-        ew = None if edge_w is None else np.ascontiguousarray(edge_w, dtype=np.float64)
-        if eu.shape != ev.shape or eu.ndim != 1 or (ew is not None and ew.shape != eu.shape):
-            raise ValueError('diffusion: edge_u, edge_v (and edge_w) must be one-dimensional arrays of one length')
+        eu, ev, ew = _edges(edge_u, edge_v, edge_w, 'diffusion')
         kernel = np.empty((int(n), int(n)), dtype=np.float64) if want_kernel else None
         h = C.c_void_p()
         check(lib.safe_nbr_diffusion(ctx.handle, int(n), eu.shape[0], _ptr(eu), _ptr(ev), _ptr(ew), float(restart), int(steps),
@@ -586,9 +589,7 @@ class Neighborhoods:
     @classmethod
     def euclidean_rows(cls, ctx, xy, radii):
         """A[i, j] = (pdist distance of i and j <= radii[i]): one radius per row (safe_nbr_euclidean_rows)."""
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[1] != 2:
-            raise ValueError('euclidean_rows: xy must be [n, 2], got shape %s' % (xy.shape,))
+        xy = _xy(xy, 'euclidean_rows')
         r = cls._radii(radii, xy.shape[0], 'euclidean_rows')
         h = C.c_void_p()
         check(lib.safe_nbr_euclidean_rows(ctx.handle, _ptr(xy), xy.shape[0], _ptr(r), C.byref(h)))
@@ -612,8 +613,7 @@ class Neighborhoods:
 
     def set_layout(self, xy):
         """Hint: the 2-D layout the membership came from (node order of the matrix-core kernel only)."""
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        assert xy.shape == (self.n, 2)
+        xy = _xy(xy, 'set_layout', self.n)
         check(lib.safe_nbr_set_layout(self.handle, _ptr(xy)))
 
     def to_dense(self):
@@ -660,9 +660,7 @@ class Neighborhoods:
     def set_weights_from_xy(self, xy, kind, radii, bandwidth=0.5):
         """Weights of every member from the pdist distance of the coordinates and the row's radius
         (safe_nbr_weights_from_xy); kind: 'uniform', 'triangular', 'epanechnikov', 'gaussian'; radii: a number or one per node."""
-        xy = np.ascontiguousarray(xy, dtype=np.float64)
-        if xy.shape != (self.n, 2):
-            raise ValueError('set_weights_from_xy: xy must be [%d, 2], got shape %s' % (self.n, xy.shape))
+        xy = _xy(xy, 'set_weights_from_xy', self.n)
         r = self._radii(np.broadcast_to(np.asarray(radii, dtype=np.float64), (self.n,)), self.n, 'set_weights_from_xy')
         check(lib.safe_nbr_weights_from_xy(self.handle, _ptr(xy), self._weight_kind(kind), _ptr(r), float(bandwidth)))
         self.has_weights = True
@@ -1590,8 +1588,7 @@ def enriched_components(ctx, n, edge_u, edge_v, member):
     node id of the component; -1 = not enriched) -- safe.py:640-655 for all attributes at once."""
     member = np.ascontiguousarray(member, dtype=np.float64)
     assert member.ndim == 2 and member.shape[0] == n
-    eu = np.ascontiguousarray(edge_u, dtype=np.int32)
-    ev = np.ascontiguousarray(edge_v, dtype=np.int32)
+    eu, ev, _ = _edges(edge_u, edge_v, None, 'enriched_components')
     out = np.empty((member.shape[1], n), dtype=np.int32)
     check(lib.safe_enriched_components(ctx.handle, int(n), eu.shape[0], _ptr(eu), _ptr(ev), _ptr(member), member.shape[1], _ptr(out)))
     return out

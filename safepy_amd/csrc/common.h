@@ -614,6 +614,25 @@ void nbr_free(safe_nbr *nbr);
 using NbrPtr = std::unique_ptr<safe_nbr, void (*)(safe_nbr *)>;
 int nbr_new(safe_ctx *ctx, int64_t n, NbrPtr *out);
 int nbr_build_transpose(safe_nbr *nbr);      // at_ptr / at_col (nbr.hip)
+// Where node distances are read from on the device: the layout xy [n][2] (recomputed with pdist's roundings wherever they are
+// needed) or the matrix dist [n][n] a handle kept (+inf = unreached), read in place.  Exactly one of the two is set.
+struct DistSource {
+    const double *xy;
+    const double *dist;
+    int64_t n;
+};
+// Host checks and uploads the neighborhood entry points share (nbr.hip); `fn` prefixes the message.
+// every coordinate of xy_host [n][2] is finite, else SAFE_E_VALUE
+int check_layout_finite(const char *fn, const double *xy_host, int64_t n);
+// radii of the per-row builders and of the weights: none NaN, none negative (+inf is a radius), else SAFE_E_VALUE
+int check_radii(const char *fn, const double *radii, int64_t n);
+// xy_host [n][2] into a block of the call's `b`, copied on the context's stream: xy_host is read until the stream has been waited for
+int upload_layout(safe_ctx *ctx, CallBufs *b, const char *fn, const double *xy_host, int64_t n, const double **d_xy_out);
+// Undirected CSR adjacency of an edge list, on the host: one entry per direction, a self-loop once, duplicates kept, a row's
+// entries in input order; edge_w NULL = 1 per edge.  ptr [n + 1], col and w [max(entries, 1)].  SAFE_E_INVALID for an end point
+// outside [0, n), a negative, infinite or NaN weight, or more entries than int32 offsets hold.
+int build_undirected_csr(const char *fn, int64_t n, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v, const double *edge_w,
+                         std::vector<int32_t> *ptr, std::vector<int32_t> *col, std::vector<double> *w);
 int attr_build_support(safe_attr *attr);     // sup_ptr / sup_row of a binary matrix (attr.hip)
 // an attribute handle that owns nothing on the device yet (the checks of safe_attr_create_*; attr.hip)
 int attr_new(safe_ctx *ctx, int dtype, int64_t n, int64_t m, int64_t rs, int64_t cs, safe_attr **out);

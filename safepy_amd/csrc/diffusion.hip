@@ -193,42 +193,23 @@ int safe_nbr_diffusion(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t 
         safe_set_error("%s: n = %lld exceeds SAFE_SELECT_MAX_NODES = %d", fn, (long long)n, SAFE_SELECT_MAX_NODES);
         return SAFE_E_UNSUPPORTED;
     }
-    // undirected CSR on the host: one entry per direction, a self-loop once, duplicates kept; a row's entries by (neighbor id,
-    // input order) -- filled in input order, then sorted stably by neighbor id
-    std::vector<int32_t> ptr(n + 1, 0);
-    for (int64_t e = 0; e < n_edges; ++e) {
-        const int32_t u = edge_u[e], v = edge_v[e];
-        SAFE_REQUIRE(u >= 0 && u < n && v >= 0 && v < n, "%s: edge %lld has an end point outside [0,%lld)", fn, (long long)e,
-                     (long long)n);
-        if (edge_w)
-            SAFE_REQUIRE(edge_w[e] >= 0.0 && std::isfinite(edge_w[e]), "%s: edge %lld has a negative, infinite or NaN weight", fn,
-                         (long long)e);
-        ptr[u + 1]++;
-        if (u != v) ptr[v + 1]++;
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        SAFE_REQUIRE(static_cast<int64_t>(ptr[i]) + ptr[i + 1] < (1ll << 31), "%s: too many entries for int32 CSR offsets", fn);
-        ptr[i + 1] += ptr[i];
-    }
+    // the undirected CSR, a row's entries by (neighbor id, input order): filled in input order, then sorted stably by neighbor id
+    std::vector<int32_t> ptr, h_col;
+    std::vector<double> h_w;
+    SAFE_TRY(build_undirected_csr(fn, n, n_edges, edge_u, edge_v, edge_w, &ptr, &h_col, &h_w));
     const int64_t n_adj = ptr[n];
-    std::vector<std::pair<int32_t, double>> ent(std::max<int64_t>(n_adj, 1));
     {
-        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (int64_t e = 0; e < n_edges; ++e) {
-            const int32_t u = edge_u[e], v = edge_v[e];
-            const double w = edge_w ? edge_w[e] : 1.0;
-            ent[fill[u]++] = {v, w};
-            if (u != v) ent[fill[v]++] = {u, w};
+        std::vector<std::pair<int32_t, double>> ent;
+        for (int64_t i = 0; i < n; ++i) {
+            ent.clear();
+            for (int32_t e = ptr[i]; e < ptr[i + 1]; ++e) ent.emplace_back(h_col[e], h_w[e]);
+            std::stable_sort(ent.begin(), ent.end(),
+                             [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) { return a.first < b.first; });
+            for (int32_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+                h_col[e] = ent[e - ptr[i]].first;
+                h_w[e] = ent[e - ptr[i]].second;
+            }
         }
-    }
-    for (int64_t i = 0; i < n; ++i)
-        std::stable_sort(ent.begin() + ptr[i], ent.begin() + ptr[i + 1],
-                         [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) { return a.first < b.first; });
-    std::vector<int32_t> h_col(std::max<int64_t>(n_adj, 1));
-    std::vector<double> h_w(std::max<int64_t>(n_adj, 1));
-    for (int64_t e = 0; e < n_adj; ++e) {
-        h_col[e] = ent[e].first;
-        h_w[e] = ent[e].second;
     }
     std::vector<int32_t> h_order(n);
     std::iota(h_order.begin(), h_order.end(), 0);

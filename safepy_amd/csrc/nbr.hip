@@ -5,16 +5,24 @@
 // calculate_edge_lengths (safepy/safe_io.py:311-333).  Compiled with -ffp-contract=off:
 // the reference arithmetic is scipy pdist's sqrt(dx*dx + dy*dy) with every operation
 // rounded separately, and bit-exact masks need the same roundings.
+//
+// Where the distances come from -- coordinates, recomputed with pdist's roundings, or an N x N matrix a handle kept -- is one
+// DistSource (common.h) from the exports down to the kernel launch: the two pair selections and the two row selections are thin
+// wrappers over one function each, and k_euclid_bits<ROWS> is the one Euclidean bit kernel (one strict threshold, or one `<=`
+// threshold per row).  The host pieces every entry point shares live here too: check_layout_finite, check_radii, upload_layout
+// and build_undirected_csr (the adjacency of safe_nbr_shortpath and, sorted afterwards, of safe_nbr_diffusion).
 #include <algorithm>
 #include <cmath>
 #include <numeric>
+#include <type_traits>
 
 #include "common.h"
 
 // --------------------------------------------------------------------------------------
-// Strict threshold without a square root.  sqrt is correctly rounded and monotone, so
-//   sqrt(s) < nr   <=>   s < T,   T = min{ s : sqrt(s) >= nr }.
-// T is found on the host by stepping from nr*nr to the exact boundary.
+// Thresholds without a square root.  sqrt is correctly rounded and monotone, so
+//   sqrt(s) <  nr  <=>  s <  T,   T = min{ s : sqrt(s) >= nr }   (squared_threshold: the reference's strict rule)
+//   sqrt(s) <= r   <=>  s <= C,   C = max{ s : sqrt(s) <= r }    (squared_threshold_le: one radius per row, r >= 0)
+// Both are found on the host by stepping from the square of the radius to the exact boundary.
 // --------------------------------------------------------------------------------------
 static double squared_threshold(double nr) {
     if (!(nr > 0.0)) return 0.0;                 // D >= 0 is never < nr
@@ -26,11 +34,28 @@ static double squared_threshold(double nr) {
     return c;
 }
 
+static double squared_threshold_le(double r) {
+    if (std::isinf(r)) return r;
+    double c = r * r;
+    while (c > 0.0 && std::sqrt(c) > r) c = std::nextafter(c, 0.0);
+    for (;;) {
+        const double up = std::nextafter(c, INFINITY);
+        if (std::isinf(up) || std::sqrt(up) > r) return c;
+        c = up;
+    }
+}
+
 // --------------------------------------------------------------------------------------
 // K1a: distance + threshold -> bit matrix.  One lane owns one (row, 64-column word):
 // the 64 lanes of a wave share the word index, so x[j], y[j] are LDS broadcasts.
+// ROWS = false: bit (i, j) = (s_ij < thr), one squared_threshold for the matrix.  ROWS = true: bit (i, j) = (s_ij <= thr[i]),
+// one squared_threshold_le per row, so the rule is sqrt(s) <= r_i without a root per pair.
 // --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_euclid_bits(const double *__restrict__ xy, int64_t n, double thr_sq,
+template <bool ROWS>
+using EuclidThreshold = std::conditional_t<ROWS, const double *__restrict__, double>;
+
+template <bool ROWS>
+__global__ __launch_bounds__(256) void k_euclid_bits(const double *__restrict__ xy, int64_t n, EuclidThreshold<ROWS> thr,
                                                      uint64_t *__restrict__ bits, int64_t words) {
     __shared__ double sx[64], sy[64];
     const int64_t w = blockIdx.x;                                   // word (column block)
@@ -44,6 +69,9 @@ __global__ __launch_bounds__(256) void k_euclid_bits(const double *__restrict__ 
     __syncthreads();
     if (i >= n) return;
     const double xi = xy[2 * i], yi = xy[2 * i + 1];
+    double c;
+    if constexpr (ROWS) c = thr[i];
+    else c = thr;
     const int jn = static_cast<int>(n - j0 < 64 ? n - j0 : 64);
     uint64_t word = 0;
 #pragma unroll 8
@@ -51,7 +79,7 @@ __global__ __launch_bounds__(256) void k_euclid_bits(const double *__restrict__ 
         const double dx = xi - sx[t];
         const double dy = yi - sy[t];
         const double s = dx * dx + dy * dy;                          // no FMA (-ffp-contract=off)
-        word |= static_cast<uint64_t>((s < thr_sq) & (t < jn)) << t;
+        word |= static_cast<uint64_t>((ROWS ? s <= c : s < c) & (t < jn)) << t;
     }
     bits[i * words + w] = word;
 }
@@ -593,34 +621,6 @@ __global__ __launch_bounds__(256) void k_row_select(const double *__restrict__ s
     if (tid == 0) keys_out[i] = prefix;
 }
 
-// The twin of k_euclid_bits with one threshold per row: bit (i, j) = (s_ij <= c[i]), where c[i] is the largest double whose
-// root is at most the row's radius (squared_threshold_le, on the host), so the rule is sqrt(s) <= r_i without a root per pair.
-__global__ __launch_bounds__(256) void k_euclid_bits_rows(const double *__restrict__ xy, int64_t n, const double *__restrict__ c_row,
-                                                          uint64_t *__restrict__ bits, int64_t words) {
-    __shared__ double sx[64], sy[64];
-    const int64_t w = blockIdx.x;
-    const int64_t i = static_cast<int64_t>(blockIdx.y) * 256 + threadIdx.x;
-    const int64_t j0 = w * 64;
-    if (threadIdx.x < 64) {
-        const int64_t j = j0 + threadIdx.x;
-        sx[threadIdx.x] = j < n ? xy[2 * j] : 0.0;
-        sy[threadIdx.x] = j < n ? xy[2 * j + 1] : 0.0;
-    }
-    __syncthreads();
-    if (i >= n) return;
-    const double xi = xy[2 * i], yi = xy[2 * i + 1], ci = c_row[i];
-    const int jn = static_cast<int>(n - j0 < 64 ? n - j0 : 64);
-    uint64_t word = 0;
-#pragma unroll 8
-    for (int t = 0; t < 64; ++t) {
-        const double dx = xi - sx[t];
-        const double dy = yi - sy[t];
-        const double s = dx * dx + dy * dy;                          // no FMA (-ffp-contract=off)
-        word |= static_cast<uint64_t>((s <= ci) & (t < jn)) << t;
-    }
-    bits[i * words + w] = word;
-}
-
 // Membership from a kept distance matrix and one radius per row: bit (i, j) = (D[i][j] <= r[i]) and D[i][j] reached.  One
 // workgroup per row, a wave per 64-column word (the ballot is the word).  masked_out, when given, receives D[i][j] where the bit
 // is set and +inf elsewhere: the matrix a handle built with a cutoff keeps.
@@ -642,26 +642,69 @@ __global__ __launch_bounds__(256) void k_dist_bits_rows(const double *__restrict
 // --------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------
-// The `<=` twin of squared_threshold:  sqrt(s) <= r   <=>   s <= C,   C = max{ s : sqrt(s) <= r }  (r >= 0).
-static double squared_threshold_le(double r) {
-    if (std::isinf(r)) return r;
-    double c = r * r;
-    while (c > 0.0 && std::sqrt(c) > r) c = std::nextafter(c, 0.0);
-    for (;;) {
-        const double up = std::nextafter(c, INFINITY);
-        if (std::isinf(up) || std::sqrt(up) > r) return c;
-        c = up;
-    }
+int check_layout_finite(const char *fn, const double *xy_host, int64_t n) {
+    for (int64_t i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy_host[i])) {
+            safe_set_error("%s: node %lld has a coordinate that is not finite", fn, (long long)(i / 2));
+            return SAFE_E_VALUE;
+        }
+    return SAFE_OK;
 }
 
-// where K3's keys come from: coordinates on the device (xy) or a kept distance matrix (dist)
-struct SelSource {
-    const double *xy = nullptr, *dist = nullptr;
-    int64_t n = 0;
-};
+int check_radii(const char *fn, const double *radii, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(radii[i] >= 0.0)) {
+            safe_set_error("%s: the radius of row %lld is negative or NaN", fn, (long long)i);
+            return SAFE_E_VALUE;
+        }
+    return SAFE_OK;
+}
+
+int upload_layout(safe_ctx *ctx, CallBufs *b, const char *fn, const double *xy_host, int64_t n, const double **d_xy_out) {
+    double *d_xy = nullptr;
+    SAFE_TRY(b->alloc(&d_xy, 2 * n));
+    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    *d_xy_out = d_xy;
+    return SAFE_OK;
+}
+
+int build_undirected_csr(const char *fn, int64_t n, int64_t n_edges, const int32_t *edge_u, const int32_t *edge_v, const double *edge_w,
+                         std::vector<int32_t> *ptr, std::vector<int32_t> *col, std::vector<double> *w) {
+    ptr->assign(n + 1, 0);
+    for (int64_t e = 0; e < n_edges; ++e) {
+        const int32_t u = edge_u[e], v = edge_v[e];
+        SAFE_REQUIRE(u >= 0 && u < n && v >= 0 && v < n, "%s: edge %lld has an end point outside [0,%lld)", fn, (long long)e,
+                     (long long)n);
+        // +inf is refused too: the shortest-path kernel's +inf means "unreached", networkx's "reached over a path of length +inf"
+        if (edge_w)
+            SAFE_REQUIRE(edge_w[e] >= 0.0 && std::isfinite(edge_w[e]), "%s: edge %lld has a negative, infinite or NaN weight", fn,
+                         (long long)e);
+        (*ptr)[u + 1]++;
+        if (u != v) (*ptr)[v + 1]++;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        SAFE_REQUIRE(static_cast<int64_t>((*ptr)[i]) + (*ptr)[i + 1] < (1ll << 31), "%s: too many entries for int32 CSR offsets", fn);
+        (*ptr)[i + 1] += (*ptr)[i];
+    }
+    const int64_t n_adj = (*ptr)[n];
+    col->assign(std::max<int64_t>(n_adj, 1), 0);
+    w->assign(std::max<int64_t>(n_adj, 1), 0.0);
+    std::vector<int32_t> fill(ptr->begin(), ptr->end() - 1);
+    for (int64_t e = 0; e < n_edges; ++e) {
+        const int32_t u = edge_u[e], v = edge_v[e];
+        const double we = edge_w ? edge_w[e] : 1.0;
+        (*col)[fill[u]] = v;
+        (*w)[fill[u]++] = we;
+        if (u != v) {
+            (*col)[fill[v]] = u;
+            (*w)[fill[v]++] = we;
+        }
+    }
+    return SAFE_OK;
+}
 
 // one pass for up to SEL_SLOTS prefixes: the histograms, on the host
-static int sel_pass(safe_ctx *ctx, const SelSource &src, const SelPass &ps, unsigned long long *d_hist,
+static int sel_pass(safe_ctx *ctx, const DistSource &src, const SelPass &ps, unsigned long long *d_hist,
                     std::vector<unsigned long long> &h_hist) {
     hipStream_t s = ctx->stream;
     const size_t bytes = static_cast<size_t>(SEL_SLOTS) * SEL_BINS * sizeof(unsigned long long);
@@ -681,7 +724,7 @@ static int sel_pass(safe_ctx *ctx, const SelSource &src, const SelPass &ps, unsi
 
 // keys[t] = the key of rank ranks[t] (0-based, ascending multiset) among the source's keys; *count = how many keys there are.
 // Ranks are checked against the count, which the first pass delivers.
-static int sel_keys(safe_ctx *ctx, const SelSource &src, const char *who, const int64_t *ranks, int64_t n_ranks,
+static int sel_keys(safe_ctx *ctx, const DistSource &src, const char *who, const int64_t *ranks, int64_t n_ranks,
                     std::vector<unsigned long long> *keys, int64_t *count) {
     *count = 0;
     keys->assign(n_ranks, 0);
@@ -878,28 +921,61 @@ int nbr_build_transpose(safe_nbr *nbr) {
     return SAFE_OK;
 }
 
-// K3b on the context's stream: keys[i] of every row into a host vector (src is xy [n,2] or a kept matrix [n,n], on the device)
-template <bool XY>
-static int row_select_keys(safe_ctx *ctx, const char *fn, const double *d_src, int64_t n, int64_t k,
-                           std::vector<unsigned long long> *keys) {
+// K3b on the context's stream: keys[i] of every row into a host vector
+static int row_select_keys(safe_ctx *ctx, const char *fn, const DistSource &src, int64_t k, std::vector<unsigned long long> *keys) {
+    const int64_t n = src.n;
     keys->assign(n, 0);
     CallBufs b;                                         // (behind *keys: the read-back writes it)
     unsigned long long *d_keys = nullptr;
     SAFE_TRY(b.alloc(&d_keys, n));
-    hipLaunchKernelGGL(k_row_select<XY>, dim3(n), dim3(256), 0, ctx->stream, d_src, n, k, d_keys);
+    if (src.xy) hipLaunchKernelGGL(k_row_select<true>, dim3(n), dim3(256), 0, ctx->stream, src.xy, n, k, d_keys);
+    else hipLaunchKernelGGL(k_row_select<false>, dim3(n), dim3(256), 0, ctx->stream, src.dist, n, k, d_keys);
     SAFE_HIP_CHECK_AS(fn, hipGetLastError());
     SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(keys->data(), d_keys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));
     return SAFE_OK;
 }
 
-// radii of the per-row builders: none NaN, none negative (+inf is a radius)
-static int check_radii(const char *fn, const double *radii, int64_t n) {
-    for (int64_t i = 0; i < n; ++i)
-        if (!(radii[i] >= 0.0)) {
-            safe_set_error("%s: the radius of row %lld is negative or NaN", fn, (long long)i);
-            return SAFE_E_VALUE;
-        }
+// The selections behind the exports, over either source.  xy_host given: the source is that layout -- checked, uploaded into src.xy,
+// keys are squared distances and the caller's values the one root per key (k_select_xy, k_row_select); else src.dist is read in place.
+static void keys_to_distances(const std::vector<unsigned long long> &keys, bool squared, double *out_host) {
+    if (keys.empty()) return;
+    std::memcpy(out_host, keys.data(), keys.size() * sizeof(double));
+    if (squared)
+        for (size_t t = 0; t < keys.size(); ++t) out_host[t] = std::sqrt(out_host[t]);
+}
+
+static int pair_distance_select(safe_ctx *ctx, DistSource src, const double *xy_host, const char *fn, const int64_t *ranks, int64_t n_ranks,
+                                double *out_host, int64_t *count_out) {
+    SAFE_REQUIRE(n_ranks == 0 || (ranks && out_host), "%s: NULL rank or output array", fn);
+    if (count_out) *count_out = 0;
+    if (src.n > SAFE_SELECT_MAX_NODES) {
+        safe_set_error("%s: n=%lld is above the %d nodes the selection takes", fn, (long long)src.n, SAFE_SELECT_MAX_NODES);
+        return SAFE_E_UNSUPPORTED;
+    }
+    if (xy_host) SAFE_TRY(check_layout_finite(fn, xy_host, src.n));
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    CallBufs b;
+    if (xy_host) SAFE_TRY(upload_layout(ctx, &b, fn, xy_host, src.n, &src.xy));
+    int64_t count = 0;
+    const int rc = sel_keys(ctx, src, fn, ranks, n_ranks, &keys, &count);
+    if (count_out) *count_out = count;                                // (known even where a rank is refused)
+    SAFE_TRY(rc);
+    if (xy_host) SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));   // (n = 1 launches nothing: the upload still reads xy_host)
+    keys_to_distances(keys, xy_host != nullptr, out_host);
+    return SAFE_OK;
+}
+
+static int row_distance_select(safe_ctx *ctx, DistSource src, const double *xy_host, const char *fn, int64_t k, double *radii_out_host) {
+    SAFE_REQUIRE(k >= 1, "%s: k=%lld, the number of nearest nodes must be at least 1", fn, (long long)k);
+    if (xy_host) SAFE_TRY(check_layout_finite(fn, xy_host, src.n));
+    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<unsigned long long> keys;
+    CallBufs b;
+    if (xy_host) SAFE_TRY(upload_layout(ctx, &b, fn, xy_host, src.n, &src.xy));
+    SAFE_TRY(row_select_keys(ctx, fn, src, k, &keys));
+    keys_to_distances(keys, xy_host != nullptr, radii_out_host);
     return SAFE_OK;
 }
 
@@ -912,10 +988,9 @@ int safe_nbr_euclidean(safe_ctx *ctx, const double *xy_host, int64_t n, double n
     NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
     CallBufs b;
-    double *d_xy = nullptr;
-    SAFE_TRY(b.alloc(&d_xy, 2 * n));
-    SAFE_HIP_CHECK_AS("safe_nbr_euclidean", hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_euclid_bits, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n,
+    const double *d_xy = nullptr;
+    SAFE_TRY(upload_layout(ctx, &b, "safe_nbr_euclidean", xy_host, n, &d_xy));
+    hipLaunchKernelGGL(k_euclid_bits<false>, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n,
                        squared_threshold(nr), nbr->bits, nbr->words);
     SAFE_HIP_CHECK_AS("safe_nbr_euclidean", hipGetLastError());
     SAFE_TRY(nbr_finalize_from_bits(nbr.get()));
@@ -980,14 +1055,14 @@ int safe_edge_lengths(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t n
         SAFE_REQUIRE(edge_u[e] >= 0 && edge_u[e] < n && edge_v[e] >= 0 && edge_v[e] < n,
                      "safe_edge_lengths: edge %lld has an end point outside [0,%lld)", (long long)e, (long long)n);
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    double *d_xy = nullptr, *d_out = nullptr;
+    const double *d_xy = nullptr;
+    double *d_out = nullptr;
     int32_t *d_u = nullptr, *d_v = nullptr;
     CallBufs b;
-    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    SAFE_TRY(upload_layout(ctx, &b, "safe_edge_lengths", xy_host, n, &d_xy));
     SAFE_TRY(b.alloc(&d_out, n_edges));
     SAFE_TRY(b.alloc(&d_u, n_edges));
     SAFE_TRY(b.alloc(&d_v, n_edges));
-    SAFE_HIP_CHECK(hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_u, edge_u, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK(hipMemcpyAsync(d_v, edge_v, n_edges * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_edge_lengths, dim3(ceil_div(n_edges, 256)), dim3(256), 0, ctx->stream, d_xy, n_edges, d_u,
@@ -1004,36 +1079,13 @@ int safe_nbr_shortpath(safe_ctx *ctx, int64_t n, int64_t n_edges, const int32_t 
     SAFE_REQUIRE(n_edges == 0 || (edge_u && edge_v), "safe_nbr_shortpath: NULL edge arrays");
     *out = nullptr;
     SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    // undirected CSR adjacency on the host (both directions; self loops once; two edges between one pair are both kept, so the
-    // lighter one counts -- nx.Graph would keep the weight added last: de-duplicating is the caller's job)
-    std::vector<int32_t> deg(n + 1, 0);
-    for (int64_t e = 0; e < n_edges; ++e) {
-        const int32_t u = edge_u[e], v = edge_v[e];
-        SAFE_REQUIRE(u >= 0 && u < n && v >= 0 && v < n, "safe_nbr_shortpath: edge %lld has an end point outside [0,%lld)",
-                     (long long)e, (long long)n);
-        // +inf is refused too: the kernel's +inf means "unreached", networkx's "reached over a path of length +inf"
-        if (edge_w)
-            SAFE_REQUIRE(edge_w[e] >= 0.0 && std::isfinite(edge_w[e]),
-                         "safe_nbr_shortpath: edge %lld has a negative, infinite or NaN weight", (long long)e);
-        deg[u + 1]++;
-        if (u != v) deg[v + 1]++;
-    }
-    for (int64_t i = 0; i < n; ++i) deg[i + 1] += deg[i];
-    const int64_t n_adj = deg[n];
-    std::vector<int32_t> adj_col(std::max<int64_t>(n_adj, 1));
-    std::vector<double> adj_w(std::max<int64_t>(n_adj, 1));
-    std::vector<int32_t> fill(deg.begin(), deg.end() - 1);
-    for (int64_t e = 0; e < n_edges; ++e) {
-        const int32_t u = edge_u[e], v = edge_v[e];
-        const double w = edge_w ? edge_w[e] : 1.0;
-        adj_col[fill[u]] = v;
-        adj_w[fill[u]++] = w;
-        if (u != v) {
-            adj_col[fill[v]] = u;
-            adj_w[fill[v]++] = w;
-        }
-    }
     const char *fn = "safe_nbr_shortpath";
+    // two edges between one pair are both kept, so the lighter one counts -- nx.Graph would keep the weight added last:
+    // de-duplicating is the caller's job
+    std::vector<int32_t> deg, adj_col;
+    std::vector<double> adj_w;
+    SAFE_TRY(build_undirected_csr(fn, n, n_edges, edge_u, edge_v, edge_w, &deg, &adj_col, &adj_w));
+    const int64_t n_adj = deg[n];
     hipStream_t s = ctx->stream;
     NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
@@ -1173,99 +1225,28 @@ int safe_pair_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n
                                  double *out_host, int64_t *n_pairs) {
     const char *fn = "safe_pair_distance_select_xy";
     SAFE_REQUIRE(ctx && xy_host && n >= 1 && n_ranks >= 0, "%s: bad argument", fn);
-    SAFE_REQUIRE(n_ranks == 0 || (ranks && out_host), "%s: NULL rank or output array", fn);
-    if (n_pairs) *n_pairs = 0;
-    if (n > SAFE_SELECT_MAX_NODES) {
-        safe_set_error("%s: n=%lld is above the %d nodes the selection takes", fn, (long long)n, SAFE_SELECT_MAX_NODES);
-        return SAFE_E_UNSUPPORTED;
-    }
-    for (int64_t i = 0; i < 2 * n; ++i)
-        if (!std::isfinite(xy_host[i])) {
-            safe_set_error("%s: node %lld has a coordinate that is not finite", fn, (long long)(i / 2));
-            return SAFE_E_VALUE;
-        }
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    std::vector<unsigned long long> keys;
-    CallBufs b;
-    double *d_xy = nullptr;
-    SAFE_TRY(b.alloc(&d_xy, 2 * n));
-    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SelSource src;
-    src.xy = d_xy;
-    src.n = n;
-    int64_t count = 0;
-    const int rc = sel_keys(ctx, src, fn, ranks, n_ranks, &keys, &count);
-    if (n_pairs) *n_pairs = count;                                    // (known even where a rank is refused)
-    SAFE_TRY(rc);
-    SAFE_HIP_CHECK_AS(fn, safe_stream_sync(ctx->stream));             // (n = 1 launches nothing: the upload still reads xy_host)
-    for (int64_t t = 0; t < n_ranks; ++t) {
-        double s;
-        std::memcpy(&s, &keys[t], sizeof s);
-        out_host[t] = std::sqrt(s);                                   // the one root per rank (k_select_xy)
-    }
-    return SAFE_OK;
+    return pair_distance_select(ctx, DistSource{nullptr, nullptr, n}, xy_host, fn, ranks, n_ranks, out_host, n_pairs);
 }
 
 int safe_nbr_distance_select(safe_nbr *nbr, const int64_t *ranks, int64_t n_ranks, double *out_host, int64_t *n_finite_pairs) {
     const char *fn = "safe_nbr_distance_select";
     SAFE_REQUIRE(nbr && n_ranks >= 0, "%s: bad argument", fn);
-    SAFE_REQUIRE(n_ranks == 0 || (ranks && out_host), "%s: NULL rank or output array", fn);
     SAFE_REQUIRE(nbr->dist != nullptr, "%s: handle was built without keep_distances", fn);
-    if (n_finite_pairs) *n_finite_pairs = 0;
-    if (nbr->n > SAFE_SELECT_MAX_NODES) {
-        safe_set_error("%s: n=%lld is above the %d nodes the selection takes", fn, (long long)nbr->n, SAFE_SELECT_MAX_NODES);
-        return SAFE_E_UNSUPPORTED;
-    }
-    safe_ctx *ctx = nbr->ctx;
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    std::vector<unsigned long long> keys;
-    SelSource src;
-    src.dist = nbr->dist;
-    src.n = nbr->n;
-    int64_t count = 0;
-    const int rc = sel_keys(ctx, src, fn, ranks, n_ranks, &keys, &count);
-    if (n_finite_pairs) *n_finite_pairs = count;                      // (known even where a rank is refused)
-    SAFE_TRY(rc);
-    for (int64_t t = 0; t < n_ranks; ++t) std::memcpy(&out_host[t], &keys[t], sizeof(double));
-    return SAFE_OK;
+    return pair_distance_select(nbr->ctx, DistSource{nullptr, nbr->dist, nbr->n}, nullptr, fn, ranks, n_ranks, out_host, n_finite_pairs);
 }
 
 int safe_row_distance_select_xy(safe_ctx *ctx, const double *xy_host, int64_t n, int64_t k, double *radii_out_host) {
     const char *fn = "safe_row_distance_select_xy";
     SAFE_REQUIRE(ctx && xy_host && radii_out_host, "%s: NULL argument", fn);
     SAFE_REQUIRE(n >= 1 && n < (1ll << 31) - 64, "%s: n=%lld out of range", fn, (long long)n);
-    SAFE_REQUIRE(k >= 1, "%s: k=%lld, the number of nearest nodes must be at least 1", fn, (long long)k);
-    for (int64_t i = 0; i < 2 * n; ++i)
-        if (!std::isfinite(xy_host[i])) {
-            safe_set_error("%s: node %lld has a coordinate that is not finite", fn, (long long)(i / 2));
-            return SAFE_E_VALUE;
-        }
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    std::vector<unsigned long long> keys;
-    CallBufs b;
-    double *d_xy = nullptr;
-    SAFE_TRY(b.alloc(&d_xy, 2 * n));
-    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    SAFE_TRY(row_select_keys<true>(ctx, fn, d_xy, n, k, &keys));
-    for (int64_t i = 0; i < n; ++i) {
-        double s;
-        std::memcpy(&s, &keys[i], sizeof s);
-        radii_out_host[i] = std::sqrt(s);                                 // the one root per row (k_row_select)
-    }
-    return SAFE_OK;
+    return row_distance_select(ctx, DistSource{nullptr, nullptr, n}, xy_host, fn, k, radii_out_host);
 }
 
 int safe_nbr_row_distance_select(safe_nbr *nbr, int64_t k, double *radii_out_host) {
     const char *fn = "safe_nbr_row_distance_select";
     SAFE_REQUIRE(nbr && radii_out_host, "%s: NULL argument", fn);
     SAFE_REQUIRE(nbr->dist != nullptr, "%s: handle was built without keep_distances", fn);
-    SAFE_REQUIRE(k >= 1, "%s: k=%lld, the number of nearest nodes must be at least 1", fn, (long long)k);
-    safe_ctx *ctx = nbr->ctx;
-    SAFE_HIP_CHECK(hipSetDevice(ctx->device));
-    std::vector<unsigned long long> keys;
-    SAFE_TRY(row_select_keys<false>(ctx, fn, nbr->dist, nbr->n, k, &keys));
-    std::memcpy(radii_out_host, keys.data(), nbr->n * sizeof(double));
-    return SAFE_OK;
+    return row_distance_select(nbr->ctx, DistSource{nullptr, nbr->dist, nbr->n}, nullptr, fn, k, radii_out_host);
 }
 
 int safe_nbr_euclidean_rows(safe_ctx *ctx, const double *xy_host, int64_t n, const double *radii_host, safe_nbr **out) {
@@ -1280,13 +1261,13 @@ int safe_nbr_euclidean_rows(safe_ctx *ctx, const double *xy_host, int64_t n, con
     NbrPtr nbr(nullptr, nbr_free);
     SAFE_TRY(nbr_new(ctx, n, &nbr));
     CallBufs b;                                         // (behind c: the upload reads it)
-    double *d_xy = nullptr, *d_c = nullptr;
-    SAFE_TRY(b.alloc(&d_xy, 2 * n));
+    const double *d_xy = nullptr;
+    double *d_c = nullptr;
+    SAFE_TRY(upload_layout(ctx, &b, fn, xy_host, n, &d_xy));
     SAFE_TRY(b.alloc(&d_c, n));
-    SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_xy, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     SAFE_HIP_CHECK_AS(fn, hipMemcpyAsync(d_c, c.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_euclid_bits_rows, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n, d_c, nbr->bits,
-                       nbr->words);
+    hipLaunchKernelGGL(k_euclid_bits<true>, dim3(nbr->words, ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_xy, n,
+                       static_cast<const double *>(d_c), nbr->bits, nbr->words);
     SAFE_HIP_CHECK_AS(fn, hipGetLastError());
     SAFE_TRY(nbr_finalize_from_bits(nbr.get()));        // (waits for the stream: the uploads have read xy_host and c)
     nbr->h_xy.assign(xy_host, xy_host + 2 * n);         // node order of the block-sparse form (mfma.hip)

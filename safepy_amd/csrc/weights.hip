@@ -426,11 +426,7 @@ int weights_install(safe_nbr *nbr, const char *who, CallBufs *bufs, double *d_w)
 
 int check_kind(const char *who, int kind, const double *radii_host, int64_t n, double bandwidth) {
     SAFE_REQUIRE(kind >= SAFE_WEIGHT_UNIFORM && kind <= SAFE_WEIGHT_GAUSSIAN, "%s: unknown weight kind %d", who, kind);
-    for (int64_t i = 0; i < n; ++i)
-        if (!(radii_host[i] >= 0.0)) {
-            safe_set_error("%s: radius %lld is %g: every radius must be a number >= 0", who, (long long)i, radii_host[i]);
-            return SAFE_E_VALUE;
-        }
+    SAFE_TRY(check_radii(who, radii_host, n));
     if (!(std::isfinite(bandwidth) && bandwidth > 0.0)) {
         safe_set_error("%s: bandwidth %g must be finite and > 0", who, bandwidth);
         return SAFE_E_VALUE;
@@ -446,11 +442,12 @@ int weights_build(safe_nbr *nbr, const char *who, const double *xy_host, int kin
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_WEIGHT_INPUTS, static_cast<size_t>(3 * n) * sizeof(double), reinterpret_cast<void **>(&d_in)));
     SAFE_HIP_CHECK_AS(who, hipMemcpyAsync(d_in, radii_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (xy_host) SAFE_HIP_CHECK_AS(who, hipMemcpyAsync(d_in + n, xy_host, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const DistSource src = xy_host ? DistSource{d_in + n, nullptr, n} : DistSource{nullptr, nbr->dist, n};
     CallBufs bufs;
     double *d_w = nullptr;
     SAFE_TRY(bufs.alloc(&d_w, static_cast<size_t>(nbr->nnz)));
     hipLaunchKernelGGL(k_weights_build, dim3(static_cast<unsigned int>(ceil_div(n, 4))), dim3(256), 0, ctx->stream, nbr->row_ptr, nbr->col, n,
-                       xy_host ? d_in + n : nullptr, xy_host ? nullptr : nbr->dist, d_in, kind, bandwidth, d_w);
+                       src.xy, src.dist, d_in, kind, bandwidth, d_w);
     SAFE_HIP_CHECK_AS(who, hipGetLastError());
     return weights_install(nbr, who, &bufs, d_w);
 }
@@ -463,11 +460,7 @@ int safe_nbr_weights_from_xy(safe_nbr *nbr, const double *xy_host, int kind, con
     const char *who = "safe_nbr_weights_from_xy";
     SAFE_REQUIRE(nbr && xy_host && radii_host, "%s: NULL argument", who);
     SAFE_TRY(check_kind(who, kind, radii_host, nbr->n, bandwidth));
-    for (int64_t i = 0; i < 2 * nbr->n; ++i)
-        if (!std::isfinite(xy_host[i])) {
-            safe_set_error("%s: coordinate %lld of node %lld is not finite", who, (long long)(i & 1), (long long)(i >> 1));
-            return SAFE_E_VALUE;
-        }
+    SAFE_TRY(check_layout_finite(who, xy_host, nbr->n));
     return weights_build(nbr, who, xy_host, kind, radii_host, bandwidth);
 }
 

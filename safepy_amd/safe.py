@@ -212,6 +212,145 @@ def _graph_arrays(graph):
     return xy, eu, ev, length, weight
 
 
+def _x_extent(xy):
+    x = xy[:, 0]
+    return np.max(x) - np.min(x)                        # safe.py:390-391, 404-405
+
+
+class _DistanceSource:
+    """Where the node distances of a neighborhood definition come from: the one object that define_neighborhoods,
+    compute_node_distances, node_distance_percentile and the within-reach relation ask for radii, membership handles and
+    weights (SAFE._distance_source picks it).  A context manager: leaving it releases whatever it opened on the device."""
+    keeps_distances = False       # the handles it builds keep the N x N distances on the device (what node_distances then is)
+    rule = '<'                    # how a distance compares with a scalar radius (safe.py:399 against networkx's cutoff)
+    layout_hint = None            # the layout a new handle should be told of, or None (it knows it already, or there is none)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        pass
+
+    def percentiles(self, qs):
+        """np.percentile(v, q), bit for bit, for every q of `qs`.  v is the multiset of node distances of the pairs i < j:
+        pdist(xy), or the finite D[i, j] of the kept matrix (row i = the search from i).  v is never stored: the device
+        counts it, then selects the order statistics the interpolations need."""
+        plan = _percentile_plan(self.select([])[1], qs)
+        return _percentile_values(plan, self.select(plan[0])[0])
+
+
+class _LayoutDistances(_DistanceSource):
+    """'euclidean': scipy's pdist of the layout coordinates, recomputed by every device call; nothing stays on the device."""
+
+    def __init__(self, ctx, xy):
+        self.ctx, self.xy = ctx, xy
+
+    def diameter_radius(self, fraction):
+        return fraction * _x_extent(self.xy)
+
+    def select(self, ranks):
+        return self.ctx.pair_distance_select(self.xy, ranks)
+
+    def nearest_radii(self, k):
+        return self.ctx.row_distance_select(self.xy, k)
+
+    def members(self, radius, keep_distances=True):
+        return be.Neighborhoods.euclidean(self.ctx, self.xy, radius)
+
+    def members_rows(self, radii):
+        return be.Neighborhoods.euclidean_rows(self.ctx, self.xy, radii)
+
+    def set_weights(self, nbr, kind, radii, bandwidth):
+        nbr.set_weights_from_xy(self.xy, kind, radii, bandwidth)
+
+    def dense_distances(self, radius):
+        """f64 [N, N] == squareform(pdist(xy)) (safe.py:397)"""
+        n = self.xy.shape[0]
+        d_xy = self.ctx.alloc(self.xy.nbytes)
+        d_out = self.ctx.alloc_f64(n, n)
+        try:
+            d_xy.upload(self.xy)
+            self.ctx.euclidean_dense(d_xy.ptr, n, radius, None, d_out.ptr)
+            return d_out.download((n, n))
+        finally:
+            d_xy.free()
+            d_out.free()
+
+    def check_reach(self, r, t):
+        if not np.isfinite(self.xy).all():
+            raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs finite "
+                             'x and y coordinates for every node')
+        if not t > 0:                                # `distance < t` would drop the diagonal: no node within its own reach
+            raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs a "
+                             'neighborhood radius greater than 0: it resolved to %r' % (r,))
+
+
+class _NetworkDistances(_DistanceSource):
+    """The network metrics: all-pairs shortest paths bounded by a cutoff over the edge weights `w` (None = 1 per edge), or,
+    with diffusion = (restart, steps), the random-walk-with-restart distance of 'diffusion' (the graph's 'weight' edge
+    attribute; 'length' is never used) with members D <= cutoff.  Percentiles and per-node radii read ONE unbounded search
+    whose matrix stays on the device: made when first asked for, owned here, and closed before a bounded handle is built, once
+    the per-row handle is built from it, and on close()."""
+    keeps_distances = True
+    rule = '<='
+
+    def __init__(self, ctx, xy, eu, ev, w, diffusion=None, diameter_in_layout_units=True):
+        self.ctx, self.xy, self.eu, self.ev, self.w, self.diffusion = ctx, xy, eu, ev, w, diffusion
+        self.diameter_in_layout_units = diameter_in_layout_units
+        self._unbounded = None
+        # the layout only orders the nodes on the device.  'diffusion' needs none: an edge list without finite coordinates gets no hint
+        self.layout_hint = xy if diffusion is None or np.isfinite(xy).all() else None
+
+    def _open(self, cutoff, keep_distances=True):
+        n, eu, ev = self.xy.shape[0], self.eu, self.ev
+        if eu.size and (eu.min() < 0 or ev.min() < 0 or eu.max() >= n or ev.max() >= n):
+            raise ValueError('shortest-path metrics index the neighborhood matrix by node id: ids must be 0..N-1')
+        if self.diffusion is not None:
+            return be.Neighborhoods.diffusion(self.ctx, n, eu, ev, self.w, self.diffusion[0], self.diffusion[1], cutoff)
+        return be.Neighborhoods.shortpath(self.ctx, n, eu, ev, self.w, cutoff, keep_distances=keep_distances)
+
+    def _all_pairs(self):
+        if self._unbounded is None:
+            self._unbounded = self._open(np.inf)
+        return self._unbounded
+
+    def close(self):
+        nbr, self._unbounded = self._unbounded, None
+        if nbr is not None:
+            nbr.close()
+
+    def diameter_radius(self, fraction):
+        if not self.diameter_in_layout_units:
+            return fraction                             # 'shortpath' + 'diameter': the reference's hop cutoff, safe.py:409
+        return fraction * _x_extent(self.xy)
+
+    def select(self, ranks):
+        return self._all_pairs().distance_select(ranks)
+
+    def nearest_radii(self, k):
+        return self._all_pairs().row_distance_select(k)
+
+    def members(self, radius, keep_distances=True):
+        self.close()
+        return self._open(radius, keep_distances)
+
+    def members_rows(self, radii):
+        """A[i, j] = (D[i, j] <= r_i); the handle keeps the masked distances (D where A is 1)."""
+        try:
+            return be.Neighborhoods.from_distances_rows(self._all_pairs(), radii, keep_distances=True)
+        finally:
+            self.close()
+
+    def set_weights(self, nbr, kind, radii, bandwidth):
+        nbr.set_weights_from_distances(kind, radii, bandwidth)
+
+    def check_reach(self, r, t):
+        pass
+
+
 class _DeviceResult:
     """An [n, m] float64 result of compute_pvalues still on the device: copied to the host the first
     time the attribute is read (see `_LazyArray`).  Owns its device buffer."""
@@ -884,121 +1023,70 @@ class SAFE:
     def node_distances(self, value):
         self._node_distances = value
 
-    def _radius(self, xy):
-        x = xy[:, 0]
-        return self.neighborhood_radius * (np.max(x) - np.min(x))      # safe.py:390-391, 404-405
-
     def _override_neighborhood_settings(self, kwargs):
-        if 'node_distance_metric' in kwargs:
-            self.node_distance_metric = kwargs['node_distance_metric']
-        if 'neighborhood_radius_type' in kwargs:
-            self.neighborhood_radius_type = kwargs['neighborhood_radius_type']
-        if 'neighborhood_radius' in kwargs:
-            self.neighborhood_radius = kwargs['neighborhood_radius']
-        for name in ('neighborhood_weighting', 'neighborhood_weight_bandwidth', 'diffusion_restart', 'diffusion_steps'):
+        for name in ('node_distance_metric', 'neighborhood_radius_type', 'neighborhood_radius', 'neighborhood_weighting',
+                     'neighborhood_weight_bandwidth', 'diffusion_restart', 'diffusion_steps'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
         self.validate_config()
 
-    def _shortpath_weights(self, xy, eu, ev, length, weight):
-        n = xy.shape[0]
-        if eu.size and (eu.min() < 0 or ev.min() < 0 or eu.max() >= n or ev.max() >= n):
-            raise ValueError('shortest-path metrics index the neighborhood matrix by node id: ids must be 0..N-1')
-        if self.node_distance_metric == 'shortpath_weighted_layout':
-            return length                               # weight='length', missing -> 1 (networkx)
-        return weight                                   # default weight attr 'weight', missing -> 1
+    def _distance_source(self):
+        """The _DistanceSource of the current node_distance_metric over the graph's arrays; no device work yet."""
+        xy, eu, ev, length, weight = _graph_arrays(self.graph)
+        ctx, metric = self._ctx(), self.node_distance_metric
+        if metric == 'euclidean':
+            return _LayoutDistances(ctx, xy)
+        if metric == 'diffusion':
+            return _NetworkDistances(ctx, xy, eu, ev, weight, diffusion=(self.diffusion_restart, self.diffusion_steps))
+        if metric == 'shortpath_weighted_layout':
+            return _NetworkDistances(ctx, xy, eu, ev, length)           # weight='length', missing -> 1 (networkx)
+        return _NetworkDistances(ctx, xy, eu, ev, weight, diameter_in_layout_units=False)   # default weight attr 'weight', missing -> 1
 
-    def _graph_distances(self, ctx, arrays, cutoff):
-        """The membership handle of the network metrics with its kept distance matrix: all-pairs shortest paths bounded by
-        `cutoff` ('shortpath', 'shortpath_weighted_layout'), or the random-walk-with-restart distance of 'diffusion' (the
-        graph's 'weight' edge attribute, 1 where missing; 'length' is never used) with members D <= cutoff."""
-        xy, eu, ev, length, weight = arrays
-        w = self._shortpath_weights(xy, eu, ev, length, weight)
-        if self.node_distance_metric == 'diffusion':
-            return be.Neighborhoods.diffusion(ctx, xy.shape[0], eu, ev, w, self.diffusion_restart, self.diffusion_steps, cutoff)
-        return be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, cutoff, keep_distances=True)
-
-    def _distance_percentiles(self, ctx, arrays, qs):
-        """np.percentile(v, q), bit for bit, for every q of `qs`.  v is the multiset of node distances of the pairs i < j
-        under the current metric: pdist(xy), or the finite D[i, j] of the all-pairs shortest paths (row i = the search
-        from i: one unbounded search whose matrix stays on the device).  v is never stored: the device counts it, then
-        selects the order statistics the interpolations need."""
-        xy, eu, ev, length, weight = arrays
-        if self.node_distance_metric == 'euclidean':
-            plan = _percentile_plan(ctx.pair_distance_select(xy, [])[1], qs)
-            return _percentile_values(plan, ctx.pair_distance_select(xy, plan[0])[0])
-        nbr = self._graph_distances(ctx, arrays, np.inf)
-        try:
-            plan = _percentile_plan(nbr.distance_select([])[1], qs)
-            return _percentile_values(plan, nbr.distance_select(plan[0])[0])
-        finally:
-            nbr.close()
-
-    def _nearest_radii(self, ctx, arrays):
-        """neighborhood_radius_type = 'nearest': (the unbounded shortest-path handle with its kept matrix, or None for
-        'euclidean'; every node's distance to its k-th nearest other node, f64 [N]), k = int(neighborhood_radius).  The
-        caller closes the handle."""
-        xy, eu, ev, length, weight = arrays
-        k = min(int(self.neighborhood_radius), 2 ** 62)
-        if self.node_distance_metric == 'euclidean':
-            return None, ctx.row_distance_select(xy, k)
-        src = self._graph_distances(ctx, arrays, np.inf)
-        try:
-            return src, src.row_distance_select(k)
-        except Exception:
-            src.close()
-            raise
+    def _radius_type(self):
+        return self.neighborhood_radius_type or 'diameter'              # None: the reference's default
 
     def _refuse_diffusion_diameter(self):
         """'diffusion' distances are 1 - a similarity, in [0, 1]: a fraction of the layout's extent ('diameter') means nothing."""
-        if self.node_distance_metric == 'diffusion' and self.neighborhood_radius_type in (None, 'diameter'):
+        if self.node_distance_metric == 'diffusion' and self._radius_type() == 'diameter':
             raise ValueError("neighborhood_radius_type = 'diameter' is not defined for node_distance_metric = 'diffusion' (the "
                              "distance does not come from a layout): use 'percentile', 'nearest' or 'absolute'")
 
-    def _set_layout_hint(self, xy):
-        """The layout only orders the nodes on the device.  'diffusion' needs none: an edge list without finite coordinates gets no hint."""
-        if self.node_distance_metric != 'diffusion' or np.isfinite(xy).all():
-            self._nbr.set_layout(xy)
+    def _nearest_radii(self, src):
+        """neighborhood_radius_type = 'nearest': every node's distance to its k-th nearest other node, f64 [N],
+        k = int(neighborhood_radius)."""
+        return src.nearest_radii(min(int(self.neighborhood_radius), 2 ** 62))
 
     def _set_nearest_radii(self, radii):
         self.neighborhood_radii = radii
         self.neighborhood_radius_resolved = float(np.median(radii))
         return self.neighborhood_radius_resolved
 
-    def _nearest_neighborhoods(self, ctx, arrays):
-        """The membership handle of neighborhood_radius_type = 'nearest', A[i, j] = (D[i, j] <= r_i); sets neighborhood_radii
-        and neighborhood_radius_resolved.  A shortest-path handle keeps the masked distances (D where A is 1)."""
-        src, radii = self._nearest_radii(ctx, arrays)
-        try:
-            if src is None:
-                nbr = be.Neighborhoods.euclidean_rows(ctx, arrays[0], radii)
-            else:
-                nbr = be.Neighborhoods.from_distances_rows(src, radii, keep_distances=True)
-        finally:
-            if src is not None:
-                src.close()
-        self._set_nearest_radii(radii)
-        return nbr
-
-    def _resolve_radius(self, ctx, arrays):
+    def _resolve_radius(self, src):
         """The radius in distance units (the hop cutoff for 'shortpath') that neighborhood_radius stands for under
         neighborhood_radius_type; kept as self.neighborhood_radius_resolved."""
-        kind = self.neighborhood_radius_type
+        kind = self._radius_type()
         self._refuse_diffusion_diameter()
         if kind == 'nearest':                           # one radius per node: the typical one stands for them
-            src, radii = self._nearest_radii(ctx, arrays)
-            if src is not None:
-                src.close()
-            return self._set_nearest_radii(radii)
+            return self._set_nearest_radii(self._nearest_radii(src))
         self.neighborhood_radii = None
         if kind == 'percentile':
-            r = self._distance_percentiles(ctx, arrays, [self.neighborhood_radius])[0]
-        elif kind == 'absolute' or self.node_distance_metric == 'shortpath':
-            r = self.neighborhood_radius                # 'shortpath' + 'diameter': the reference's hop cutoff, safe.py:409
+            r = src.percentiles([self.neighborhood_radius])[0]
+        elif kind == 'absolute':
+            r = self.neighborhood_radius
         else:
-            r = self._radius(arrays[0])
+            r = src.diameter_radius(self.neighborhood_radius)
         self.neighborhood_radius_resolved = float(r)
         return r
+
+    def _build_neighborhoods(self, src):
+        """The membership handle under the current radius type: A[i, j] = (D[i, j] <= r_i) for 'nearest', the source's rule
+        against the resolved radius otherwise; sets neighborhood_radii and neighborhood_radius_resolved."""
+        if self._radius_type() != 'nearest':
+            return src.members(self._resolve_radius(src))
+        radii = self._nearest_radii(src)
+        nbr = src.members_rows(radii)
+        self._set_nearest_radii(radii)
+        return nbr
 
     def node_distance_percentile(self, q):
         """Additive: np.percentile(v, q) (linear method, bit for bit) of the distances v of all node pairs i < j under the
@@ -1009,7 +1097,8 @@ class SAFE:
         qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
         if qs.ndim != 1 or not all(_is_percentage(v) for v in qs.tolist()):
             raise ValueError('Percentiles must be in the range [0, 100]')
-        out = np.array(self._distance_percentiles(self._ctx(), _graph_arrays(self.graph), qs.tolist()), dtype=np.float64)
+        with self._distance_source() as src:
+            out = np.array(src.percentiles(qs.tolist()), dtype=np.float64)
         return float(out[0]) if np.ndim(q) == 0 else out
 
     def define_neighborhoods(self, **kwargs):
@@ -1047,33 +1136,22 @@ class SAFE:
         if weighting == 'custom':                    # before any device work; nothing changes
             raise ValueError("neighborhood_weighting = 'custom' is not something define_neighborhoods can build: define the "
                              "neighborhoods under another setting (or 'none'), then give the weights to set_neighborhood_weights()")
-        xy, eu, ev, length, weight = _graph_arrays(self.graph)
-        ctx = self._ctx()
-        if self.node_distance_metric != 'euclidean':
-            self._node_distances = None          # replaced below (a copy still on the device is not fetched first)
-        self._invalidate_neighborhoods()
-        self.neighborhood_radii = None               # (a call that fails below leaves no radii of an earlier one behind)
-        nearest = self.neighborhood_radius_type == 'nearest'
-        if nearest:
-            self.neighborhood_radius_resolved = None
-            self._nbr = self._nearest_neighborhoods(ctx, (xy, eu, ev, length, weight))
-            if self.node_distance_metric != 'euclidean':
-                self._set_layout_hint(xy)
+        nearest = self._radius_type() == 'nearest'
+        with self._distance_source() as src:
+            if src.keeps_distances:
+                self._node_distances = None          # replaced below (a copy still on the device is not fetched first)
+            self._invalidate_neighborhoods()
+            self.neighborhood_radii = None           # (a call that fails below leaves no radii of an earlier one behind)
+            if nearest:
+                self.neighborhood_radius_resolved = None
+            self._nbr = self._build_neighborhoods(src)
+            if src.layout_hint is not None:
+                self._nbr.set_layout(src.layout_hint)
+            if src.keeps_distances:
                 self._node_distances = ('device-shortpath', self._nbr)
-        elif self.node_distance_metric == 'euclidean':
-            radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
-            self._nbr = be.Neighborhoods.euclidean(ctx, xy, radius)
-        else:
-            radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
-            self._nbr = self._graph_distances(ctx, (xy, eu, ev, length, weight), radius)
-            self._set_layout_hint(xy)
-            self._node_distances = ('device-shortpath', self._nbr)
-        if weighting != 'none':
-            radii = self.neighborhood_radii if nearest else self.neighborhood_radius_resolved
-            if self.node_distance_metric == 'euclidean':
-                self._nbr.set_weights_from_xy(xy, weighting, radii, self.neighborhood_weight_bandwidth)
-            else:
-                self._nbr.set_weights_from_distances(weighting, radii, self.neighborhood_weight_bandwidth)
+            if weighting != 'none':
+                radii = self.neighborhood_radii if nearest else self.neighborhood_radius_resolved
+                src.set_weights(self._nbr, weighting, radii, self.neighborhood_weight_bandwidth)
         if self.verbose:
             num_neighbors = self._nbr.row_counts()
             logging.info('Node distance metric: %s' % self.node_distance_metric)
@@ -1084,7 +1162,7 @@ class SAFE:
                                 float(np.max(self.neighborhood_radii))))
             else:
                 logging.info('Neighborhood definition: %.2f x %s' % (self.neighborhood_radius, self.neighborhood_radius_type))
-            if self.neighborhood_radius_type not in (None, 'diameter', 'nearest'):
+            if self._radius_type() not in ('diameter', 'nearest'):
                 logging.info('Neighborhood radius in distance units: %r' % self.neighborhood_radius_resolved)
             logging.info('Number of nodes per neighborhood (mean +/- std): %.2f +/- %.2f'
                          % (np.mean(num_neighbors), np.std(num_neighbors)))
@@ -1096,31 +1174,15 @@ class SAFE:
         dict-of-dicts define_neighborhoods stores (safe.py:417)."""
         self._override_neighborhood_settings(kwargs)
         self._refuse_diffusion_diameter()
-        xy, eu, ev, length, weight = _graph_arrays(self.graph)
-        ctx = self._ctx()
-        n = xy.shape[0]
-        if self.neighborhood_radius_type == 'nearest' and self.node_distance_metric != 'euclidean':
-            nbr = self._nearest_neighborhoods(ctx, (xy, eu, ev, length, weight))      # the distances inside every node's own radius
+        with self._distance_source() as src:
+            if not src.keeps_distances:
+                self._node_distances = src.dense_distances(self._resolve_radius(src))
+                return
+            nbr = self._build_neighborhoods(src)     # its kept matrix: the distances inside the radius (every node's own under 'nearest')
             try:
                 self._node_distances = ('dense-shortpath', nbr.distances())
             finally:
                 nbr.close()
-            return
-        radius = self._resolve_radius(ctx, (xy, eu, ev, length, weight))
-        if self.node_distance_metric == 'euclidean':
-            d_xy = ctx.alloc(xy.nbytes)
-            d_out = ctx.alloc_f64(n, n)
-            try:
-                d_xy.upload(xy)
-                ctx.euclidean_dense(d_xy.ptr, n, radius, None, d_out.ptr)
-                self._node_distances = d_out.download((n, n))
-            finally:
-                d_xy.free()
-                d_out.free()
-        else:
-            nbr = self._graph_distances(ctx, (xy, eu, ev, length, weight), radius)
-            self._node_distances = ('dense-shortpath', nbr.distances())
-            nbr.close()
 
     # -------------------------------------------------------------- enrichment ----
     def compute_pvalues(self, **kwargs):
@@ -1546,40 +1608,30 @@ class SAFE:
         ev = np.fromiter((v for _, v in g.edges()), dtype=np.int64, count=g.number_of_edges())
         return eu, ev
 
-    def _within_reach(self, ctx):
+    def _within_reach(self):
         """The within-reach relation of attribute_unimodality_metric = 'radius' as a device membership handle (the caller closes
         it): what define_neighborhoods would build under the current node_distance_metric with the radius
         t = attribute_unimodality_radius_multiple x neighborhood_radius_resolved in place of the radius -- the same constructors,
-        so `<` against `<=`, the kept diagonal and unreached pairs are the neighborhood rule.  Returns (handle, t)."""
-        xy, eu, ev, length, weight = arrays = _graph_arrays(self.graph)
-        r = self._resolve_radius(ctx, arrays)
-        t = float(self.attribute_unimodality_radius_multiple) * float(r)
-        if not np.isfinite(t):
-            raise ValueError("attribute_unimodality_metric = 'radius' needs a finite neighborhood radius: it resolved to %r "
-                             '(does every node have x and y coordinates?)' % (r,))
-        if self.node_distance_metric == 'euclidean':
-            if not np.isfinite(xy).all():
-                raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs finite "
-                                 'x and y coordinates for every node')
-            if not t > 0:                                # `distance < t` would drop the diagonal: no node within its own reach
-                raise ValueError("attribute_unimodality_metric = 'radius' with node_distance_metric = 'euclidean' needs a "
-                                 'neighborhood radius greater than 0: it resolved to %r' % (r,))
-            return be.Neighborhoods.euclidean(ctx, xy, t), t
-        if self.node_distance_metric == 'diffusion':
-            return self._graph_distances(ctx, arrays, t), t
-        w = self._shortpath_weights(xy, eu, ev, length, weight)
-        return be.Neighborhoods.shortpath(ctx, xy.shape[0], eu, ev, w, t, keep_distances=False), t
+        so `<` against `<=`, the kept diagonal and unreached pairs are the neighborhood rule.  Returns (handle, t, '<' or '<=')."""
+        with self._distance_source() as src:
+            r = self._resolve_radius(src)
+            t = float(self.attribute_unimodality_radius_multiple) * float(r)
+            if not np.isfinite(t):
+                raise ValueError("attribute_unimodality_metric = 'radius' needs a finite neighborhood radius: it resolved to %r "
+                                 '(does every node have x and y coordinates?)' % (r,))
+            src.check_reach(r, t)
+            return src.members(t, keep_distances=False), t, src.rule
 
     def _enriched_pair_counts(self, cand):
         """(pairs, within) int64 [len(cand)] of the candidate columns `cand` of nes_binary: the unordered pairs of a column's
         enriched nodes (nes_binary > 0), and those of them that are within reach of each other.  One device call on the
         device-resident nes_binary while nobody has read it (it stays there), else on the host slice."""
         ctx = self._ctx()
-        within_nbr, t = self._within_reach(ctx)
+        within_nbr, t, rule = self._within_reach()
         try:
             if self.verbose:
                 logging.info('Within reach: %s distance %s %r (%r x the neighborhood radius %r)'
-                             % (self.node_distance_metric, '<' if self.node_distance_metric == 'euclidean' else '<=', t,
+                             % (self.node_distance_metric, rule, t,
                                 self.attribute_unimodality_radius_multiple, self.neighborhood_radius_resolved))
             src = self.__dict__.get('_r_nes_binary')
             if isinstance(src, _DeviceResult) and cand.dtype.kind in 'iu' and cand.min() >= 0 and cand.max() < src.shape[1]:

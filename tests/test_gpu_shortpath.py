@@ -295,3 +295,13 @@ def test_non_finite_weights_are_refused(amd, ctx, bad, where):
     assert err.value.code == -1                             # the same code as a negative weight
     want_a, want_d = sr.oracle_reference(g, 1.0)
     _check(_run(amd, ctx, g, 1.0), want_a, want_d, 'after the refusals')
+
+
+@pytest.mark.parametrize('u,v', [(3, 0), (0, 3), (-1, 1), (1, -1)])
+def test_an_end_point_outside_the_nodes_is_refused(amd, ctx, u, v):
+    """the adjacency builder indexes its rows by end point: one outside [0, n) is SAFE_E_INVALID, with and without weights"""
+    eu, ev = np.array([0, u], dtype=np.int32), np.array([1, v], dtype=np.int32)
+    for ew in (None, np.array([1.0, 1.0])):
+        with pytest.raises(amd.SafeHipError) as err:
+            amd.Neighborhoods.shortpath(ctx, 3, eu, ev, ew, np.inf, keep_distances=True)
+        assert err.value.code == -1                         # SAFE_E_INVALID
