@@ -27,7 +27,7 @@
  *     a flag or a timing event back or keep host memory alive for their kernels:
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
  *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_score_weighted, safe_moments_test_weighted,
- *     safe_permtest_counts_weighted, safe_fdr_adjust, safe_fdr_adjust_rows,
+ *     safe_permtest_counts_weighted, safe_permtest_extremes, safe_counts_from_extremes, safe_fdr_adjust, safe_fdr_adjust_rows,
  *     safe_fdr_adjust_scope, safe_fdr_adjust_matrix,
  *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
@@ -665,6 +665,44 @@ int safe_moments_test_weighted(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, in
  * k_permtest_weighted. */
 int safe_permtest_counts_weighted(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1,
                                   double *ns_dev, double *counts_neg_dev, double *counts_pos_dev);
+
+/* ---- family-wise adjustment: Westfall-Young single-step max-statistic (maxt.hip) -------------------------------------------
+ * Every permutation is a joint draw of all n scores of a column under the null, so the extreme of the standardised scores over
+ * a family, per permutation, is the null of the family's extreme whatever the dependence between overlapping neighborhoods.
+ * All arithmetic is f64, every operation rounded, in the order written.  Columns j in [col0, col1), rows i, permutations p in
+ * [0, P), T_p = row p of the table as safe_perms_read delivers it:
+ *   S_p[i,j]    the permuted 'sum' score of safe_permtest_counts_weighted: members added in ascending node order, one
+ *               accumulator per cell, NaN -> 0, with the handle's weights if it has some and weight 1.0 otherwise (a flat handle
+ *               is accepted: 1.0 * v is exact, the sum is the plain ascending sum)
+ *   loc_i, scale_i   k_i and f_i of safe_moments_test on a flat handle, W1_i and g_i of safe_moments_test_weighted (with all its
+ *               zeroing rules) on a weighted one; mu_j, Q_j those of safe_attr_column_moments
+ *   z_p[i,j]    var = scale_i * Q_j;  z_p = (S_p - loc_i * mu_j) / sqrt(var) when var > 0; otherwise the cell is degenerate,
+ *               for every p alike
+ *   z_obs[i,j]  the same expression on the observed score: the z_dev of the matching moments entry point, bit for bit, 0 at a
+ *               degenerate cell.  live[i,j] = 1 where var > 0, else 0: z_obs = 0 alone does not tell a degenerate cell from a
+ *               score that sits on its mean, so the flags travel beside it
+ *   tmax[p,j]   the maximum of z_p[i,j] over the non-degenerate i, -inf where there is none; tmin[p,j] the minimum, +inf
+ * safe_permtest_extremes: z_dev f64 [n, col1 - col0] and live_dev u8 [n, col1 - col0] row-major (each may be NULL), tmax_dev and
+ * tmin_dev f64 [P, col1 - col0] row-major.  Any safe_perms handle.  safe_last_kernel_stats names k_maxt_extremes.
+ *
+ * safe_counts_from_extremes: z_dev, live_dev [n, m] and tmax_dev, tmin_dev [P, m] as above, complete for all m columns;
+ *   scope SAFE_FAMILY_COLUMN   the family is the n neighborhoods of one attribute: E+[p,j] = tmax[p,j], E-[p,j] = tmin[p,j]
+ *         SAFE_FAMILY_MATRIX   the family is all n * m cells: E+[p,j] = max over the m columns of tmax[p,.], E- the minimum likewise
+ *   counts_pos[i,j] = #{p : E+[p,j] >= z_obs[i,j]},  counts_neg[i,j] = #{p : E-[p,j] <= z_obs[i,j]}  as f64 [n, m];
+ *   a degenerate cell gets P in both, the permutation test's own limit (p = 1)
+ *   min_counts_neg_dev / min_counts_pos_dev f64 [m] (each may be NULL): the smallest count of column j over its non-degenerate
+ *   cells, P if it has none -- divided by P, the attribute's p-value for "enriched somewhere on the network"
+ * safe_outputs_from_counts turns the counts into p-values, nes and nes_binary.  safe_last_kernel_stats names k_maxt_counts.
+ * Refusals (SAFE_E_INVALID, nothing written): a NULL argument, a bad column range, a table whose row count differs from the
+ * membership's, P < 1, an unknown scope.  Both run on the context's stream and return once it has drained. */
+#define SAFE_FAMILY_COLUMN 0  /* familywise_scope == 'neighborhoods' */
+#define SAFE_FAMILY_MATRIX 1  /* familywise_scope == 'all'           */
+int safe_permtest_extremes(safe_ctx *ctx, safe_nbr *nbr, safe_attr *attr, safe_perms *perms, int64_t col0, int64_t col1,
+                           double *z_dev /* may be NULL */, uint8_t *live_dev /* may be NULL */, double *tmax_dev, double *tmin_dev);
+int safe_counts_from_extremes(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int scope, const double *z_dev,
+                              const uint8_t *live_dev, const double *tmax_dev, const double *tmin_dev, double *counts_neg_dev,
+                              double *counts_pos_dev, double *min_counts_neg_dev /* may be NULL */,
+                              double *min_counts_pos_dev /* may be NULL */);
 
 /* ---- consumers of nes_binary (SAFE.define_top_attributes / define_domains) ---------------- */
 /* Connected components of the subgraph induced by the enriched nodes of each candidate

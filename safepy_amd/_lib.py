@@ -15,6 +15,7 @@ DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 FDR_SCOPE_ROWS, FDR_SCOPE_COLS, FDR_SCOPE_ALL = 0, 1, 2      # SAFE_FDR_SCOPE_*
+FAMILY_COLUMN, FAMILY_MATRIX = 0, 1                          # SAFE_FAMILY_*
 WEIGHT_KINDS = {'uniform': 0, 'triangular': 1, 'epanechnikov': 2, 'gaussian': 3}      # SAFE_WEIGHT_*
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
 SELECT_MAX_NODES = 65536            # SAFE_SELECT_MAX_NODES: nodes safe_pair_distance_select_xy / safe_nbr_distance_select take
@@ -164,6 +165,8 @@ PROTOTYPES = {
     'safe_score_weighted': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     'safe_moments_test_weighted': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_permtest_counts_weighted': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'safe_permtest_extremes': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'safe_counts_from_extremes': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_export_packed_counts': (C.c_int, [_vp, _vp, _i64, _pi64, _pi64, C.POINTER(C.c_int)]),
     'safe_nes_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, _vp, _vp]),
     'safe_outputs_from_packed_counts': (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),

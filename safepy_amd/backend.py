@@ -1420,6 +1420,28 @@ def permtest_counts_weighted(ctx, nbr, attr, perms, ns_ptr, neg_ptr, pos_ptr, co
                                             C.c_void_p(ns_ptr) if ns_ptr else None, C.c_void_p(neg_ptr), C.c_void_p(pos_ptr)))
 
 
+# familywise_scope -> SAFE_FAMILY_*: the family whose extreme every observed statistic is compared with
+FAMILY_SCOPES = {'neighborhoods': _lib.FAMILY_COLUMN, 'all': _lib.FAMILY_MATRIX}
+
+
+def permtest_extremes(ctx, nbr, attr, perms, z_ptr, live_ptr, tmax_ptr, tmin_ptr, col0=0, col1=None):
+    """Per permutation and column, the extremes over the rows of the standardised permuted 'sum' scores
+    (safe_permtest_extremes): tmax / tmin f64 [P, col1 - col0]; z_ptr (f64) and live_ptr (u8), each [n, col1 - col0] or None:
+    the observed statistic and the flags of the non-degenerate cells.  Flat and weighted handles."""
+    col1 = attr.m if col1 is None else col1
+    check(lib.safe_permtest_extremes(ctx.handle, nbr.handle, attr.handle, perms.handle, col0, col1,
+                                     *[C.c_void_p(p) if p else None for p in (z_ptr, live_ptr, tmax_ptr, tmin_ptr)]))
+
+
+def counts_from_extremes(ctx, n, m, num_permutations, scope, z_ptr, live_ptr, tmax_ptr, tmin_ptr, neg_ptr, pos_ptr,
+                         min_neg_ptr=None, min_pos_ptr=None):
+    """The max-statistic adjusted counts (safe_counts_from_extremes): scope 'neighborhoods' or 'all' (or a SAFE_FAMILY_* value);
+    counts f64 [n, m] at neg_ptr / pos_ptr, the columns' smallest counts f64 [m] at min_neg_ptr / min_pos_ptr (or None)."""
+    check(lib.safe_counts_from_extremes(ctx.handle, int(n), int(m), int(num_permutations), int(FAMILY_SCOPES.get(scope, scope)),
+                                        *[C.c_void_p(p) if p else None for p in (z_ptr, live_ptr, tmax_ptr, tmin_ptr, neg_ptr, pos_ptr,
+                                                                                 min_neg_ptr, min_pos_ptr)]))
+
+
 def fdr_adjust_rows(ctx, n, m, p_ptr):
     """Benjamini-Hochberg on every row of one f64 [n, m] device matrix, in place."""
     check(lib.safe_fdr_adjust_rows(ctx.handle, int(n), int(m), C.c_void_p(p_ptr) if p_ptr else None))

@@ -147,6 +147,13 @@ enum ScratchSlot {
     SCRATCH_DIFFUSION_GRAPH,// CSR of the network: row starts i32 [n + 1] | neighbor ids i32 [entries] | entry weights, then the scaled entries
                             //   s_ik, f64 [entries] | row scales r f64 [n] | rows by descending entry count i32 [n] | safe_nbr_diffusion
                             //   (diffusion.hip) | within the call
+    SCRATCH_MAXT_ROWS,      // loc f64 [n] | scale f64 [n] | column means f64 [tiles * 16] | centred sums of squares f64 [tiles * 16] |
+                            //   safe_permtest_extremes (maxt.hip) | within the call
+    SCRATCH_MAXT_TILES,     // the attribute operand of k_maxt_extremes: f64 tiles [tile][n][16] | safe_permtest_extremes | within the call
+    SCRATCH_MAXT_TABLE,     // the permutation table transposed, i32 [n][P] | safe_permtest_extremes | within the call
+    SCRATCH_MAXT_KEYS,      // ordered 64-bit keys of the running maxima | minima, u64 [2][columns][P] | safe_permtest_extremes | within the call
+    SCRATCH_MAXT_FAMILY,    // whole-matrix extremes f64 [2][P] | smallest counts per column u32 [2][m] | safe_counts_from_extremes (maxt.hip) |
+                            //   within the call
     N_SCRATCH
 };
 static_assert(SCRATCH_STREAM_B == SCRATCH_STREAM_A + 1 && SCRATCH_MFMA_AMB_B == SCRATCH_MFMA_AMB_A + 1,
@@ -607,6 +614,11 @@ struct safe_perms {
 int safe_attr_prepare(safe_attr *attr);   // row flags + stats (attr.hip)
 // mu_j and Q_j of columns [col0, col1) into d_mean / d_css [col1 - col0], enqueued on the context's stream (moments.hip)
 int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col1, const char *who, double *d_mean, double *d_css);
+// the row side of the permutation moments into two f64 [n] arrays, enqueued on the context's stream; the attribute handle is
+// prepared.  Flat: k_i and f_i of safe_moments_test (moments.hip); a handle with weights: W1_i and g_i of
+// safe_moments_test_weighted (weights.hip)
+int moments_row_factors_dev(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const char *who, double *d_size, double *d_factor);
+int weights_row_factors_dev(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const char *who, double *d_w1, double *d_g);
 int nbr_finalize_from_bits(safe_nbr *nbr);   // bits -> CSR + SELL (nbr.hip)
 // a handle under construction (nbr.hip; diffusion.hip builds one too): nbr_new allocates the bit matrix, and the handle is freed
 // on every return path until it is released into the caller's *out

@@ -208,6 +208,16 @@ int column_moments_dev(safe_ctx *ctx, safe_attr *attr, int64_t col0, int64_t col
     return SAFE_OK;
 }
 
+// k_i and f_i of every row into d_size / d_factor [n], enqueued on the context's stream (also maxt.hip); the attribute handle is prepared
+int moments_row_factors_dev(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const char *who, double *d_size, double *d_factor) {
+    const int64_t n = nbr->n;
+    const double nv = static_cast<double>(attr->n_rows_with_value);
+    hipLaunchKernelGGL(k_hyp_tails_nbr_size, dim3(ceil_div(n, 4)), dim3(256), 0, ctx->stream, nbr->row_ptr, nbr->col, attr->row_flags, n, d_size);
+    hipLaunchKernelGGL(k_moments_row_factor, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_size, n, nv, d_factor);
+    SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    return SAFE_OK;
+}
+
 extern "C" {
 
 int safe_attr_column_moments(safe_attr *attr, int64_t col0, int64_t col1, double *mean_host, double *css_host) {

@@ -454,6 +454,16 @@ int weights_build(safe_nbr *nbr, const char *who, const double *xy_host, int kin
 
 }  // namespace
 
+// W1_i and g_i of every row of a handle that carries weights into d_w1 / d_g [n], enqueued on the context's stream (also maxt.hip);
+// the attribute handle is prepared
+int weights_row_factors_dev(safe_ctx *ctx, const safe_nbr *nbr, const safe_attr *attr, const char *who, double *d_w1, double *d_g) {
+    const int64_t n = nbr->n;
+    hipLaunchKernelGGL(k_weights_row_sums, dim3(static_cast<unsigned int>(ceil_div(n, 4))), dim3(256), 0, ctx->stream, nbr->row_ptr, nbr->col,
+                       nbr->w_csr, attr->row_flags, n, static_cast<double>(attr->n_rows_with_value), d_w1, d_g);
+    SAFE_HIP_CHECK_AS(who, hipGetLastError());
+    return SAFE_OK;
+}
+
 extern "C" {
 
 int safe_nbr_weights_from_xy(safe_nbr *nbr, const double *xy_host, int kind, const double *radii_host, double bandwidth) {

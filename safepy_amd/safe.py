@@ -46,6 +46,8 @@ _DEFAULTS = {
     # additive (no counterpart in the reference's file): restricted permutations, see SAFE.compute_pvalues
     'permutationStrata': '',
     'permutationStrataBins': '10',
+    'familywiseAdjustment': 'none',
+    'familywiseScope': 'neighborhoods',
     # additive: the random-walk-with-restart kernel of node_distance_metric = 'diffusion', see SAFE.define_neighborhoods
     'diffusionRestart': '0.5',
     'diffusionSteps': '32',
@@ -431,6 +433,7 @@ class SAFE:
     pvalues_pos = _LazyArray('pvalues_pos')
     nes = _LazyArray('nes')
     nes_binary = _LazyArray('nes_binary')
+    familywise_statistic = _LazyArray('familywise_statistic')
 
     def __init__(self, path_to_ini_file='', path_to_safe_data=None, verbose=True, device=0):
         self.verbose = verbose
@@ -476,6 +479,11 @@ class SAFE:
         self.permutation_strata_bins = 10
         self.permutation_strata_resolved = None      # int32 [N]: every node's stratum in the last stratified call
         self.permutation_strata_sizes = None         # int64 [S]: movable rows per stratum in that call
+        # family-wise error control of how='randomization' (compute_pvalues): 'none', or 'maxT' -- Westfall-Young single-step
+        # max-statistic adjusted p-values over familywise_scope: 'neighborhoods' (every attribute's column) or 'all' (the matrix)
+        self.familywise_adjustment = 'none'
+        self.familywise_scope = 'neighborhoods'
+        self.familywise_statistic = None             # 'maxT' only: the observed standardised score z [N, M] of the last call
         self.neighborhood_score_type = 'sum'
         self.enrichment_type = 'auto'
         self.hypergeom_tails = 'upper'   # 'attribute_sign': the hypergeometric test follows attribute_sign (both tails, ns, signed nes)
@@ -513,6 +521,7 @@ class SAFE:
         self._weights_host = None        # (indptr, indices, data) of neighborhood_weights once fetched or given; pickled
         self._node_distances = None
         self._pending_binary = None
+        self._maxt_pending = None        # (observed statistic buffer, smallest adjusted p-values [2, M]) between the device call and the results
         self._attr_dev = None            # resident node2attribute (load_attributes(keep_on_device=True))
         self._attr_dev_host = None
         self._missing_rows = None        # sparse node2attribute only: uint8 [N], 1 = the node's whole row is missing (NaN)
@@ -566,6 +575,8 @@ class SAFE:
             self.permutation_strata_bins = int(bins)
         except (ValueError, TypeError):                    # validate_config names the bad value
             self.permutation_strata_bins = bins
+        self.familywise_adjustment = option('Analysis parameters', 'familywiseAdjustment') or 'none'     # empty = none
+        self.familywise_scope = option('Analysis parameters', 'familywiseScope') or 'neighborhoods'
         restart, steps = option('Analysis parameters', 'diffusionRestart'), option('Analysis parameters', 'diffusionSteps')
         try:
             self.diffusion_restart = float(restart)
@@ -639,6 +650,16 @@ class SAFE:
         if not isinstance(bins, (int, np.integer)) or isinstance(bins, (bool, np.bool_)) or bins < 1:
             self.permutation_strata_bins = 10
             raise ValueError('permutation_strata_bins = %r is not valid: it must be an integer equal or greater than 1.' % (bins,))
+        adjustment = getattr(self, 'familywise_adjustment', 'none')
+        if not isinstance(adjustment, str) or adjustment not in ['none', 'maxT']:
+            self.familywise_adjustment = 'none'
+            raise ValueError('%s is not a valid setting for familywise_adjustment. '
+                             'Valid options are: none, maxT' % (adjustment,))
+        family = getattr(self, 'familywise_scope', 'neighborhoods')
+        if not isinstance(family, str) or family not in ['neighborhoods', 'all']:
+            self.familywise_scope = 'neighborhoods'
+            raise ValueError('%s is not a valid setting for familywise_scope. '
+                             'Valid options are: neighborhoods, all' % (family,))
         weighting = getattr(self, 'neighborhood_weighting', 'none')
         if not isinstance(weighting, str) or weighting not in _WEIGHTINGS:
             self.neighborhood_weighting = 'none'
@@ -683,7 +704,7 @@ class SAFE:
 
     # pickling drops device handles (the reference pickles the whole object, safe.py:237-242)
     def __getstate__(self):
-        for name in ('ns', 'pvalues_neg', 'pvalues_pos', 'nes', 'nes_binary'):
+        for name in ('ns', 'pvalues_neg', 'pvalues_pos', 'nes', 'nes_binary', 'familywise_statistic'):
             getattr(self, name)              # results still on the device come to the host first
         self.neighborhood_weights            # (weights still on the device become _weights_host: host arrays)
         nd = self._node_distances
@@ -719,6 +740,9 @@ class SAFE:
         self.__dict__.setdefault('permutation_strata_bins', 10)
         self.__dict__.setdefault('permutation_strata_resolved', None)
         self.__dict__.setdefault('permutation_strata_sizes', None)
+        self.__dict__.setdefault('familywise_adjustment', 'none')
+        self.__dict__.setdefault('familywise_scope', 'neighborhoods')
+        self.__dict__.setdefault('_r_familywise_statistic', None)
         self.__dict__.setdefault('neighborhood_weighting', 'none')
         self.__dict__.setdefault('neighborhood_weight_bandwidth', 0.5)
         self.__dict__.setdefault('_weights_host', None)
@@ -1238,12 +1262,36 @@ class SAFE:
         'rank', background = 'network', the three signs and lazy_outputs work as without weights.  Refused with a ValueError
         before any result changes: a hypergeometric route ('auto' on 0/1 data included: pass how = 'analytic' or
         how = 'randomization') and neighborhood_score_type = 'z-score'.  safe_extras, safepy_amd.sharding and run_batch.py do
-        not take the setting: they score flat neighborhoods."""
+        not take the setting: they score flat neighborhoods.
+
+        familywise_adjustment = 'maxT' (additive; keyword or setting, default 'none' = today's bytes; with familywise_scope):
+        Westfall-Young single-step max-statistic adjusted p-values on the randomization route.  Every permutation is a joint
+        draw of all N scores of a column, so comparing each observed statistic with the per-permutation extreme over the whole
+        family controls the family-wise error rate under any dependence between the overlapping neighborhoods.  The scores
+        are made comparable across neighborhoods of different sizes by their exact permutation mean and variance (those of
+        how = 'analytic'): z = (S - loc_i mu_j) / sqrt(scale_i Q_j).
+          familywise_scope = 'neighborhoods' (default)  the family is the N neighborhoods of one attribute;
+          familywise_scope = 'all'                      the family is all N M cells.
+        ns is the observed score; pvalues_pos = #{p : max over the family of z_p >= z_obs} / P and pvalues_neg = #{p : min over
+        the family of z_p <= z_obs} / P; nes, nes_binary and num_neighborhoods_enriched follow from them through the usual
+        epilogue (its 1 / P substitution included) for all three attribute_sign values; a cell that cannot vary gets p = 1.
+        attributes['familywise_pvalue_pos'] / ['familywise_pvalue_neg'] hold the smallest adjusted p-value of every attribute --
+        its p-value for "enriched (depleted) somewhere on the network" -- and familywise_statistic the observed z [N, M], on
+        the device until read like the other results.  permutation_strata, attribute_transform = 'rank', background =
+        'network', neighborhood_weighting and every kind of permutation table work unchanged.  Under permutation_strata the
+        standardiser stays the unrestricted moments: the adjustment is valid with any fixed per-cell transform, because the
+        observed and the permuted scores pass through the same one.  Refused with a ValueError before any device work, every
+        result left as it was: how = 'analytic', a hypergeometric route ('auto' on 0/1 data included: pass
+        how = 'randomization'), neighborhood_score_type = 'z-score', and multiple_testing = True.  The attribute-sharded
+        drivers and safe_extras do not take the keyword."""
         for name in ('permutation_strata', 'permutation_strata_bins'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
         if 'multiple_testing_scope' in kwargs:
             self.multiple_testing_scope = kwargs['multiple_testing_scope']
+        for name in ('familywise_adjustment', 'familywise_scope'):
+            if name in kwargs:
+                setattr(self, name, kwargs[name])
         if 'how' in kwargs:
             self.enrichment_type = kwargs['how']
         if 'neighborhood_score_type' in kwargs:
@@ -1275,6 +1323,11 @@ class SAFE:
             self._require_sum_scores_for_weights()
             if self.enrichment_type == 'hypergeometric':
                 self._refuse_hypergeom_on_weights()
+        maxt = self.familywise_adjustment == 'maxT'            # before any device work, too
+        if maxt:
+            self._require_randomization_sums_for_maxt()
+            if self.enrichment_type == 'hypergeometric':
+                self._refuse_hypergeom_on_maxt()
 
         resident = self._resident_attributes()
         if self.background == 'network':
@@ -1319,6 +1372,8 @@ class SAFE:
                 self._refuse_hypergeom_on_strata()
             if weighted and hypergeom:
                 self._refuse_hypergeom_on_weights()
+            if maxt and hypergeom:
+                self._refuse_hypergeom_on_maxt()
             if ranked:
                 if hypergeom:
                     self._refuse_hypergeom_on_ranks()
@@ -1365,7 +1420,7 @@ class SAFE:
         logging.info('Using randomization to calculate enrichment...')
         if 'num_permutations' in kwargs:
             self.num_permutations = kwargs['num_permutations']
-        for name in ('permutation_strata', 'permutation_strata_bins'):
+        for name in ('permutation_strata', 'permutation_strata_bins', 'familywise_adjustment', 'familywise_scope'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
         self.validate_config()
@@ -1373,6 +1428,9 @@ class SAFE:
         weighted = self._weighted()                        # (refusals come before any device work)
         if weighted:
             self._require_sum_scores_for_weights()
+        maxt = self.familywise_adjustment == 'maxT'
+        if maxt:
+            self._require_randomization_sums_for_maxt(direct=True)
 
         strata = None
         if self.permutation_strata is not None:            # (refusals come before any device work)
@@ -1389,7 +1447,9 @@ class SAFE:
             raise
         bufs = [ctx.alloc_f64(n, m) for _ in range(5)] + [ctx.alloc_f64(m)]
         try:
-            if weighted:                               # the weighted counts, then the epilogue every count route shares
+            if maxt:                                   # the adjusted counts, then the epilogue every count route shares
+                self._maxt_counts(ctx, nbr, attr, perms, weighted, bufs)
+            elif weighted:                             # the weighted counts, then the epilogue every count route shares
                 counts = [ctx.alloc_f64(n, m) for _ in range(2)]
                 try:
                     be.permtest_counts_weighted(ctx, nbr, attr, perms, bufs[0].ptr, counts[0].ptr, counts[1].ptr)
@@ -1409,12 +1469,68 @@ class SAFE:
             bufs = bufs[5:] if self.lazy_outputs else bufs       # handed over: the results own their buffers now
             self.ns, self.pvalues_neg, self.pvalues_pos, self.nes = res[:4]
             self._pending_binary = (res[4], enriched)
+            if maxt:
+                self._publish_maxt(n, m)
         finally:
+            self._maxt_pending = None
             for b in bufs:
                 b.free()
             perms.close()
             if _attr is None:
                 attr.close()
+
+    def _maxt_counts(self, ctx, nbr, attr, perms, weighted, bufs):
+        """familywise_adjustment = 'maxT': the observed score, the extremes of the standardised permuted scores of all M columns
+        (familywise_scope = 'all' needs them complete), the adjusted counts and the shared epilogue into bufs = (ns,
+        pvalues_neg, pvalues_pos, nes, nes_binary, num_enriched).  The observed statistic and the columns' smallest counts
+        wait in _maxt_pending until the results are published."""
+        n, m, P = attr.n, attr.m, self.num_permutations
+        z = ctx.alloc_f64(n, m)
+        work = [ctx.alloc(n * m), ctx.alloc_f64(P, m), ctx.alloc_f64(P, m), ctx.alloc_f64(n, m), ctx.alloc_f64(n, m), ctx.alloc_f64(2 * m)]
+        live, tmax, tmin, neg, pos, least = work
+        try:
+            if weighted:
+                be.score_weighted(ctx, nbr, attr, bufs[0].ptr)
+            else:
+                be.score(ctx, nbr, attr, 'sum', bufs[0].ptr)
+            be.permtest_extremes(ctx, nbr, attr, perms, z.ptr, live.ptr, tmax.ptr, tmin.ptr)
+            be.counts_from_extremes(ctx, n, m, P, self.familywise_scope, z.ptr, live.ptr, tmax.ptr, tmin.ptr, neg.ptr, pos.ptr,
+                                    least.ptr, least.ptr + 8 * m)
+            be.outputs_from_counts(ctx, n, m, P, self.attribute_sign, self.enrichment_threshold, neg.ptr, pos.ptr, bufs[0].ptr,
+                                   [b.ptr for b in bufs[1:]])
+            self._maxt_pending = (z, least.download((2, m)) / P)
+        except Exception:
+            z.free()
+            raise
+        finally:
+            for b in work:
+                b.free()
+
+    def _publish_maxt(self, n, m):
+        z, least = self._maxt_pending
+        self.familywise_statistic = self._result(z, (n, m))
+        if not self.lazy_outputs:
+            z.free()
+        if self.attributes is None:
+            self.attributes = pd.DataFrame({'id': np.arange(m), 'name': [str(j) for j in range(m)]})
+        self.attributes['familywise_pvalue_neg'] = least[0]
+        self.attributes['familywise_pvalue_pos'] = least[1]
+
+    def _require_randomization_sums_for_maxt(self, direct=False):
+        if self.enrichment_type == 'analytic' and not direct:
+            raise ValueError("familywise_adjustment = 'maxT' compares with the extremes of the permuted scores; how = 'analytic' "
+                             "draws no permutation: pass how = 'randomization'")
+        if self.neighborhood_score_type == 'z-score':
+            raise ValueError("familywise_adjustment = 'maxT' is defined for neighborhood_score_type = 'sum' only (it standardises "
+                             "the sums with their exact permutation moments); it does not go with 'z-score'")
+        if self.multiple_testing:
+            raise ValueError("familywise_adjustment = 'maxT' and multiple_testing = True are two corrections of the same p-values: "
+                             "choose one")
+
+    def _refuse_hypergeom_on_maxt(self):
+        raise ValueError("familywise_adjustment = 'maxT' compares with the extremes of the permuted scores; this call takes the "
+                         "hypergeometric test (how = '%s'%s), which has none: pass how = 'randomization'"
+                         % (self.enrichment_type, ' on 0/1 attribute values' if self.enrichment_type == 'auto' else ''))
 
     def compute_pvalues_by_hypergeom(self, _attr=None, **kwargs):
         """safepy/safe.py:556-608.  Sets pvalues_pos and nes only (ns / pvalues_neg untouched) -- the reference's behaviour,
