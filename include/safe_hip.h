@@ -28,7 +28,7 @@
  *     safe_score, safe_permtest_counts, safe_randomization, safe_hypergeom,
  *     safe_hypergeom_tails, safe_hypergeom_outputs, safe_moments_test, safe_score_weighted, safe_moments_test_weighted,
  *     safe_permtest_counts_weighted, safe_permtest_extremes, safe_counts_from_extremes, safe_fdr_adjust, safe_fdr_adjust_rows,
- *     safe_fdr_adjust_scope, safe_fdr_adjust_matrix,
+ *     safe_fdr_adjust_scope, safe_fdr_adjust_matrix, safe_mt_adjust_scope, safe_mt_adjust_matrix,
  *     safe_outputs_from_counts, safe_outputs_from_packed_counts,
  *     safe_nes_from_packed_counts and safe_attr_nan_to_zero
  *     (tests/test_gpu_stream_order.py measures both lists).
@@ -566,6 +566,31 @@ int safe_fdr_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permu
  * matrix is checked read-only, and anything that is not such a ratio, or a P beyond the count form's limit, goes through the
  * sort with the same result.  Errors as safe_fdr_adjust_scope. */
 int safe_fdr_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int64_t count_denominator, double *p_dev);
+
+/* safe_fdr_adjust_scope / safe_fdr_adjust_matrix with the procedure named by `method` (additive: multiple_testing_method), each
+ * statsmodels' multipletests operation by operation on a family of `count` entries (m, n or n m), ps the family sorted as
+ * np.argsort does, k = 1 ... count the sorted position:
+ *   SAFE_MT_FDR_BH      ps_k / (k / count), running minimum from the right, clamp at 1: the bytes of the safe_fdr_* calls
+ *   SAFE_MT_FDR_BY      ps_k / ((k / count) / by_constant), the same scan; by_constant = sum_{i <= count} 1 / i comes from the
+ *                       caller as a double (the library sums nothing): not finite or below 1 is SAFE_E_VALUE
+ *   SAFE_MT_HOCHBERG    (count - k + 1) ps_k, the same scan
+ *   SAFE_MT_HOLM        (count - k + 1) ps_k, running MAXIMUM from the LEFT, clamp
+ *   SAFE_MT_BONFERRONI  ps count, clamp: element-wise, no sort, no histogram, no limit on n m
+ * by_constant is ignored unless method is SAFE_MT_FDR_BY.  -0.0 is the value 0.0 everywhere.  BH, BY and Hochberg: one NaN turns
+ * its whole family into 0x7FF8... (the rule of safe_fdr_adjust).  Holm and Bonferroni: a NaN entry becomes 0x7FF8... on its own
+ * and the numbers are adjusted as members of a family of `count` entries, NaNs counted (np.maximum.accumulate from the left never
+ * passes a NaN that np.argsort put last).  Forms, stream behaviour, SAFE_HIP_FDR_SORT and refusals are those of the safe_fdr_*
+ * counterparts; a method outside 0 ... 4 is SAFE_E_VALUE as well; nothing is written on any refusal. */
+#define SAFE_MT_FDR_BH 0
+#define SAFE_MT_FDR_BY 1
+#define SAFE_MT_HOLM 2
+#define SAFE_MT_HOCHBERG 3
+#define SAFE_MT_BONFERRONI 4
+int safe_mt_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
+                         double enrichment_threshold, int scope, int method, double by_constant, double *pvalues_neg_dev,
+                         double *pvalues_pos_dev, double *nes_dev, double *nes_binary_dev, double *num_enriched_dev);
+int safe_mt_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int method, double by_constant,
+                          int64_t count_denominator, double *p_dev);
 
 /* The hypergeometric test with BOTH tails, for 0/1 attributes (NaN allowed): what compute_pvalues_by_hypergeom would set if it
  * followed attribute_sign the way the randomization route does (safepy/safe.py:546-554; the reference computes the upper tail

@@ -15,6 +15,7 @@ DTYPE_F32, DTYPE_F64, DTYPE_U8 = 0, 1, 2
 SCORE_SUM, SCORE_ZSCORE = 0, 1
 SIGN_HIGHEST, SIGN_LOWEST, SIGN_BOTH = 0, 1, 2
 FDR_SCOPE_ROWS, FDR_SCOPE_COLS, FDR_SCOPE_ALL = 0, 1, 2      # SAFE_FDR_SCOPE_*
+MT_FDR_BH, MT_FDR_BY, MT_HOLM, MT_HOCHBERG, MT_BONFERRONI = 0, 1, 2, 3, 4      # SAFE_MT_*
 FAMILY_COLUMN, FAMILY_MATRIX = 0, 1                          # SAFE_FAMILY_*
 WEIGHT_KINDS = {'uniform': 0, 'triangular': 1, 'epanechnikov': 2, 'gaussian': 3}      # SAFE_WEIGHT_*
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED, E_VALUE = -1, -2, -3, -4, -5
@@ -154,6 +155,8 @@ PROTOTYPES = {
     'safe_fdr_adjust_rows': (C.c_int, [_vp, _i64, _i64, _vp]),
     'safe_fdr_adjust_scope': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'safe_fdr_adjust_matrix': (C.c_int, [_vp, _i64, _i64, C.c_int, _i64, _vp]),
+    'safe_mt_adjust_scope': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'safe_mt_adjust_matrix': (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_int, C.c_double, _i64, _vp]),
     'safe_hypergeom_tails': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'safe_hypergeom_outputs': (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'safe_moments_test': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -6,6 +6,7 @@ library reports an error (no HIP device, bad arguments, ...).
 """
 import collections
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -1468,6 +1469,55 @@ def fdr_adjust_scope(ctx, n, m, num_permutations, attribute_sign, enrichment_thr
     nes_binary, num_enriched); num_permutations = 0 selects the hypergeometric form."""
     check(lib.safe_fdr_adjust_scope(ctx.handle, int(n), int(m), int(num_permutations), _SIGN[attribute_sign], float(enrichment_threshold),
                                     _fdr_scope(scope), *[C.c_void_p(p) if p else None for p in out_ptrs]))
+
+
+# multiple_testing_method -> SAFE_MT_*: the procedure that adjusts a family (statsmodels' multipletests names)
+MT_METHODS = {'fdr_bh': _lib.MT_FDR_BH, 'fdr_by': _lib.MT_FDR_BY, 'holm': _lib.MT_HOLM, 'hochberg': _lib.MT_HOCHBERG,
+              'bonferroni': _lib.MT_BONFERRONI}
+_BY_CHUNK = 1 << 24
+_by_constants = {}
+
+
+def by_constant(count):
+    """Benjamini-Yekutieli's constant of a family of `count` tests, sum_{i <= count} 1 / i, as a float: statsmodels' own
+    expression np.sum(1. / np.arange(1, count + 1)) up to 2^24 terms; beyond that the same expression on chunks of at most 2^24
+    terms, the chunk sums joined with math.fsum (a 2 10^8-cell matrix does not allocate gigabytes).  Cached per count."""
+    count = int(count)
+    if count < 1:
+        raise ValueError('by_constant: a family has at least one test, not %d' % count)
+    if count not in _by_constants:
+        if count <= _BY_CHUNK:
+            value = float(np.sum(1. / np.arange(1, count + 1)))
+        else:
+            value = math.fsum(float(np.sum(1. / np.arange(lo, min(lo + _BY_CHUNK, count + 1))))
+                              for lo in range(1, count + 1, _BY_CHUNK))
+        _by_constants[count] = value
+    return _by_constants[count]
+
+
+def _mt_method(method, n, m, scope):
+    """(SAFE_MT_* number, by_constant of the scope's family or 0.0)"""
+    method = MT_METHODS[method] if isinstance(method, str) else int(method)
+    if method != _lib.MT_FDR_BY:
+        return method, 0.0
+    scope = _fdr_scope(scope)
+    count = {_lib.FDR_SCOPE_ROWS: int(m), _lib.FDR_SCOPE_COLS: int(n), _lib.FDR_SCOPE_ALL: int(n) * int(m)}.get(scope, 0)
+    return method, by_constant(count) if count >= 1 else 1.0        # (sizes and scopes the library refuses: it names them)
+
+
+def mt_adjust_matrix(ctx, n, m, scope, method, p_ptr, count_denominator=0, by_const=None):
+    """fdr_adjust_matrix with the procedure `method` ('fdr_bh', 'fdr_by', 'holm', 'hochberg', 'bonferroni', or a SAFE_MT_* number);
+    by_const: Benjamini-Yekutieli's constant, by default by_constant of the scope's family."""
+    number, c = _mt_method(method, n, m, scope) if by_const is None else (MT_METHODS.get(method, method), by_const)
+    check(lib.safe_mt_adjust_matrix(ctx.handle, int(n), int(m), _fdr_scope(scope), int(number), float(c), int(count_denominator),
+                                    C.c_void_p(p_ptr) if p_ptr else None))
+
+
+def mt_adjust_scope(ctx, n, m, num_permutations, attribute_sign, enrichment_threshold, scope, method, out_ptrs, by_const=None):
+    """fdr_adjust_scope with the procedure `method` (see mt_adjust_matrix)."""
+    number, c = _mt_method(method, n, m, scope) if by_const is None else (MT_METHODS.get(method, method), by_const)
+    check(lib.safe_mt_adjust_scope(ctx.handle, int(n), int(m), int(num_permutations), _SIGN[attribute_sign], float(enrichment_threshold),
+                                   _fdr_scope(scope), int(number), float(c), *[C.c_void_p(p) if p else None for p in out_ptrs]))
 
 
 def packed_counts_info(ctx):

@@ -1,4 +1,4 @@
-// multiple_testing=True: Benjamini-Hochberg adjustment of the p-value matrices along multiple_testing_scope, followed by the NES /
+// multiple_testing=True: Benjamini-Hochberg (and, further down, multiple_testing_method's other procedures) adjustment of the p-value matrices along multiple_testing_scope, followed by the NES /
 // binarisation steps that depend on the adjusted values (safe.py:546-554, 608, 468-472).  The family of one adjustment is every
 // ROW (one node's neighborhood across its m attributes), i.e. np.apply_along_axis(fdrcorrection, 1, pvalues)[:, 1, :] of
 // safepy/safe.py:536-542 (randomization) and 599-605 (hypergeometric); or every COLUMN (one attribute across the n neighborhoods:
@@ -36,17 +36,38 @@
 //                         from the right as per-block minima (k_fdr_all_blockmin), a carry pass (k_fdr_all_carry) and the apply
 //                         pass, which scatters back (k_fdr_all_apply).  The keys-only sort with a binary search per cell was not
 //                         built.  n m >= 2^31 is beyond the library sort: SAFE_E_UNSUPPORTED.
+//
+// multiple_testing_method (safe_mt_adjust_scope / safe_mt_adjust_matrix): the same passes with another per-entry value, statsmodels'
+// multipletests operation by operation (fdr_plan.h: fdr_proc_raw).  Every kernel that scans takes the procedure as a template
+// parameter M -- no switch inside the unrolled loops of the block sort -- and the M = Benjamini-Hochberg instantiation is the code
+// above, operation for operation.
+//     fdr_by      raw = ps / ((k / count) / c), c = sum 1 / i from the caller: the running minimum from the right
+//     hochberg    raw = (count - k + 1) ps: the running minimum from the right
+//     holm        the same raw: the running MAXIMUM from the LEFT -- prefix_max beside suffix_min; k_fdr_all_blockmin keeps block
+//                 maxima, k_fdr_all_carry carries from the left, k_fdr_all_apply scans upwards
+//     bonferroni  ps count: k_fdr_bonferroni, element-wise, no form at all
+// A tie group gets one value whatever its order: the minimum from the right passes through the group's LAST sorted position, the
+// maximum from the left through its FIRST, so the count forms evaluate Holm at rank before[c] + 1 = cum[c] - hist[c] + 1 and the
+// others at rank cum[c], on the same doubles as the sort forms.  NaN: the minimum from the right carries it through the family;
+// np.maximum.accumulate from the left reaches the NaNs (sorted last) only after every number, and the element-wise product never
+// mixes entries, so under Holm and Bonferroni a NaN entry becomes 0x7FF8... on its own and the numbers are adjusted as members
+// of a family of `count` entries, NaNs counted.  fmax skips a NaN, so the Holm kernels write those entries explicitly; the
+// library sort puts NaNs whose sign bit is set in FRONT of the numbers, which k_fdr_row counts and takes off Holm's ranks.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "fdr_plan.h"
 
 static_assert(FDR_SCOPE_ROWS == SAFE_FDR_SCOPE_ROWS && FDR_SCOPE_COLS == SAFE_FDR_SCOPE_COLS && FDR_SCOPE_ALL == SAFE_FDR_SCOPE_ALL,
               "fdr_plan.h numbers the scopes as safe_hip.h does");
+static_assert(FDR_PROC_BH == SAFE_MT_FDR_BH && FDR_PROC_BY == SAFE_MT_FDR_BY && FDR_PROC_HOLM == SAFE_MT_HOLM &&
+                  FDR_PROC_HOCHBERG == SAFE_MT_HOCHBERG && FDR_PROC_BONFERRONI == SAFE_MT_BONFERRONI,
+              "fdr_plan.h numbers the procedures as safe_hip.h does");
 
 namespace {
 
@@ -67,13 +88,22 @@ __device__ __forceinline__ double suffix_min(const double *part, int t, double c
     return carry;
 }
 
+// Holm's counterpart: part[u]: the maximum of thread u's share; `carry` joined with the shares left of thread t's
+__device__ __forceinline__ double prefix_max(const double *part, int t, double carry) {
+    for (int u = 0; u < t; ++u) carry = fmax(carry, part[u]);
+    return carry;
+}
+
 // A family's histogram over the counts -> table[c] = the adjusted value of every entry with count c, by one workgroup.  All
 // members of a tie end up with the value of the tie's LAST sorted position (header above), so cum[c] = #entries with count <= c
 // is that position, raw[c] = (c / P) / (cum[c] / count) the value statsmodels computes there, and table[c] = min over the occupied
 // c' >= c: block scan (thread t owns the bins fdr_span gives it), reverse running minimum.  H: the counters (u32 in LDS, u64 in
-// memory); unoccupied bins count as +inf.
-template <typename H>
-__device__ __forceinline__ void hist_to_table(const H *__restrict__ hist, int bins, double P, double count_d, double *__restrict__ table) {
+// memory); unoccupied bins count as +inf.  M: the procedure (fdr_proc_raw at the same position).  Holm runs the other way:
+// the tie takes the value of its FIRST position before[c] + 1 = cum[c] - hist[c] + 1, table[c] = max over the occupied c' <= c,
+// unoccupied bins count as -inf; count_d counts the NaN entries the histogram leaves out.
+template <int M, typename H>
+__device__ __forceinline__ void hist_to_table(const H *__restrict__ hist, int bins, double P, double count_d, double c_by,
+                                              double *__restrict__ table) {
     __shared__ H part_u[FDR_THREADS];
     __shared__ double part_d[FDR_THREADS];
     const int t = threadIdx.x;
@@ -85,20 +115,38 @@ __device__ __forceinline__ void hist_to_table(const H *__restrict__ hist, int bi
     __syncthreads();
     H cum = 0;
     for (int u = 0; u < t; ++u) cum += part_u[u];
-    double mn = fdr_inf();
-    for (int c = b0; c < b1; ++c) {
-        const H h = hist[c];
-        cum += h;
-        const double raw = h ? fdr_raw(static_cast<double>(c) / P, static_cast<double>(cum), count_d) : fdr_inf();
-        table[c] = raw;
-        mn = fmin(mn, raw);
-    }
-    part_d[t] = mn;
-    __syncthreads();
-    double carry = suffix_min(part_d, t, fdr_inf());
-    for (int c = b1 - 1; c >= b0; --c) {
-        carry = fmin(carry, table[c]);
-        table[c] = fdr_clamp(carry);
+    if constexpr (fdr_proc_from_left(M)) {
+        double mx = -fdr_inf();
+        for (int c = b0; c < b1; ++c) {
+            const H h = hist[c];
+            const double raw = h ? fdr_step_raw(static_cast<double>(c) / P, static_cast<double>(cum + 1), count_d) : -fdr_inf();
+            cum += h;
+            table[c] = raw;
+            mx = fmax(mx, raw);
+        }
+        part_d[t] = mx;
+        __syncthreads();
+        double carry = prefix_max(part_d, t, -fdr_inf());
+        for (int c = b0; c < b1; ++c) {
+            carry = fmax(carry, table[c]);
+            table[c] = fdr_clamp(carry);
+        }
+    } else {
+        double mn = fdr_inf();
+        for (int c = b0; c < b1; ++c) {
+            const H h = hist[c];
+            cum += h;
+            const double raw = h ? fdr_proc_raw(M, static_cast<double>(c) / P, static_cast<double>(cum), count_d, c_by) : fdr_inf();
+            table[c] = raw;
+            mn = fmin(mn, raw);
+        }
+        part_d[t] = mn;
+        __syncthreads();
+        double carry = suffix_min(part_d, t, fdr_inf());
+        for (int c = b1 - 1; c >= b0; --c) {
+            carry = fmin(carry, table[c]);
+            table[c] = fdr_clamp(carry);
+        }
     }
 }
 
@@ -114,33 +162,64 @@ __global__ void k_fdr_offsets(int64_t *__restrict__ off, int64_t rows, int64_t m
     if (i <= rows) off[i] = i * m;
 }
 
-// one workgroup per row of the batch; ps / cols: the row sorted ascending with its column ids
+// one workgroup per row of the batch; ps / cols: the row sorted ascending with its column ids.  M: the procedure
+template <int M>
 __global__ __launch_bounds__(FDR_THREADS) void k_fdr_row(const double *__restrict__ ps, const int32_t *__restrict__ cols, int64_t m,
-                                                         double *__restrict__ out) {
+                                                         double c_by, double *__restrict__ out) {
     __shared__ double part[FDR_THREADS];
     const int64_t row = blockIdx.x;
     const double *p = ps + row * m;
     const int32_t *c = cols + row * m;
     double *o = out + row * m;
     const int t = threadIdx.x;
-    // The library's float key puts a NaN whose sign bit is set (0xFFF8...: what x86 makes of 0 / 0) BEFORE every number and
-    // the others behind them (it treats -0.0 as +0.0): a row has a NaN iff one of its two ends is one.
-    const double first = p[0], last = p[m - 1];
-    if (first != first || last != last) {                           // a NaN anywhere poisons the whole row
-        for (int64_t r = t; r < m; r += FDR_THREADS) o[r] = fdr_qnan();
-        return;
-    }
     const double n_d = static_cast<double>(m);
     int64_t r0, r1;
     fdr_span<int64_t>(m, FDR_THREADS, t, r0, r1);
-    double mine = fdr_inf();
-    for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, fdr_raw(fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d));
-    part[t] = mine;
-    __syncthreads();
-    double carry = suffix_min(part, t, fdr_inf());                  // minimum over everything right of this thread's chunk
-    for (int64_t r = r1 - 1; r >= r0; --r) {
-        carry = fmin(carry, fdr_raw(fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d));
-        o[c[r]] = fdr_clamp(carry);
+    // The library's float key puts a NaN whose sign bit is set (0xFFF8...: what x86 makes of 0 / 0) BEFORE every number and
+    // the others behind them (it treats -0.0 as +0.0): a row has a NaN iff one of its two ends is one.
+    if constexpr (fdr_proc_from_left(M)) {
+        // Holm: the numbers keep their ranks among the numbers (np.argsort puts every NaN last): position r minus the NaNs in
+        // front of the numbers, which are the NaNs whose sign bit is set
+        __shared__ unsigned int lead_nans;
+        if (t == 0) lead_nans = 0u;
+        __syncthreads();
+        unsigned int here = 0;
+        for (int64_t r = r0; r < r1; ++r) here += (p[r] != p[r]) && __double_as_longlong(p[r]) < 0;
+        if (here) atomicAdd(&lead_nans, here);
+        __syncthreads();
+        const int64_t lead = lead_nans;
+        double mine = -fdr_inf();
+        for (int64_t r = r0; r < r1; ++r) {
+            const double v = p[r];
+            if (v == v) mine = fmax(mine, fdr_step_raw(fdr_plus_zero(v), static_cast<double>(r - lead + 1), n_d));
+        }
+        part[t] = mine;
+        __syncthreads();
+        double carry = prefix_max(part, t, -fdr_inf());             // maximum over everything left of this thread's chunk
+        for (int64_t r = r0; r < r1; ++r) {
+            const double v = p[r];
+            if (v != v) {                                           // (fmax would skip it: written explicitly)
+                o[c[r]] = fdr_qnan();
+                continue;
+            }
+            carry = fmax(carry, fdr_step_raw(fdr_plus_zero(v), static_cast<double>(r - lead + 1), n_d));
+            o[c[r]] = fdr_clamp(carry);
+        }
+    } else {
+        const double first = p[0], last = p[m - 1];
+        if (first != first || last != last) {                       // a NaN anywhere poisons the whole row
+            for (int64_t r = t; r < m; r += FDR_THREADS) o[r] = fdr_qnan();
+            return;
+        }
+        double mine = fdr_inf();
+        for (int64_t r = r1 - 1; r >= r0; --r) mine = fmin(mine, fdr_proc_raw(M, fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d, c_by));
+        part[t] = mine;
+        __syncthreads();
+        double carry = suffix_min(part, t, fdr_inf());              // minimum over everything right of this thread's chunk
+        for (int64_t r = r1 - 1; r >= r0; --r) {
+            carry = fmin(carry, fdr_proc_raw(M, fdr_plus_zero(p[r]), static_cast<double>(r + 1), n_d, c_by));
+            o[c[r]] = fdr_clamp(carry);
+        }
     }
 }
 
@@ -153,8 +232,9 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_row(const double *__restric
 #ifndef FDR_RADIX_BITS
 #define FDR_RADIX_BITS 8
 #endif
-template <int IPT>
-__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_sort(double *__restrict__ pvals, int64_t m) {
+// M: the procedure, a template parameter so that the unrolled loops over the registers hold one arithmetic and no switch.
+template <int IPT, int M>
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_sort(double *__restrict__ pvals, int64_t m, double c_by) {
     using BlockSort = hipcub::BlockRadixSort<unsigned long long, FDR_THREADS, IPT, unsigned short, FDR_RADIX_BITS>;
     __shared__ typename BlockSort::TempStorage temp;
     __shared__ double part[FDR_THREADS];
@@ -175,28 +255,53 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_sort(double *__restrict
     // the same arithmetic, in the same order, as k_fdr_row, on the registers that hold the sorted row; rank of key[i] = t * IPT + i
     const double n_d = static_cast<double>(m);
     const int r0 = t * IPT;
-    double mine = fdr_inf();
-    bool nan_here = false;
+    if constexpr (fdr_proc_from_left(M)) {
+        // Holm: the running maximum from the left; the NaN keys sit behind the numbers and keep the numbers' ranks
+        double mine = -fdr_inf();
 #pragma unroll
-    for (int i = IPT - 1; i >= 0; --i) {
-        if (r0 + i >= m) continue;
-        const double v = fdr_key_value(key[i]);
-        nan_here |= v != v;
-        mine = fmin(mine, fdr_raw(v, static_cast<double>(r0 + i + 1), n_d));
-    }
-    part[t] = mine;
-    if (nan_here) has_nan = 1;
-    __syncthreads();
-    if (has_nan) {                                                  // a NaN anywhere poisons the whole row
-        for (int64_t r = t; r < m; r += FDR_THREADS) p[r] = fdr_qnan();
-        return;
-    }
-    double carry = suffix_min(part, t, fdr_inf());                  // minimum over everything right of this thread's chunk
+        for (int i = 0; i < IPT; ++i) {
+            if (r0 + i >= m) continue;
+            const double v = fdr_key_value(key[i]);
+            if (v == v) mine = fmax(mine, fdr_step_raw(v, static_cast<double>(r0 + i + 1), n_d));
+        }
+        part[t] = mine;
+        __syncthreads();
+        double carry = prefix_max(part, t, -fdr_inf());             // maximum over everything left of this thread's chunk
 #pragma unroll
-    for (int i = IPT - 1; i >= 0; --i) {
-        if (r0 + i >= m) continue;
-        carry = fmin(carry, fdr_raw(fdr_key_value(key[i]), static_cast<double>(r0 + i + 1), n_d));
-        p[idx[i]] = fdr_clamp(carry);
+        for (int i = 0; i < IPT; ++i) {
+            if (r0 + i >= m) continue;
+            const double v = fdr_key_value(key[i]);
+            if (v != v) {                                           // (fmax would skip it: written explicitly)
+                p[idx[i]] = fdr_qnan();
+                continue;
+            }
+            carry = fmax(carry, fdr_step_raw(v, static_cast<double>(r0 + i + 1), n_d));
+            p[idx[i]] = fdr_clamp(carry);
+        }
+    } else {
+        double mine = fdr_inf();
+        bool nan_here = false;
+#pragma unroll
+        for (int i = IPT - 1; i >= 0; --i) {
+            if (r0 + i >= m) continue;
+            const double v = fdr_key_value(key[i]);
+            nan_here |= v != v;
+            mine = fmin(mine, fdr_proc_raw(M, v, static_cast<double>(r0 + i + 1), n_d, c_by));
+        }
+        part[t] = mine;
+        if (nan_here) has_nan = 1;
+        __syncthreads();
+        if (has_nan) {                                              // a NaN anywhere poisons the whole row
+            for (int64_t r = t; r < m; r += FDR_THREADS) p[r] = fdr_qnan();
+            return;
+        }
+        double carry = suffix_min(part, t, fdr_inf());              // minimum over everything right of this thread's chunk
+#pragma unroll
+        for (int i = IPT - 1; i >= 0; --i) {
+            if (r0 + i >= m) continue;
+            carry = fmin(carry, fdr_proc_raw(M, fdr_key_value(key[i]), static_cast<double>(r0 + i + 1), n_d, c_by));
+            p[idx[i]] = fdr_clamp(carry);
+        }
     }
 }
 
@@ -206,7 +311,10 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_sort(double *__restrict
 // P + 1 values): a row needs only its histogram over the counts (hist_to_table).  One workgroup per row: LDS histogram, the table,
 // one table look-up per entry.  0.9 ms -> HBM speed per matrix at 3971 x 4373.  An entry that is not exactly c / P raises `flag`
 // (the caller then sorts instead).
-__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_counts(double *__restrict__ pvals, int64_t m, int64_t n_perm, unsigned int *__restrict__ flag) {
+// M: the procedure.  Under Holm a NaN stays out of the histogram, stays in the count m and becomes 0x7FF8... on its own.
+template <int M>
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_counts(double *__restrict__ pvals, int64_t m, int64_t n_perm, double c_by,
+                                                                unsigned int *__restrict__ flag) {
     extern __shared__ unsigned char fdr_lds[];
     const int bins = static_cast<int>(n_perm) + 1;
     double *adj = reinterpret_cast<double *>(fdr_lds);                    // [bins]
@@ -226,13 +334,20 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_row_counts(double *__restri
         if (t == 0) atomicOr(flag, 1u);
         return;
     }
-    if (bad & 1) {                                                        // np.minimum propagates the NaN through the whole row
+    if (fdr_proc_nan_poisons(M) && (bad & 1)) {                           // np.minimum propagates the NaN through the whole row
         for (int64_t e = t; e < m; e += FDR_THREADS) p[e] = fdr_qnan();
         return;
     }
-    hist_to_table(hist, bins, P, static_cast<double>(m), adj);
+    hist_to_table<M>(hist, bins, P, static_cast<double>(m), c_by, adj);
     __syncthreads();
-    for (int64_t e = t; e < m; e += FDR_THREADS) p[e] = adj[static_cast<int>(fdr_count_of(p[e], P))];
+    if constexpr (fdr_proc_nan_poisons(M)) {
+        for (int64_t e = t; e < m; e += FDR_THREADS) p[e] = adj[static_cast<int>(fdr_count_of(p[e], P))];
+    } else {
+        for (int64_t e = t; e < m; e += FDR_THREADS) {
+            const double v = p[e];
+            p[e] = v != v ? fdr_qnan() : adj[static_cast<int>(fdr_count_of(v, P))];
+        }
+    }
 }
 
 // read-only: is every non-NaN entry a count ratio c / P, c in [0, P]?  (what the count forms need; anything else is sorted)
@@ -243,8 +358,11 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_check_ratio(const double *_
 }
 
 // slot[col][bin]: first the histogram (low word), then -- written by the lane that owns the bin -- the adjusted value
+// M: the procedure (Holm: the first position of a tie and the running maximum over the lanes from the left; a NaN stays out of
+// its column's histogram and becomes 0x7FF8... on its own)
+template <int M>
 __global__ __launch_bounds__(FDR_COL_THREADS) void k_fdr_col_counts(double *__restrict__ pvals, int64_t n, int64_t m, int64_t n_perm, int tile,
-                                                        unsigned int *__restrict__ flag) {
+                                                        double c_by, unsigned int *__restrict__ flag) {
     extern __shared__ unsigned long long col_slot[];
     __shared__ int col_nan[FDR_COL_TILE_MAX];
     const int bins = static_cast<int>(n_perm) + 1;
@@ -270,7 +388,7 @@ __global__ __launch_bounds__(FDR_COL_THREADS) void k_fdr_col_counts(double *__re
     int b0, b1;
     fdr_span(bins, 64, lane, b0, b1);
     for (int wc = t >> 6; wc < w; wc += FDR_COL_THREADS / 64) {
-        if (col_nan[wc]) continue;
+        if (fdr_proc_nan_poisons(M) && col_nan[wc]) continue;
         unsigned long long *slot = col_slot + wc * bins;
         unsigned int local = 0;
         for (int c = b0; c < b1; ++c) local += static_cast<unsigned int>(slot[c]);
@@ -279,12 +397,34 @@ __global__ __launch_bounds__(FDR_COL_THREADS) void k_fdr_col_counts(double *__re
             const unsigned int o = __shfl_up(upto, d);
             if (lane >= d) upto += o;
         }
-        double mn = fdr_inf();
         unsigned int cum = upto - local;
+        if constexpr (fdr_proc_from_left(M)) {
+            double mx = -fdr_inf();
+            for (int c = b0; c < b1; ++c) {
+                const unsigned int h = static_cast<unsigned int>(slot[c]);
+                const double raw = h ? fdr_step_raw(static_cast<double>(c) / P, static_cast<double>(cum + 1u), n_d) : -fdr_inf();
+                cum += h;
+                slot[c] = static_cast<unsigned long long>(__double_as_longlong(raw));
+                mx = fmax(mx, raw);
+            }
+            double left = mx;                                           // inclusive maximum over the lanes from the left
+            for (int d = 1; d < 64; d <<= 1) {
+                const double o = __shfl_up(left, d);
+                if (lane >= d) left = fmax(left, o);
+            }
+            double carry = __shfl_up(left, 1);
+            if (lane == 0) carry = -fdr_inf();
+            for (int c = b0; c < b1; ++c) {
+                carry = fmax(carry, fdr_key_value(slot[c]));
+                slot[c] = static_cast<unsigned long long>(__double_as_longlong(fdr_clamp(carry)));
+            }
+            continue;
+        }
+        double mn = fdr_inf();
         for (int c = b0; c < b1; ++c) {
             const unsigned int h = static_cast<unsigned int>(slot[c]);
             cum += h;
-            const double raw = h ? fdr_raw(static_cast<double>(c) / P, static_cast<double>(cum), n_d) : fdr_inf();
+            const double raw = h ? fdr_proc_raw(M, static_cast<double>(c) / P, static_cast<double>(cum), n_d, c_by) : fdr_inf();
             slot[c] = static_cast<unsigned long long>(__double_as_longlong(raw));
             mn = fmin(mn, raw);
         }
@@ -303,7 +443,7 @@ __global__ __launch_bounds__(FDR_COL_THREADS) void k_fdr_col_counts(double *__re
     __syncthreads();
     for (int64_t row = row0; row < n; row += step) {
         double *cell = pvals + row * m + c0 + col;
-        if (col_nan[col]) {                                             // np.minimum carries the NaN through the whole column
+        if (fdr_proc_nan_poisons(M) ? col_nan[col] != 0 : *cell != *cell) {   // np.minimum carries the NaN through the whole column
             *cell = fdr_qnan();
             continue;
         }
@@ -332,18 +472,36 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_hist(const double *__re
 }
 
 // one workgroup: table[c] = the adjusted value of every entry with count c, from the one histogram in memory
+template <int M>
 __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_table(const unsigned long long *__restrict__ hist, int64_t n_perm, double total_d,
-                                                               double *__restrict__ table) {
-    hist_to_table(hist, static_cast<int>(n_perm) + 1, static_cast<double>(n_perm), total_d, table);
+                                                               double c_by, double *__restrict__ table) {
+    hist_to_table<M>(hist, static_cast<int>(n_perm) + 1, static_cast<double>(n_perm), total_d, c_by, table);
 }
 
+// POISON: a NaN anywhere turns the whole matrix into NaN (the procedures of the running minimum); else every NaN on its own
+template <bool POISON>
 __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_map(double *__restrict__ p, int64_t total, int64_t n_perm, const double *__restrict__ table,
                                                              const unsigned int *__restrict__ flags) {
     const unsigned int f = *flags;
     if (f & 2u) return;                                                 // (cannot happen: the caller checked the matrix)
     const double P = static_cast<double>(n_perm);
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * FDR_THREADS)
-        p[i] = (f & 1u) ? fdr_qnan() : table[static_cast<int>(fdr_count_of(p[i], P))];
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * FDR_THREADS) {
+        if constexpr (POISON) {
+            p[i] = (f & 1u) ? fdr_qnan() : table[static_cast<int>(fdr_count_of(p[i], P))];
+        } else {
+            const double v = p[i];
+            p[i] = v != v ? fdr_qnan() : table[static_cast<int>(fdr_count_of(v, P))];
+        }
+    }
+}
+
+// Bonferroni, every scope: p count, clamped; a NaN becomes 0x7FF8... on its own, -0.0 is the value 0.0.  No sort, no histogram,
+// no limit on n m.
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_bonferroni(double *__restrict__ p, int64_t total, double count_d) {
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * FDR_THREADS + threadIdx.x; i < total; i += static_cast<int64_t>(gridDim.x) * FDR_THREADS) {
+        const double v = p[i];
+        p[i] = v != v ? fdr_qnan() : fdr_clamp(fdr_bonferroni_raw(fdr_plus_zero(v), count_d));
+    }
 }
 
 // -------------------------------------------------------------------------------------------------- columns, sort form ----
@@ -375,68 +533,108 @@ __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_keys(const double *__re
     cells[i] = static_cast<unsigned int>(i);
 }
 
-__device__ __forceinline__ double all_raw(const unsigned long long *__restrict__ keys, int64_t r, double total_d) {
-    return fdr_raw(fdr_key_value(keys[r]), static_cast<double>(r + 1), total_d);
+template <int M>
+__device__ __forceinline__ double all_raw(const unsigned long long *__restrict__ keys, int64_t r, double total_d, double c_by) {
+    return fdr_proc_raw(M, fdr_key_value(keys[r]), static_cast<double>(r + 1), total_d, c_by);
 }
+// the identity and the join of a procedure's running extreme: -inf / fmax from the left (Holm), +inf / fmin from the right
+template <bool LEFT>
+__device__ __forceinline__ double scan_identity() { return LEFT ? -fdr_inf() : fdr_inf(); }
+template <bool LEFT>
+__device__ __forceinline__ double scan_join(double a, double b) { return LEFT ? fmax(a, b) : fmin(a, b); }
 
-// workgroup b: the minimum of the raw values of the sorted ranks [b FDR_ALL_BLOCK, (b + 1) FDR_ALL_BLOCK)
-__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_blockmin(const unsigned long long *__restrict__ keys, int64_t total, double *__restrict__ blockmin) {
+// workgroup b: the minimum (Holm: the maximum, over the numbers) of the raw values of the sorted ranks
+// [b FDR_ALL_BLOCK, (b + 1) FDR_ALL_BLOCK)
+template <int M>
+__global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_blockmin(const unsigned long long *__restrict__ keys, int64_t total, double c_by,
+                                                                  double *__restrict__ blockmin) {
+    constexpr bool LEFT = fdr_proc_from_left(M);
     __shared__ double part[FDR_THREADS];
     const int t = threadIdx.x;
     const double total_d = static_cast<double>(total);
     const int64_t r0 = static_cast<int64_t>(blockIdx.x) * FDR_ALL_BLOCK + t * FDR_ALL_IPT;
-    double mine = fdr_inf();
+    double mine = scan_identity<LEFT>();
     for (int i = 0; i < FDR_ALL_IPT; ++i)
-        if (r0 + i < total) mine = fmin(mine, all_raw(keys, r0 + i, total_d));
+        if (r0 + i < total && !(LEFT && keys[r0 + i] == FDR_KEY_NAN)) mine = scan_join<LEFT>(mine, all_raw<M>(keys, r0 + i, total_d, c_by));
     part[t] = mine;
     __syncthreads();
     for (int s = FDR_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) part[t] = fmin(part[t], part[t + s]);
+        if (t < s) part[t] = scan_join<LEFT>(part[t], part[t + s]);
         __syncthreads();
     }
     if (t == 0) blockmin[blockIdx.x] = part[0];
 }
 
-// one workgroup: carry[b] = the minimum over every workgroup right of b
+// one workgroup: carry[b] = the minimum over every workgroup right of b; LEFT (Holm): the maximum over every workgroup left of b
+template <bool LEFT>
 __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_carry(const double *__restrict__ blockmin, int64_t blocks, double *__restrict__ carry) {
     __shared__ double part[FDR_THREADS];
     const int t = threadIdx.x;
     int64_t b0, b1;
     fdr_span<int64_t>(blocks, FDR_THREADS, t, b0, b1);
-    double mine = fdr_inf();
-    for (int64_t b = b0; b < b1; ++b) mine = fmin(mine, blockmin[b]);
+    double mine = scan_identity<LEFT>();
+    for (int64_t b = b0; b < b1; ++b) mine = scan_join<LEFT>(mine, blockmin[b]);
     part[t] = mine;
     __syncthreads();
-    double run = suffix_min(part, t, fdr_inf());
-    for (int64_t b = b1 - 1; b >= b0; --b) {
-        carry[b] = run;
-        run = fmin(run, blockmin[b]);
+    if constexpr (LEFT) {
+        double run = prefix_max(part, t, -fdr_inf());
+        for (int64_t b = b0; b < b1; ++b) {
+            carry[b] = run;
+            run = fmax(run, blockmin[b]);
+        }
+    } else {
+        double run = suffix_min(part, t, fdr_inf());
+        for (int64_t b = b1 - 1; b >= b0; --b) {
+            carry[b] = run;
+            run = fmin(run, blockmin[b]);
+        }
     }
 }
 
-// the running minimum from the right inside the workgroup's ranks, joined with carry[b], written to the cells the ranks came from
+// the running minimum from the right inside the workgroup's ranks, joined with carry[b], written to the cells the ranks came from;
+// Holm: the running maximum from the left, and every NaN key (they sit behind the numbers) written as NaN on its own
+template <int M>
 __global__ __launch_bounds__(FDR_THREADS) void k_fdr_all_apply(const unsigned long long *__restrict__ keys, const unsigned int *__restrict__ cells,
-                                                               int64_t total, const double *__restrict__ carry, double *__restrict__ out) {
+                                                               int64_t total, double c_by, const double *__restrict__ carry,
+                                                               double *__restrict__ out) {
     __shared__ double part[FDR_THREADS];
     const int t = threadIdx.x;
     const double total_d = static_cast<double>(total);
     const int64_t r0 = static_cast<int64_t>(blockIdx.x) * FDR_ALL_BLOCK + t * FDR_ALL_IPT;
-    // every NaN carries the largest key: the matrix has one iff the last sorted key is one, and then all of it becomes NaN
-    if (keys[total - 1] == FDR_KEY_NAN) {
+    if constexpr (fdr_proc_from_left(M)) {
+        double mine = -fdr_inf();
         for (int i = 0; i < FDR_ALL_IPT; ++i)
-            if (r0 + i < total) out[cells[r0 + i]] = fdr_qnan();
-        return;
-    }
-    double mine = fdr_inf();
-    for (int i = 0; i < FDR_ALL_IPT; ++i)
-        if (r0 + i < total) mine = fmin(mine, all_raw(keys, r0 + i, total_d));
-    part[t] = mine;
-    __syncthreads();
-    double run = suffix_min(part, t, carry[blockIdx.x]);
-    for (int i = FDR_ALL_IPT - 1; i >= 0; --i) {
-        if (r0 + i >= total) continue;
-        run = fmin(run, all_raw(keys, r0 + i, total_d));
-        out[cells[r0 + i]] = fdr_clamp(run);
+            if (r0 + i < total && keys[r0 + i] != FDR_KEY_NAN) mine = fmax(mine, all_raw<M>(keys, r0 + i, total_d, c_by));
+        part[t] = mine;
+        __syncthreads();
+        double run = prefix_max(part, t, carry[blockIdx.x]);
+        for (int i = 0; i < FDR_ALL_IPT; ++i) {
+            if (r0 + i >= total) continue;
+            if (keys[r0 + i] == FDR_KEY_NAN) {
+                out[cells[r0 + i]] = fdr_qnan();
+                continue;
+            }
+            run = fmax(run, all_raw<M>(keys, r0 + i, total_d, c_by));
+            out[cells[r0 + i]] = fdr_clamp(run);
+        }
+    } else {
+        // every NaN carries the largest key: the matrix has one iff the last sorted key is one, and then all of it becomes NaN
+        if (keys[total - 1] == FDR_KEY_NAN) {
+            for (int i = 0; i < FDR_ALL_IPT; ++i)
+                if (r0 + i < total) out[cells[r0 + i]] = fdr_qnan();
+            return;
+        }
+        double mine = fdr_inf();
+        for (int i = 0; i < FDR_ALL_IPT; ++i)
+            if (r0 + i < total) mine = fmin(mine, all_raw<M>(keys, r0 + i, total_d, c_by));
+        part[t] = mine;
+        __syncthreads();
+        double run = suffix_min(part, t, carry[blockIdx.x]);
+        for (int i = FDR_ALL_IPT - 1; i >= 0; --i) {
+            if (r0 + i >= total) continue;
+            run = fmin(run, all_raw<M>(keys, r0 + i, total_d, c_by));
+            out[cells[r0 + i]] = fdr_clamp(run);
+        }
     }
 }
 
@@ -517,28 +715,52 @@ int count_form_done(const char *who, unsigned int bad, int64_t n_perm) {
     return SAFE_E_VALUE;
 }
 
-template <int K = 0>
-void launch_row_sort(int ipt, hipStream_t stream, double *p_dev, int64_t n, int64_t m) {
-    if constexpr (K < FDR_IPT_RUNGS) {
-        if (ipt == FDR_IPT_LADDER[K]) hipLaunchKernelGGL(k_fdr_row_sort<FDR_IPT_LADDER[K]>, dim3(n), dim3(FDR_THREADS), 0, stream, p_dev, m);
-        else launch_row_sort<K + 1>(ipt, stream, p_dev, n, m);
+// The procedure of a call: `proc` (FdrProcedure, one of the four that sort) and Benjamini-Yekutieli's constant
+struct FdrProc {
+    int proc;
+    double c_by;
+};
+
+// f(std::integral_constant<int, M>) for the sorted procedure `proc`: the kernels take it as a template parameter
+template <typename F>
+auto with_proc(int proc, F f) {
+    switch (proc) {
+    case FDR_PROC_BY: return f(std::integral_constant<int, FDR_PROC_BY>{});
+    case FDR_PROC_HOLM: return f(std::integral_constant<int, FDR_PROC_HOLM>{});
+    case FDR_PROC_HOCHBERG: return f(std::integral_constant<int, FDR_PROC_HOCHBERG>{});
+    default: return f(std::integral_constant<int, FDR_PROC_BH>{});
     }
 }
 
-// Benjamini-Hochberg on every row of p_dev (f64 [n, m] row-major) in place, in the row form `kind` of f.  n_perm: the count
+template <int M, int K = 0>
+void launch_row_sort(int ipt, hipStream_t stream, double *p_dev, int64_t n, int64_t m, double c_by) {
+    if constexpr (K < FDR_IPT_RUNGS) {
+        if (ipt == FDR_IPT_LADDER[K])
+            hipLaunchKernelGGL((k_fdr_row_sort<FDR_IPT_LADDER[K], M>), dim3(n), dim3(FDR_THREADS), 0, stream, p_dev, m, c_by);
+        else launch_row_sort<M, K + 1>(ipt, stream, p_dev, n, m, c_by);
+    }
+}
+
+// The procedure pr on every row of p_dev (f64 [n, m] row-major) in place, in the row form `kind` of f.  n_perm: the count
 // denominator of the histogram form.  The stream has drained when it returns.
-int adjust_rows(safe_ctx *ctx, const char *who, FdrKind kind, const FdrForm &f, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
+int adjust_rows(safe_ctx *ctx, const char *who, FdrProc pr, FdrKind kind, const FdrForm &f, double *p_dev, int64_t n, int64_t m,
+                int64_t n_perm) {
     if (kind == FDR_ROW_HIST) {
         unsigned int bad = 0;
-        SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_row_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(f.lds_bytes)));
+        SAFE_HIP_CHECK(with_proc(pr.proc, [&](auto M) {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_row_counts<decltype(M)::value>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
+        }));
         SAFE_TRY(with_flag(ctx, who, [&](unsigned int *flag) {
-            hipLaunchKernelGGL(k_fdr_row_counts, dim3(n), dim3(FDR_THREADS), f.lds_bytes, ctx->stream, p_dev, m, n_perm, flag);
+            with_proc(pr.proc, [&](auto M) {
+                hipLaunchKernelGGL(k_fdr_row_counts<decltype(M)::value>, dim3(n), dim3(FDR_THREADS), f.lds_bytes, ctx->stream, p_dev, m, n_perm,
+                                   pr.c_by, flag);
+            });
         }, &bad));
         return count_form_done(who, bad, n_perm);
     }
     if (kind == FDR_ROW_BLOCK_SORT) {
-        launch_row_sort(f.ipt, ctx->stream, p_dev, n, m);
+        with_proc(pr.proc, [&](auto M) { launch_row_sort<decltype(M)::value>(f.ipt, ctx->stream, p_dev, n, m, pr.c_by); });
         return drained(ctx, who);
     }
     SAFE_REQUIRE(kind == FDR_ROW_LIBRARY_SORT, "%s: %lld attributes per row are too many", who, (long long)m);
@@ -565,36 +787,42 @@ int adjust_rows(safe_ctx *ctx, const char *who, FdrKind kind, const FdrForm &f, 
         SAFE_HIP_CHECK_AS(who, hipcub::DeviceSegmentedRadixSort::SortPairs(temp, temp_bytes, block, keys_out, vals_in, vals_out,
                                                                            static_cast<int>(rows * m), static_cast<int>(rows), offsets,
                                                                            offsets + 1, 0, 64, ctx->stream));
-        hipLaunchKernelGGL(k_fdr_row, dim3(rows), dim3(FDR_THREADS), 0, ctx->stream, keys_out, vals_out, m, block);
+        with_proc(pr.proc, [&](auto M) {
+            hipLaunchKernelGGL(k_fdr_row<decltype(M)::value>, dim3(rows), dim3(FDR_THREADS), 0, ctx->stream, keys_out, vals_out, m, pr.c_by, block);
+        });
         SAFE_HIP_CHECK_AS(who, hipGetLastError());
     }
     return drained(ctx, who);
 }
 
-int adjust_cols_counts(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
+int adjust_cols_counts(safe_ctx *ctx, const char *who, FdrProc pr, const FdrForm &f, double *p_dev, int64_t n, int64_t m, int64_t n_perm) {
     unsigned int bad = 0;
-    SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_col_counts), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(f.lds_bytes)));
+    SAFE_HIP_CHECK(with_proc(pr.proc, [&](auto M) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_col_counts<decltype(M)::value>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
+    }));
     SAFE_TRY(with_flag(ctx, who, [&](unsigned int *flag) {
-        hipLaunchKernelGGL(k_fdr_col_counts, dim3(ceil_div(m, f.tile)), dim3(FDR_COL_THREADS), f.lds_bytes, ctx->stream, p_dev, n, m, n_perm,
-                           f.tile, flag);
+        with_proc(pr.proc, [&](auto M) {
+            hipLaunchKernelGGL(k_fdr_col_counts<decltype(M)::value>, dim3(ceil_div(m, f.tile)), dim3(FDR_COL_THREADS), f.lds_bytes, ctx->stream,
+                               p_dev, n, m, n_perm, f.tile, pr.c_by, flag);
+        });
     }, &bad));
     return count_form_done(who, bad, n_perm);
 }
 
-int adjust_cols_sort(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t n, int64_t m) {
+int adjust_cols_sort(safe_ctx *ctx, const char *who, FdrProc pr, const FdrForm &f, double *p_dev, int64_t n, int64_t m) {
     CallBufs b;
     double *t_dev = nullptr;
     SAFE_TRY(b.alloc(&t_dev, n * m));
     const int64_t tiles = ceil_div(n, FDR_TR_TILE) * ceil_div(m, FDR_TR_TILE);
     hipLaunchKernelGGL(k_fdr_transpose, dim3(tiles), dim3(FDR_THREADS), 0, ctx->stream, p_dev, n, m, t_dev);
     SAFE_HIP_CHECK_AS(who, hipGetLastError());
-    SAFE_TRY(adjust_rows(ctx, who, f.row_kind, f, t_dev, m, n, 0));
+    SAFE_TRY(adjust_rows(ctx, who, pr, f.row_kind, f, t_dev, m, n, 0));
     hipLaunchKernelGGL(k_fdr_transpose, dim3(tiles), dim3(FDR_THREADS), 0, ctx->stream, t_dev, m, n, p_dev);
     return drained(ctx, who);
 }
 
-int adjust_all_counts(safe_ctx *ctx, const char *who, const FdrForm &f, double *p_dev, int64_t total, int64_t n_perm) {
+int adjust_all_counts(safe_ctx *ctx, const char *who, FdrProc pr, const FdrForm &f, double *p_dev, int64_t total, int64_t n_perm) {
     const int64_t bins = n_perm + 1;
     unsigned long long *hist = nullptr;                              // [bins], then the table f64 [bins], then the u32 flags
     SAFE_TRY(ctx_scratch(ctx, SCRATCH_FDR_SCOPE, static_cast<size_t>(bins) * 16 + 16, reinterpret_cast<void **>(&hist)));
@@ -605,13 +833,18 @@ int adjust_all_counts(safe_ctx *ctx, const char *who, const FdrForm &f, double *
     SAFE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fdr_all_hist), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(f.lds_bytes)));
     hipLaunchKernelGGL(k_fdr_all_hist, dim3(grid), dim3(FDR_THREADS), f.lds_bytes, ctx->stream, p_dev, total, n_perm, hist, flags);
-    hipLaunchKernelGGL(k_fdr_all_table, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, hist, n_perm, static_cast<double>(total), table);
-    hipLaunchKernelGGL(k_fdr_all_map, dim3(grid), dim3(FDR_THREADS), 0, ctx->stream, p_dev, total, n_perm, table, flags);
+    with_proc(pr.proc, [&](auto M) {
+        constexpr int proc = decltype(M)::value;
+        hipLaunchKernelGGL(k_fdr_all_table<proc>, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, hist, n_perm, static_cast<double>(total), pr.c_by,
+                           table);
+        hipLaunchKernelGGL(k_fdr_all_map<fdr_proc_nan_poisons(proc)>, dim3(grid), dim3(FDR_THREADS), 0, ctx->stream, p_dev, total, n_perm, table,
+                           flags);
+    });
     SAFE_TRY(read_flag(ctx, who, flags, &bad));
     return count_form_done(who, bad & 2u, n_perm);
 }
 
-int adjust_all_sort(safe_ctx *ctx, const char *who, double *p_dev, int64_t total) {
+int adjust_all_sort(safe_ctx *ctx, const char *who, FdrProc pr, double *p_dev, int64_t total) {
     CallBufs b;
     unsigned long long *keys_in = nullptr, *keys_out = nullptr;
     unsigned int *cells_in = nullptr, *cells_out = nullptr;
@@ -632,25 +865,37 @@ int adjust_all_sort(safe_ctx *ctx, const char *who, double *p_dev, int64_t total
     SAFE_HIP_CHECK_AS(who, hipGetLastError());
     SAFE_HIP_CHECK_AS(who, hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, cells_in, cells_out,
                                                               static_cast<int>(total), 0, 64, ctx->stream));
-    hipLaunchKernelGGL(k_fdr_all_blockmin, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, total, blockmin);
-    hipLaunchKernelGGL(k_fdr_all_carry, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, blockmin, blocks, carry);
-    hipLaunchKernelGGL(k_fdr_all_apply, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, cells_out, total, carry, p_dev);
+    with_proc(pr.proc, [&](auto M) {
+        constexpr int proc = decltype(M)::value;
+        hipLaunchKernelGGL(k_fdr_all_blockmin<proc>, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, total, pr.c_by, blockmin);
+        hipLaunchKernelGGL(k_fdr_all_carry<fdr_proc_from_left(proc)>, dim3(1), dim3(FDR_THREADS), 0, ctx->stream, blockmin, blocks, carry);
+        hipLaunchKernelGGL(k_fdr_all_apply<proc>, dim3(blocks), dim3(FDR_THREADS), 0, ctx->stream, keys_out, cells_out, total, pr.c_by, carry,
+                           p_dev);
+    });
     return drained(ctx, who);
 }
 
 // One matrix along `scope`, in place: the form from fdr_plan.h, then its launches.  hist_perm > 0: every entry is a count ratio
-// c / hist_perm (checked).  The stream has drained when it returns.
-int adjust_matrix(safe_ctx *ctx, const char *who, FdrSwitch sw, int scope, double *p_dev, int64_t n, int64_t m, int64_t hist_perm) {
+// c / hist_perm (checked).  Bonferroni takes no form: one element-wise pass with the size of the family.  The stream has drained
+// when it returns.
+int adjust_matrix(safe_ctx *ctx, const char *who, FdrProc pr, FdrSwitch sw, int scope, double *p_dev, int64_t n, int64_t m,
+                  int64_t hist_perm) {
+    if (!fdr_proc_sorts(pr.proc)) {
+        const int64_t total = n * m, grid = std::min<int64_t>(ceil_div(total, FDR_THREADS), 8192);
+        const int64_t count = scope == FDR_SCOPE_ROWS ? m : scope == FDR_SCOPE_COLS ? n : total;
+        hipLaunchKernelGGL(k_fdr_bonferroni, dim3(grid), dim3(FDR_THREADS), 0, ctx->stream, p_dev, total, static_cast<double>(count));
+        return drained(ctx, who);
+    }
     const FdrForm f = fdr_form(scope, n, m, hist_perm, sw);
     switch (f.kind) {
     case FDR_UNSUPPORTED:
         safe_set_error("%s: %lld x %lld p-values as one family are beyond the library sort (2^31 items)", who, (long long)n, (long long)m);
         return SAFE_E_UNSUPPORTED;
-    case FDR_COL_COUNTS: return adjust_cols_counts(ctx, who, f, p_dev, n, m, hist_perm);
-    case FDR_COL_SORT: return adjust_cols_sort(ctx, who, f, p_dev, n, m);
-    case FDR_ALL_COUNTS: return adjust_all_counts(ctx, who, f, p_dev, n * m, hist_perm);
-    case FDR_ALL_SORT: return adjust_all_sort(ctx, who, p_dev, n * m);
-    default: return adjust_rows(ctx, who, f.kind, f, p_dev, n, m, hist_perm);
+    case FDR_COL_COUNTS: return adjust_cols_counts(ctx, who, pr, f, p_dev, n, m, hist_perm);
+    case FDR_COL_SORT: return adjust_cols_sort(ctx, who, pr, f, p_dev, n, m);
+    case FDR_ALL_COUNTS: return adjust_all_counts(ctx, who, pr, f, p_dev, n * m, hist_perm);
+    case FDR_ALL_SORT: return adjust_all_sort(ctx, who, pr, p_dev, n * m);
+    default: return adjust_rows(ctx, who, pr, f.kind, f, p_dev, n, m, hist_perm);
     }
 }
 
@@ -664,6 +909,8 @@ struct FdrCall {
     int scope, sign_mode;
     double enrichment_threshold;
     double *neg, *pos, *nes, *nes_binary, *num_enriched;
+    int method = SAFE_MT_FDR_BH;   // SAFE_MT_*: the safe_fdr_* entry points are Benjamini-Hochberg
+    double by_constant = 0.0;      // SAFE_MT_FDR_BY only
 };
 
 // (SAFE_REQUIRE: SAFE_E_INVALID, which run turns into the entry point's own code)
@@ -676,6 +923,9 @@ int validate(const safe_ctx *ctx, const FdrCall &c) {
         SAFE_REQUIRE(c.enrichment_threshold > 0.0 && c.enrichment_threshold < 1.0, "%s: enrichment_threshold must be in (0,1)", c.who);
     }
     SAFE_REQUIRE(c.scope >= SAFE_FDR_SCOPE_ROWS && c.scope <= SAFE_FDR_SCOPE_ALL, "%s: bad scope %d", c.who, c.scope);
+    SAFE_REQUIRE(c.method >= SAFE_MT_FDR_BH && c.method <= SAFE_MT_BONFERRONI, "%s: bad method %d", c.who, c.method);
+    SAFE_REQUIRE(c.method != SAFE_MT_FDR_BY || (std::isfinite(c.by_constant) && c.by_constant >= 1.0),
+                 "%s: by_constant %g is not the harmonic sum of a family (finite, at least 1)", c.who, c.by_constant);
     return SAFE_OK;
 }
 
@@ -689,8 +939,9 @@ int run(safe_ctx *ctx, const FdrCall &c) {
     const FdrSwitch sw = fdr_switch(getenv("SAFE_HIP_FDR_SORT"));
     const int n_mats = c.epilogue && c.n_perm > 0 ? 2 : 1;             // the randomization form: pvalues_neg, then pvalues_pos
     double *mats[2] = {n_mats == 2 ? c.neg : c.pos, c.pos};
+    const FdrProc pr = {c.method, c.method == SAFE_MT_FDR_BY ? c.by_constant : 0.0};
     int64_t hist_perm = 0;
-    if (fdr_count_form_exists(c.scope, c.n_perm, sw)) {
+    if (fdr_proc_sorts(pr.proc) && fdr_count_form_exists(c.scope, c.n_perm, sw)) {
         unsigned int bad = 0;
         SAFE_TRY(with_flag(ctx, c.who, [&](unsigned int *flag) {
             for (int k = 0; k < n_mats; ++k)
@@ -699,7 +950,7 @@ int run(safe_ctx *ctx, const FdrCall &c) {
         }, &bad));
         if (!bad) hist_perm = c.n_perm;
     }
-    for (int k = 0; k < n_mats; ++k) SAFE_TRY(adjust_matrix(ctx, c.who, sw, c.scope, mats[k], c.n, c.m, hist_perm));
+    for (int k = 0; k < n_mats; ++k) SAFE_TRY(adjust_matrix(ctx, c.who, pr, sw, c.scope, mats[k], c.n, c.m, hist_perm));
     if (!c.epilogue) return SAFE_OK;
     CallBufs b;
     unsigned int *d_enr = nullptr;
@@ -737,4 +988,19 @@ extern "C" int safe_fdr_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_
 extern "C" int safe_fdr_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int64_t count_denominator, double *p_dev) {
     return run(ctx, {"safe_fdr_adjust_matrix", SAFE_E_VALUE, false, n, m, count_denominator, scope, 0, 0.0, nullptr, p_dev, nullptr, nullptr,
                      nullptr});
+}
+
+// safe_fdr_adjust_scope with the procedure named by `method` (SAFE_MT_*); SAFE_MT_FDR_BH gives its bytes
+extern "C" int safe_mt_adjust_scope(safe_ctx *ctx, int64_t n, int64_t m, int64_t num_permutations, int sign_mode,
+                                    double enrichment_threshold, int scope, int method, double by_constant, double *pvalues_neg_dev,
+                                    double *pvalues_pos_dev, double *nes_dev, double *nes_binary_dev, double *num_enriched_dev) {
+    return run(ctx, {"safe_mt_adjust_scope", SAFE_E_VALUE, true, n, m, num_permutations, scope, sign_mode, enrichment_threshold,
+                     pvalues_neg_dev, pvalues_pos_dev, nes_dev, nes_binary_dev, num_enriched_dev, method, by_constant});
+}
+
+// safe_fdr_adjust_matrix with the procedure named by `method`
+extern "C" int safe_mt_adjust_matrix(safe_ctx *ctx, int64_t n, int64_t m, int scope, int method, double by_constant,
+                                     int64_t count_denominator, double *p_dev) {
+    return run(ctx, {"safe_mt_adjust_matrix", SAFE_E_VALUE, false, n, m, count_denominator, scope, 0, 0.0, nullptr, p_dev, nullptr, nullptr,
+                     nullptr, method, by_constant});
 }

@@ -153,3 +153,34 @@ FDR_HD int fdr_ratio_bin(double v, double P) {
 // the same doubles; then the running minimum from the right, and values above 1 become 1
 FDR_HD double fdr_raw(double p, double rank1, double count) { return p / (rank1 / count); }
 FDR_HD double fdr_clamp(double v) { return v > 1.0 ? 1.0 : v; }
+
+// ----------------------------------------------------------------------------------------------- the other procedures ----
+
+// multiple_testing_method (SAFE_MT_* of safe_hip.h): statsmodels' multipletests restated.  The form of a call (fdr_form) does
+// not depend on the procedure; Bonferroni alone takes no form at all (element-wise).
+enum FdrProcedure { FDR_PROC_BH = 0, FDR_PROC_BY = 1, FDR_PROC_HOLM = 2, FDR_PROC_HOCHBERG = 3, FDR_PROC_BONFERRONI = 4 };
+constexpr int FDR_PROC_COUNT = 5;
+
+// Hochberg's and Holm's raw value at sorted position `rank1` (from 1): the integer count - rank1 + 1 is exact in f64, one
+// rounded product
+FDR_HD double fdr_step_raw(double p, double rank1, double count) { return (count - rank1 + 1.0) * p; }
+// Benjamini-Yekutieli's: statsmodels divides the rank fractions by c = sum 1 / i first, then the p-values by the result --
+// three divisions in this order; c comes from the caller (backend.by_constant)
+FDR_HD double fdr_by_raw(double p, double rank1, double count, double c_by) { return p / ((rank1 / count) / c_by); }
+// Bonferroni's: one rounded product (then the clamp)
+FDR_HD double fdr_bonferroni_raw(double p, double count) { return p * count; }
+
+// The raw value of a sorted procedure.  `proc` is a compile-time constant in every kernel, so one branch is left.
+FDR_HD double fdr_proc_raw(int proc, double p, double rank1, double count, double c_by) {
+    return proc == FDR_PROC_BH ? fdr_raw(p, rank1, count)
+           : proc == FDR_PROC_BY ? fdr_by_raw(p, rank1, count, c_by)
+                                 : fdr_step_raw(p, rank1, count);
+}
+// Holm is step-down: the running MAXIMUM from the LEFT (a tie group takes the value of its FIRST sorted position); the others
+// take the running minimum from the right (a tie group takes the value of its LAST position)
+constexpr bool fdr_proc_from_left(int proc) { return proc == FDR_PROC_HOLM; }
+// np.minimum.accumulate from the right carries a NaN (sorted last) through the whole family; np.maximum.accumulate from the left
+// and the element-wise product leave it where it is: the NaN entries become 0x7FF8... and the numbers are adjusted as members
+// of a family of `count` entries, NaNs counted
+constexpr bool fdr_proc_nan_poisons(int proc) { return proc == FDR_PROC_BH || proc == FDR_PROC_BY || proc == FDR_PROC_HOCHBERG; }
+constexpr bool fdr_proc_sorts(int proc) { return proc != FDR_PROC_BONFERRONI; }

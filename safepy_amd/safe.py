@@ -48,6 +48,8 @@ _DEFAULTS = {
     'permutationStrataBins': '10',
     'familywiseAdjustment': 'none',
     'familywiseScope': 'neighborhoods',
+    # additive: the procedure of multiple_testing, see SAFE.compute_pvalues
+    'multipleTestingMethod': 'fdr_bh',
     # additive: the random-walk-with-restart kernel of node_distance_metric = 'diffusion', see SAFE.define_neighborhoods
     'diffusionRestart': '0.5',
     'diffusionSteps': '32',
@@ -55,6 +57,7 @@ _DEFAULTS = {
 
 
 _WEIGHTINGS = ('none', 'uniform', 'triangular', 'epanechnikov', 'gaussian', 'custom')     # neighborhood_weighting
+_MT_METHODS = ('fdr_bh', 'fdr_by', 'holm', 'hochberg', 'bonferroni')                      # multiple_testing_method (backend.MT_METHODS)
 
 
 def _member_weights(w, indptr, indices):
@@ -473,6 +476,9 @@ class SAFE:
         # read only when multiple_testing is on: the family one Benjamini-Hochberg run adjusts -- 'attributes' (every node's row, the
         # reference), 'neighborhoods' (every attribute's column), 'all' (the whole matrix); compute_pvalues
         self.multiple_testing_scope = 'attributes'
+        # read only when multiple_testing is on: the procedure -- 'fdr_bh' (Benjamini-Hochberg, the reference), 'fdr_by'
+        # (Benjamini-Yekutieli: FDR under any dependence), 'holm', 'hochberg', 'bonferroni' (family-wise error rate); compute_pvalues
+        self.multiple_testing_method = 'fdr_bh'
         # restricted permutations of how='randomization' (compute_pvalues): None, one label per node, or 'neighborhood_size'
         # (nodes binned into permutation_strata_bins groups by the size of their neighborhood)
         self.permutation_strata = None
@@ -577,6 +583,7 @@ class SAFE:
             self.permutation_strata_bins = bins
         self.familywise_adjustment = option('Analysis parameters', 'familywiseAdjustment') or 'none'     # empty = none
         self.familywise_scope = option('Analysis parameters', 'familywiseScope') or 'neighborhoods'
+        self.multiple_testing_method = option('Analysis parameters', 'multipleTestingMethod') or 'fdr_bh'      # empty = fdr_bh
         restart, steps = option('Analysis parameters', 'diffusionRestart'), option('Analysis parameters', 'diffusionSteps')
         try:
             self.diffusion_restart = float(restart)
@@ -637,6 +644,11 @@ class SAFE:
             self.multiple_testing_scope = 'attributes'
             raise ValueError('%s is not a valid setting for multiple_testing_scope. '
                              'Valid options are: attributes, neighborhoods, all' % (scope,))
+        method = getattr(self, 'multiple_testing_method', 'fdr_bh')
+        if not isinstance(method, str) or method not in _MT_METHODS:
+            self.multiple_testing_method = 'fdr_bh'
+            raise ValueError('%s is not a valid setting for multiple_testing_method. '
+                             'Valid options are: %s' % (method, ', '.join(_MT_METHODS)))
         strata = getattr(self, 'permutation_strata', None)
         if isinstance(strata, str) and strata != 'neighborhood_size':
             self.permutation_strata = None
@@ -733,6 +745,7 @@ class SAFE:
         self.__dict__.setdefault('hypergeom_tails', 'upper')     # (objects pickled before the setting existed)
         self.__dict__.setdefault('attribute_transform', 'none')
         self.__dict__.setdefault('multiple_testing_scope', 'attributes')
+        self.__dict__.setdefault('multiple_testing_method', 'fdr_bh')
         self.__dict__.setdefault('attribute_unimodality_radius_multiple', 2.0)
         self.__dict__.setdefault('attribute_unimodality_min_fraction', 0.65)
         self.__dict__.setdefault('neighborhood_radii', None)
@@ -1233,6 +1246,22 @@ class SAFE:
         node without a score) turns its whole family NaN -- its column under 'neighborhoods', the WHOLE matrix under 'all'.
         The attribute-sharded drivers (safepy_amd.sharding, run_batch.py) keep the row scope and do not take the keyword.
 
+        multiple_testing_method (additive; keyword, setting or INI key multipleTestingMethod, default 'fdr_bh' = today's bytes;
+        read only when multiple_testing is on): the procedure that adjusts every family of multiple_testing_scope, each
+        statsmodels' multipletests operation by operation, on every route that honours multiple_testing (randomization flat
+        and weighted, both hypergeometric routes, how = 'analytic') at Benjamini-Hochberg's cost.
+          'fdr_bh'      Benjamini-Hochberg: the false discovery rate under independence or positive dependence;
+          'fdr_by'      Benjamini-Yekutieli: the false discovery rate under ANY dependence -- overlapping neighborhoods included --
+                        BH with the constant sum 1 / i over the family (backend.by_constant);
+          'holm'        Holm's step-down and
+          'hochberg'    Hochberg's step-up procedure: the family-wise error rate;
+          'bonferroni'  p times the size of the family: the family-wise error rate, element-wise.
+        nes, nes_binary and num_neighborhoods_enriched come from the adjusted values through the same epilogue.  NaN rule:
+        under 'fdr_bh', 'fdr_by' and 'hochberg' one NaN turns its family NaN (np.minimum.accumulate carries it); under 'holm'
+        and 'bonferroni' only the NaN cell itself is NaN and the numbers are adjusted as members of the full family, NaNs
+        counted.  What refuses multiple_testing refuses it under every method (familywise_adjustment = 'maxT' with it
+        included); the attribute-sharded drivers and safe_extras keep 'fdr_bh' on rows and do not take the keyword.
+
         permutation_strata (additive; keyword or setting, default None = the free shuffle and its bytes; with
         permutation_strata_bins): a RESTRICTED permutation null for how = 'randomization' -- the attribute rows are shuffled only
         among nodes of one stratum, so an attribute that merely tracks a node property that also shapes the neighborhoods
@@ -1289,6 +1318,8 @@ class SAFE:
                 setattr(self, name, kwargs[name])
         if 'multiple_testing_scope' in kwargs:
             self.multiple_testing_scope = kwargs['multiple_testing_scope']
+        if 'multiple_testing_method' in kwargs:
+            self.multiple_testing_method = kwargs['multiple_testing_method']
         for name in ('familywise_adjustment', 'familywise_scope'):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
@@ -1406,9 +1437,14 @@ class SAFE:
     def _fdr_adjust(self, ctx, n, m, num_permutations, out_ptrs):
         """multiple_testing on the randomization and the upper-tail hypergeometric route: Benjamini-Hochberg along
         multiple_testing_scope, then nes, nes_binary and the counts from the adjusted values.  The library chooses the form of
-        every scope; 'attributes' gives the bytes of backend.fdr_adjust, the reference's behaviour."""
-        be.fdr_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
-                            self.multiple_testing_scope, out_ptrs)
+        every scope; 'attributes' gives the bytes of backend.fdr_adjust, the reference's behaviour.  Another
+        multiple_testing_method takes the same path with its own per-entry arithmetic (backend.mt_adjust_scope)."""
+        if self.multiple_testing_method == 'fdr_bh':
+            be.fdr_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
+                                self.multiple_testing_scope, out_ptrs)
+        else:
+            be.mt_adjust_scope(ctx, n, m, num_permutations, self.attribute_sign, self.enrichment_threshold,
+                               self.multiple_testing_scope, self.multiple_testing_method, out_ptrs)
 
     def compute_pvalues_by_randomization(self, _attr=None, **kwargs):
         """safepy/safe.py:474-554 (no 1 s sleep, no multiprocessing split: `processes` is
@@ -1697,7 +1733,10 @@ class SAFE:
                 if self.verbose:
                     logging.info('Running FDR-adjustment of p-values...')
                 for b in bufs[1:3]:
-                    be.fdr_adjust_matrix(ctx, n, m, self.multiple_testing_scope, b.ptr)
+                    if self.multiple_testing_method == 'fdr_bh':
+                        be.fdr_adjust_matrix(ctx, n, m, self.multiple_testing_scope, b.ptr)
+                    else:
+                        be.mt_adjust_matrix(ctx, n, m, self.multiple_testing_scope, self.multiple_testing_method, b.ptr)
                 be.hypergeom_outputs(ctx, n, m, self.attribute_sign, self.enrichment_threshold, bufs[1].ptr, bufs[2].ptr,
                                      [b.ptr for b in bufs[3:]])
             enriched = bufs[5].download((m,))
